@@ -11,6 +11,11 @@ GPU.  N > 1 (configs[2]): STRONG scaling -- the same global batch of 64 clips sp
 RCCL all-reduce of the 178 MB gradient in chunks that overlap the backward pass; the weak-scaling form (64 clips on every rank,
 global batch 64*N) is timed in the same run and reported beside it (`weak_scaling`; `--weak` makes it the headline instead).
 Inputs are resident in HBM before timing starts.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds everything else, each part a run
+of its own after the timed steps: the first step against the oracle's committed answer, per-launch times and the roofline, the
+forward-only rate, the opt-in conv arithmetics, the other scaling form (N > 1) and the CPU baseline.  --dump-outputs DIR writes
+what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -130,6 +135,37 @@ def oracle_first_step(eng, frames, onehot, clips, fpc, classes):
                        and np.abs(logits - gold["cfg2_ref/logits"]).max() < 1e-3)}
 
 
+DUMP_SAMPLE = 1 << 21          # elements kept of a parameter larger than this (fc6W, the LSTM kernel): the whole dump stays < 64 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(eng):
+    """What a caller of train_step_u8(fetch=True) would receive from the step that just ran -- loss, accuracy and gradient norm as
+    it returns them, the logits (logits_host) and the updated parameters (get_params) -- read from the engine's buffers without
+    another step.  A parameter of more than DUMP_SAMPLE elements is kept as the sorted sample default_rng(0).choice(size, DUMP_SAMPLE)
+    of its flattened elements (the same indices in every run)."""
+    logits = eng.logits_host()                         # synchronises and checks the step's status
+    rows = logits.shape[0]
+    st = eng.stats.cpu().numpy()
+    out = {"loss": np.float64(float(st[0]) / max(rows, 1)), "accuracy": np.float64(float(st[1]) / max(rows, 1)),
+           "grad_norm": np.float64(np.sqrt(float(eng.ss.item()))), "logits": logits.astype(np.float32)}
+    for name, a in eng.get_params().items():
+        a = a.astype(np.float32)
+        if a.size > DUMP_SAMPLE:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out["param_" + name.replace("/", "_")] = a
+    return out
+
+
+def write_outputs(outputs, path):
+    total = sum(np.asarray(v).nbytes for v in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,14 +177,20 @@ def main():
     ap.add_argument("--weak", action="store_true", help="N > 1: weak scaling (every rank runs a whole batch) is the headline, strong the side field")
     ap.add_argument("--fpc", type=int, default=16)
     ap.add_argument("--classes", type=int, default=101)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the checks and side measurements (oracle check, roofline, forward only, "
+                                                        "opt-in arithmetics, other scaling form, CPU baseline); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, accuracy, grad norm, logits and updated "
+                                                          "parameters (a fixed sample of the large ones) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-clips", type=int, default=16)
     ap.add_argument("--dropout", type=float, default=0.5, help="dropout keep probability of the timed steps (SURVEY 8d: 0.5; 0 disables)")
-    ap.add_argument("--no-side", action="store_true", help="N > 1: skip the other scaling form's measurement")
+    ap.add_argument("--no-side", action="store_true", help="--full, N > 1: skip the other scaling form's measurement")
     ap.add_argument("--conv-math", default="f32", choices=["f32", "bf16x3", "bf16x6", "bf16"],
                     help="arithmetic of the MAIN measurement (default f32 = the headline; anything else is labelled in `dtype`)")
-    ap.add_argument("--no-split-math", action="store_true", help="N = 1: skip the extra bf16x3 / bf16x6 / bf16 (opt-in conv arithmetic) measurements")
+    ap.add_argument("--no-split-math", action="store_true", help="--full, N = 1: skip the extra bf16x3 / bf16x6 / bf16 (opt-in conv arithmetic) measurements")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from vltf_amd import dp as dpmod
     # `python bench.py --gpus N` as the driver starts it (no launcher): become the launcher -- N ranks under torch.distributed.run --
@@ -217,8 +259,9 @@ def main():
 
     host_issue = [0.0]
 
-    def timed(eng, frames, onehot, clips, global_clips, probe):
-        """W warm-up steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks."""
+    def timed(eng, frames, onehot, clips, global_clips, probe, capture=False, check=True):
+        """W warm-up steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks.  capture: the last timed
+        step's outputs (step_outputs); check: one more step with its loss / gradient norm fetched, after the timed region."""
         def step(fetch=False):
             if clips == 0:                                 # more ranks than clips: this rank only joins the exchange
                 return eng.train_step_empty(1e-3, 10.0, fetch=fetch)
@@ -245,7 +288,8 @@ def main():
             elapsed = float(t.item())
         times = eng.probe_times_ms() if probe else []
         eng.set_probe(None)
-        return elapsed, times, step(fetch=True)
+        outputs = step_outputs(eng) if capture else None
+        return elapsed, times, outputs, (step(fetch=True) if check else None)
 
     scaling = "weak" if (args.weak and world > 1) else "strong"
     clips, total_clips = job(scaling)
@@ -253,16 +297,17 @@ def main():
     frames, onehot = inputs(clips)
     n = clips * args.fpc
     oracle_check = None
-    if world == 1 and args.conv_math == "f32":
+    if args.full and world == 1 and args.conv_math == "f32":
         oracle_check = oracle_first_step(eng, frames, onehot, clips, args.fpc, args.classes)
         eng.load_params(init_params(cfg, seed=2))
         eng.step_count = 0
     eng_chunks = list(eng.grad_chunks)
-    elapsed, times, out = timed(eng, frames, onehot, clips, total_clips, probe=True)
+    elapsed, times, outputs, out = timed(eng, frames, onehot, clips, total_clips, probe=args.full,
+                                         capture=bool(args.dump_outputs) and rank == 0, check=args.full)
     host_issue_main = host_issue[0]
     overlapped = clips > 0 and eng._side_stream() is not None      # the backward ran its independent launches on two streams
     serial_times = None
-    if overlapped and world == 1:
+    if args.full and overlapped and world == 1:
         # per-launch times of the conv stack need launches that run alone: the same steps once more with the second stream off
         # (after the timed region, not part of `value`)
         keep = os.environ.get("VLTF_WGRAD_STREAM")
@@ -283,7 +328,7 @@ def main():
                 os.environ["VLTF_WGRAD_STREAM"] = keep
     # forward only (sess.run(model.logits), run_task.py:95; SURVEY 8d asks for it beside the train step): per rank, untimed for `value`
     fwd_ms = None
-    if clips > 0:
+    if args.full and clips > 0:
         for _ in range(2):
             eng.forward_u8(frames, mean_bgr=MEAN_BGR)
         torch.cuda.synchronize()
@@ -298,7 +343,7 @@ def main():
     # the same job timed the same way, reported BESIDE `value` (which stays the fp32 path), with its own loss / gradient norm
     # after the same number of steps from the same initial parameters as evidence of what the arithmetic changes.
     split, split6, plain = None, None, None
-    if world == 1 and not args.no_split_math and args.conv_math == "f32":
+    if args.full and world == 1 and not args.no_split_math and args.conv_math == "f32":
         import dataclasses
 
         def first_step(e):
@@ -346,47 +391,22 @@ def main():
 
     # N > 1: the other scaling form of the same job, timed the same way, reported beside `value`
     side = None
-    if world > 1 and not args.no_side:
+    if args.full and world > 1 and not args.no_side:
         other = "weak" if scaling == "strong" else "strong"
         sc, stotal = job(other)
         del eng
         eng_s = build(sc)
         f_s, o_s = inputs(sc)
-        es, _, _ = timed(eng_s, f_s, o_s, sc, stotal, probe=False)
+        es, _, _, _ = timed(eng_s, f_s, o_s, sc, stotal, probe=False)
         side = {"scaling": other, "global_batch": stotal, "clips_per_gpu": sc, "value": round(stotal * args.steps / es, 2),
                 "unit": "clips/s", "ms_per_step": round(es / args.steps * 1e3, 3)}
         del eng_s
     if rank != 0:
         return
-
-    # ---- roofline of the dominant kernel symbol, from the live HIP-event brackets --------------------
-    per = {}
-    for label, ms in times:
-        per.setdefault(label, []).append(ms)
-    avg = {k: sum(v) / len(v) for k, v in per.items()}
-    # The fp32 backward runs its independent launches on two streams (engine._side_stream): a bracket around a launch that has a
-    # neighbour times both.  The dominant symbol is measured live, in the timed region, on the launches that run alone there (the
-    # forward ones: 3 of its 4 launches per step); the conv-stack table comes from the serial pass above.
-    dominant = tuple(l for l in DOMINANT if not overlapped or l.endswith(".fwd"))
-    dom_flop = sum(2.0 * CONV_MACS[l.split(".")[0]] * n for l in dominant) / len(dominant)      # per launch
-    dom_ms = sum(avg[l] for l in dominant) / len(dominant)                                       # per launch
-    achieved = dom_flop / (dom_ms * 1e-3) / 1e12
-    timed_avg = avg
-    if serial_times is not None:
-        per_s = {}
-        for label, ms in serial_times:
-            per_s.setdefault(label, []).append(ms)
-        avg = {k: sum(v) / len(v) for k, v in per_s.items()}
-    stack_flop = sum(2.0 * CONV_MACS[l.split(".")[0]] * n for l in avg)
-    stack_ms = sum(avg.values())
-    traffic_rec, traffic_src = committed_traffic(DOMINANT_SYMBOL)
-    alg_bytes = sum(4.0 * (DOMINANT_ELEMS_PER_FRAME[l] * n + DOMINANT_WEIGHT_ELEMS[l]) for l in dominant) / len(dominant)
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_clips * args.steps / elapsed
-    # --conv-math other than f32: the same launches run the split-product kernels; their bound is the bf16 matrix pipe at one
-    # MFMA per product (bf16x3: 3, bf16x6: 6), so the peak of an fp32-equivalent FLOP is the dense bf16 peak / products
-    f32_main = args.conv_math == "f32"
-    peak = PEAK_FP32_MFMA_TFLOPS if f32_main else PEAK_BF16_MFMA_TFLOPS / {"bf16x3": 3, "bf16x6": 6, "bf16": 1}[args.conv_math]
     rec = {
         "metric": "clips/sec (16-frame 227x227) LRCN train step" if args.fpc == 16 else
                   "clips/sec (%d-frame 227x227) LRCN train step" % args.fpc,
@@ -406,42 +426,71 @@ def main():
                    "dist_world_size": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
                    "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
                    "grad_exchange": None if gar is None else {"all_reduces_issued": gar.issued, "chunks_per_step": len(eng_chunks)}},
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4),
-                     "traffic": traffic_rec["bytes_per_launch"] if (traffic_rec and n == 1024 and f32_main) else None,
-                     "traffic_unit": "HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc passes)",
-                     "traffic_source": traffic_src if n == 1024 else None,
-                     "algorithmic_bytes_per_launch": alg_bytes if f32_main else None,
-                     "kernel": DOMINANT_SYMBOL if f32_main else
-                               ("conv_c8_kernel<4, 2, 2, 2> (packed-bf16 operands, csrc/conv_c8.hip)" if args.conv_math == "bf16" else
-                                "conv_ring4_kernel / conv_ring_kernel (%s)" % args.conv_math),
-                     "launches": list(dominant),
-                     "backward_overlap": None if not overlapped else
-                                         ("conv weight gradients (and fc6's input gradient) run on a second stream beside the input "
-                                          "gradients; forward launches run alone"
-                                          + ("; conv_stack below = the same steps with the second stream off (%d extra steps after "
-                                             "the timed region)" % args.steps if serial_times is not None else
-                                             "; conv_stack is not a serial sum")),
-                     "per_launch_ms_in_timed_region": {k: round(v, 3) for k, v in sorted(timed_avg.items())} if overlapped else None,
-                     "flop_per_launch": dom_flop, "ms_per_launch": round(dom_ms, 4),
-                     "conv_stack": {"tflops": round(stack_flop / (stack_ms * 1e-3) / 1e12, 2),
-                                    "frac": round(stack_flop / (stack_ms * 1e-3) / 1e12 / peak, 4),
-                                    "ms_per_step": round(stack_ms, 3),
-                                    "per_launch_ms": {k: round(v, 3) for k, v in sorted(avg.items())}},
-                     "flop_per_clip_train": train_flop,
-                     "step_frac_of_mfma_roofline": round(value / world * train_flop / 1e12 / peak, 4)},
-        "forward_only": None if fwd_ms is None else
-                        {"value": round(clips / (fwd_ms * 1e-3), 2), "unit": "clips/s per GPU", "ms_per_batch": round(fwd_ms, 3),
-                         "frac_of_mfma_roofline": round(clips / (fwd_ms * 1e-3) * fwd_flop / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
-        "oracle_check": oracle_check,
-        ("weak_scaling" if scaling == "strong" else "strong_scaling"): side,
-        "bf16x3": split,
-        "bf16x6": split6,
-        "bf16": plain,
-        "check": {"loss": round(out["loss"], 4), "grad_norm": round(out["grad_norm"], 3)},
     }
-    if world == 1 and not args.no_cpu_baseline:
-        rec["cpu_baseline"] = cpu_baseline(args.cpu_clips, args.fpc, args.classes)
+    if args.full:
+        # ---- roofline of the dominant kernel symbol, from the live HIP-event brackets --------------------
+        per = {}
+        for label, ms in times:
+            per.setdefault(label, []).append(ms)
+        avg = {k: sum(v) / len(v) for k, v in per.items()}
+        # The fp32 backward runs its independent launches on two streams (engine._side_stream): a bracket around a launch that has a
+        # neighbour times both.  The dominant symbol is measured live, in the timed region, on the launches that run alone there (the
+        # forward ones: 3 of its 4 launches per step); the conv-stack table comes from the serial pass above.
+        dominant = tuple(l for l in DOMINANT if not overlapped or l.endswith(".fwd"))
+        dom_flop = sum(2.0 * CONV_MACS[l.split(".")[0]] * n for l in dominant) / len(dominant)      # per launch
+        dom_ms = sum(avg[l] for l in dominant) / len(dominant)                                       # per launch
+        achieved = dom_flop / (dom_ms * 1e-3) / 1e12
+        timed_avg = avg
+        if serial_times is not None:
+            per_s = {}
+            for label, ms in serial_times:
+                per_s.setdefault(label, []).append(ms)
+            avg = {k: sum(v) / len(v) for k, v in per_s.items()}
+        stack_flop = sum(2.0 * CONV_MACS[l.split(".")[0]] * n for l in avg)
+        stack_ms = sum(avg.values())
+        traffic_rec, traffic_src = committed_traffic(DOMINANT_SYMBOL)
+        alg_bytes = sum(4.0 * (DOMINANT_ELEMS_PER_FRAME[l] * n + DOMINANT_WEIGHT_ELEMS[l]) for l in dominant) / len(dominant)
+        # --conv-math other than f32: the same launches run the split-product kernels; their bound is the bf16 matrix pipe at one
+        # MFMA per product (bf16x3: 3, bf16x6: 6), so the peak of an fp32-equivalent FLOP is the dense bf16 peak / products
+        f32_main = args.conv_math == "f32"
+        peak = PEAK_FP32_MFMA_TFLOPS if f32_main else PEAK_BF16_MFMA_TFLOPS / {"bf16x3": 3, "bf16x6": 6, "bf16": 1}[args.conv_math]
+        rec.update({
+            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                         "frac": round(achieved / peak, 4),
+                         "traffic": traffic_rec["bytes_per_launch"] if (traffic_rec and n == 1024 and f32_main) else None,
+                         "traffic_unit": "HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc passes)",
+                         "traffic_source": traffic_src if n == 1024 else None,
+                         "algorithmic_bytes_per_launch": alg_bytes if f32_main else None,
+                         "kernel": DOMINANT_SYMBOL if f32_main else
+                                   ("conv_c8_kernel<4, 2, 2, 2> (packed-bf16 operands, csrc/conv_c8.hip)" if args.conv_math == "bf16" else
+                                    "conv_ring4_kernel / conv_ring_kernel (%s)" % args.conv_math),
+                         "launches": list(dominant),
+                         "backward_overlap": None if not overlapped else
+                                             ("conv weight gradients (and fc6's input gradient) run on a second stream beside the input "
+                                              "gradients; forward launches run alone"
+                                              + ("; conv_stack below = the same steps with the second stream off (%d extra steps after "
+                                                 "the timed region)" % args.steps if serial_times is not None else
+                                                 "; conv_stack is not a serial sum")),
+                         "per_launch_ms_in_timed_region": {k: round(v, 3) for k, v in sorted(timed_avg.items())} if overlapped else None,
+                         "flop_per_launch": dom_flop, "ms_per_launch": round(dom_ms, 4),
+                         "conv_stack": {"tflops": round(stack_flop / (stack_ms * 1e-3) / 1e12, 2),
+                                        "frac": round(stack_flop / (stack_ms * 1e-3) / 1e12 / peak, 4),
+                                        "ms_per_step": round(stack_ms, 3),
+                                        "per_launch_ms": {k: round(v, 3) for k, v in sorted(avg.items())}},
+                         "flop_per_clip_train": train_flop,
+                         "step_frac_of_mfma_roofline": round(value / world * train_flop / 1e12 / peak, 4)},
+            "forward_only": None if fwd_ms is None else
+                            {"value": round(clips / (fwd_ms * 1e-3), 2), "unit": "clips/s per GPU", "ms_per_batch": round(fwd_ms, 3),
+                             "frac_of_mfma_roofline": round(clips / (fwd_ms * 1e-3) * fwd_flop / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
+            "oracle_check": oracle_check,
+            ("weak_scaling" if scaling == "strong" else "strong_scaling"): side,
+            "bf16x3": split,
+            "bf16x6": split6,
+            "bf16": plain,
+            "check": {"loss": round(out["loss"], 4), "grad_norm": round(out["grad_norm"], 3)},
+        })
+        if world == 1 and not args.no_cpu_baseline:
+            rec["cpu_baseline"] = cpu_baseline(args.cpu_clips, args.fpc, args.classes)
     print(json.dumps(rec))
 
 

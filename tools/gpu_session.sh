@@ -12,6 +12,7 @@ steps="${*:-tests bench c8 fpc32}"
 out="gpurun_out/$tag"
 mkdir -p "$out"
 export TMPDIR=/tmp
+root="$(pwd)"
 for s in $steps; do
   case "$s" in
     tests)
@@ -21,11 +22,11 @@ for s in $steps; do
       timeout -k 10 1000 python -m pytest tests -m gpu -q --durations=15 > "$out/pytest.log" 2>&1 || { tail -60 "$out/pytest.log"; }
       tail -3 "$out/pytest.log" ;;
     bench)
-      timeout -k 10 600 python bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err" || { tail -20 "$out/bench_n1.err"; exit 1; }
+      timeout -k 10 600 python bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err" || { tail -20 "$out/bench_n1.err"; exit 1; }
       tail -c 600 "$out/bench_n1.json"; echo ;;
     c8)
       for c in 8 16 32; do
-        timeout -k 10 300 python bench.py --clips-per-gpu $c --no-split-math --no-cpu-baseline --steps 20 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err" \
+        timeout -k 10 300 python bench.py --full --clips-per-gpu $c --no-split-math --no-cpu-baseline --steps 20 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err" \
           || { tail -20 "$out/bench_c$c.err"; exit 1; }
         python - "$out/bench_c$c.json" <<'PY'
 import json, sys
@@ -34,12 +35,12 @@ print("clips", r["config"]["clips_per_gpu"], "ms/step", r["ms_per_step"], "clips
 PY
       done
       cd /tmp
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$out/prof_c8" -o c8 -- python3 "$GRAFT_REPO_ROOT/bench.py" --clips-per-gpu 8 \
-          --no-split-math --no-cpu-baseline --steps 20 > "$GRAFT_REPO_ROOT/$out/prof_c8.json" 2> "$GRAFT_REPO_ROOT/$out/prof_c8.err" || { tail -20 "$GRAFT_REPO_ROOT/$out/prof_c8.err"; exit 1; }
-      cd "$GRAFT_REPO_ROOT"
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$root/$out/prof_c8" -o c8 -- python3 "$root/bench.py" --full --clips-per-gpu 8 \
+          --no-split-math --no-cpu-baseline --steps 20 > "$root/$out/prof_c8.json" 2> "$root/$out/prof_c8.err" || { tail -20 "$root/$out/prof_c8.err"; exit 1; }
+      cd "$root"
       python tools/summarize_profile.py "$out" "$out/c8" --prof prof_c8 || true ;;
     fpc32)
-      timeout -k 10 400 python bench.py --fpc 32 --no-split-math --no-cpu-baseline --steps 5 --warmup 2 > "$out/bench_fpc32.json" 2> "$out/bench_fpc32.err" \
+      timeout -k 10 400 python bench.py --full --fpc 32 --no-split-math --no-cpu-baseline --steps 5 --warmup 2 > "$out/bench_fpc32.json" 2> "$out/bench_fpc32.err" \
           || { tail -20 "$out/bench_fpc32.err"; exit 1; }
       tail -c 300 "$out/bench_fpc32.json"; echo ;;
     bf16probe)

@@ -5,9 +5,9 @@ set -eo pipefail
 out=gpurun_out/bf16
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py --conv-math bf16 --no-cpu-baseline --no-side > $out/bench_fpc16.json 2> $out/bench_fpc16.err
-python3 bench.py --conv-math bf16 --fpc 32 --no-cpu-baseline --no-side > $out/bench_fpc32.json 2> $out/bench_fpc32.err
-rocprofv3 --kernel-trace --stats -d $out/prof -o b16 -- python3 bench.py --conv-math bf16 --no-cpu-baseline --no-side --steps 8 --warmup 2 > /dev/null 2> $out/prof.err
+python3 bench.py --full --conv-math bf16 --no-cpu-baseline --no-side > $out/bench_fpc16.json 2> $out/bench_fpc16.err
+python3 bench.py --full --conv-math bf16 --fpc 32 --no-cpu-baseline --no-side > $out/bench_fpc32.json 2> $out/bench_fpc32.err
+rocprofv3 --kernel-trace --stats -d $out/prof -o b16 -- python3 bench.py --full --conv-math bf16 --no-cpu-baseline --no-side --steps 8 --warmup 2 > /dev/null 2> $out/prof.err
 python3 - <<'P' > $out/kernel_stats.csv
 import sqlite3,glob
 c=sqlite3.connect(sorted(glob.glob('gpurun_out/bf16/prof/*.db'))[-1])

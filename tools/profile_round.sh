@@ -12,19 +12,19 @@ tag="${1:-r01}"
 out="gpurun_out/$tag"
 mkdir -p "$out"
 export TMPDIR=/tmp
-python bench.py > "$out/bench_n1.json" 2> "$out/bench_n1.err"
+python bench.py --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"
 tail -c 400 "$out/bench_n1.json"; echo
-rocprofv3 --kernel-trace --stats -d "$out/prof" -o runc -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline \
+rocprofv3 --kernel-trace --stats -d "$out/prof" -o runc -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline \
     > "$out/prof_bench.json" 2> "$out/prof_bench.err"
 echo "kernel-trace pass done"
 for c in FETCH_SIZE WRITE_SIZE; do
   d="$out/pmc_$(echo $c | tr 'A-Z' 'a-z' | cut -d_ -f1)"
-  rocprofv3 --kernel-trace --pmc $c -d "$d" -o runc -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-split-math \
+  rocprofv3 --kernel-trace --pmc $c -d "$d" -o runc -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-split-math \
       > "$d.json" 2> "$d.err"
   echo "pmc pass $c done"
 done
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 \
-    bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench_torchrun1.json" 2> "$out/bench_torchrun1.err"
+    bench.py --gpus 1 --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench_torchrun1.json" 2> "$out/bench_torchrun1.err"
 tail -c 300 "$out/bench_torchrun1.json"; echo
 # 5. issue/stall counters of the dominant kernel alone (conv3 forward, the bench's frame count)
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES \

@@ -126,7 +126,7 @@ def main():
             cal_w = write.get("sgd_apply_kernel", (0, 0))[1] * 1024 / (GRAD_FLOATS * 4)
             rec = {"kernel": DOM, "read_bytes_per_launch": int(fk * 1024 * 2), "write_bytes_per_launch": int(wk * 1024),
                    "bytes_per_launch": int(fk * 1024 * 2 + wk * 1024), "launches_averaged": fetch[DOM][0],
-                   "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --steps 2 --warmup 1`; "
+                   "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --full --steps 2 --warmup 1`; "
                              "FETCH_SIZE x2 (gfx950: 128-B requests tallied at 64 B)",
                    "calibration": {"sumsq_stage1 corrected read / known": round(cal_r, 3),
                                    "sgd_apply write / known": round(cal_w, 3)}}
