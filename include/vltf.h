@@ -33,6 +33,17 @@ extern "C" {
 typedef void* vl_stream_t;                 /* hipStream_t */
 typedef struct vl_conv_desc vl_conv_desc;  /* opaque convolution descriptor */
 
+/* Device-resident scalars of one training step (a block in device memory, vl_step_state_bytes() bytes, caller allocated).  The
+ * _st entry points read them when they run instead of taking them as kernel arguments, so that a captured step (hipGraph) replays
+ * with the values of the current step: the host writes the block with vl_step_state_set on the stream before each replay. */
+typedef struct vl_step_state {
+    int64_t step;          /* the step count BEFORE the step's update: the dropout seed is (step << 20) ^ 0x5DEECE66D */
+    float lr;              /* learning rate */
+    uint32_t tag_origin;   /* origin of the LSTM exchange tags of vl_lstm_seq_*_st */
+    float adam_lr;         /* Adam's bias-corrected step size for count step + 1 (written by vl_step_state_set, see there) */
+    uint32_t reserved[3];
+} vl_step_state;
+
 const char* vl_last_error(void);
 int vl_version(void);
 /* Number of HIP devices visible; <0 on error.  Does not create a context. */
@@ -260,12 +271,29 @@ int vl_lstm_step_bwd(const float* dout, const float* dh_next, const float* act, 
  * the sticky time-out flag of vl_lstm_seq_status, which no launch clears; the rest holds the exchange words, whose tags are unique
  * per launch within the process (no launch zeroes them), so it must not be handed anything else to scribble on. */
 size_t vl_lstm_seq_ws_bytes(int batch, int T, int H);
+/* vl_lstm_seq_fwd / vl_lstm_seq_bwd take each launch's tag base from a process-wide host counter and pass it as a kernel argument: a
+ * captured launch would replay the same tags over the words its previous replay left behind and read stale values.  So both return
+ * an error, and launch nothing, when `stream` is being captured (hipStreamIsCapturing); a graph uses the _st variants below. */
 int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
                     float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes, vl_stream_t stream);
 /* BPTT over all steps: dout may be NULL; writes dz[r][4H]; c0 as given to the forward call (NULL = zero state);
  * dh0 / dc0 (nullable, [batch][H]) receive the gradients w.r.t. the initial output / cell state. */
 int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
                     float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, vl_stream_t stream);
+/* Replay-safe variants (capturable): the tag base of launch k of the call is state->tag_origin, read from device memory when the
+ * kernel runs, + tag_offset + k (T + 1).  A call uses the tags origin + tag_offset + 1 .. origin + tag_offset +
+ * vl_lstm_seq_tag_span(batch, T, H) - 1 (span 0: the per-clip form, no tags).  The caller owns the tag stream: `ws` must not be
+ * used by the eager variants, every replay needs an origin above the tags of the previous replays on `ws`, and before the origin
+ * starts over the exchange words are zeroed (vl_lstm_seq_ws_clear).  The eager variants' limit of the tag range is 0xfff00000. */
+size_t vl_lstm_seq_tag_span(int batch, int T, int H);
+int vl_lstm_seq_fwd_st(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
+                       float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes, const vl_step_state* state,
+                       uint32_t tag_offset, vl_stream_t stream);
+int vl_lstm_seq_bwd_st(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
+                       float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                       uint32_t tag_offset, vl_stream_t stream);
+/* Zeroes the exchange words of `ws` (not its time-out word), on the stream: lets the owner of a workspace restart its tags. */
+int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream);
 /* Synchronous read-and-reset of the time-out flag in `ws`: *timed_out = 1 if a workgroup of ANY cluster-form launch on `ws` since
  * the last call of this function gave up waiting for its peers (the cluster form needs all its workgroups resident at once: one
  * per CU; a launch that shares the device with another kernel holding CUs can starve).  Results are then invalid -- it never
@@ -313,6 +341,9 @@ int vl_fuse_n_grad(const float* const* ins, int n, const float* d, float* const*
  * Counter-based RNG keyed by (seed, element index); mask (uint8) is written for the backward. */
 int vl_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t count, float keep, uint64_t seed, vl_stream_t stream);
 int vl_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t count, float keep, vl_stream_t stream);
+/* vl_dropout_fwd with seed = (state->step << 20) ^ 0x5DEECE66D, read from the step state when the kernel runs. */
+int vl_dropout_fwd_st(const float* x, float* y, uint8_t* mask, int64_t count, float keep, const vl_step_state* state,
+                      vl_stream_t stream);
 
 /* ---- loss: mean_b softmax_cross_entropy_with_logits (train.py:120-123) + accuracy (142-149) ----
  * labels: int32 one/multi-hot [batch][classes] (the reference's labels placeholder, train.py:117).
@@ -341,6 +372,18 @@ int vl_adam_apply(float* w, const float* g, float* m, float* v, int64_t count, f
  * step without a host round trip (init != 0 for the step's first workspace; the workspace's own word stays set until
  * vl_lstm_seq_status reads it). */
 int vl_status_or(uint32_t* dst, const void* lstm_ws, int init, vl_stream_t stream);
+
+/* ---- step state (vl_step_state above) ---------------------------------------------------------------------------------------
+ * vl_step_state_set: one single-lane launch that writes step, lr and tag_origin, and adam_lr = lr sqrt(1 - 0.999^(step+1)) /
+ * (1 - 0.9^(step+1)) computed on the HOST by the same code as vl_adam_apply (device pow need not round like the host's: the
+ * replayed update must equal the eager one bit for bit).  step >= 0. */
+size_t vl_step_state_bytes(void);
+int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag_origin, vl_stream_t stream);
+/* vl_sgd_apply with lr = state->lr; vl_adam_apply with the step size state->adam_lr (= count state->step + 1). */
+int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
+                    float gscale, const uint32_t* skip, vl_stream_t stream);
+int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
+                     const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream);
 
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);

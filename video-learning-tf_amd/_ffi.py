@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLTF_HIP_LIB") or os.path.join(_HERE, "libvltf_hip.so")   # override: kernel experiments only
 
 p = C.c_void_p
-i32, i64, f32, u64, sz = C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
+i32, i64, f32, u32, u64, sz = C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_uint64, C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/vltf.h one to one
 SIGNATURES = {
@@ -64,6 +64,10 @@ SIGNATURES = {
     "vl_lstm_seq_ws_bytes": (sz, [i32, i32, i32]),
     "vl_lstm_seq_fwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, f32, p, sz, p]),
     "vl_lstm_seq_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p]),
+    "vl_lstm_seq_tag_span": (sz, [i32, i32, i32]),
+    "vl_lstm_seq_fwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, f32, p, sz, p, u32, p]),
+    "vl_lstm_seq_bwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p, u32, p]),
+    "vl_lstm_seq_ws_clear": (i32, [p, sz, p]),
     "vl_lstm_seq_status": (i32, [p, C.POINTER(i32)]),
     "vl_lstm_seq_test_hooks": (i32, [C.c_uint, i32]),
     "vl_transpose": (i32, [p, i64, p, i32, i32, p]),
@@ -71,11 +75,16 @@ SIGNATURES = {
     "vl_temporal_fusion_bwd": (i32, [p, p, i32, i32, i32, i32, p]),
     "vl_dropout_fwd": (i32, [p, p, p, i64, f32, u64, p]),
     "vl_dropout_bwd": (i32, [p, p, p, i64, f32, p]),
+    "vl_dropout_fwd_st": (i32, [p, p, p, i64, f32, p, p]),
     "vl_softmax_xent": (i32, [p, p, p, p, p, i32, i32, f32, p]),
     "vl_sumsq": (i32, [p, i64, p, p, i32, p]),
     "vl_sgd_apply": (i32, [p, p, i64, f32, f32, p, f32, p, p]),
     "vl_adam_apply": (i32, [p, p, p, p, i64, f32, f32, p, f32, i32, p, p]),
     "vl_status_or": (i32, [p, p, i32, p]),
+    "vl_step_state_bytes": (sz, []),
+    "vl_step_state_set": (i32, [p, i64, f32, u32, p]),
+    "vl_sgd_apply_st": (i32, [p, p, i64, p, f32, p, f32, p, p]),
+    "vl_adam_apply_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),

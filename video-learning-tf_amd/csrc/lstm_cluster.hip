@@ -112,13 +112,16 @@ struct LstmClusterArgs {
     float forget_bias;
     unsigned spin_limit;
     int mute;             // test hook: this workgroup (blockIdx.x) publishes nothing; -1 = none
-    unsigned ebase;       // tag of epoch e = ebase + e (unique per launch)
+    unsigned ebase;       // tag of epoch e = ebase + e (unique per launch); + state->tag_origin in the replay-safe (ST) kernels
+    const vl_step_state* state;   // ST kernels: the tag origin, read when the kernel runs (vl_lstm_seq_fwd_st / _bwd_st)
 };
 
 // ---- forward ------------------------------------------------------------------------------------------------------------
+template <bool ST>
 __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmClusterArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int H = p.H, Hp = p.Hp, H4 = 4 * p.H, T = p.T;
+    const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
     float* Ks = sm;                   // [Hp][LC]  (rows H .. Hp - 1: zeros)
     float* hb = Ks + (size_t)Hp * LC; // [CPG][Hp]   h_{t-1} of the group's clips
     float* zb = hb + CPG * Hp;        // [KP][2 S][LC] recurrent part of the own columns' pre-activations per reduction slice (KP * 2 S = 8 rows)
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
                 constexpr int N = decltype(tag)::value;
                 float v[N];
                 gather_granules<N>(src, myn, [&](int m) { const int i = tid + LNT * m; const int c = i / H; return c * Hp + (i - c * H); },
-                                   p.ebase + (unsigned)t, v, p.status, p.spin_limit);
+                                   ebase + (unsigned)t, v, p.status, p.spin_limit);
 #pragma unroll
                 for (int m = 0; m < N; ++m)
                     if (m < myn) {
@@ -227,7 +230,7 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
             const float gi = sigm(zi), gj = tanhf(zj), gf = sigm(zf + p.forget_bias), go = sigm(zo);
             cst = cst * gf + gi * gj;
             const float h = tanhf(cst) * go;
-            if (t + 1 < T && (int)blockIdx.x != p.mute) store_granule(xg + (t & 1) * xpar + gc * Hp + gu, p.ebase + (unsigned)(t + 1), h);
+            if (t + 1 < T && (int)blockIdx.x != p.mute) store_granule(xg + (t & 1) * xpar + gc * Hp + gu, ebase + (unsigned)(t + 1), h);
             float* a = p.act + r * H4 + gu;
             a[0] = gi; a[H] = gj; a[2 * H] = gf; a[3 * H] = go;
             p.cseq[r * H + gu] = cst;
@@ -278,9 +281,11 @@ __device__ __forceinline__ void publish_partials(const float* KsT, const float* 
     }
 }
 
+template <bool ST>
 __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmClusterArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int H = p.H, Hp = p.Hp, H4 = 4 * p.H, T = p.T, W = p.W;
+    const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
     float* KsT = sm;                      // [LC][Hp]  KsT[j][k] = kh[k][column j of this workgroup]
     float* zl = KsT + (size_t)LC * Hp;    // [CPG][LC] dz_t of the own columns
     const int tid = threadIdx.x;
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
         auto run = [&](auto tag) {
             constexpr int N = decltype(tag)::value;
             float v[N];
-            gather_granules<N>(src, glive ? W : 0, [&](int m) { return (size_t)m * wstride; }, p.ebase + epoch, v, p.status, p.spin_limit);
+            gather_granules<N>(src, glive ? W : 0, [&](int m) { return (size_t)m * wstride; }, ebase + epoch, v, p.status, p.spin_limit);
             float s = 0.f;
 #pragma unroll
             for (int m = 0; m < N; ++m)
@@ -346,10 +351,10 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
         __syncthreads();                                        // own dz_t in LDS
         if ((t > 0 || p.dh0) && (int)blockIdx.x != p.mute) {
             u64* dst = pg + (epoch & 1) * ppar + (size_t)w * CPG * Hp;
-            if (nclips > 4) publish_partials<8>(KsT, zl, dst, H, Hp, nclips, p.ebase + epoch, tid);
-            else if (nclips > 2) publish_partials<4>(KsT, zl, dst, H, Hp, nclips, p.ebase + epoch, tid);
-            else if (nclips > 1) publish_partials<2>(KsT, zl, dst, H, Hp, nclips, p.ebase + epoch, tid);
-            else publish_partials<1>(KsT, zl, dst, H, Hp, nclips, p.ebase + epoch, tid);
+            if (nclips > 4) publish_partials<8>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else if (nclips > 2) publish_partials<4>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else if (nclips > 1) publish_partials<2>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else publish_partials<1>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
         }
         __syncthreads();                                        // zl consumed before the next step rewrites it
     }
@@ -397,8 +402,10 @@ size_t vl_lstm_cluster_ws_bytes(int H) {
     return STATUS_BYTES + sizeof(u64) * (c.xch_fwd > c.xch_bwd ? c.xch_fwd : c.xch_bwd);
 }
 
-// Runs one direction over all clips, in chunks of at most maxG * 8 clips (one launch each).
-int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t ws_bytes, hipStream_t s) {
+// Runs one direction over all clips, in chunks of at most maxG * 8 clips (one launch each).  st == nullptr: tag bases from the
+// process-wide counter; else the replay-safe kernels, launch k with base tag_offset + k (T + 1) over st->tag_origin.
+static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t ws_bytes, const vl_step_state* st,
+                               unsigned tag_offset, hipStream_t s) {
     const ClusterPlan c = cluster_plan(a.H);
     VL_CHECK(ws && ws_bytes >= vl_lstm_cluster_ws_bytes(a.H), "vl_lstm_seq: workspace too small (%zu < %zu bytes)", ws_bytes,
              vl_lstm_cluster_ws_bytes(a.H));
@@ -406,18 +413,21 @@ int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t
     a.Hp = c.Hp;
     a.status = (unsigned*)ws;
     a.xch = (u64*)((char*)ws + STATUS_BYTES);
+    a.state = st;
     const size_t lds = bwd ? sizeof(float) * ((size_t)LC * c.Hp + CPG * LC) : sizeof(float) * ((size_t)c.Hp * LC + CPG * c.Hp + CPG * LC);   // zb: KP * clips <= 8 rows
-    static bool attr_set[2] = {false, false};
-    const void* kern = bwd ? reinterpret_cast<const void*>(lstm_cluster_bwd_kernel) : reinterpret_cast<const void*>(lstm_cluster_fwd_kernel);
-    if (!attr_set[bwd]) {
-        VL_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set[bwd] = true;
+    // all four kernels at the first call of any: a graph's first (captured) call of the replay-safe ones then sets nothing
+    static bool attr_set = false;
+    if (!attr_set) {
+        const void* kerns[4] = {reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<false>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<false>),
+                                reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<true>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<true>)};
+        for (const void* k : kerns) VL_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr_set = true;
     }
     a.spin_limit = g_spin_limit;
     a.mute = g_mute_workgroup;
     const float *gx = a.gx, *h0 = a.h0, *c0 = a.c0, *dout = a.dout;
     float *act = a.act, *cseq = a.cseq, *hseq = a.hseq, *hprev = a.hprev, *dz = a.dz, *dh0 = a.dh0, *dc0 = a.dc0;
-    for (int b0 = 0; b0 < batch; b0 += c.chunk) {
+    for (int b0 = 0, k = 0; b0 < batch; b0 += c.chunk, ++k) {
         const int nb = batch - b0 < c.chunk ? batch - b0 : c.chunk;
         int G = nb < c.maxG ? nb : c.maxG;
         const int cpg = (nb + G - 1) / G;
@@ -436,6 +446,14 @@ int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t
         a.dh0 = dh0 ? dh0 + so : nullptr;
         a.dc0 = dc0 ? dc0 + so : nullptr;
         a.xch = (u64*)((char*)ws + STATUS_BYTES);                 // the kernels index parity blocks by their own G: [parity][G][...]
+        if (st) {
+            // replay-safe: the base over the origin the host writes before every replay (vl_lstm_seq_tag_span counts these launches)
+            a.ebase = tag_offset + (unsigned)k * ((unsigned)a.T + 1u);
+            if (bwd) hipLaunchKernelGGL(lstm_cluster_bwd_kernel<true>, dim3(G * c.W), dim3(LNT), lds, s, a);
+            else hipLaunchKernelGGL(lstm_cluster_fwd_kernel<true>, dim3(G * c.W), dim3(LNT), lds, s, a);
+            VL_LAUNCH_CHECK();
+            continue;
+        }
         // this launch's tags: base + 1 .. base + T, never used before in this process (any workspace, either direction)
         a.ebase = __atomic_fetch_add(&g_epoch_base, (unsigned)a.T + 1u, __ATOMIC_RELAXED);
         if (a.ebase > 0xfff00000u) {                             // (after ~10^8 launches) start over behind a memset of the whole exchange
@@ -443,8 +461,8 @@ int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t
             __atomic_store_n(&g_epoch_base, (unsigned)a.T + 1u, __ATOMIC_RELAXED);
             a.ebase = 0;
         }
-        if (bwd) hipLaunchKernelGGL(lstm_cluster_bwd_kernel, dim3(G * c.W), dim3(LNT), lds, s, a);
-        else hipLaunchKernelGGL(lstm_cluster_fwd_kernel, dim3(G * c.W), dim3(LNT), lds, s, a);
+        if (bwd) hipLaunchKernelGGL(lstm_cluster_bwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
+        else hipLaunchKernelGGL(lstm_cluster_fwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
         VL_LAUNCH_CHECK();
     }
     return 0;
@@ -460,9 +478,17 @@ extern "C" size_t vl_lstm_seq_ws_bytes(int batch, int T, int H) {
     return a > b ? a : b;
 }
 
-extern "C" int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq,
-                               float* hseq, float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes,
-                               vl_stream_t stream) {
+// The eager entry points bake their tag bases into the launch: refused on a stream that is being captured (vltf.h)
+static int refuse_capture(hipStream_t s, const char* what) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    VL_HIP(hipStreamIsCapturing(s, &cs));
+    VL_CHECK(cs == hipStreamCaptureStatusNone, "%s: the stream is being captured; its tags would be replayed stale -- use %s_st", what, what);
+    return 0;
+}
+
+static int lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
+                        float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes, const vl_step_state* st,
+                        unsigned tag_offset, hipStream_t stream) {
     VL_CHECK(gx && kh && act && cseq && hseq && hprev, "vl_lstm_seq_fwd: null argument");
     VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= 1024, "vl_lstm_seq_fwd: bad shape (hidden size must be <= 1024)");
     VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "vl_lstm_seq_fwd: workspace smaller than vl_lstm_seq_ws_bytes");
@@ -470,13 +496,14 @@ extern "C" int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0
         LstmClusterArgs a = {};
         a.gx = gx; a.kh = kh; a.h0 = h0; a.c0 = c0; a.act = act; a.cseq = cseq; a.hseq = hseq; a.hprev = hprev;
         a.T = T; a.H = H; a.forget_bias = forget_bias;
-        return vl_lstm_cluster_run(false, a, batch, ws, ws_bytes, (hipStream_t)stream);
+        return vl_lstm_cluster_run(false, a, batch, ws, ws_bytes, st, tag_offset, stream);
     }
-    return vl_lstm_perclip_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, (hipStream_t)stream);
+    return vl_lstm_perclip_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, stream);
 }
 
-extern "C" int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
-                               float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, vl_stream_t stream) {
+static int lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz, float* dh0,
+                        float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* st, unsigned tag_offset,
+                        hipStream_t stream) {
     VL_CHECK(kh && act && cseq && dz, "vl_lstm_seq_bwd: null argument");
     VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= 1024, "vl_lstm_seq_bwd: bad shape (hidden size must be <= 1024)");
     VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "vl_lstm_seq_bwd: workspace smaller than vl_lstm_seq_ws_bytes");
@@ -484,11 +511,51 @@ extern "C" int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* 
         LstmClusterArgs a = {};
         a.kh = kh; a.c0 = c0; a.act = const_cast<float*>(act); a.cseq = const_cast<float*>(cseq); a.dout = dout; a.dz = dz;
         a.dh0 = dh0; a.dc0 = dc0; a.T = T; a.H = H;
-        return vl_lstm_cluster_run(true, a, batch, ws, ws_bytes, (hipStream_t)stream);
+        return vl_lstm_cluster_run(true, a, batch, ws, ws_bytes, st, tag_offset, stream);
     }
     float* kh_t = (float*)((char*)ws + STATUS_BYTES);
     if (vl_transpose(kh, (int64_t)4 * H, kh_t, H, 4 * H, stream)) return 1;
-    return vl_lstm_perclip_bwd(dout, kh_t, act, cseq, c0, dz, dh0, dc0, batch, T, H, (hipStream_t)stream);
+    return vl_lstm_perclip_bwd(dout, kh_t, act, cseq, c0, dz, dh0, dc0, batch, T, H, stream);
+}
+
+extern "C" int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq,
+                               float* hseq, float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes,
+                               vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_fwd")) return 1;
+    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
+                               float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_bwd")) return 1;
+    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" size_t vl_lstm_seq_tag_span(int batch, int T, int H) {
+    if (batch < 1 || T < 1 || !vl_lstm_cluster_ok(H) || kPerClip) return 0;
+    const ClusterPlan c = cluster_plan(H);
+    return (size_t)((batch + c.chunk - 1) / c.chunk) * ((size_t)T + 1);
+}
+
+extern "C" int vl_lstm_seq_fwd_st(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq,
+                                  float* hseq, float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes,
+                                  const vl_step_state* state, uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_lstm_seq_fwd_st: null state");
+    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, ws, ws_bytes, state, tag_offset,
+                        (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_bwd_st(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
+                                  float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                                  uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_lstm_seq_bwd_st: null state");
+    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, ws, ws_bytes, state, tag_offset, (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream) {
+    VL_CHECK(ws && ws_bytes > STATUS_BYTES, "vl_lstm_seq_ws_clear: bad workspace");
+    VL_HIP(hipMemsetAsync((char*)ws + STATUS_BYTES, 0, ws_bytes - STATUS_BYTES, (hipStream_t)stream));
+    return 0;
 }
 
 extern "C" int vl_lstm_seq_status(void* ws, int* timed_out) {

@@ -1613,15 +1613,22 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
-__global__ void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, int64_t count,
-                                   float keep, uint64_t seed) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
+// one body for the eager kernel and the step-state one (vl_dropout_fwd_st): only where the seed comes from differs
+// (the grid-stride start and step come from the kernel: blockDim read there, where the compiler knows the work-group size is uniform)
+__device__ __forceinline__ void dropout_fwd_body(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, int64_t count,
+                                                 float keep, uint64_t seed, int64_t e0, int64_t step) {
+    for (int64_t e = e0; e < count; e += step) {
         const uint64_t h = splitmix64(seed ^ splitmix64((uint64_t)e));
         const float uni = (float)(h >> 40) * (1.0f / 16777216.0f);
         const uint8_t m = uni < keep ? 1 : 0;
         mask[e] = m;
         y[e] = m ? x[e] / keep : 0.f;
     }
+}
+
+__global__ void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, int64_t count,
+                                   float keep, uint64_t seed) {
+    dropout_fwd_body(x, y, mask, count, keep, seed, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void dropout_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ mask, float* __restrict__ dx,
@@ -1635,6 +1642,22 @@ extern "C" int vl_dropout_fwd(const float* x, float* y, uint8_t* mask, int64_t c
     VL_CHECK(x && y && mask && count > 0 && keep > 0.f && keep <= 1.f, "vl_dropout_fwd: bad argument");
     hipLaunchKernelGGL(dropout_fwd_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, x, y, mask, count,
                        keep, seed);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// the seed of vl_dropout_fwd as the engine forms it from its step count, read from the step state (a replayed step's own count)
+__global__ void dropout_fwd_st_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, int64_t count,
+                                      float keep, const vl_step_state* __restrict__ st) {
+    dropout_fwd_body(x, y, mask, count, keep, ((uint64_t)st->step << 20) ^ 0x5DEECE66Dull, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                     (int64_t)gridDim.x * blockDim.x);
+}
+
+extern "C" int vl_dropout_fwd_st(const float* x, float* y, uint8_t* mask, int64_t count, float keep, const vl_step_state* state,
+                                 vl_stream_t stream) {
+    VL_CHECK(x && y && mask && state && count > 0 && keep > 0.f && keep <= 1.f, "vl_dropout_fwd_st: bad argument");
+    hipLaunchKernelGGL(dropout_fwd_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, x, y, mask, count,
+                       keep, state);
     VL_LAUNCH_CHECK();
     return 0;
 }
@@ -1815,20 +1838,21 @@ __device__ __forceinline__ float clip_scale(float clip_norm, const float* sumsq,
     return gscale * clip_norm / fmaxf(norm, clip_norm);
 }
 
-__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t count, float lr, float clip_norm,
-                                 const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;                                        // the step's results are invalid (vl_status_or): no update
+// the update bodies, shared by the eager kernels and the step-state ones (vl_sgd_apply_st / vl_adam_apply_st): only where lr / the
+// Adam step size comes from differs, so a replayed update and the eager one get the same bits
+// (grid-stride start and step from the kernel, as dropout_fwd_body)
+__device__ __forceinline__ void sgd_apply_body(float* __restrict__ w, const float* __restrict__ g, int64_t count, float lr, float clip_norm,
+                                               const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
     const float a = lr * clip_scale(clip_norm, sumsq, gscale);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
+    for (int64_t i = i0; i < count; i += step)
         w[i] -= a * g[i];
 }
 
-__global__ void adam_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                  int64_t count, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
-                                  const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
+__device__ __forceinline__ void adam_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                int64_t count, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                                int64_t i0, int64_t step) {
     const float sc = clip_scale(clip_norm, sumsq, gscale);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = i0; i < count; i += step) {
         const float gi = g[i] * sc;
         const float mi = 0.9f * m[i] + 0.1f * gi;
         const float vi = 0.999f * v[i] + 0.001f * gi * gi;
@@ -1836,6 +1860,19 @@ __global__ void adam_apply_kernel(float* __restrict__ w, const float* __restrict
         v[i] = vi;
         w[i] -= lr_t * mi / (sqrtf(vi) + 1e-8f);
     }
+}
+
+__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t count, float lr, float clip_norm,
+                                 const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;                                        // the step's results are invalid (vl_status_or): no update
+    sgd_apply_body(w, g, count, lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void adam_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                  int64_t count, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                  const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    adam_apply_body(w, g, m, v, count, lr_t, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // *dst |= first word of an LSTM cluster workspace (its sticky time-out word, lstm_cluster.hip): the optimizer's `skip` word of a step
@@ -1859,13 +1896,72 @@ extern "C" int vl_sgd_apply(float* w, const float* g, int64_t count, float lr, f
     return 0;
 }
 
+// Adam's bias-corrected step size at count `step` (TF: lr * sqrt(1 - beta2^t) / (1 - beta1^t)); host code, shared by vl_adam_apply and
+// vl_step_state_set so that a replayed update and the eager one get the same bits
+static float adam_step_size(float lr, int step) {
+    const double b1t = 1.0 - pow(0.9, (double)step), b2t = 1.0 - pow(0.999, (double)step);
+    return (float)(lr * sqrt(b2t) / b1t);
+}
+
 extern "C" int vl_adam_apply(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
                              const float* sumsq, float gscale, int step, const uint32_t* skip, vl_stream_t stream) {
     VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply: bad argument");
-    const double b1t = 1.0 - pow(0.9, (double)step), b2t = 1.0 - pow(0.999, (double)step);
-    const float lr_t = (float)(lr * sqrt(b2t) / b1t);
+    const float lr_t = adam_step_size(lr, step);
     hipLaunchKernelGGL(adam_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, count,
                        lr_t, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- step state (vltf.h: vl_step_state): the scalars a replayed step reads from device memory -------------------------------
+static_assert(sizeof(vl_step_state) == 32, "vl_step_state layout");
+
+__global__ void step_state_set_kernel(vl_step_state* __restrict__ st, int64_t step, float lr, uint32_t tag_origin, float adam_lr) {
+    st->step = step;
+    st->lr = lr;
+    st->tag_origin = tag_origin;
+    st->adam_lr = adam_lr;
+}
+
+extern "C" size_t vl_step_state_bytes(void) { return sizeof(vl_step_state); }
+
+extern "C" int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag_origin, vl_stream_t stream) {
+    VL_CHECK(state && step >= 0 && step < INT32_MAX, "vl_step_state_set: bad argument");
+    hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, step, lr, tag_origin,
+                       adam_step_size(lr, (int)step + 1));
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// the update kernels above with lr / Adam's step size read from the step state
+__global__ void sgd_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t count, const vl_step_state* __restrict__ st,
+                                    float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    sgd_apply_body(w, g, count, st->lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void adam_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                     int64_t count, const vl_step_state* __restrict__ st, float clip_norm, const float* __restrict__ sumsq,
+                                     float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    adam_apply_body(w, g, m, v, count, st->adam_lr, clip_norm, sumsq, gscale,
+                    (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+extern "C" int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
+                               float gscale, const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_st: bad argument");
+    hipLaunchKernelGGL(sgd_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, count, state,
+                       clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
+                                const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_st: bad argument");
+    hipLaunchKernelGGL(adam_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, count,
+                       state, clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
 }

@@ -18,6 +18,7 @@ from typing import Optional, Tuple
 
 import contextlib
 import os
+import time
 
 import numpy as np
 import torch
@@ -53,6 +54,7 @@ class NetConfig:
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
     conv_math: str = "f32"                      # "f32" | "bf16x3" | "bf16x6" | "bf16" (ops.set_conv_math: opt-in bf16-MFMA conv products)
+    step_graph: bool = False                    # train_step_u8 / forward_u8 captured once per input key and replayed (LRCNEngine docstring)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -130,13 +132,25 @@ def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
 
 
 class LRCNEngine:
+    """NetConfig.step_graph: train_step_u8 and forward_u8 run the first call of each input key (kind, frame count, raw frame shape,
+    resize chain, crop / mirror / mean given, clip_norm, loss scale, dropout) eagerly, capture the second as a hipGraph
+    (torch.cuda.graph, thread-local capture mode: the feeder uploads from its own thread meanwhile) and replay it from then on.  A
+    graph reads its inputs from static device buffers and its per-step scalars (lr, the step count behind Adam's bias correction
+    and the dropout seed, the origin of its LSTM exchange tags) from a device block (vl_step_state): before each replay the host
+    copies the caller's tensors into the buffers, writes the block (ops.step_state_set) and replays.  Its LSTM launches run on a
+    workspace of their own (lstm_ws_graph) whose tag stream the engine keeps: graph_tag_next, advanced by the graph's span per
+    replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe."""
     FC6_CHUNKS = 4          # row blocks of the fc6 weight gradient = all-reduce chunks of the data-parallel exchange
+    GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
     def __init__(self, cfg: NetConfig, max_clips: int, device="cuda:0", training=True, dp=None, flat=None):
         """flat: optional (w, g) slices of a larger flat parameter / gradient buffer to live in (vltf_amd.composed: several
         pipelines share one buffer so that the global-norm clip and the update run over all of them at once)."""
         if not torch.cuda.is_available():
             raise VltfError("LRCNEngine needs a HIP device; there is no CPU fallback")
+        if cfg.step_graph and dp is not None:
+            raise VltfError("step_graph is refused with data parallelism: capturing the gradient exchange's collectives is unmeasured "
+                            "on this stack")
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
         self.dev = torch.device(device)
@@ -361,11 +375,24 @@ class LRCNEngine:
         self.probe, self.probe_events = None, []
         self._resizers = {}
         self.mean_dev = torch.zeros(3, device=dev)
+        # ---- captured steps (cfg.step_graph, class docstring)
+        self.step_graph = cfg.step_graph
+        self.lstm_ws_graph = None
+        self._tag_off = None                  # while a step is being captured: the tag offset of its next LSTM launch
+        if self.step_graph:
+            self.state = ops.step_state(dev)
+            if getattr(self, "lstm_ws", None) is not None:
+                self.lstm_ws_graph = ops.lstm_seq_ws(B, T, H, dev)     # zeroed; never handed to an eager launch
+            self.graph_tag_next = 1
+            self._graphs, self._graph_warm = {}, set()
+            self.graph_capture_ms = []
 
     # ---- live kernel timing (bench.py roofline): HIP events around labelled launches -------------
     def set_probe(self, labels):
         """labels: iterable of '<layer>.<fwd|dgrad|wgrad>' whose launches get bracketed by events
         recorded on the launch stream.  None disables."""
+        if labels and self.step_graph:
+            raise VltfError("step_graph is refused with a per-launch timing probe: a replayed graph has no launches to bracket")
         self.probe = set(labels) if labels else None
         self.probe_events = []
 
@@ -444,7 +471,7 @@ class LRCNEngine:
         """Raises when a cluster-form LSTM launch since the last check timed out (ops.lstm_seq_check: the flag is sticky over the
         launches of a step and reset here).  Synchronises; called wherever results are fetched to the host."""
         if getattr(self, "lstm_ws", None) is not None:
-            ops.lstm_seq_check(self.lstm_ws)
+            ops.lstm_seq_check(self.lstm_ws, self.lstm_ws_graph)
 
     def logits_host(self, rows=None):
         torch.cuda.synchronize(self.dev)
@@ -471,6 +498,10 @@ class LRCNEngine:
         if mean_bgr is not None:
             self.mean_dev.copy_(torch.as_tensor(np.asarray(mean_bgr, np.float32)), non_blocking=True)
             mean = self.mean_dev
+        return self._feed_dev(frames_u8, n, b, mean, crop_y, crop_x, mirror)
+
+    def _feed_dev(self, frames_u8, n, b, mean, crop_y, crop_x, mirror):
+        """feed_u8 from here on, every input on the device (what a captured step runs)."""
         if self.c8:     # bf16 path: the frames go straight into conv1's packed (space-to-depth) input; x0 is not written
             self.layers[0]["conv"].input_prep_u8_s2d(frames_u8, self.layers[0]["xb"][:n], crop_y, crop_x, mirror, mean)
             self._xb_fed = True
@@ -564,7 +595,11 @@ class LRCNEngine:
                     ops.gemm_kc8(a, w, S["gx"], n, 4 * H, d, bias=P[pre + "bias"], ws=self.ws)
                 else:
                     ops.gemm(xin, K, S["gx"], n, 4 * H, d, bias=P[pre + "bias"], ws=self.ws)
-                if H <= 1024:
+                if H <= 1024 and self._tag_off is not None:           # captured: replay-safe tags on the graph workspace
+                    ops.lstm_seq_fwd_st(S["gx"], K[d:], S["act"], S["cseq"], S["hseq"], S["hprev"], b, T, H, FORGET_BIAS,
+                                        ws=self.lstm_ws_graph, state=self.state, tag_offset=self._tag_off)
+                    self._tag_off += ops.lstm_seq_tag_span(b, T, H)
+                elif H <= 1024:
                     ops.lstm_seq_fwd(S["gx"], K[d:], S["act"], S["cseq"], S["hseq"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws)
                 else:
                     for t in range(T):
@@ -580,7 +615,10 @@ class LRCNEngine:
                 ops.temporal_fusion_fwd(xin, self.fused, b, T, H, self.lstm_fusion)
                 v = self.fused
             self._dropout = train and cfg.dropout_keep_prob > 0 and cfg.fusion != "state"
-            if self._dropout:
+            if self._dropout and self._tag_off is not None:          # captured: the seed follows the step state's count
+                ops.dropout_fwd_st(v[:r], self.dropped[:r], self.drop_mask[:r], cfg.dropout_keep_prob, self.state)
+                v = self.dropped
+            elif self._dropout:
                 ops.dropout_fwd(v[:r], self.dropped[:r], self.drop_mask[:r], cfg.dropout_keep_prob,
                                 (self.step_count << 20) ^ 0x5DEECE66D)
                 v = self.dropped
@@ -606,6 +644,10 @@ class LRCNEngine:
 
     def forward_u8(self, frames_u8, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None):
         """sess.run(model.logits, fdict) (run_task.py:95).  Returns a device view [rows, classes]."""
+        if self.step_graph:
+            done, out = self._graph_step(False, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
+            if done:
+                return out
         n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
         rows = self._forward(n, b, train=False)
         return self.logits[:rows]
@@ -670,7 +712,11 @@ class LRCNEngine:
                 K = P[pre + "kernel"]
                 din = D if l == 0 else H
                 xin = self.feat if l == 0 else self.lstm[l - 1]["hseq"]
-                if H <= 1024:
+                if H <= 1024 and self._tag_off is not None:
+                    ops.lstm_seq_bwd_st(S["dout"], K[din:], S["act"], S["cseq"], S["dz"], b, T, H, ws=self.lstm_ws_graph, state=self.state,
+                                        tag_offset=self._tag_off)
+                    self._tag_off += ops.lstm_seq_tag_span(b, T, H)
+                elif H <= 1024:
                     ops.lstm_seq_bwd(S["dout"], K[din:], S["act"], S["cseq"], S["dz"], b, T, H, ws=self.lstm_ws)
                 else:
                     ops.fill(self.dc, 0.0)
@@ -937,11 +983,19 @@ class LRCNEngine:
         self.step_count += 1
         # a step whose LSTM cluster launch timed out must not reach the weights -- also with fetch=False, where the host reads the
         # status only later: the optimizer launch drops the update on the device (ops.step_guard), check_status raises at the next fetch
-        skip = ops.step_guard(self._skip, getattr(self, "lstm_ws", None))
-        if self.cfg.optimizer == "adam":
+        skip = ops.step_guard(self._skip, getattr(self, "lstm_ws", None), self.lstm_ws_graph)
+        if self._tag_off is not None:             # captured: lr and Adam's step size from the step state (written before each replay)
+            if self.cfg.optimizer == "adam":
+                ops.adam_apply_st(self.w, self.g, self.adam_m, self.adam_v, self.state, clip_norm, self.ss, 1.0, skip=skip)
+            else:
+                ops.sgd_apply_st(self.w, self.g, self.state, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.cfg.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
+        return self._fetch(rows, fetch)
+
+    def _fetch(self, rows, fetch):
         if not fetch:
             return None
         torch.cuda.synchronize(self.dev)
@@ -958,9 +1012,94 @@ class LRCNEngine:
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
                       fetch=True, global_rows=None, resize=None):
         """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44)."""
+        if self.step_graph:
+            done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
+                                         global_rows)
+            if done:
+                return out
         n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
         return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows)
 
     def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True):
         n, b = self.feed_f32_nhwc(frames_nhwc)
         return self._train(n, b, onehot, lr, clip_norm, fetch)
+
+    # ---- captured steps (NetConfig.step_graph, class docstring) ---------------------------------------------------------------
+    def _graph_step(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot=None, lr=0.0, clip_norm=0.0, fetch=True,
+                    global_rows=None):
+        """(True, the call's result) when the call was replayed; (False, None) when it runs eagerly (the first call of its key)."""
+        rz = tuple((tuple(int(v) for v in s_), tuple(int(v) for v in d_)) for s_, d_ in (resize or ()))
+        key = ("train" if train else "forward", int(frames_u8.shape[0]), tuple(frames_u8.shape[1:]), rz, crop_y is not None,
+               crop_x is not None, mirror is not None, mean_bgr is not None, float(clip_norm) if train else None,
+               global_rows if train else None, self.cfg.dropout_keep_prob if train else None)
+        g = self._graphs.get(key)
+        if g is None:
+            if key not in self._graph_warm:   # warm-up: one-time set-up (function attributes, tables, resizers, side-stream buffers)
+                self._graph_warm.add(key)
+                return False, None
+            g = self._graphs[key] = self._capture(train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm,
+                                                  global_rows)
+        for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x), ("mirror", mirror), ("onehot", onehot)):
+            dst = g["inputs"].get(name)
+            if dst is None:
+                continue
+            if t.dtype != dst.dtype or tuple(t.shape) != tuple(dst.shape) or t.device != dst.device:
+                raise VltfError("%s: %s %s on %s, the captured step reads %s %s" % (name, t.dtype, tuple(t.shape), t.device, dst.dtype,
+                                                                                  tuple(dst.shape)))
+            dst.copy_(t)
+        if mean_bgr is not None:
+            self.mean_dev.copy_(torch.as_tensor(np.asarray(mean_bgr, np.float32)), non_blocking=True)
+        ops.step_state_set(self.state, self.step_count, lr, self._graph_tag_origin(g["span"]))
+        g["graph"].replay()
+        self._rows = g["rows"]
+        if not train:
+            return True, self.logits[:g["rows"]]
+        self.step_count += 1
+        return True, self._fetch(g["rows"], fetch)
+
+    def _graph_tag_origin(self, span):
+        """Tag origin of the next replay on lstm_ws_graph (its launches use origin + 1 .. origin + span - 1).  Past the limit the exchange
+        words are zeroed on the stream, outside any graph, and the tags start over at 1."""
+        if self.graph_tag_next + span > self.GRAPH_TAG_LIMIT:
+            ops.lstm_seq_ws_clear(self.lstm_ws_graph)
+            self.graph_tag_next = 1
+        origin = self.graph_tag_next
+        self.graph_tag_next += span
+        return origin
+
+    def _capture(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm, global_rows):
+        """Captures one call over static input buffers.  Nothing runs and no host state moves: the replay that follows is the step."""
+        t0 = time.perf_counter()
+        inputs = {name: torch.empty_like(t) for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x),
+                                                              ("mirror", mirror), ("onehot", onehot)) if t is not None}
+        n = frames_u8.shape[0]
+        b = self._check_frames(n)
+        # every buffer the capture bakes in lives as long as the graph: the resize chain's outputs and intermediates are the graph's
+        # own (a resizer's shared intermediate is replaced when a larger batch comes, and would then be freed under the graph)
+        chain = []
+        for src_hw, dst_hw in (resize or ()):
+            rs = self._resizers[(tuple(src_hw), tuple(dst_hw))]                               # made by the warm-up call
+            need = rs.tmp_bytes(n)
+            chain.append((rs, torch.empty((n, rs.oh, rs.ow, 3), dtype=torch.uint8, device=self.dev),
+                          torch.empty(need, dtype=torch.uint8, device=self.dev) if need else None))
+        graph = torch.cuda.CUDAGraph()
+        step_count = self.step_count
+        self._tag_off = 0
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                frames = inputs["frames"]
+                for rs, dst, tmp in chain:
+                    frames = rs(frames, dst=dst, tmp=tmp)
+                self._feed_dev(frames, n, b, self.mean_dev if mean_bgr is not None else None, inputs.get("crop_y"), inputs.get("crop_x"),
+                               inputs.get("mirror"))
+                if train:
+                    self._train(n, b, inputs["onehot"], 0.0, clip_norm, False, global_rows)
+                    rows = self._rows
+                else:
+                    rows = self._forward(n, b, train=False)
+            span = self._tag_off
+        finally:
+            self._tag_off = None
+            self.step_count = step_count
+        self.graph_capture_ms.append((time.perf_counter() - t0) * 1e3)
+        return dict(graph=graph, inputs=inputs, rows=rows, span=span, resize_buffers=[(dst, tmp) for _, dst, tmp in chain])

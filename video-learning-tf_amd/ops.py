@@ -481,6 +481,34 @@ def lstm_seq_bwd(dout, kh, act, cseq, dz, batch, T, H, ws=None, c0=None, dh0=Non
               ws.numel() * 4, stream())
 
 
+def lstm_seq_tag_span(batch, T, H):
+    """Exchange tags one lstm_seq_fwd_st / lstm_seq_bwd_st call uses above its tag offset (0: the per-clip form, no tags)."""
+    return int(_ffi.lib().vl_lstm_seq_tag_span(int(batch), int(T), int(H)))
+
+
+def lstm_seq_fwd_st(gx, kh, act, cseq, hseq, hprev, batch, T, H, forget_bias=1.0, ws=None, state=None, tag_offset=0, h0=None, c0=None):
+    """lstm_seq_fwd with replay-safe tags: base = state's tag origin (read on the device) + tag_offset (vl_lstm_seq_fwd_st)."""
+    _f32(gx, kh, act, cseq, hseq, hprev, h0, c0, ws)
+    if ws is None or state is None:
+        raise _ffi.VltfError("lstm_seq_fwd_st: a workspace from lstm_seq_ws() and a step state are required")
+    _ffi.call("vl_lstm_seq_fwd_st", _p(gx), _p(kh), _p(h0), _p(c0), _p(act), _p(cseq), _p(hseq), _p(hprev), batch, T, H, forget_bias,
+              _p(ws), ws.numel() * 4, _state(state), int(tag_offset), stream())
+
+
+def lstm_seq_bwd_st(dout, kh, act, cseq, dz, batch, T, H, ws=None, state=None, tag_offset=0, c0=None, dh0=None, dc0=None):
+    _f32(dout, kh, act, cseq, dz, c0, dh0, dc0, ws)
+    if ws is None or state is None:
+        raise _ffi.VltfError("lstm_seq_bwd_st: a workspace from lstm_seq_ws() and a step state are required")
+    _ffi.call("vl_lstm_seq_bwd_st", _p(dout), _p(kh), _p(act), _p(cseq), _p(c0), _p(dz), _p(dh0), _p(dc0), batch, T, H, _p(ws),
+              ws.numel() * 4, _state(state), int(tag_offset), stream())
+
+
+def lstm_seq_ws_clear(ws):
+    """Zeroes the exchange words of a workspace (not its time-out word), on the stream: its owner restarts its tags."""
+    _f32(ws)
+    _ffi.call("vl_lstm_seq_ws_clear", _p(ws), ws.numel() * 4, stream())
+
+
 def lstm_seq_timed_out(ws):
     """True if a workgroup of any cluster-form launch on `ws` since the last call gave up waiting for its peers; the flag is
     sticky across launches and reset by this read (synchronises)."""
@@ -526,6 +554,12 @@ def dropout_fwd(x, y, mask, keep, seed):
     _ffi.call("vl_dropout_fwd", _p(x), _p(y), _p(mask), x.numel(), keep, seed, stream())
 
 
+def dropout_fwd_st(x, y, mask, keep, state):
+    """dropout_fwd with the seed formed on the device from the step state's count (vl_dropout_fwd_st)."""
+    _f32(x, y)
+    _ffi.call("vl_dropout_fwd_st", _p(x), _p(y), _p(mask), x.numel(), keep, _state(state), stream())
+
+
 def dropout_bwd(dy, mask, dx, keep):
     _f32(dy, dx)
     _ffi.call("vl_dropout_bwd", _p(dy), _p(mask), _p(dx), dy.numel(), keep, stream())
@@ -567,6 +601,37 @@ def sgd_apply(w, g, lr, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
 def adam_apply(w, g, m, v, lr, step, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
     _f32(w, g, m, v, sumsq_t)
     _ffi.call("vl_adam_apply", _p(w), _p(g), _p(m), _p(v), w.numel(), lr, clip_norm, _p(sumsq_t), gscale, step, _skip_word(skip), stream())
+
+
+# ---- step state (vltf.h: vl_step_state): the scalars a replayed step reads from device memory ----------------------------------
+def step_state(device):
+    """A zeroed device block for vl_step_state (int32 words)."""
+    n = int(_ffi.lib().vl_step_state_bytes())
+    return torch.zeros((n + 3) // 4, dtype=torch.int32, device=device)
+
+
+def _state(state):
+    if state is None or not (state.is_cuda and state.dtype == torch.int32 and state.numel() * 4 >= int(_ffi.lib().vl_step_state_bytes())):
+        raise _ffi.VltfError("expected a step state from step_state()")
+    return _p(state)
+
+
+def step_state_set(state, step, lr, tag_origin):
+    """state = (step, lr, tag_origin, Adam's step size for count step + 1), written on the stream (vl_step_state_set)."""
+    _ffi.call("vl_step_state_set", _state(state), int(step), lr, int(tag_origin), stream())
+
+
+def sgd_apply_st(w, g, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """sgd_apply with lr read from the step state."""
+    _f32(w, g, sumsq_t)
+    _ffi.call("vl_sgd_apply_st", _p(w), _p(g), w.numel(), _state(state), clip_norm, _p(sumsq_t), gscale, _skip_word(skip), stream())
+
+
+def adam_apply_st(w, g, m, v, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """adam_apply with the step size for the state's count + 1 read from the step state."""
+    _f32(w, g, m, v, sumsq_t)
+    _ffi.call("vl_adam_apply_st", _p(w), _p(g), _p(m), _p(v), w.numel(), _state(state), clip_norm, _p(sumsq_t), gscale, _skip_word(skip),
+              stream())
 
 
 def step_guard(skip, *lstm_workspaces):
@@ -674,7 +739,13 @@ class Resize:
         except Exception:
             pass
 
-    def __call__(self, src, dst=None):
+    def tmp_bytes(self, n):
+        """Bytes of the uint8 intermediate of n images (0 when at most one axis changes size)."""
+        return int(_ffi.lib().vl_resize_tmp_bytes(self._d, int(n)))
+
+    def __call__(self, src, dst=None, tmp=None):
+        """tmp: the caller's intermediate (uint8, >= tmp_bytes(n)); None = this object's own, grown (replaced) on demand -- a captured
+        call must own its tmp and dst, which the graph writes on every replay."""
         if src.dtype != torch.uint8 or not src.is_cuda or not src.is_contiguous() or tuple(src.shape[1:]) != (self.h, self.w, 3):
             raise _ffi.VltfError("resize: expected contiguous device uint8 [n, %d, %d, 3], got %s" % (self.h, self.w, tuple(src.shape)))
         n = src.shape[0]
@@ -682,8 +753,13 @@ class Resize:
             dst = torch.empty((n, self.oh, self.ow, 3), dtype=torch.uint8, device=src.device)
         elif dst.dtype != torch.uint8 or tuple(dst.shape) != (n, self.oh, self.ow, 3) or not dst.is_contiguous():
             raise _ffi.VltfError("resize: destination must be contiguous uint8 %s" % ((n, self.oh, self.ow, 3),))
-        need = int(_ffi.lib().vl_resize_tmp_bytes(self._d, n))
-        if need and (self._tmp is None or self._tmp.numel() < need):
-            self._tmp = torch.empty(need, dtype=torch.uint8, device=src.device)
-        _ffi.call("vl_resize_u8", self._d, _p(src), _p(self._tmp) if need else None, _p(dst), n, stream())
+        need = self.tmp_bytes(n)
+        if need and tmp is not None:
+            if tmp.dtype != torch.uint8 or not tmp.is_cuda or tmp.numel() < need:
+                raise _ffi.VltfError("resize: tmp must be a device uint8 tensor of >= %d bytes" % need)
+        elif need:
+            if self._tmp is None or self._tmp.numel() < need:
+                self._tmp = torch.empty(need, dtype=torch.uint8, device=src.device)
+            tmp = self._tmp
+        _ffi.call("vl_resize_u8", self._d, _p(src), _p(tmp) if need else None, _p(dst), n, stream())
         return dst

@@ -51,7 +51,8 @@ def pipeline_net_config(settings, p, dataset):
     kw = dict(image_shape=tuple(dataset.get_image_shape()), num_classes=settings.num_classes, fpc=dataset.num_frames_per_clip,
               frame_encoding_layer=p.frame_encoding_layer, classifier=p.classifier or defs.classifier.fc,
               dropout_keep_prob=settings.get_dropout(), optimizer=settings.train.optimizer if settings.train else "sgd",
-              conv_math=os.environ.get("VLTF_CONV_MATH", "f32"))     # "bf16x3": opt-in split-bf16 conv products (not a reference key)
+              conv_math=os.environ.get("VLTF_CONV_MATH", "f32"),     # "bf16x3": opt-in split-bf16 conv products (not a reference key)
+              step_graph=step_graph_requested())                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -59,6 +60,12 @@ def pipeline_net_config(settings, p, dataset):
     else:
         kw.update(frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None)
     return NetConfig(**kw)
+
+
+def step_graph_requested():
+    """VLTF_STEP_GRAPH=1: the single-pipeline engine captures its train / forward step once per input shape and replays it
+    (NetConfig.step_graph).  Refused where it is not supported, never dropped silently."""
+    return os.environ.get("VLTF_STEP_GRAPH", "0") == "1"
 
 
 def net_config(settings, dataset):
@@ -280,6 +287,10 @@ def main(init_file, seed=0, device=None):
     settings.graph_tags = None
     p0 = settings.pipelines[settings.pipeline_names[0]]
     single = len(settings.pipeline_names) == 1 and p0.representation == defs.representation.dcnn and p0.input == [defs.dataset_tag.main]
+    if step_graph_requested() and world > 1:
+        error("VLTF_STEP_GRAPH=1 is refused with data parallelism (%d ranks): capturing the gradient exchange is unmeasured" % world)
+    if step_graph_requested() and not single:
+        error("VLTF_STEP_GRAPH=1 is refused for this model: it runs on the multi-pipeline GraphEngine, which has no captured step")
     if world > 1:
         batch = -(-batch // world)           # data parallel: `batch_size` stays the GLOBAL batch of the config
     if single:
@@ -349,6 +360,9 @@ def cli(argv=None):
     parser.add_argument("init_file", help="Configuration .yml file for the run.")
     parser.add_argument("--gpus", type=int, default=int(os.environ.get("VLTF_GPUS", "1")), help="ranks to start on this node (default 1)")
     args = parser.parse_args(argv)
+    if step_graph_requested() and args.gpus > 1:      # before any rank is started
+        error("VLTF_STEP_GRAPH=1 is refused with --gpus %d: data parallelism has no captured step (the gradient exchange's "
+              "collectives are not captured)" % args.gpus)
     rc = dpmod.self_launch(args.gpus)
     if rc is not None:
         raise SystemExit(rc)
