@@ -280,6 +280,24 @@ int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const flo
  * dh0 / dc0 (nullable, [batch][H]) receive the gradients w.r.t. the initial output / cell state. */
 int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
                     float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, vl_stream_t stream);
+/* ---- per-clip sequence lengths (tf.nn.dynamic_rnn(sequence_length=...), lstm.py:132-142) ------------------------------------------
+ * seq_len: device int32 [batch], one entry per sequence; steps t >= seq_len[b] of clip b are DEAD (values are clamped to 0..T on
+ * the device; callers validate 1..T).  NULL = the call without _len.  The recurrence is dynamic_rnn's:
+ *   - state is copied through a dead step (c_t = c_{t-1}, h_t = h_{t-1}), so cseq[b][T-1] is still the final cell state, and the
+ *     output of a dead step is zero;
+ *   - backward: dout of a dead row is ignored, its dz is exactly 0, nothing flows into dh / dc there (dead steps are a suffix and
+ *     there is no gradient into the final state); dh0 / dc0 are the gradients of the live prefix.
+ * THE DEAD-ROW CONTRACT: every row of every output is written, and no output depends on a dead row of gx or dout, not even as
+ * 0 * x -- they may hold NaN.  Dead rows get act = 0, cseq = the carried c, hseq = 0, hprev = the carried h, dz = 0, so the
+ * whole-sequence GEMMs that follow (x^T dz, hprev^T dz, dz K^T) can sum over them.
+ * The cluster form's exchange does not depend on the lengths: every workgroup publishes and gathers at every step.
+ * Like the eager pair, these refuse a stream that is being captured. */
+int vl_lstm_seq_fwd_len(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
+                        float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, void* ws, size_t ws_bytes,
+                        vl_stream_t stream);
+int vl_lstm_seq_bwd_len(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
+                        float* dh0, float* dc0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes,
+                        vl_stream_t stream);
 /* Replay-safe variants (capturable): the tag base of launch k of the call is state->tag_origin, read from device memory when the
  * kernel runs, + tag_offset + k (T + 1).  A call uses the tags origin + tag_offset + 1 .. origin + tag_offset +
  * vl_lstm_seq_tag_span(batch, T, H) - 1 (span 0: the per-clip form, no tags).  The caller owns the tag stream: `ws` must not be
@@ -309,6 +327,14 @@ int vl_transpose(const float* src, int64_t ld, float* dst, int rows, int cols, v
  * method 0 = avg, 1 = last. */
 int vl_temporal_fusion_fwd(const float* x, float* y, int batch, int T, int H, int method, vl_stream_t stream);
 int vl_temporal_fusion_bwd(const float* dy, float* dx, int batch, int T, int H, int method, vl_stream_t stream);
+/* With per-clip lengths (seq_len as above, clamped to 1..T; NULL = the calls above): a clip of length L in a T-step batch gives what it
+ * gives in an L-step model.  last = step L - 1 (dynamic_rnn's final output; NOT what tf_util.py would read from the zero-filled
+ * output at step T - 1, a zero row: the reference never combines the two, and nobody wants that artefact); avg = the mean over
+ * the first L steps (not sum / T).  The backward writes zeros to the dead rows of dx. */
+int vl_temporal_fusion_fwd_len(const float* x, float* y, int batch, int T, int H, int method, const int32_t* seq_len,
+                               vl_stream_t stream);
+int vl_temporal_fusion_bwd_len(const float* dy, float* dx, int batch, int T, int H, int method, const int32_t* seq_len,
+                               vl_stream_t stream);
 
 /* ---- imresize: scipy.misc.imresize(image, shape) of Dataset.process_image (dataset_.py:481-495: imgproc `raw_resize` to the raw
  * shape, `resize` to the network input size; also serialize.py:424-425) = PIL Image.resize(BILINEAR) on uint8, bit-exact:
@@ -353,6 +379,11 @@ int vl_dropout_fwd_st(const float* x, float* y, uint8_t* mask, int64_t count, fl
  * the whole chip, summed in a fixed order); NULL walks every row in one workgroup (same result, for small batches only). */
 int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows,
                     int batch, int classes, float grad_scale, vl_stream_t stream);
+/* Rows are the steps of batch / T sequences (row r = b T + t) with per-clip lengths seq_len[batch / T]: a row with t >= seq_len[b]
+ * is padding (the reference's non_padding_index, dataset_.py:327-383).  It is not read (it may hold NaN), adds nothing to `stats`
+ * and gets dlogits = 0.  The caller divides by the live-row count: grad_scale = 1 / sum(seq_len).  seq_len NULL = vl_softmax_xent. */
+int vl_softmax_xent_len(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows,
+                        int batch, int classes, float grad_scale, const int32_t* seq_len, int T, vl_stream_t stream);
 
 /* ---- optimizer: clip_by_global_norm + GradientDescentOptimizer (train.py:199-222) ---------------
  * vl_sumsq: out[0] (+)= sum g^2 over count elements (ws: float[1024]); accumulate != 0 adds to out. */

@@ -64,6 +64,8 @@ SIGNATURES = {
     "vl_lstm_seq_ws_bytes": (sz, [i32, i32, i32]),
     "vl_lstm_seq_fwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, f32, p, sz, p]),
     "vl_lstm_seq_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p]),
+    "vl_lstm_seq_fwd_len": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, f32, p, p, sz, p]),
+    "vl_lstm_seq_bwd_len": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, p, sz, p]),
     "vl_lstm_seq_tag_span": (sz, [i32, i32, i32]),
     "vl_lstm_seq_fwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, f32, p, sz, p, u32, p]),
     "vl_lstm_seq_bwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p, u32, p]),
@@ -73,10 +75,13 @@ SIGNATURES = {
     "vl_transpose": (i32, [p, i64, p, i32, i32, p]),
     "vl_temporal_fusion_fwd": (i32, [p, p, i32, i32, i32, i32, p]),
     "vl_temporal_fusion_bwd": (i32, [p, p, i32, i32, i32, i32, p]),
+    "vl_temporal_fusion_fwd_len": (i32, [p, p, i32, i32, i32, i32, p, p]),
+    "vl_temporal_fusion_bwd_len": (i32, [p, p, i32, i32, i32, i32, p, p]),
     "vl_dropout_fwd": (i32, [p, p, p, i64, f32, u64, p]),
     "vl_dropout_bwd": (i32, [p, p, p, i64, f32, p]),
     "vl_dropout_fwd_st": (i32, [p, p, p, i64, f32, p, p]),
     "vl_softmax_xent": (i32, [p, p, p, p, p, i32, i32, f32, p]),
+    "vl_softmax_xent_len": (i32, [p, p, p, p, p, i32, i32, f32, p, i32, p]),
     "vl_sumsq": (i32, [p, i64, p, p, i32, p]),
     "vl_sgd_apply": (i32, [p, p, i64, f32, f32, p, f32, p, p]),
     "vl_adam_apply": (i32, [p, p, p, p, i64, f32, f32, p, f32, i32, p, p]),

@@ -88,6 +88,6 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // ---- LSTM recurrence: per-clip form (pointwise.hip), the fallback / A-B reference of the cluster form (lstm_cluster.hip) ------
 int vl_lstm_perclip_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
-                        float* hprev, int batch, int T, int H, float forget_bias, hipStream_t stream);
+                        float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, hipStream_t stream);
 int vl_lstm_perclip_bwd(const float* dout, const float* kh_t, const float* act, const float* cseq, const float* c0, float* dz,
-                        float* dh0, float* dc0, int batch, int T, int H, hipStream_t stream);
+                        float* dh0, float* dc0, int batch, int T, int H, const int32_t* seq_len, hipStream_t stream);

@@ -31,6 +31,13 @@
 //   slowest workgroup's epoch-e values; the slowest one publishes those only after it finished reading epoch e-1.  So while
 //   anyone still reads epoch e-1, nobody can have written epoch e+1 (same parity).
 //
+// Per-clip lengths (seq_len, nullable; vltf.h "per-clip sequence lengths"): a gate thread owns (clip, unit) for the whole sequence, so
+// it reads its clip's length once and predicates on `t < len` its reads of gx / dout, its state update and what it stores.  The
+// EXCHANGE IS LENGTH-BLIND: every workgroup publishes and gathers at every epoch whatever the lengths are -- a dead step publishes the
+// carried h (forward) or the partials of a zero dz (backward) -- so no wait ever depends on data, and the trip count is T for every
+// workgroup (no group-uniform early stop: it would save steps only when a whole group is short, and a protocol whose epochs are a
+// function of an input array is the kind that times out on one machine only).  seq_len == nullptr: len = T, today's arithmetic.
+//
 // Groups are dealt so that a group's workgroups share blockIdx.x % 8 (= one XCD, one L2) when the group count is a multiple of
 // 8: speed only, nothing depends on it.
 #include <stdlib.h>
@@ -106,6 +113,7 @@ struct LstmClusterArgs {
     float* dz;            // bwd out [B T][4H]
     float* dh0;           // bwd: nullable out [B][H]
     float* dc0;           // bwd: nullable out [B][H]
+    const int32_t* seq_len;   // nullable [B]: steps t >= seq_len[b] of clip b are dead (state carried, output 0, dz 0)
     u64* xch;             // exchange granules
     unsigned* status;
     int B, T, H, Hp, G, W, cpg;
@@ -142,6 +150,7 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
     const int gc = tid / LU, gul = tid - gc * LU, gu = w * LU + gul;
     const bool glive = tid < CPG * LU && gc < nclips && gu < H;
     float cst = (glive && p.c0) ? p.c0[(int64_t)(clip0 + gc) * H + gu] : 0.f;
+    const int len = (glive && p.seq_len) ? min(max(p.seq_len[clip0 + gc], 0), T) : T;   // this thread's clip; dead steps: t >= len
     // matvec threads: wave wv works on column j for the clip pair (slot, slot + S) over the kpart-th slice of the reduction.
     // More than 4 clips: 4 pairs, whole reduction each; 3-4 clips: 2 pairs x 2 slices; 1-2 clips: 1 pair x 4 slices -- so the
     // 8-clip shard of the 8-GPU job (one clip per group) does not leave three waves idle behind one 256-long dot product.
@@ -160,7 +169,8 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
     for (int t = 0; t < T; ++t) {
         float zx[4] = {0.f, 0.f, 0.f, 0.f};
         const int64_t r = (int64_t)(clip0 + gc) * T + t;
-        if (glive) {
+        const bool alive = t < len;
+        if (glive && alive) {                                  // a dead row of gx is never read (it may hold anything)
 #pragma unroll
             for (int q = 0; q < 4; ++q) zx[q] = p.gx[r * H4 + q * H + gu];
         }
@@ -222,15 +232,21 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
         }
         __syncthreads();                                       // own columns complete; everyone has consumed h_{t-1}
         if (glive) {
-            float zr[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int kp_ = 0; kp_ < KP; ++kp_)                   // fixed order: reproducible
+            // dead step: gates 0, output 0, c carried in cst, and the carried h (= hp: h_{t-1} as gathered) is what the peers get
+            float gi = 0.f, gj = 0.f, gf = 0.f, go = 0.f, h = 0.f, hpub = hp;
+            if (alive) {
+                float zr[4] = {0.f, 0.f, 0.f, 0.f};
+                for (int kp_ = 0; kp_ < KP; ++kp_)               // fixed order: reproducible
 #pragma unroll
-                for (int q = 0; q < 4; ++q) zr[q] += zb[(kp_ * 2 * S + gc) * LC + q * LU + gul];
-            const float zi = zx[0] + zr[0], zj = zx[1] + zr[1], zf = zx[2] + zr[2], zo = zx[3] + zr[3];
-            const float gi = sigm(zi), gj = tanhf(zj), gf = sigm(zf + p.forget_bias), go = sigm(zo);
-            cst = cst * gf + gi * gj;
-            const float h = tanhf(cst) * go;
-            if (t + 1 < T && (int)blockIdx.x != p.mute) store_granule(xg + (t & 1) * xpar + gc * Hp + gu, ebase + (unsigned)(t + 1), h);
+                    for (int q = 0; q < 4; ++q) zr[q] += zb[(kp_ * 2 * S + gc) * LC + q * LU + gul];
+                const float zi = zx[0] + zr[0], zj = zx[1] + zr[1], zf = zx[2] + zr[2], zo = zx[3] + zr[3];
+                gi = sigm(zi); gj = tanhf(zj); gf = sigm(zf + p.forget_bias); go = sigm(zo);
+                cst = cst * gf + gi * gj;
+                h = tanhf(cst) * go;
+                hpub = h;
+            }
+            // published at every epoch, alive or dead: the exchange does not depend on the lengths
+            if (t + 1 < T && (int)blockIdx.x != p.mute) store_granule(xg + (t & 1) * xpar + gc * Hp + gu, ebase + (unsigned)(t + 1), hpub);
             float* a = p.act + r * H4 + gu;
             a[0] = gi; a[H] = gj; a[2 * H] = gf; a[3 * H] = go;
             p.cseq[r * H + gu] = cst;
@@ -300,6 +316,7 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
     const int gc = tid / LU, gul = tid - gc * LU, gu = w * LU + gul;
     const bool glive = tid < CPG * LU && gc < nclips && gu < H;
     float dc = 0.f, dh = 0.f;
+    const int len = (glive && p.seq_len) ? min(max(p.seq_len[clip0 + gc], 0), T) : T;   // as in the forward
     // exchange: P[parity][group][source workgroup][clip][k]
     const size_t pgrp = (size_t)W * CPG * Hp, ppar = (size_t)p.G * pgrp;
     u64* pg = p.xch + (size_t)grp * pgrp;
@@ -327,7 +344,8 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
         const int64_t r = (int64_t)(clip0 + gc) * T + t;
         const unsigned epoch = (unsigned)(T - t);               // 1 .. T
         float din = 0.f, gi = 0.f, gj = 0.f, gf = 0.f, go = 0.f, cc = 0.f, cp = 0.f;
-        if (glive) {
+        const bool alive = t < len;
+        if (glive && alive) {                                   // a dead row of dout / act is never read
             din = p.dout ? p.dout[r * H + gu] : 0.f;
             const float* a = p.act + r * H4 + gu;
             gi = a[0]; gj = a[H]; gf = a[2 * H]; go = a[3 * H];
@@ -336,13 +354,18 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
         }
         if (t < T - 1) dh = gather_dh(epoch - 1);               // published by every workgroup of the group at step t + 1
         if (glive) {
-            din += dh;
-            const float tc = tanhf(cc);
-            const float d_o = din * tc;
-            const float dcv = dc + din * go * (1.f - tc * tc);
-            const float zi = dcv * gj * gi * (1.f - gi), zj = dcv * gi * (1.f - gj * gj);
-            const float zf = dcv * cp * gf * (1.f - gf), zo = d_o * go * (1.f - go);
-            dc = dcv * gf;
+            // dead step: dz = 0 exactly (its partials, published below like any others, are zeros); dc stays 0 and the gathered dh is
+            // a sum of zeros, because dead steps are a suffix of the sequence
+            float zi = 0.f, zj = 0.f, zf = 0.f, zo = 0.f;
+            if (alive) {
+                din += dh;
+                const float tc = tanhf(cc);
+                const float d_o = din * tc;
+                const float dcv = dc + din * go * (1.f - tc * tc);
+                zi = dcv * gj * gi * (1.f - gi); zj = dcv * gi * (1.f - gj * gj);
+                zf = dcv * cp * gf * (1.f - gf); zo = d_o * go * (1.f - go);
+                dc = dcv * gf;
+            }
             float* zp = p.dz + r * H4 + gu;
             zp[0] = zi; zp[H] = zj; zp[2 * H] = zf; zp[3 * H] = zo;
             float* zz = zl + gc * LC + gul;
@@ -426,6 +449,7 @@ static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws,
     a.spin_limit = g_spin_limit;
     a.mute = g_mute_workgroup;
     const float *gx = a.gx, *h0 = a.h0, *c0 = a.c0, *dout = a.dout;
+    const int32_t* seq_len = a.seq_len;
     float *act = a.act, *cseq = a.cseq, *hseq = a.hseq, *hprev = a.hprev, *dz = a.dz, *dh0 = a.dh0, *dc0 = a.dc0;
     for (int b0 = 0, k = 0; b0 < batch; b0 += c.chunk, ++k) {
         const int nb = batch - b0 < c.chunk ? batch - b0 : c.chunk;
@@ -445,6 +469,7 @@ static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws,
         a.dz = dz ? dz + ro * 4 * a.H : nullptr;
         a.dh0 = dh0 ? dh0 + so : nullptr;
         a.dc0 = dc0 ? dc0 + so : nullptr;
+        a.seq_len = seq_len ? seq_len + b0 : nullptr;
         a.xch = (u64*)((char*)ws + STATUS_BYTES);                 // the kernels index parity blocks by their own G: [parity][G][...]
         if (st) {
             // replay-safe: the base over the origin the host writes before every replay (vl_lstm_seq_tag_span counts these launches)
@@ -479,56 +504,73 @@ extern "C" size_t vl_lstm_seq_ws_bytes(int batch, int T, int H) {
 }
 
 // The eager entry points bake their tag bases into the launch: refused on a stream that is being captured (vltf.h)
-static int refuse_capture(hipStream_t s, const char* what) {
+static int refuse_capture(hipStream_t s, const char* what, bool has_st = true) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     VL_HIP(hipStreamIsCapturing(s, &cs));
-    VL_CHECK(cs == hipStreamCaptureStatusNone, "%s: the stream is being captured; its tags would be replayed stale -- use %s_st", what, what);
+    VL_CHECK(cs == hipStreamCaptureStatusNone || !has_st, "%s: the stream is being captured; its tags would be replayed stale -- use %s_st", what, what);
+    VL_CHECK(cs == hipStreamCaptureStatusNone, "%s: the stream is being captured; its tags would be replayed stale (there is no replay-safe variant with lengths)", what);
     return 0;
 }
 
 static int lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
-                        float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes, const vl_step_state* st,
-                        unsigned tag_offset, hipStream_t stream) {
+                        float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, void* ws, size_t ws_bytes,
+                        const vl_step_state* st, unsigned tag_offset, hipStream_t stream) {
     VL_CHECK(gx && kh && act && cseq && hseq && hprev, "vl_lstm_seq_fwd: null argument");
     VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= 1024, "vl_lstm_seq_fwd: bad shape (hidden size must be <= 1024)");
     VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "vl_lstm_seq_fwd: workspace smaller than vl_lstm_seq_ws_bytes");
     if (vl_lstm_cluster_ok(H) && !kPerClip) {
         LstmClusterArgs a = {};
         a.gx = gx; a.kh = kh; a.h0 = h0; a.c0 = c0; a.act = act; a.cseq = cseq; a.hseq = hseq; a.hprev = hprev;
-        a.T = T; a.H = H; a.forget_bias = forget_bias;
+        a.T = T; a.H = H; a.forget_bias = forget_bias; a.seq_len = seq_len;
         return vl_lstm_cluster_run(false, a, batch, ws, ws_bytes, st, tag_offset, stream);
     }
-    return vl_lstm_perclip_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, stream);
+    return vl_lstm_perclip_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, seq_len, stream);
 }
 
 static int lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz, float* dh0,
-                        float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* st, unsigned tag_offset,
-                        hipStream_t stream) {
+                        float* dc0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, const vl_step_state* st,
+                        unsigned tag_offset, hipStream_t stream) {
     VL_CHECK(kh && act && cseq && dz, "vl_lstm_seq_bwd: null argument");
     VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= 1024, "vl_lstm_seq_bwd: bad shape (hidden size must be <= 1024)");
     VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "vl_lstm_seq_bwd: workspace smaller than vl_lstm_seq_ws_bytes");
     if (vl_lstm_cluster_ok(H) && !kPerClip) {
         LstmClusterArgs a = {};
         a.kh = kh; a.c0 = c0; a.act = const_cast<float*>(act); a.cseq = const_cast<float*>(cseq); a.dout = dout; a.dz = dz;
-        a.dh0 = dh0; a.dc0 = dc0; a.T = T; a.H = H;
+        a.dh0 = dh0; a.dc0 = dc0; a.T = T; a.H = H; a.seq_len = seq_len;
         return vl_lstm_cluster_run(true, a, batch, ws, ws_bytes, st, tag_offset, stream);
     }
     float* kh_t = (float*)((char*)ws + STATUS_BYTES);
     if (vl_transpose(kh, (int64_t)4 * H, kh_t, H, 4 * H, stream)) return 1;
-    return vl_lstm_perclip_bwd(dout, kh_t, act, cseq, c0, dz, dh0, dc0, batch, T, H, stream);
+    return vl_lstm_perclip_bwd(dout, kh_t, act, cseq, c0, dz, dh0, dc0, batch, T, H, seq_len, stream);
 }
 
 extern "C" int vl_lstm_seq_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq,
                                float* hseq, float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes,
                                vl_stream_t stream) {
     if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_fwd")) return 1;
-    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, nullptr, ws, ws_bytes, nullptr, 0,
+                        (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_fwd_len(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq,
+                                   float* hseq, float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len,
+                                   void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_fwd_len", false)) return 1;
+    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, seq_len, ws, ws_bytes, nullptr, 0,
+                        (hipStream_t)stream);
 }
 
 extern "C" int vl_lstm_seq_bwd(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
                                float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, vl_stream_t stream) {
     if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_bwd")) return 1;
-    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, nullptr, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_bwd_len(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
+                                   float* dh0, float* dc0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes,
+                                   vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_bwd_len", false)) return 1;
+    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, seq_len, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" size_t vl_lstm_seq_tag_span(int batch, int T, int H) {
@@ -541,7 +583,7 @@ extern "C" int vl_lstm_seq_fwd_st(const float* gx, const float* kh, const float*
                                   float* hseq, float* hprev, int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes,
                                   const vl_step_state* state, uint32_t tag_offset, vl_stream_t stream) {
     VL_CHECK(state, "vl_lstm_seq_fwd_st: null state");
-    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, ws, ws_bytes, state, tag_offset,
+    return lstm_seq_fwd(gx, kh, h0, c0, act, cseq, hseq, hprev, batch, T, H, forget_bias, nullptr, ws, ws_bytes, state, tag_offset,
                         (hipStream_t)stream);
 }
 
@@ -549,7 +591,7 @@ extern "C" int vl_lstm_seq_bwd_st(const float* dout, const float* kh, const floa
                                   float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
                                   uint32_t tag_offset, vl_stream_t stream) {
     VL_CHECK(state, "vl_lstm_seq_bwd_st: null state");
-    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, ws, ws_bytes, state, tag_offset, (hipStream_t)stream);
+    return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, nullptr, ws, ws_bytes, state, tag_offset, (hipStream_t)stream);
 }
 
 extern "C" int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream) {

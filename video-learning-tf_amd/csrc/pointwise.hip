@@ -1383,12 +1383,14 @@ extern "C" int vl_lstm_step_bwd(const float* dout, const float* dh_next, const f
 // Loads are staged through a register array so a whole batch is in flight (hipcc otherwise waits after every
 // load), and every clip starts at a different row so the CUs do not hit one L2 channel in lockstep.
 // Replaces T x {vl_gemm(M = clips), vl_lstm_step_*} launches.
+// seq_len (nullable, vltf.h "per-clip sequence lengths"): the workgroup IS the clip, so it runs the first L = seq_len[b] steps only and
+// fills the dead rows t >= L afterwards (forward: act 0, cseq = the carried c, hseq 0, hprev = the carried h; backward: dz 0).
 template <bool BWD>
 __global__ void lstm_seq_kernel(const float* __restrict__ gx, const float* __restrict__ kmat, float* __restrict__ act,
                                 float* __restrict__ cseq, float* __restrict__ hseq, float* __restrict__ hprev,
                                 const float* __restrict__ dout, float* __restrict__ dz, int T, int H, float forget_bias, int KQ,
                                 const float* __restrict__ h0, const float* __restrict__ c0, float* __restrict__ dh0,
-                                float* __restrict__ dc0) {
+                                float* __restrict__ dc0, const int32_t* __restrict__ seq_len) {
     // blockDim = KQ * HP threads (HP = H rounded up to the wave): thread (u, kq) accumulates the kq-th slice of the recurrent
     // reduction for hidden unit u; the KQ partial sums meet in LDS and the kq = 0 threads do the gate math.  The recurrence is a
     // chain of T dependent steps whose length is set by load latency, not bandwidth (1 MB of weights per step from L2): splitting
@@ -1399,6 +1401,7 @@ __global__ void lstm_seq_kernel(const float* __restrict__ gx, const float* __res
     const bool live = u < H;
     const int uc = live ? u : 0;                       // clamped: idle lanes load valid addresses, results unused
     const int H4 = 4 * H;
+    const int L = seq_len ? min(max(seq_len[b], 0), T) : T;   // live steps of this clip
     constexpr int KB = 16;
     if (!BWD) {
         float* hs = sm;                                // [H] h_{t-1}
@@ -1409,7 +1412,7 @@ __global__ void lstm_seq_kernel(const float* __restrict__ gx, const float* __res
         const bool rec0 = h0 != nullptr;               // an initial state makes step 0 a full recurrent step
         const int klen = (H + KQ - 1) / KQ, k0 = kq * klen, k1 = min(H, k0 + klen);
         const int nb = (k1 - k0) / KB, rot = (b * 5) % (nb > 0 ? nb : 1);
-        for (int t = 0; t < T; ++t) {
+        for (int t = 0; t < L; ++t) {
             const int64_t r = (int64_t)b * T + t;
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (t > 0 || rec0) {
@@ -1458,6 +1461,17 @@ __global__ void lstm_seq_kernel(const float* __restrict__ gx, const float* __res
             }
             __syncthreads();                           // h_t visible before the next step
         }
+        if (live && kq == 0) {                         // dead rows: state carried, output zero (hs[u] is this thread's own last write)
+            const float hc = hs[u];
+            for (int t = L; t < T; ++t) {
+                const int64_t r = (int64_t)b * T + t;
+                float* a = act + r * H4 + u;
+                a[0] = 0.f; a[H] = 0.f; a[2 * H] = 0.f; a[3 * H] = 0.f;
+                cseq[r * H + u] = c;
+                hseq[r * H + u] = 0.f;
+                hprev[r * H + u] = hc;
+            }
+        }
     } else {
         // kmat = khT [4H][H]: dh_prev[u] = sum_g dz[g] * khT[g][u]
         float* zs = sm;                                // [4H] dz_t
@@ -1465,7 +1479,12 @@ __global__ void lstm_seq_kernel(const float* __restrict__ gx, const float* __res
         float dc = 0.f, dh = 0.f;
         const int glen = (H4 + KQ - 1) / KQ, g0 = kq * glen, g1 = min(H4, g0 + glen);
         const int nb = (g1 - g0) / KB, rot = (b * 5) % (nb > 0 ? nb : 1);
-        for (int t = T - 1; t >= 0; --t) {
+        if (live && kq == 0)                           // dead rows: dz = 0, nothing read
+            for (int t = L; t < T; ++t) {
+                float* zp = dz + ((int64_t)b * T + t) * H4 + u;
+                zp[0] = 0.f; zp[H] = 0.f; zp[2 * H] = 0.f; zp[3 * H] = 0.f;
+            }
+        for (int t = L - 1; t >= 0; --t) {
             const int64_t r = (int64_t)b * T + t;
             if (live && kq == 0) {
                 const float din = (dout ? dout[r * H + u] : 0.f) + dh;
@@ -1520,21 +1539,21 @@ static int lstm_seq_kq(int H) { return lstm_seq_hp(H) * 4 <= 1024 ? 4 : (lstm_se
 // Per-clip form: the fallback of vl_lstm_seq_fwd / _bwd (lstm_cluster.hip) for hidden sizes its LDS-resident weight slices do
 // not hold (H > 512), and the A/B reference of the cluster form (VL_LSTM_PERCLIP=1).
 int vl_lstm_perclip_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
-                        float* hprev, int batch, int T, int H, float forget_bias, hipStream_t stream) {
+                        float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, hipStream_t stream) {
     const int kq = lstm_seq_kq(H);
     hipLaunchKernelGGL((lstm_seq_kernel<false>), dim3(batch), dim3(lstm_seq_hp(H) * kq), (size_t)(1 + 4 * kq) * H * sizeof(float),
                        stream, gx, kh, act, cseq, hseq, hprev, (const float*)nullptr, (float*)nullptr, T, H, forget_bias, kq, h0, c0,
-                       (float*)nullptr, (float*)nullptr);
+                       (float*)nullptr, (float*)nullptr, seq_len);
     VL_LAUNCH_CHECK();
     return 0;
 }
 
 int vl_lstm_perclip_bwd(const float* dout, const float* kh_t, const float* act, const float* cseq, const float* c0, float* dz,
-                        float* dh0, float* dc0, int batch, int T, int H, hipStream_t stream) {
+                        float* dh0, float* dc0, int batch, int T, int H, const int32_t* seq_len, hipStream_t stream) {
     const int kq = lstm_seq_kq(H);
     hipLaunchKernelGGL((lstm_seq_kernel<true>), dim3(batch), dim3(lstm_seq_hp(H) * kq), (size_t)(4 + kq) * H * sizeof(float),
                        stream, (const float*)nullptr, kh_t, const_cast<float*>(act), const_cast<float*>(cseq),
-                       (float*)nullptr, (float*)nullptr, dout, dz, T, H, 0.f, kq, (const float*)nullptr, c0, dh0, dc0);
+                       (float*)nullptr, (float*)nullptr, dout, dz, T, H, 0.f, kq, (const float*)nullptr, c0, dh0, dc0, seq_len);
     VL_LAUNCH_CHECK();
     return 0;
 }
@@ -1562,47 +1581,75 @@ extern "C" int vl_transpose(const float* src, int64_t ld, float* dst, int rows, 
 }
 
 // ---- temporal fusion (tf_util.py:4-30) --------------------------------------------------------
+// seq_len (nullable): clip b fuses its first L = seq_len[b] steps only, as an L-step model would (`last` = step L - 1, `avg` = sum / L);
+// the backward writes zeros to the dead rows.  nullptr: L = T.
+__device__ __forceinline__ int fusion_len(const int32_t* __restrict__ seq_len, int b, int T) {
+    return seq_len ? min(max(seq_len[b], 1), T) : T;
+}
+
 __global__ void temporal_fusion_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int batch, int T, int H,
-                                           int method) {
+                                           int method, const int32_t* __restrict__ seq_len) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= batch * H) return;
     const int b = e / H, u = e - b * H;
+    const int L = fusion_len(seq_len, b, T);
     const float* p = x + (int64_t)b * T * H + u;
     if (method == 1) {
-        y[e] = p[(int64_t)(T - 1) * H];
+        y[e] = p[(int64_t)(L - 1) * H];
     } else {
         float a = 0.f;
-        for (int t = 0; t < T; ++t) a += p[(int64_t)t * H];
-        y[e] = a / (float)T;
+        for (int t = 0; t < L; ++t) a += p[(int64_t)t * H];
+        y[e] = a / (float)L;
     }
 }
 
 __global__ void temporal_fusion_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int batch, int T, int H,
-                                           int method) {
+                                           int method, const int32_t* __restrict__ seq_len) {
     const int64_t total = (int64_t)batch * T * H;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int u = (int)(e % H);
         const int t = (int)((e / H) % T);
         const int b = (int)(e / ((int64_t)H * T));
         const float g = dy[(int64_t)b * H + u];
-        dx[e] = method == 1 ? (t == T - 1 ? g : 0.f) : g / (float)T;
+        const int L = fusion_len(seq_len, b, T);
+        dx[e] = method == 1 ? (t == L - 1 ? g : 0.f) : (t < L ? g / (float)L : 0.f);
     }
+}
+
+static int temporal_fusion_fwd(const float* x, float* y, int batch, int T, int H, int method, const int32_t* seq_len, hipStream_t stream) {
+    hipLaunchKernelGGL(temporal_fusion_fwd_kernel, dim3(ceil_div((int64_t)batch * H, 256)), dim3(256), 0, stream, x, y, batch, T, H,
+                       method, seq_len);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+static int temporal_fusion_bwd(const float* dy, float* dx, int batch, int T, int H, int method, const int32_t* seq_len, hipStream_t stream) {
+    hipLaunchKernelGGL(temporal_fusion_bwd_kernel, dim3(grid_for((int64_t)batch * T * H, 256, 4096)), dim3(256), 0, stream, dy, dx, batch,
+                       T, H, method, seq_len);
+    VL_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int vl_temporal_fusion_fwd(const float* x, float* y, int batch, int T, int H, int method, vl_stream_t stream) {
     VL_CHECK(x && y && batch > 0 && T > 0 && H > 0 && (method == 0 || method == 1), "vl_temporal_fusion_fwd: bad argument");
-    hipLaunchKernelGGL(temporal_fusion_fwd_kernel, dim3(ceil_div((int64_t)batch * H, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                       y, batch, T, H, method);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return temporal_fusion_fwd(x, y, batch, T, H, method, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vl_temporal_fusion_fwd_len(const float* x, float* y, int batch, int T, int H, int method, const int32_t* seq_len,
+                                          vl_stream_t stream) {
+    VL_CHECK(x && y && batch > 0 && T > 0 && H > 0 && (method == 0 || method == 1), "vl_temporal_fusion_fwd_len: bad argument");
+    return temporal_fusion_fwd(x, y, batch, T, H, method, seq_len, (hipStream_t)stream);
 }
 
 extern "C" int vl_temporal_fusion_bwd(const float* dy, float* dx, int batch, int T, int H, int method, vl_stream_t stream) {
     VL_CHECK(dy && dx && batch > 0 && T > 0 && H > 0 && (method == 0 || method == 1), "vl_temporal_fusion_bwd: bad argument");
-    hipLaunchKernelGGL(temporal_fusion_bwd_kernel, dim3(grid_for((int64_t)batch * T * H, 256, 4096)), dim3(256), 0,
-                       (hipStream_t)stream, dy, dx, batch, T, H, method);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return temporal_fusion_bwd(dy, dx, batch, T, H, method, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int vl_temporal_fusion_bwd_len(const float* dy, float* dx, int batch, int T, int H, int method, const int32_t* seq_len,
+                                          vl_stream_t stream) {
+    VL_CHECK(dy && dx && batch > 0 && T > 0 && H > 0 && (method == 0 || method == 1), "vl_temporal_fusion_bwd_len: bad argument");
+    return temporal_fusion_bwd(dy, dx, batch, T, H, method, seq_len, (hipStream_t)stream);
 }
 
 // ---- dropout (lstm.py:50-56) ------------------------------------------------------------------
@@ -1715,13 +1762,29 @@ __device__ __forceinline__ void softmax_xent_row(const float* __restrict__ z, co
     hit = (cand == ycand) ? 1.f : 0.f;
 }
 
+// seq_len (nullable) with T: row r = b T + t is live iff t < seq_len[b].  A dead row is not read: it adds nothing to the sums and its
+// dlogits row is zeros (the reference's non_padding_index, dataset_.py:327-383).
+__device__ __forceinline__ bool xent_row_dead(const int32_t* __restrict__ seq_len, int T, int r) {
+    return seq_len && (r % T) >= seq_len[r / T];
+}
+
+__device__ __forceinline__ void xent_zero_row(float* __restrict__ dz, int C, int lane) {
+    if (dz)
+        for (int c = lane; c < C; c += 64) dz[c] = 0.f;
+}
+
 __global__ void softmax_xent_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                    float* __restrict__ dlogits, float* __restrict__ stats, int batch, int C, float gscale) {
+                                    float* __restrict__ dlogits, float* __restrict__ stats, int batch, int C, float gscale,
+                                    const int32_t* __restrict__ seq_len, int T) {
     __shared__ float sl[4], sc[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float loss_acc = 0.f, corr_acc = 0.f;
     for (int b = wv; b < batch; b += 4) {
         float l, h;
+        if (xent_row_dead(seq_len, T, b)) {
+            xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+            continue;
+        }
         softmax_xent_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
                          lane, l, h);
         loss_acc += l;
@@ -1739,10 +1802,19 @@ __global__ void softmax_xent_kernel(const float* __restrict__ logits, const int3
 }
 
 __global__ void softmax_xent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                         float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale) {
+                                         float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale,
+                                         const int32_t* __restrict__ seq_len, int T) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= batch) return;
     float l, h;
+    if (xent_row_dead(seq_len, T, b)) {
+        xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+        if (lane == 0) {
+            rows[b] = 0.f;
+            rows[batch + b] = 0.f;
+        }
+        return;
+    }
     softmax_xent_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, lane,
                      l, h);
     if (lane == 0) {
@@ -1775,21 +1847,33 @@ __global__ void softmax_xent_sum_kernel(const float* __restrict__ rows, float* _
     }
 }
 
-extern "C" int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
-                               int classes, float grad_scale, vl_stream_t stream) {
-    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent: bad argument");
+static int softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
+                        float grad_scale, const int32_t* seq_len, int T, hipStream_t stream) {
     if (!rows) {
-        hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch,
-                           classes, grad_scale);
+        hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(256), 0, stream, logits, labels, dlogits, stats, batch, classes, grad_scale,
+                           seq_len, T);
         VL_LAUNCH_CHECK();
         return 0;
     }
-    hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits,
-                       rows, batch, classes, grad_scale);
+    hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, stream, logits, labels, dlogits, rows, batch,
+                       classes, grad_scale, seq_len, T);
     VL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(softmax_xent_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch);
+    hipLaunchKernelGGL(softmax_xent_sum_kernel, dim3(1), dim3(256), 0, stream, rows, stats, batch);
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                               int classes, float grad_scale, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent: bad argument");
+    return softmax_xent(logits, labels, dlogits, stats, rows, batch, classes, grad_scale, nullptr, 1, (hipStream_t)stream);
+}
+
+extern "C" int vl_softmax_xent_len(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                   int classes, float grad_scale, const int32_t* seq_len, int T, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_len: bad argument");
+    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_len: batch (%d rows) is not whole sequences of T = %d", batch, T);
+    return softmax_xent(logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, seq_len ? T : 1, (hipStream_t)stream);
 }
 
 // ---- global norm + SGD / Adam (train.py:199-222) ----------------------------------------------

@@ -23,6 +23,13 @@ ALL parameters live in one flat buffer ordered last pipeline first and, inside a
 produces the gradients; global-norm clip, update and the data-parallel exchange run over the whole buffer as for one pipeline.
 A pipeline the last one does not depend on is never evaluated by sess.run(logits) and is not built (a warning says so).
 
+Per-clip sequence lengths (tf.nn.dynamic_rnn's sequence_length, lstm.py:132-142; the `nonzero` value of the LSTM.build plug point):
+forward / train_step take seq_len = {pipeline name: host int32 lengths, one per clip of that `classifier: lstm` pipeline}.  Steps
+at or beyond a clip's length are dead: the recurrence of every layer carries the state through them and outputs zero, fusion
+state | last | avg read the live prefix only, and when the last pipeline's fusion is `reshape` the loss, its gradient and the
+accuracy are taken over the live rows (the reference's non_padding_index, dataset_.py:327-383).  include/vltf.h states the
+contract of the kernels; without seq_len every call is what it was.
+
 The oracle of this class is oracle.lrcn_oracle.model_forward / model_backward (cross-checked against torch autograd)."""
 import math
 from dataclasses import dataclass
@@ -301,6 +308,7 @@ class PipeNode:
             self.lstm_ws = ops.lstm_seq_ws(B, T, H, dev) if H <= 1024 else None
             if self.lstm_ws is None:
                 raise VltfError("GraphEngine: LSTM hidden size above 1024 is not built")
+            self.seq_len_buf = torch.zeros(B, dtype=torch.int32, device=dev)     # per-clip lengths of a call that gives them
             r = R0 if self.per_step else B
             self.fused = buf(r, H) if not self.per_step else None
             self.dropped = buf(r, H)
@@ -335,6 +343,63 @@ class PipeNode:
             self.dout = buf(self.max_rows, self.out_dim)       # d(loss) / d(output): the loss (last pipeline) or the consumers write it
             self.din = [buf(x.max_rows, x.dim) if x.kind == "pipe" else None for x in self.srcs]
         return off
+
+    # ---- per-clip lengths ------------------------------------------------------------------------------------------------------------------
+    seq_len = None          # device int32 [clips] for the current call, or None (every clip runs all fpc steps)
+
+    def planned_rows(self, feeds):
+        """Rows this pipeline will output for `feeds`, from the feeds' shapes alone (no launch): lets the engine check a length
+        count before the first kernel."""
+        x = self.srcs[0]
+        if x.kind == "pipe":
+            rows = x.ref.planned_rows(feeds)
+        else:
+            f = feeds[x.ref]
+            rows = int((f["frames_u8"] if x.kind == "video" else f).shape[0])
+        if self.fusion == "ibias" and self.tower is None:
+            rows = rows // x.fpc * (x.fpc + 1)
+        self._planned_rows0 = rows
+        if self.early:
+            rows //= self.fpc
+        if self.cls == "lstm" and not self.per_step:
+            rows //= self.fpc
+        if self.late:
+            rows //= self.fpc
+        return rows
+
+    def check_seq_len(self, lengths, feeds):
+        """Host validation of one pipeline's lengths -> int32 numpy [clips].  Raises VltfError; launches nothing."""
+        name = self.spec.name
+        if self.cls != "lstm":
+            raise VltfError("seq_len: pipeline [%s] has no LSTM classifier to give sequence lengths to" % name)
+        if self.H > 1024:
+            raise VltfError("seq_len: pipeline [%s] has hidden size %d; the one-launch recurrence that takes lengths holds <= 1024" %
+                            (name, self.H))
+        if self.fusion in ("concat", "ibias"):
+            raise VltfError("seq_len: pipeline [%s] fuses its inputs by %s, which changes what a time step is; lengths are built for "
+                            "pipelines without it (refused rather than guessed)" % (name, self.fusion))
+        if self.state_src is not None and self.state_ratio > 1:
+            raise VltfError("seq_len: pipeline [%s] replicates its state input at clips-per-video ratio %d; lengths are not built "
+                            "for that (refused rather than guessed)" % (name, self.state_ratio))
+        if torch.is_tensor(lengths):
+            if lengths.device.type != "cpu":
+                raise VltfError("seq_len: the lengths of pipeline [%s] must be host data (numpy / list / CPU tensor)" % name)
+            lengths = lengths.numpy()
+        a = np.asarray(lengths)
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise VltfError("seq_len: the lengths of pipeline [%s] must be a 1-d integer array" % name)
+        self.planned_rows(feeds)
+        clips = self._planned_rows0 // self.fpc
+        if a.size != clips:
+            raise VltfError("seq_len: pipeline [%s] has %d clips in this batch, %d lengths were given" % (name, clips, a.size))
+        if a.min() < 1 or a.max() > self.fpc:
+            raise VltfError("seq_len: the lengths of pipeline [%s] must lie in 1..%d (its steps per clip), got %d..%d" %
+                            (name, self.fpc, a.min(), a.max()))
+        return np.ascontiguousarray(a, np.int32)
+
+    def _len_kw(self):
+        """The keyword for the length-aware ops: passed only when this call was given lengths."""
+        return {} if self.seq_len is None else {"seq_len": self.seq_len}
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------------------
     def _src_tensor(self, x, feeds):
@@ -451,6 +516,9 @@ class PipeNode:
     def _lstm_forward(self, x, rows, train):
         g, P, sc, C, H, T = self.g, self.P, self.scope, self.g.num_classes, self.H, self.fpc
         b = rows // T
+        lk = self._len_kw()
+        if lk and lk["seq_len"].numel() != b:
+            raise VltfError("pipeline [%s]: %d lengths for %d clips" % (self.spec.name, lk["seq_len"].numel(), b))
         s0 = None
         if self.state_src is not None:                  # model.py:128-134, lstm.py:34-42,74-77
             st = self._replicate(self.state_src, self.state_ratio, b, self.rep_state)
@@ -465,13 +533,15 @@ class PipeNode:
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]
             ops.gemm(xin, K, S["gx"], rows, 4 * H, d, bias=P[pre + "bias"], ws=g.ws)
-            ops.lstm_seq_fwd(S["gx"], K[d:], S["act"], S["cseq"], S["hseq"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws, h0=s0, c0=s0)
+            ops.lstm_seq_fwd(S["gx"], K[d:], S["act"], S["cseq"], S["hseq"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws, h0=s0, c0=s0,
+                             **lk)
             xin, d = S["hseq"], H
         r = rows if self.per_step else b
         if self.per_step:
             v = xin                                                     # reshape fusion: every step's output (tf_util.py:26-27)
         else:
-            ops.temporal_fusion_fwd(xin, self.fused, b, T, H, "last" if self.lfusion == "state" else self.lfusion)
+            # with lengths `state` and `last` are h of step len - 1 (dynamic_rnn's final state), `avg` the mean over the live steps
+            ops.temporal_fusion_fwd(xin, self.fused, b, T, H, "last" if self.lfusion == "state" else self.lfusion, **lk)
             v = self.fused
         self._dropout = train and g.dropout_keep_prob > 0 and self.lfusion != "state"       # lstm.py:80-93
         if self._dropout:
@@ -546,7 +616,7 @@ class PipeNode:
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
         else:
-            ops.temporal_fusion_bwd(d, top["dout"], b, T, H, "last" if self.lfusion == "state" else self.lfusion)
+            ops.temporal_fusion_bwd(d, top["dout"], b, T, H, "last" if self.lfusion == "state" else self.lfusion, **self._len_kw())
         has_state = self._s0 is not None
         for l in reversed(range(self.L)):
             S = self.lstm[l]
@@ -555,7 +625,7 @@ class PipeNode:
             din = self.feat_dim if l == 0 else H
             xin = self._xcls if l == 0 else self.lstm[l - 1]["hseq"]
             ops.lstm_seq_bwd(S["dout"], K[din:], S["act"], S["cseq"], S["dz"], b, T, H, ws=self.lstm_ws, c0=self._s0,
-                             dh0=S["dh0"] if has_state else None, dc0=S["dc0"] if has_state else None)
+                             dh0=S["dh0"] if has_state else None, dc0=S["dc0"] if has_state else None, **self._len_kw())
             ops.gemm(xin, S["dz"], G[pre + "kernel"], din, 4 * H, rows, transa=True, ws=g.ws)
             ops.gemm(S["hprev"], S["dz"], G[pre + "kernel"][din:], H, 4 * H, rows, transa=True, ws=g.ws)
             ops.colsum(S["dz"], G[pre + "bias"], sw, rows, 4 * H)
@@ -829,23 +899,61 @@ class GraphEngine:
             nd.forward(feeds, train)
         return self.last.rows
 
-    def forward(self, feeds):
+    def _set_seq_len(self, seq_len, feeds):
+        """Validates the lengths of a call on the host (VltfError before anything is launched), copies them into the pipelines'
+        device buffers and returns the live-row count of a masked loss (None: the loss is over all rows).  seq_len None: every
+        pipeline runs all its steps, and no op is handed a length."""
+        for nd in self.nodes:
+            nd.seq_len = None
+        if seq_len is None:
+            return None
+        if self.dp is not None and self.dp.world > 1:
+            raise VltfError("seq_len under data parallelism is not built: the masked loss needs the live-row count of all ranks")
+        if not isinstance(seq_len, dict):
+            raise VltfError("seq_len must be a dict {pipeline name: lengths}")
+        checked = {}
+        for name, lengths in seq_len.items():
+            if name not in self.by_name:
+                raise VltfError("seq_len: [%s] is not a pipeline of this model (%s)" % (name, [nd.spec.name for nd in self.nodes]))
+            checked[name] = self.by_name[name].check_seq_len(lengths, feeds)
+        n_valid = None
+        for name, a in checked.items():
+            nd = self.by_name[name]
+            nd.seq_len = nd.seq_len_buf[:a.size]
+            nd.seq_len.copy_(torch.from_numpy(a))
+            if nd is self.last and nd.per_step:
+                n_valid = int(a.sum())
+        return n_valid
+
+    def forward(self, feeds, seq_len=None):
         """sess.run(model.logits, fdict).  feeds: {dataset tag: dict(frames_u8=, mean_bgr=, crop_y=, crop_x=, mirror=, resize=) for a
-        frame dataset | float32 device tensor [rows, dim] for a vectors dataset}.  Returns a device view [rows, classes]."""
+        frame dataset | float32 device tensor [rows, dim] for a vectors dataset}.  Returns a device view [rows, classes].
+        seq_len: {pipeline name: host int32 lengths [clips of that pipeline]} (module docstring); under fusion `reshape` the rows of
+        dead steps are still produced (the head applied to a zero vector)."""
+        self._set_seq_len(seq_len, feeds)
         rows = self._forward(feeds, train=False)
         return self.last.out[:rows]
 
-    def train_step(self, feeds, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None):
-        """sess.run([.., loss, .., optimizer], fdict): labels int32 one-hot [rows, classes] for the LAST pipeline's rows."""
+    def train_step(self, feeds, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, seq_len=None):
+        """sess.run([.., loss, .., optimizer], fdict): labels int32 one-hot [rows, classes] for the LAST pipeline's rows.
+        seq_len as in forward; when the last pipeline has lengths and fusion `reshape`, loss and accuracy are means over the
+        n_valid = sum(lengths) live rows (labels still hold every row) and the returned `rows` is n_valid."""
         if not self.training:
             raise VltfError("engine was built with training=False")
+        n_valid = self._set_seq_len(seq_len, feeds)
+        if n_valid is not None and global_rows is not None:
+            raise VltfError("global_rows is the data-parallel row count; a loss masked by seq_len takes its own live-row count")
         rows = self._forward(feeds, train=True)
         if onehot.dtype != torch.int32 or tuple(onehot.shape) != (rows, self.num_classes):
             raise VltfError("labels must be int32 one-hot of shape (%d, %d)" % (rows, self.num_classes))
         world = self.dp.world if self.dp is not None else 1
         ops.fill(self.stats, 0.0)
         last = self.last
-        ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or rows * world), self.loss_rows)
+        if n_valid is not None:       # padded steps are kept out of the loss (non_padding_index, dataset_.py:327-383)
+            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / n_valid, self.loss_rows, seq_len=last.seq_len,
+                             T=last.fpc)
+        else:
+            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or rows * world), self.loss_rows)
         # backward, last pipeline first.  RCCL chunks are held back while an LSTM backward launch is still to come: the cluster
         # form of the recurrence needs every CU and must not spin under an all-reduce kernel that holds some (vl_lstm_seq_status)
         self._pending_lstm = sum(1 for nd in self.nodes if nd.cls == "lstm")
@@ -855,7 +963,7 @@ class GraphEngine:
         for nd in reversed(self.nodes):
             nd.backward()
         self._flush()
-        return self._finish_step(rows, lr, clip_norm, fetch)
+        return self._finish_step(rows if n_valid is None else n_valid, lr, clip_norm, fetch)
 
     def _reduce(self, off, cnt):
         if self.dp is None or cnt == 0:

@@ -463,20 +463,38 @@ def lstm_seq_ws(batch, T, H, device):
     return torch.zeros((n + 3) // 4, dtype=torch.float32, device=device)
 
 
-def lstm_seq_fwd(gx, kh, act, cseq, hseq, hprev, batch, T, H, forget_bias=1.0, ws=None, h0=None, c0=None):
-    """All T steps in one launch; kh = kernel[D:] view ([H, 4H]); h0 / c0: initial state [batch, H] (None = zeros)."""
+def _seq_len(seq_len, batch, what):
+    """Per-clip lengths of the *_len entry points: int32, contiguous, on the device, at least `batch` entries."""
+    if not (torch.is_tensor(seq_len) and seq_len.dtype == torch.int32 and seq_len.is_cuda and seq_len.is_contiguous()
+            and seq_len.numel() >= batch):
+        raise _ffi.VltfError("%s: seq_len must be a contiguous int32 device tensor of at least %d entries" % (what, batch))
+    return seq_len
+
+
+def lstm_seq_fwd(gx, kh, act, cseq, hseq, hprev, batch, T, H, forget_bias=1.0, ws=None, h0=None, c0=None, seq_len=None):
+    """All T steps in one launch; kh = kernel[D:] view ([H, 4H]); h0 / c0: initial state [batch, H] (None = zeros).
+    seq_len: int32 device tensor [batch] of per-clip lengths (vl_lstm_seq_fwd_len: dead steps carry the state and output zero)."""
     _f32(gx, kh, act, cseq, hseq, hprev, h0, c0, ws)
     if ws is None:
         raise _ffi.VltfError("lstm_seq_fwd: a workspace from lstm_seq_ws() is required")
+    if seq_len is not None:
+        _ffi.call("vl_lstm_seq_fwd_len", _p(gx), _p(kh), _p(h0), _p(c0), _p(act), _p(cseq), _p(hseq), _p(hprev), batch, T, H,
+                  forget_bias, _p(_seq_len(seq_len, batch, "lstm_seq_fwd")), _p(ws), ws.numel() * 4, stream())
+        return
     _ffi.call("vl_lstm_seq_fwd", _p(gx), _p(kh), _p(h0), _p(c0), _p(act), _p(cseq), _p(hseq), _p(hprev), batch, T, H, forget_bias,
               _p(ws), ws.numel() * 4, stream())
 
 
-def lstm_seq_bwd(dout, kh, act, cseq, dz, batch, T, H, ws=None, c0=None, dh0=None, dc0=None):
-    """BPTT in one launch; kh = kernel[D:] view (not transposed); dh0 / dc0: optional outputs [batch, H]."""
+def lstm_seq_bwd(dout, kh, act, cseq, dz, batch, T, H, ws=None, c0=None, dh0=None, dc0=None, seq_len=None):
+    """BPTT in one launch; kh = kernel[D:] view (not transposed); dh0 / dc0: optional outputs [batch, H].
+    seq_len: the lengths given to the forward call (vl_lstm_seq_bwd_len: dead rows of dout are ignored, their dz is 0)."""
     _f32(dout, kh, act, cseq, dz, c0, dh0, dc0, ws)
     if ws is None:
         raise _ffi.VltfError("lstm_seq_bwd: a workspace from lstm_seq_ws() is required")
+    if seq_len is not None:
+        _ffi.call("vl_lstm_seq_bwd_len", _p(dout), _p(kh), _p(act), _p(cseq), _p(c0), _p(dz), _p(dh0), _p(dc0), batch, T, H,
+                  _p(_seq_len(seq_len, batch, "lstm_seq_bwd")), _p(ws), ws.numel() * 4, stream())
+        return
     _ffi.call("vl_lstm_seq_bwd", _p(dout), _p(kh), _p(act), _p(cseq), _p(c0), _p(dz), _p(dh0), _p(dc0), batch, T, H, _p(ws),
               ws.numel() * 4, stream())
 
@@ -539,13 +557,22 @@ def transpose(src, dst, rows, cols, ld=None):
 FUSION_CODE = {"avg": 0, "last": 1}
 
 
-def temporal_fusion_fwd(x, y, batch, T, H, method):
+def temporal_fusion_fwd(x, y, batch, T, H, method, seq_len=None):
+    """seq_len: int32 device tensor [batch]; clip b fuses its first seq_len[b] steps (last = step len - 1, avg = sum / len)."""
     _f32(x, y)
+    if seq_len is not None:
+        _ffi.call("vl_temporal_fusion_fwd_len", _p(x), _p(y), batch, T, H, FUSION_CODE[method],
+                  _p(_seq_len(seq_len, batch, "temporal_fusion_fwd")), stream())
+        return
     _ffi.call("vl_temporal_fusion_fwd", _p(x), _p(y), batch, T, H, FUSION_CODE[method], stream())
 
 
-def temporal_fusion_bwd(dy, dx, batch, T, H, method):
+def temporal_fusion_bwd(dy, dx, batch, T, H, method, seq_len=None):
     _f32(dy, dx)
+    if seq_len is not None:
+        _ffi.call("vl_temporal_fusion_bwd_len", _p(dy), _p(dx), batch, T, H, FUSION_CODE[method],
+                  _p(_seq_len(seq_len, batch, "temporal_fusion_bwd")), stream())
+        return
     _ffi.call("vl_temporal_fusion_bwd", _p(dy), _p(dx), batch, T, H, FUSION_CODE[method], stream())
 
 
@@ -566,8 +593,10 @@ def dropout_bwd(dy, mask, dx, keep):
 
 
 # ---- loss / optimizer ----------------------------------------------------------------------------
-def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None):
-    """rows: float32 workspace of >= 2*batch elements (per-row losses and hits); without it one workgroup walks the batch."""
+def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None, seq_len=None, T=None):
+    """rows: float32 workspace of >= 2*batch elements (per-row losses and hits); without it one workgroup walks the batch.
+    seq_len with T: the rows are the steps of batch / T sequences; row b T + t with t >= seq_len[b] is padding -- not read, nothing
+    added to `stats`, dlogits 0 (vl_softmax_xent_len; grad_scale is the caller's 1 / live rows)."""
     _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
     if labels.dtype != torch.int32:
         raise _ffi.VltfError("softmax_xent: labels must be int32 one-hot")
@@ -576,6 +605,12 @@ def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None):
         _f32(rows)
         if rows.numel() < 2 * b:
             raise _ffi.VltfError("softmax_xent: rows workspace needs 2*batch floats")
+    if seq_len is not None:
+        if not T or T < 1 or b % int(T):
+            raise _ffi.VltfError("softmax_xent: seq_len needs T with rows = clips * T (rows %d, T %s)" % (b, T))
+        _ffi.call("vl_softmax_xent_len", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale,
+                  _p(_seq_len(seq_len, b // int(T), "softmax_xent")), int(T), stream())
+        return
     _ffi.call("vl_softmax_xent", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, stream())
 
 
