@@ -18,7 +18,7 @@
  *     [kh][kw][cin/group][cout] (alexnet.py:73,113), fc weights [in][out] (alexnet.py:225),
  *     LSTM kernel [D+H][4H] with gate order i, j, f, o (TF BasicLSTMCell; lstm.py:17).
  *   - Thread-compatible: one stream/descriptor set per host thread (exceptions, both process-wide words: vl_set_conv_math
- *     and the test hooks vl_lstm_seq_test_hooks, vl_pool_lrn_bwd_test_ranges).
+ *     and the test hooks vl_lstm_seq_test_hooks, vl_pool_lrn_bwd_test_ranges, vl_conv_set_row_classes).
  */
 #ifndef VLTF_H
 #define VLTF_H
@@ -106,6 +106,14 @@ int vl_conv_x_phase(const vl_conv_desc* d);
  * different modes need an external lock around (set, launches). */
 int vl_set_conv_math(int math);
 int vl_conv_math(void);
+/* Test hook of vl_conv_fwd / vl_conv_dgrad in fp32 arithmetic, process-wide, default on.  A stride-1 layer with kh > 1 in the padded
+ * layout whose launch has many frames enumerates its output pixels by ROW CLASS (runs of output rows that share one set of in-range
+ * kernel rows: 3 x 3 pad 1 gives {0}, {1 .. OH-2}, {OH-1}), every 128-pixel tile inside one class, and a tile's reduction leaves out
+ * the kernel rows that lie in the SAME-padding halo for all of its pixels.  Those terms are w * (+0) added to a sum that starts at +0:
+ * for finite weights the results are bitwise those of on = 0, which enumerates pixels flat and multiplies the halo's zeros like data.
+ * The one difference: with on = 0 a non-finite weight reaches every output through its padding taps as well (inf * 0 = NaN); with
+ * on = 1 it no longer poisons the border rows through the kernel rows left out. */
+int vl_conv_set_row_classes(int on);
 /* y[n][cout][oh][ow] = conv(x[n][cin][h][w], w_hwio) + bias, optional fused ReLU (alexnet.py:77). */
 int vl_conv_fwd(const vl_conv_desc* d, const float* x, const float* w_hwio, const float* bias, float* y,
                 int n, int relu, vl_stream_t stream);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Runs one AlexNet conv layer's fwd / dgrad / wgrad kernels in isolation (for rocprofv3 / timing).
-usage: conv_probe.py <conv1..conv5> <fwd|dgrad|wgrad> [frames] [iters]"""
+usage: conv_probe.py <conv1..conv5> <fwd|dgrad|wgrad> [frames] [iters]
+VL_PROBE_ROW_CLASSES=0: the flat pixel order of fwd / dgrad (ops.conv_set_row_classes)."""
 import os
 import sys
 import time
@@ -34,6 +35,7 @@ def main():
     yh = int(os.environ.get("VL_PROBE_YHALO", "0"))             # halo of the OUTPUT (y of fwd, dx of dgrad): the engine's 13 x 13 layers write
     dxh = int(os.environ.get("VL_PROBE_DXHALO", "0"))           # into halo layouts (y3, y4: 1; dp2, dy3, dy4: 1; dp1: 2)
     conv.set_halo(xh, yh, dyh, dxh)
+    ops.conv_set_row_classes(os.environ.get("VL_PROBE_ROW_CLASSES", "1") != "0")
     if s > 1 and padded and os.environ.get("VL_PROBE_NO_PHASE") is None:
         conv.set_x_phase_split(True)            # the engine's layout of a strided conv's input (vl_conv_set_x_phase_split)
 

@@ -4,6 +4,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// Row classes of a forward / dgrad launch (build_ktabs): maximal runs of output rows that share one set of in-range kernel rows, in
+// dispatch order (longest reduction first).  A class whose every kernel row is in range uses the full tables (tab0 = rt0 = 0).
+struct vl_conv_rowcls {
+    int ncls;       // 0: the launch has none (one kernel row, strided, phase split, unpermuted order, or more than 5 classes)
+    int oh0[5];     // first output row
+    int rows[5];    // output rows
+    int K[5];       // reduction length: in-range kernel rows * kw * channels per group
+    int tab0[5];    // first entry of the class's gather table within ptab_*
+    int rt0[5];     // first entry of its row table within rowtab_*
+};
+
 struct vl_conv_desc {
     int cin, h, w, cout, kh, kw, stride, groups;
     int oh, ow, pt, pl, pb, pr;   // SAME padding before / after
@@ -23,6 +34,7 @@ struct vl_conv_desc {
     int* rowtab_fwd;
     int* rowtab_bwd;
     int fwd_padded, bwd_padded;
+    vl_conv_rowcls rc_fwd, rc_bwd;
     uint32_t* wsplit_fwd;   // conv_wsplit_kernel's image of the forward / dgrad weights (split-product arithmetic only)
     uint32_t* wsplit_bwd;
     int* c8_toff_fwd;       // conv_c8.hip: byte offset of every reduction tap (channel block, ky, kx) in the c8 layout, forward / dgrad

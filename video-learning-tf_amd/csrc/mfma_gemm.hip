@@ -1050,8 +1050,68 @@ struct ConvDmaParams {
     int nblk;                // ceil(K / 16) blocks
 };
 
+// Pixel order of a conv_dma launch.  The pixel axis of forward and dgrad is the OUTPUT axis, so it may be enumerated in any order
+// without touching a sum.  The flat order (frame, oh, ow) is one class of all OH rows; with row classes (vl_conv_rowcls) the tile
+// pixel index enumerates (class, frame, row within the class, ow), every class segment rounded up to whole 128-pixel tiles, so that
+// a tile is uniform in the set of kernel rows that are in range and its reduction runs over the class's own tables: the taps that
+// read only the SAME-padding halo for every pixel of the tile are not fetched and not multiplied.  A skipped term is fma(w, +0, acc)
+// on an accumulator that starts at +0 and can never become -0: it returns acc bit for bit (finite w), and the order of the other
+// terms is the full table's, so outputs are bitwise those of the flat order.
+// Workgroups blockIdx.x in [wg0[c], wg0[c + 1]) are class c's (tiles_i x its pixel tiles, XCD-swizzled within the class, so each XCD
+// gets its share of every class); the long class comes first and the short ones fill the tail of the launch.
+struct ConvRowClasses {
+    int ncls;
+    int wg0[6];
+    int S[5];                // pixels of the class: frames * rows * OW
+    int oh0[5], RW[5];       // first output row; rows * OW
+    FastDiv dRW[5];
+    int K[5], tab0[5], rt0[5];
+};
+
+struct ConvTile {            // one workgroup's tile, all scalars
+    int bid;                 // workgroup within its class, XCD-swizzled
+    int S, oh0, RW;
+    FastDiv dRW;
+    int K, nblk;             // the class's reduction length and 16-row blocks
+    const int* ktab;
+    const int* row_tab;
+};
+
+__device__ __forceinline__ ConvTile conv_pick_tile(const ConvRowClasses& rc, const ConvGeom& g, const ConvDmaParams& pa) {
+    const int id = blockIdx.x;
+    int w0 = 0, w1 = rc.wg0[1], S = rc.S[0], oh0 = rc.oh0[0], RW = rc.RW[0], K = rc.K[0], tab0 = rc.tab0[0], rt0 = rc.rt0[0];
+    FastDiv dRW = rc.dRW[0];
+#pragma unroll
+    for (int c = 1; c < 5; ++c) {
+        if (c < rc.ncls && id >= rc.wg0[c]) {
+            w0 = rc.wg0[c]; w1 = rc.wg0[c + 1]; S = rc.S[c]; oh0 = rc.oh0[c]; RW = rc.RW[c]; K = rc.K[c]; tab0 = rc.tab0[c]; rt0 = rc.rt0[c];
+            dRW = rc.dRW[c];
+        }
+    }
+    ConvTile t;
+    t.bid = xcd_swizzle(id - w0, w1 - w0);
+    t.S = S; t.oh0 = oh0; t.RW = RW; t.dRW = dRW; t.K = K; t.nblk = (K + KBLK - 1) / KBLK;
+    t.ktab = g.ktab + tab0;
+    t.row_tab = pa.row_tab + rt0;
+    return t;
+}
+
+// pixel m of a class segment -> frame n, output row oh, column ow, and p = its offset within the frame's rows of the class
+struct ConvPixel {
+    uint32_t n, p, oh, ow;
+};
+__device__ __forceinline__ ConvPixel conv_tile_pixel(const ConvTile& t, uint32_t m, const FastDiv& dOW, int OW) {
+    ConvPixel q;
+    q.n = fd_div(m, t.dRW);
+    q.p = m - q.n * t.RW;
+    const uint32_t r = fd_div(q.p, dOW);
+    q.ow = q.p - r * OW;
+    q.oh = r + t.oh0;
+    return q;
+}
+
 template <int SR>   // reduction rows per stage: 64 (one workgroup per CU) or 32 (two: one's epilogue under the other's MFMAs)
-__global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe,
+__global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe, const ConvRowClasses rc,
                                                                int tiles_i, int wide) {
     constexpr int BM = 128, BN = 128;
     constexpr int ABUF = SR * BM, BUF = SR * (BM + BN);               // floats: A tile, whole buffer
@@ -1061,8 +1121,8 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
     constexpr int FPM = 1;                                            // fetches per MFMA shadow (2 measured equal: latency is not the limit)
     static_assert(SR == 64 || SR == 32, "stage depth");
     extern __shared__ __attribute__((aligned(16))) float ldsc[];
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int ti_blk = bid % tiles_i, tj_blk = bid / tiles_i;
+    const ConvTile tl = conv_pick_tile(rc, g, pa);
+    const int ti_blk = tl.bid % tiles_i, tj_blk = tl.bid / tiles_i;   // tj_blk: pixel tile within the class segment
     const int zg = blockIdx.y;
     const int i0 = ti_blk * BM, j0 = tj_blk * BN;
     const int lane = threadIdx.x & 63;
@@ -1078,14 +1138,10 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
         const int co = i0 + hf * 64 + lane;
         voff_a[hf] = co < pe.Cog ? (uint32_t)co * 4u : OOB_OFF;
         const int m = j0 + hf * 64 + lane;
-        const bool vm = m < g.M;
-        const uint32_t mm = vm ? m : 0;
-        const uint32_t n = fd_div(mm, g.dOHW);
-        const uint32_t p = mm - n * g.OHW;
-        const uint32_t oh = fd_div(p, g.dOW);
-        const uint32_t ow = p - oh * g.OW;
-        const int ih0 = (int)oh * g.stride - g.pt + g.halo, iw0 = (int)ow * g.col_mul + g.col_add;
-        voff_b[hf] = vm ? (uint32_t)((int64_t)n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
+        const bool vm = m < tl.S;
+        const ConvPixel q = conv_tile_pixel(tl, vm ? m : 0, g.dOW, g.OW);
+        const int ih0 = (int)q.oh * g.stride - g.pt + g.halo, iw0 = (int)q.ow * g.col_mul + g.col_add;
+        voff_b[hf] = vm ? (uint32_t)((int64_t)q.n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
     }
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ldsc;
     const int ld_bytes = (int)(pa.w_ld * 4);
@@ -1097,11 +1153,11 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
     const int wrow = wave * RW;                                       // first stage row of this wave
     auto load_table = [&](int st) {
         const int k0 = st * SR + wrow;                                // position in the reduction order
-        const const_int_ptr tt = as_const(g.ktab) + k0 + st * g.zero;
+        const const_int_ptr tt = as_const(tl.ktab) + k0 + st * g.zero;
 #pragma unroll
         for (int f = 0; f < RW; ++f) tabv[f] = tt[f];
-        row0 = as_const(pa.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
-        blk_ok = k0 / KBLK < pa.nblk;                                 // blocks past K: both operands fetch zeros
+        row0 = as_const(tl.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
+        blk_ok = k0 / KBLK < tl.nblk;                                 // blocks past K: both operands fetch zeros
     };
     auto pin_table = [&]() {
 #pragma unroll
@@ -1115,7 +1171,7 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
         const uint32_t row_lds = lds0 + (uint32_t)(nb * BUF + (wrow + rr) * 128 + hf * 64 + z) * 4u;
         // reduction positions past K (the tail of a last, partial 16-block; whole blocks past the end): the im2col side
         // fetches zeros (range check) and the weight side re-reads row K - 1, so the product is exactly 0 and stays in bounds
-        const bool live = blk_ok && st * SR + wrow + rr < g.K;
+        const bool live = blk_ok && st * SR + wrow + rr < tl.K;
         if (kind < 2) lds_dma_row(rs_w, row_lds, voff_a[hf], min(row0 + rr, g.K - 1) * ld_bytes);
         else lds_dma_row(rs_x, row_lds + ABUF * 4u, live ? voff_b[hf] : OOB_OFF, tabv[rr]);
     };
@@ -1145,7 +1201,7 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
 
-    const int nstages = (pa.nblk * KBLK + SR - 1) / SR;
+    const int nstages = (tl.nblk * KBLK + SR - 1) / SR;
     load_table(0);
     pin_table();
 #pragma unroll
@@ -1220,7 +1276,7 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
         finish_stage();
     };
     // stages 0 .. nfull-1 lie entirely below K: a stage whose prefetch target is one of them runs the fast fetch form
-    const int nfull = g.K / SR;
+    const int nfull = tl.K / SR;
     int st = 0;
     for (; st + 2 < nfull; st += 2) {
         stage(0, true, st + 1);
@@ -1251,10 +1307,11 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
         __syncthreads();
         const int px = 4 * (lane & 31);
         const int m = j0 + px;
-        const uint32_t n = fd_div((uint32_t)min(m, pe.M - 1), pe.dOHW);
-        const int p = m - (int)n * pe.OHW;
-        const bool run4 = m + 3 < pe.M && p + 3 < pe.OHW;
-        const int64_t cbase = ((int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog) * pe.y_plane + p;
+        // y_halo == 0 here: the class's rows of a frame are one contiguous run of the plane, from row oh0
+        const uint32_t n = fd_div((uint32_t)min(m, tl.S - 1), tl.dRW);
+        const int p = m - (int)n * tl.RW;
+        const bool run4 = m + 3 < tl.S && p + 3 < tl.RW; 
+        const int64_t cbase = ((int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog) * pe.y_plane + tl.oh0 * pe.OW + p;
 #pragma unroll
         for (int i = 0; i < BM / 8; ++i) {                             // 2 channel rows per wave instruction, 32 rows per wave
             const int cl = wave * (BM / 4) + 2 * i + (lane >> 5);
@@ -1268,9 +1325,9 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int me = m + e;
-                    if (me < pe.M) {
-                        const uint32_t ne = fd_div((uint32_t)me, pe.dOHW);
-                        const int pe_ = me - (int)ne * pe.OHW;
+                    if (me < tl.S) {
+                        const uint32_t ne = fd_div((uint32_t)me, tl.dRW);
+                        const int pe_ = me - (int)ne * tl.RW + tl.oh0 * pe.OW;
                         pe.y[((int64_t)ne * pe.Cout_total + (int64_t)zg * pe.Cog + co) * pe.y_plane + pe_] = v[e];
                     }
                 }
@@ -1281,14 +1338,11 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const int m = j0 + wn * 64 + 32 * b + (lane & 31);
-        if (m >= pe.M) continue;
-        const uint32_t n = fd_div((uint32_t)m, pe.dOHW);
-        const uint32_t p = m - n * pe.OHW;
-        const uint32_t oh = fd_div(p, pe.dOW);
-        const uint32_t ow = p - oh * pe.OW;
-        const int64_t c0 = (int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog;
-        const int64_t ybase = c0 * pe.y_plane + (int64_t)(oh + pe.y_halo) * pe.y_wp + ow + pe.y_halo;
-        const int64_t mbase = c0 * pe.m_plane + (int64_t)(oh + pe.m_halo) * pe.m_wp + ow + pe.m_halo;
+        if (m >= tl.S) continue;
+        const ConvPixel px = conv_tile_pixel(tl, m, pe.dOW, pe.OW);
+        const int64_t c0 = (int64_t)px.n * pe.Cout_total + (int64_t)zg * pe.Cog;
+        const int64_t ybase = c0 * pe.y_plane + (int64_t)(px.oh + pe.y_halo) * pe.y_wp + px.ow + pe.y_halo;
+        const int64_t mbase = c0 * pe.m_plane + (int64_t)(px.oh + pe.m_halo) * pe.m_wp + px.ow + pe.m_halo;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             float mk[16];                                          // mask loads of these 16 channels first, all in flight (conv_dma16_kernel)
@@ -1918,6 +1972,14 @@ extern "C" int vl_set_conv_math(int math) {
 
 extern "C" int vl_conv_math(void) { return g_conv_math; }
 
+// tests: vl_conv_set_row_classes(0) runs the many-frames fp32 LDS-DMA launches in the flat pixel order (ConvRowClasses)
+static int g_conv_row_classes = 1;
+
+extern "C" int vl_conv_set_row_classes(int on) {
+    g_conv_row_classes = on ? 1 : 0;
+    return 0;
+}
+
 // ---- convolution descriptor -------------------------------------------------------------------
 // struct vl_conv_desc: conv_desc.h (shared with conv_c8.hip)
 
@@ -1972,16 +2034,39 @@ static int upload(T** dev, const T* host, size_t count) {
 //   phase > 1 (padded mode only): the tensor is stored column-phase-split, [c][phase][H + 2 halo][ceil((W + 2 halo) / phase)]
 //   with physical column iw at [iw % phase][iw / phase]; tap kx of output column ow is physical column ow * phase + kx +
 //   col_shift, so its phase and its offset within the phase plane depend on the tap only -> still "table entry + pixel".
+//   rc != null (stride-1 forward / dgrad, `pt` rows of padding above, OHout output rows): the row classes of the launch and, behind
+//   the full tables in the same allocations, every class's own gather table and row table: the full ones in the same order with the
+//   taps of out-of-range kernel rows (which read nothing but the halo's zeros for every output row of the class) absent.
 static int build_ktabs(int** dev1, int2** dev2, int** rowtab, int kh, int kw, int cg, int H, int W, int halo, bool permuted,
-                       int phase = 1, int col_shift = 0) {
+                       int phase = 1, int col_shift = 0, vl_conv_rowcls* rc = nullptr, int pt = 0, int OHout = 0) {
     const int K = kh * kw * cg;
     const int pad = ((K + 127) / 128) * 128 + 256;
     const int Wp = phase > 1 ? (W + 2 * halo + phase - 1) / phase : W + 2 * halo;
     const int64_t Pp = (int64_t)(H + 2 * halo) * Wp;
     const int ntiles = pad / KBLK;
-    int* h1 = (int*)malloc(sizeof(int) * pad);
+    // row classes: output row o reaches kernel rows lo(o) .. hi(o) of the logical plane
+    int ncls = 0, c_oh0[5], c_rows[5], c_lo[5], c_hi[5];
+    if (rc) {
+        rc->ncls = 0;
+        if (permuted && kh > 1 && phase == 1 && rowtab) {
+            for (int o = 0; o < OHout; ++o) {
+                const int lo = pt - o > 0 ? pt - o : 0, hi = H - 1 + pt - o < kh - 1 ? H - 1 + pt - o : kh - 1;
+                if (lo > hi) { ncls = 0; break; }                         // a row of padding only: leave such a layer alone
+                if (ncls > 0 && c_lo[ncls - 1] == lo && c_hi[ncls - 1] == hi) {
+                    ++c_rows[ncls - 1];
+                } else {
+                    if (ncls == 5) { ncls = 0; break; }
+                    c_oh0[ncls] = o; c_rows[ncls] = 1; c_lo[ncls] = lo; c_hi[ncls] = hi;
+                    ++ncls;
+                }
+            }
+            if (ncls < 2) ncls = 0;
+        }
+    }
+    const int slots = ncls + 1;
+    int* h1 = (int*)calloc((size_t)pad * slots, sizeof(int));
     int2* h2 = (int2*)malloc(sizeof(int2) * pad);
-    int* h3 = (int*)malloc(sizeof(int) * ntiles);
+    int* h3 = (int*)calloc((size_t)ntiles * slots, sizeof(int));
     if (!h1 || !h2 || !h3) {
         free(h1);
         free(h2);
@@ -2005,13 +2090,45 @@ static int build_ktabs(int** dev1, int2** dev2, int** rowtab, int kh, int kw, in
             if (k % KBLK == 0) h3[k / KBLK] = 0;
         }
     }
-    int rc = upload(dev1, h1, pad);
-    if (rc == 0) rc = upload(dev2, h2, pad);
-    if (rc == 0 && rowtab) rc = upload(rowtab, h3, ntiles);
+    size_t n1 = pad, n3 = ntiles;
+    if (ncls) {
+        // dispatch order: longest reduction first (stable: equal lengths keep their row order)
+        int order[5];
+        for (int i = 0; i < ncls; ++i) order[i] = i;
+        for (int i = 1; i < ncls; ++i)
+            for (int j = i; j > 0 && c_hi[order[j]] - c_lo[order[j]] > c_hi[order[j - 1]] - c_lo[order[j - 1]]; --j) {
+                const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t;
+            }
+        for (int i = 0; i < ncls; ++i) {
+            const int c = order[i], Kc = (c_hi[c] - c_lo[c] + 1) * kw * cg;
+            rc->oh0[i] = c_oh0[c]; rc->rows[i] = c_rows[c]; rc->K[i] = Kc;
+            if (Kc == K) {
+                rc->tab0[i] = 0; rc->rt0[i] = 0;
+                continue;
+            }
+            rc->tab0[i] = (int)n1; rc->rt0[i] = (int)n3;
+            int kc = 0;                                                   // a 16-row block is one tap: kept or dropped whole
+            for (int k = 0; k < K; ++k) {
+                int ky, kx, ch;
+                k_to_row(k, kh, kw, cg, true, &ky, &kx, &ch);
+                if (ky < c_lo[c] || ky > c_hi[c]) continue;
+                h1[n1 + kc] = h1[k];
+                if (kc % KBLK == 0) h3[n3 + kc / KBLK] = h3[k / KBLK];
+                ++kc;
+            }
+            n1 += ((Kc + 127) / 128) * 128 + 256;                         // zero entries behind it, as behind the full table
+            n3 += (((Kc + 127) / 128) * 128 + 256) / KBLK;
+        }
+        rc->ncls = ncls;
+    }
+    int rcode = upload(dev1, h1, n1);
+    if (rcode == 0) rcode = upload(dev2, h2, pad);
+    if (rcode == 0 && rowtab) rcode = upload(rowtab, h3, n3);
+    if (rcode && rc) rc->ncls = 0;
     free(h1);
     free(h2);
     free(h3);
-    return rc;
+    return rcode;
 }
 
 static int rebuild_tables(vl_conv_desc* d) {
@@ -2021,9 +2138,10 @@ static int rebuild_tables(vl_conv_desc* d) {
     int rc = build_ktabs(&d->ktab_fwd, &d->ktab2_fwd, nullptr, d->kh, d->kw, d->cig, d->h, d->w, d->x_halo, false, ph, shift);
     if (rc == 0)
         rc = build_ktabs(&d->ptab_fwd, &d->ptab2_fwd, &d->rowtab_fwd, d->kh, d->kw, d->cig, d->h, d->w, d->x_halo, d->cig % KBLK == 0, ph,
-                         shift);
+                         shift, d->stride == 1 ? &d->rc_fwd : nullptr, d->pt, d->oh);
     if (rc == 0 && d->stride == 1) {
-        rc = build_ktabs(&d->ptab_bwd, &d->ptab2_bwd, &d->rowtab_bwd, d->kh, d->kw, d->cog, d->oh, d->ow, d->dy_halo, d->cog % KBLK == 0);
+        rc = build_ktabs(&d->ptab_bwd, &d->ptab2_bwd, &d->rowtab_bwd, d->kh, d->kw, d->cog, d->oh, d->ow, d->dy_halo, d->cog % KBLK == 0, 1,
+                         0, &d->rc_bwd, d->kh - 1 - d->pt, d->h);
         // dgrad pads dy by K-1-pad before and by the forward pad-before after
         const int need = (d->kh - 1 - d->pt > d->pt ? d->kh - 1 - d->pt : d->pt);
         const int needw = (d->kw - 1 - d->pl > d->pl ? d->kw - 1 - d->pl : d->pl);
@@ -2145,7 +2263,7 @@ static int launch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_gr
 // y[co = 4 (l >> 4) + q][pixel = l & 15].
 
 template <int TA>   // channel tiles of 16 per workgroup: 3 (48 channels: conv2 dgrad) or 6 (96: the 192-channel layers)
-__global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe,
+__global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe, const ConvRowClasses rc,
                                                            int tiles_i, int wide) {
     constexpr int BM = 16 * TA, BN = 128, SR = 32;
     constexpr int NA = (BM + 63) / 64;                                // 64-lane fetches per weight row
@@ -2154,8 +2272,8 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
     constexpr int RW = SR / 4, FPR = NA + 2, NF = RW * FPR, NSTEP = SR / 4;   // rows per wave, fetches per row / per wave, k4-steps
     constexpr int NM = 2 * TA;                                        // MFMAs per k4-step
     extern __shared__ __attribute__((aligned(16))) float ldsc[];
-    const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int ti_blk = bid % tiles_i, tj_blk = bid / tiles_i;
+    const ConvTile tl = conv_pick_tile(rc, g, pa);
+    const int ti_blk = tl.bid % tiles_i, tj_blk = tl.bid / tiles_i;   // tj_blk: pixel tile within the class segment
     const int zg = blockIdx.y;
     const int i0 = ti_blk * BM, j0 = tj_blk * BN;
     const int lane = threadIdx.x & 63;
@@ -2173,14 +2291,10 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
         const int m = j0 + hf * 64 + lane;
-        const bool vm = m < g.M;
-        const uint32_t mm = vm ? m : 0;
-        const uint32_t n = fd_div(mm, g.dOHW);
-        const uint32_t p = mm - n * g.OHW;
-        const uint32_t oh = fd_div(p, g.dOW);
-        const uint32_t ow = p - oh * g.OW;
-        const int ih0 = (int)oh * g.stride - g.pt + g.halo, iw0 = (int)ow * g.col_mul + g.col_add;
-        voff_b[hf] = vm ? (uint32_t)((int64_t)n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
+        const bool vm = m < tl.S;
+        const ConvPixel q = conv_tile_pixel(tl, vm ? m : 0, g.dOW, g.OW);
+        const int ih0 = (int)q.oh * g.stride - g.pt + g.halo, iw0 = (int)q.ow * g.col_mul + g.col_add;
+        voff_b[hf] = vm ? (uint32_t)((int64_t)q.n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
     }
     // this lane's bias values, loaded before the main loop: fetched inside the epilogue (one dependent load in front of each of
     // the 48 stores) they cost conv1's forward 0.5 of its 2.4 ms (a run with the stores removed: 1.9 ms)
@@ -2201,11 +2315,11 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
     const int wrow = wave * RW;
     auto load_table = [&](int st) {
         const int k0 = st * SR + wrow;
-        const const_int_ptr tt = as_const(g.ktab) + k0 + st * g.zero;
+        const const_int_ptr tt = as_const(tl.ktab) + k0 + st * g.zero;
 #pragma unroll
         for (int f = 0; f < RW; ++f) tabv[f] = tt[f];
-        row0 = as_const(pa.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
-        blk_ok = k0 / KBLK < pa.nblk;
+        row0 = as_const(tl.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
+        blk_ok = k0 / KBLK < tl.nblk;
     };
     auto pin_table = [&]() {
 #pragma unroll
@@ -2215,7 +2329,7 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
     auto dma = [&](const int nb, const int f, int st) {                // f = FPR rr + {weight row pieces, then the two im2col halves}
         const int rr = f / FPR, kind = f % FPR;
         const int z = st * g.zero;
-        const bool live = blk_ok && st * SR + wrow + rr < g.K;         // positions past K: see conv_dma_kernel
+        const bool live = blk_ok && st * SR + wrow + rr < tl.K;         // positions past K: see conv_dma_kernel
         if (kind < NA) {
             lds_dma_row(rs_w, lds0 + (uint32_t)(nb * BUF + (wrow + rr) * SA + kind * 64 + z) * 4u, voff_a[kind],
                         min(row0 + rr, g.K - 1) * ld_bytes);
@@ -2251,7 +2365,7 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc[a][b][q] = 0.f;
 
-    const int nstages = (pa.nblk * KBLK + SR - 1) / SR;
+    const int nstages = (tl.nblk * KBLK + SR - 1) / SR;
     load_table(0);
     pin_table();
 #pragma unroll
@@ -2310,8 +2424,8 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
         }
         finish_stage();
     };
-    const int nfull = g.K / SR;                                        // stages entirely below K (see conv_dma_kernel)
-    const int last_steps = (g.K - (nstages - 1) * SR + 3) / 4;         // live k4-steps of the last stage
+    const int nfull = tl.K / SR;                                        // stages entirely below K (see conv_dma_kernel)
+    const int last_steps = (tl.K - (nstages - 1) * SR + 3) / 4;         // live k4-steps of the last stage
     int st = 0;
     for (; st + 2 < nfull; st += 2) {
         stage(0, true, st + 1, NSTEP);
@@ -2344,10 +2458,11 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
         __syncthreads();
         const int px = 4 * (lane & 31);
         const int m = j0 + px;
-        const uint32_t n = fd_div((uint32_t)min(m, pe.M - 1), pe.dOHW);
-        const int p = m - (int)n * pe.OHW;
-        const bool run4 = m + 3 < pe.M && p + 3 < pe.OHW;              // four pixels of one image: contiguous
-        const int64_t cbase = ((int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog) * pe.y_plane + p;
+        // y_halo == 0 here: the class's rows of a frame are one contiguous run of the plane, from row oh0
+        const uint32_t n = fd_div((uint32_t)min(m, tl.S - 1), tl.dRW);
+        const int p = m - (int)n * tl.RW;
+        const bool run4 = m + 3 < tl.S && p + 3 < tl.RW;               // four pixels of one image: contiguous
+        const int64_t cbase = ((int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog) * pe.y_plane + tl.oh0 * pe.OW + p;
 #pragma unroll
         for (int i = 0; i < BM / 8; ++i) {                             // 2 channel rows per wave instruction, BM / 4 rows per wave
             const int cl = wave * (BM / 4) + 2 * i + (lane >> 5);
@@ -2361,9 +2476,9 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int me = m + e;
-                    if (me < pe.M) {
-                        const uint32_t ne = fd_div((uint32_t)me, pe.dOHW);
-                        const int pe_ = me - (int)ne * pe.OHW;
+                    if (me < tl.S) {
+                        const uint32_t ne = fd_div((uint32_t)me, tl.dRW);
+                        const int pe_ = me - (int)ne * tl.RW + tl.oh0 * pe.OW;
                         pe.y[((int64_t)ne * pe.Cout_total + (int64_t)zg * pe.Cog + co) * pe.y_plane + pe_] = v[e];
                     }
                 }
@@ -2374,14 +2489,11 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const int m = j0 + wave * 32 + 16 * b + (lane & 15);
-        if (m >= pe.M) continue;
-        const uint32_t n = fd_div((uint32_t)m, pe.dOHW);
-        const uint32_t p = m - n * pe.OHW;
-        const uint32_t oh = fd_div(p, pe.dOW);
-        const uint32_t ow = p - oh * pe.OW;
-        const int64_t c0 = (int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog;
-        const int64_t ybase = c0 * pe.y_plane + (int64_t)(oh + pe.y_halo) * pe.y_wp + ow + pe.y_halo;
-        const int64_t mbase = c0 * pe.m_plane + (int64_t)(oh + pe.m_halo) * pe.m_wp + ow + pe.m_halo;
+        if (m >= tl.S) continue;
+        const ConvPixel px = conv_tile_pixel(tl, m, pe.dOW, pe.OW);
+        const int64_t c0 = (int64_t)px.n * pe.Cout_total + (int64_t)zg * pe.Cog;
+        const int64_t ybase = c0 * pe.y_plane + (int64_t)(px.oh + pe.y_halo) * pe.y_wp + px.ow + pe.y_halo;
+        const int64_t mbase = c0 * pe.m_plane + (int64_t)(px.oh + pe.m_halo) * pe.m_wp + px.ow + pe.m_halo;
         float mk[TA][4];                                          // mask loads first, all in flight (see conv_dma16p_kernel)
         if (pe.mask) {
 #pragma unroll
@@ -2413,7 +2525,7 @@ static int device_cus();
 
 template <int BM>   // 128: conv_dma_kernel (32x32 MFMA tiles); 48 / 96: conv_dma16_kernel (16x16 tiles)
 static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
-                           int Cout_total, const ConvOut& o, hipStream_t s) {
+                           int Cout_total, const ConvOut& o, hipStream_t s, const vl_conv_rowcls* rcd = nullptr) {
     constexpr int BN = 128, SR = 32;
     // 128-wide: 64 KB of stage buffers, 66 KB with the wide-store staging tile [128][132] (two workgroups per CU either way)
     constexpr size_t lds = BM == 128 ? (size_t)BM * (BN + 4) * sizeof(float)
@@ -2434,14 +2546,30 @@ static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int 
         VL_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
-    const int tiles_i = ceil_div(Cog, BM), tiles_j = ceil_div(g.M, BN);
-    dim3 grid(tiles_i * tiles_j, (unsigned)(Cout_total / Cog), 1);
+    // pixel order: the row classes of the layer (ConvRowClasses), or the flat order as ONE class of all rows
+    const int tiles_i = ceil_div(Cog, BM);
+    ConvRowClasses rc;
+    memset(&rc, 0, sizeof(rc));
+    if (rcd && rcd->ncls > 1 && g_conv_row_classes) {
+        const int nimg = g.M / g.OHW;
+        rc.ncls = rcd->ncls;
+        for (int c = 0; c < rc.ncls; ++c) {
+            rc.RW[c] = rcd->rows[c] * g.OW; rc.dRW[c] = make_fastdiv(rc.RW[c]); rc.S[c] = nimg * rc.RW[c];
+            rc.oh0[c] = rcd->oh0[c]; rc.K[c] = rcd->K[c]; rc.tab0[c] = rcd->tab0[c]; rc.rt0[c] = rcd->rt0[c];
+            rc.wg0[c + 1] = rc.wg0[c] + tiles_i * ceil_div(rc.S[c], BN);
+        }
+    } else {
+        rc.ncls = 1;
+        rc.RW[0] = g.OHW; rc.dRW[0] = g.dOHW; rc.S[0] = g.M; rc.K[0] = g.K;
+        rc.wg0[1] = tiles_i * ceil_div(g.M, BN);
+    }
+    dim3 grid(rc.wg0[rc.ncls], (unsigned)(Cout_total / Cog), 1);
     // wide-store epilogue: dense output planes, no mask, and the [BM][132] staging tile must fit the LDS allocation
     const int wide = (o.y_halo == 0 && !o.mask && !kConvNoWideStore && (size_t)BM * (BN + 4) * sizeof(float) <= lds) ? 1 : 0;
     if constexpr (BM == 128) {
-        hipLaunchKernelGGL(conv_dma_kernel<SR>, grid, dim3(NT), lds, s, pa, g, pe, tiles_i, wide);
+        hipLaunchKernelGGL(conv_dma_kernel<SR>, grid, dim3(NT), lds, s, pa, g, pe, rc, tiles_i, wide);
     } else {
-        hipLaunchKernelGGL((conv_dma16_kernel<BM / 16>), grid, dim3(NT), lds, s, pa, g, pe, tiles_i, wide);
+        hipLaunchKernelGGL((conv_dma16_kernel<BM / 16>), grid, dim3(NT), lds, s, pa, g, pe, rc, tiles_i, wide);
     }
     VL_LAUNCH_CHECK();
     return 0;
@@ -2495,7 +2623,7 @@ static int launch_conv_ring(const ConvGeom& g, const float* w, int64_t w_ld, int
 
 template <bool PADDED>
 static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
-                         int Cout_total, const ConvOut& o, uint32_t* wsplit, hipStream_t s) {
+                         int Cout_total, const ConvOut& o, uint32_t* wsplit, hipStream_t s, const vl_conv_rowcls* rcd) {
     // output-channel tile: 128 when it divides well, else 96 (conv1: 96, conv4: 192) or 64 (conv2 dgrad: 48)
     const int w128 = ceil_div(Cog, 128) * 128, w96 = ceil_div(Cog, 96) * 96, w64 = ceil_div(Cog, 64) * 64;
     // split products: the ring kernel (128-channel tiles; its 16-byte im2col fetches need unit column stride in memory)
@@ -2509,6 +2637,7 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
     // with the padded-row rule below (loads differ by the padding only), which then decides alone.
     const int64_t px = ceil_div(g.M, 128), cus = device_cus(), ngrp = Cout_total / Cog;
     const bool few = px * ceil_div(Cog, 128) * ngrp < 8 * cus;        // under 8 workgroups per CU at the widest tile: quantisation matters
+    // (the few-frames branch keeps the flat pixel order: its width pick and tail split count flat tiles)
     if (PADDED && few && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged && !kConvNoLoadPick) {
         const int widths[3] = {128, 96, 48};
         auto pick = [&](int64_t pxt, int64_t& load) {                 // width with the smallest per-CU load for pxt pixel tiles
@@ -2563,17 +2692,17 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
     if (w128 <= w96 && w128 <= w64) {
         // 128-wide tiles in the padded layout: the LDS-DMA kernel
         if (PADDED && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged) {
-            return launch_conv_dma<128>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
+            return launch_conv_dma<128>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
         }
         return launch_conv<128, 2, 2, PADDED>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
     }
     // 48-wide tiles beat the 64-wide ones whenever they waste fewer rows (conv2 dgrad: 48 channels per group)
     if (PADDED && ceil_div(Cog, 48) * 48 < w64 && ceil_div(Cog, 48) * 48 < w96 &&
         (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged)
-        return launch_conv_dma<48>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
+        return launch_conv_dma<48>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
     if (w96 <= w64) {
         if (PADDED && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged)
-            return launch_conv_dma<96>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
+            return launch_conv_dma<96>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
         return launch_conv<96, 1, 4, PADDED>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
     }
     return launch_conv<64, 1, 4, PADDED>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
@@ -2605,8 +2734,8 @@ extern "C" int vl_conv_fwd(const vl_conv_desc* d, const float* x, const float* w
     VL_CHECK(g.total * 4 < MAX_BUF_BYTES, "vl_conv_fwd: input of %lld elements exceeds the buffer-offset range", (long long)g.total);
     ConvOut o{y, bias, nullptr, relu, d->y_halo, 0, d->oh, d->ow};
     // HWIO weights are the [K][Cout_total] GEMM operand as they stand; group g = column block g*cog.
-    if (d->fwd_padded) return dispatch_conv<true>(g, w, d->cout, d->cog, d->rowtab_fwd, d->cog, d->cout, o, d->wsplit_fwd, (hipStream_t)stream);
-    return dispatch_conv<false>(g, w, d->cout, d->cog, d->rowtab_fwd, d->cog, d->cout, o, d->wsplit_fwd, (hipStream_t)stream);
+    if (d->fwd_padded) return dispatch_conv<true>(g, w, d->cout, d->cog, d->rowtab_fwd, d->cog, d->cout, o, d->wsplit_fwd, (hipStream_t)stream, &d->rc_fwd);
+    return dispatch_conv<false>(g, w, d->cout, d->cog, d->rowtab_fwd, d->cog, d->cout, o, d->wsplit_fwd, (hipStream_t)stream, &d->rc_fwd);
 }
 
 // wt[KH-1-ky][KW-1-kx][co][g*cig + ci] = w[ky][kx][ci][g*cog + co]: per tap and group a [cig][cog] -> [cog][cig] transpose, 64 x 64
@@ -2656,8 +2785,8 @@ extern "C" int vl_conv_dgrad(const vl_conv_desc* d, const float* dy, const float
               d->ptab_bwd, d->ptab2_bwd);
     VL_CHECK(g.total * 4 < MAX_BUF_BYTES, "vl_conv_dgrad: dy of %lld elements exceeds the buffer-offset range", (long long)g.total);
     ConvOut o{dx, nullptr, relu_mask, 0, d->dx_halo, d->x_halo, d->h, d->w};
-    if (d->bwd_padded) return dispatch_conv<true>(g, wt, d->cin, d->cig, d->rowtab_bwd, d->cig, d->cin, o, d->wsplit_bwd, (hipStream_t)stream);
-    return dispatch_conv<false>(g, wt, d->cin, d->cig, d->rowtab_bwd, d->cig, d->cin, o, d->wsplit_bwd, (hipStream_t)stream);
+    if (d->bwd_padded) return dispatch_conv<true>(g, wt, d->cin, d->cig, d->rowtab_bwd, d->cig, d->cin, o, d->wsplit_bwd, (hipStream_t)stream, &d->rc_bwd);
+    return dispatch_conv<false>(g, wt, d->cin, d->cig, d->rowtab_bwd, d->cig, d->cin, o, d->wsplit_bwd, (hipStream_t)stream, &d->rc_bwd);
 }
 
 // ---- conv wgrad -------------------------------------------------------------------------------

@@ -702,6 +702,12 @@ def conv_math():
     return {v: k for k, v in CONV_MATH.items()}[int(_ffi.lib().vl_conv_math())]
 
 
+def conv_set_row_classes(on=True):
+    """Test hook: off runs the many-frames fp32 conv forward / dgrad launches in the flat pixel order (every tap of every tile, the
+    padding taps included) instead of the row-class order; results are bitwise the same."""
+    _ffi.call("vl_conv_set_row_classes", int(bool(on)))
+
+
 def relu_grad(d, y, count=None):
     """d = y > 0 ? d : 0 in place over the first `count` elements."""
     _f32(d, y); _dense(d, y)
