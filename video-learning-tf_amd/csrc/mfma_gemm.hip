@@ -1110,6 +1110,42 @@ __device__ __forceinline__ ConvPixel conv_tile_pixel(const ConvTile& t, uint32_t
     return q;
 }
 
+// ---- pieces conv_dma_kernel (32x32 MFMA tiles) and conv_dma16_kernel (16x16 tiles, below launch_conv) share ----------------------
+// per-lane source offsets, fixed for the workgroup: weight column cl of a BM-wide tile that starts at channel i0 ...
+template <int BM>
+__device__ __forceinline__ uint32_t conv_weight_voff(int i0, int cl, int Cog) {
+    return (cl < BM && i0 + cl < Cog) ? (uint32_t)(i0 + cl) * 4u : OOB_OFF;
+}
+// ... and pixel m of the class segment
+__device__ __forceinline__ uint32_t conv_pixel_voff(const ConvTile& tl, const ConvGeom& g, int m) {
+    const bool vm = m < tl.S;
+    const ConvPixel q = conv_tile_pixel(tl, vm ? m : 0, g.dOW, g.OW);
+    const int ih0 = (int)q.oh * g.stride - g.pt + g.halo, iw0 = (int)q.ow * g.col_mul + g.col_add;
+    return vm ? (uint32_t)((int64_t)q.n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
+}
+
+// A wave fetches SR / 4 rows of a stage, all within ONE 16-row block of the reduction order: their im2col offsets and the block's first
+// weight row sit in SGPRs (see wgrad_dma_kernel).  load issues the wide s_loads; pin, a few MFMAs later, waits for them and fixes them.
+template <int SR>
+struct ConvStageTab {
+    int tabv[SR / 4];
+    int row0 = 0;
+    bool blk_ok = false;
+    __device__ __forceinline__ void load(const ConvTile& tl, const ConvGeom& g, int wrow, int st) {
+        const int k0 = st * SR + wrow;                                // position in the reduction order
+        const const_int_ptr tt = as_const(tl.ktab) + k0 + st * g.zero;
+#pragma unroll
+        for (int f = 0; f < SR / 4; ++f) tabv[f] = tt[f];
+        row0 = as_const(tl.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
+        blk_ok = k0 / KBLK < tl.nblk;                                 // blocks past K: both operands fetch zeros
+    }
+    __device__ __forceinline__ void pin() {
+#pragma unroll
+        for (int f = 0; f < SR / 4; ++f) asm volatile("" : "+s"(tabv[f]));
+        asm volatile("" : "+s"(row0));
+    }
+};
+
 template <int SR>   // reduction rows per stage: 64 (one workgroup per CU) or 32 (two: one's epilogue under the other's MFMAs)
 __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe, const ConvRowClasses rc,
                                                                int tiles_i, int wide) {
@@ -1135,35 +1171,20 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
     uint32_t voff_a[2], voff_b[2];
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-        const int co = i0 + hf * 64 + lane;
-        voff_a[hf] = co < pe.Cog ? (uint32_t)co * 4u : OOB_OFF;
-        const int m = j0 + hf * 64 + lane;
-        const bool vm = m < tl.S;
-        const ConvPixel q = conv_tile_pixel(tl, vm ? m : 0, g.dOW, g.OW);
-        const int ih0 = (int)q.oh * g.stride - g.pt + g.halo, iw0 = (int)q.ow * g.col_mul + g.col_add;
-        voff_b[hf] = vm ? (uint32_t)((int64_t)q.n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
+        voff_a[hf] = conv_weight_voff<BM>(i0, hf * 64 + lane, pe.Cog);
+        voff_b[hf] = conv_pixel_voff(tl, g, j0 + hf * 64 + lane);
     }
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ldsc;
     const int ld_bytes = (int)(pa.w_ld * 4);
 
-    // this wave fetches the stage's block `wave` (16 rows): their im2col offsets sit in SGPRs (see wgrad_dma_kernel)
-    int tabv[RW];
-    int row0 = 0;
-    bool blk_ok = false;
+    // this wave fetches the stage's block `wave` (16 rows)
+    ConvStageTab<SR> tab;
+    int (&tabv)[RW] = tab.tabv;
+    int& row0 = tab.row0;
+    bool& blk_ok = tab.blk_ok;
     const int wrow = wave * RW;                                       // first stage row of this wave
-    auto load_table = [&](int st) {
-        const int k0 = st * SR + wrow;                                // position in the reduction order
-        const const_int_ptr tt = as_const(tl.ktab) + k0 + st * g.zero;
-#pragma unroll
-        for (int f = 0; f < RW; ++f) tabv[f] = tt[f];
-        row0 = as_const(tl.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
-        blk_ok = k0 / KBLK < tl.nblk;                                 // blocks past K: both operands fetch zeros
-    };
-    auto pin_table = [&]() {
-#pragma unroll
-        for (int f = 0; f < RW; ++f) asm volatile("" : "+s"(tabv[f]));
-        asm volatile("" : "+s"(row0));
-    };
+    auto load_table = [&](int st) { tab.load(tl, g, wrow, st); };
+    auto pin_table = [&]() { tab.pin(); };
     // fetch f (0..63) of a stage into buffer nb: row rr = f >> 2 of the wave's block; f & 3 = {A half 0, A half 1, B half 0, B half 1}
     auto dma = [&](const int nb, const int f, int st) {
         const int rr = f >> 2, kind = f & 3, hf = kind & 1;
@@ -1310,7 +1331,7 @@ __global__ __launch_bounds__(NT, 64 / SR) void conv_dma_kernel(const ConvDmaPara
         // y_halo == 0 here: the class's rows of a frame are one contiguous run of the plane, from row oh0
         const uint32_t n = fd_div((uint32_t)min(m, tl.S - 1), tl.dRW);
         const int p = m - (int)n * tl.RW;
-        const bool run4 = m + 3 < tl.S && p + 3 < tl.RW; 
+        const bool run4 = m + 3 < tl.S && p + 3 < tl.RW;               // four pixels of one image: contiguous
         const int64_t cbase = ((int64_t)n * pe.Cout_total + (int64_t)zg * pe.Cog) * pe.y_plane + tl.oh0 * pe.OW + p;
 #pragma unroll
         for (int i = 0; i < BM / 8; ++i) {                             // 2 channel rows per wave instruction, 32 rows per wave
@@ -2231,6 +2252,16 @@ struct ConvOut {
     int y_halo, m_halo, OH, OW;
 };
 
+static EpiConvNCHW::Params make_epi(const ConvGeom& g, int Cog, int Cout_total, const ConvOut& o) {
+    EpiConvNCHW::Params pe;
+    pe.y = o.y; pe.bias = o.bias; pe.mask = o.mask; pe.relu = o.relu;
+    pe.Cog = Cog; pe.Cout_total = Cout_total; pe.OHW = g.OHW; pe.OW = g.OW; pe.M = g.M;
+    pe.dOHW = g.dOHW; pe.dOW = g.dOW;
+    pe.y_halo = o.y_halo; pe.y_wp = o.OW + 2 * o.y_halo; pe.y_plane = (int64_t)(o.OH + 2 * o.y_halo) * pe.y_wp;
+    pe.m_halo = o.m_halo; pe.m_wp = o.OW + 2 * o.m_halo; pe.m_plane = (int64_t)(o.OH + 2 * o.m_halo) * pe.m_wp;
+    return pe;
+}
+
 template <int BM, int WM, int WN, bool PADDED>
 static int launch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
                        int Cout_total, const ConvOut& o, hipStream_t s) {
@@ -2238,12 +2269,7 @@ static int launch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_gr
     using LA = ConvWeightKX<BM, BR>;
     using LB = ConvGather<BN, BR, PADDED>;
     typename LA::Params pa{w, w_ld, Cog, g.K, (int64_t)w_grp_stride, row_tab};
-    EpiConvNCHW::Params pe;
-    pe.y = o.y; pe.bias = o.bias; pe.mask = o.mask; pe.relu = o.relu;
-    pe.Cog = Cog; pe.Cout_total = Cout_total; pe.OHW = g.OHW; pe.OW = g.OW; pe.M = g.M;
-    pe.dOHW = g.dOHW; pe.dOW = g.dOW;
-    pe.y_halo = o.y_halo; pe.y_wp = o.OW + 2 * o.y_halo; pe.y_plane = (int64_t)(o.OH + 2 * o.y_halo) * pe.y_wp;
-    pe.m_halo = o.m_halo; pe.m_wp = o.OW + 2 * o.m_halo; pe.m_plane = (int64_t)(o.OH + 2 * o.m_halo) * pe.m_wp;
+    const EpiConvNCHW::Params pe = make_epi(g, Cog, Cout_total, o);
     const int tiles_i = ceil_div(Cog, BM), tiles_j = ceil_div(g.M, BN);
     const int rtiles = ceil_div(g.K, BR);
     dim3 grid(tiles_i * tiles_j, (unsigned)(Cout_total / Cog), 1);
@@ -2283,19 +2309,10 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
     const i32x4 rs_x = rsrc_words(g.x + (int64_t)zg * g.grp_stride, (g.total - (int64_t)zg * g.grp_stride) * 4);
     uint32_t voff_a[NA];
 #pragma unroll
-    for (int hf = 0; hf < NA; ++hf) {
-        const int cl = hf * 64 + lane;
-        voff_a[hf] = (cl < BM && i0 + cl < pe.Cog) ? (uint32_t)(i0 + cl) * 4u : OOB_OFF;
-    }
+    for (int hf = 0; hf < NA; ++hf) voff_a[hf] = conv_weight_voff<BM>(i0, hf * 64 + lane, pe.Cog);
     uint32_t voff_b[2];
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-        const int m = j0 + hf * 64 + lane;
-        const bool vm = m < tl.S;
-        const ConvPixel q = conv_tile_pixel(tl, vm ? m : 0, g.dOW, g.OW);
-        const int ih0 = (int)q.oh * g.stride - g.pt + g.halo, iw0 = (int)q.ow * g.col_mul + g.col_add;
-        voff_b[hf] = vm ? (uint32_t)((int64_t)q.n * g.img_stride + (int64_t)ih0 * g.Wp + iw0) * 4u : OOB_OFF;
-    }
+    for (int hf = 0; hf < 2; ++hf) voff_b[hf] = conv_pixel_voff(tl, g, j0 + hf * 64 + lane);
     // this lane's bias values, loaded before the main loop: fetched inside the epilogue (one dependent load in front of each of
     // the 48 stores) they cost conv1's forward 0.5 of its 2.4 ms (a run with the stores removed: 1.9 ms)
     float bias_r[TA][4];
@@ -2309,23 +2326,13 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)ldsc;
     const int ld_bytes = (int)(pa.w_ld * 4);
 
-    int tabv[RW];
-    int row0 = 0;
-    bool blk_ok = false;
+    ConvStageTab<SR> tab;
+    int (&tabv)[RW] = tab.tabv;
+    int& row0 = tab.row0;
+    bool& blk_ok = tab.blk_ok;
     const int wrow = wave * RW;
-    auto load_table = [&](int st) {
-        const int k0 = st * SR + wrow;
-        const const_int_ptr tt = as_const(tl.ktab) + k0 + st * g.zero;
-#pragma unroll
-        for (int f = 0; f < RW; ++f) tabv[f] = tt[f];
-        row0 = as_const(tl.row_tab)[k0 / KBLK + st * g.zero] + k0 % KBLK;
-        blk_ok = k0 / KBLK < tl.nblk;
-    };
-    auto pin_table = [&]() {
-#pragma unroll
-        for (int f = 0; f < RW; ++f) asm volatile("" : "+s"(tabv[f]));
-        asm volatile("" : "+s"(row0));
-    };
+    auto load_table = [&](int st) { tab.load(tl, g, wrow, st); };
+    auto pin_table = [&]() { tab.pin(); };
     auto dma = [&](const int nb, const int f, int st) {                // f = FPR rr + {weight row pieces, then the two im2col halves}
         const int rr = f / FPR, kind = f % FPR;
         const int z = st * g.zero;
@@ -2494,7 +2501,7 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
         const int64_t c0 = (int64_t)px.n * pe.Cout_total + (int64_t)zg * pe.Cog;
         const int64_t ybase = c0 * pe.y_plane + (int64_t)(px.oh + pe.y_halo) * pe.y_wp + px.ow + pe.y_halo;
         const int64_t mbase = c0 * pe.m_plane + (int64_t)(px.oh + pe.m_halo) * pe.m_wp + px.ow + pe.m_halo;
-        float mk[TA][4];                                          // mask loads first, all in flight (see conv_dma16p_kernel)
+        float mk[TA][4];                                          // mask loads first, all in flight (see conv_dma_kernel)
         if (pe.mask) {
 #pragma unroll
             for (int a = 0; a < TA; ++a)
@@ -2521,8 +2528,6 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 }
 
 
-static int device_cus();
-
 template <int BM>   // 128: conv_dma_kernel (32x32 MFMA tiles); 48 / 96: conv_dma16_kernel (16x16 tiles)
 static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
                            int Cout_total, const ConvOut& o, hipStream_t s, const vl_conv_rowcls* rcd = nullptr) {
@@ -2532,12 +2537,7 @@ static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int 
                                      : (size_t)2 * SR * ((BM + 63) / 64 * 64 + 16 + 144) * sizeof(float);   // 56 / 72 KB
     static_assert(BM != 128 || (size_t)2 * SR * (BM + BN) * sizeof(float) <= (size_t)BM * (BN + 4) * sizeof(float), "stage buffers fit");
     ConvDmaParams pa{w, w_ld, (int64_t)w_grp_stride, (int64_t)g.K * w_ld * 4, row_tab, ceil_div(g.K, KBLK)};
-    EpiConvNCHW::Params pe;
-    pe.y = o.y; pe.bias = o.bias; pe.mask = o.mask; pe.relu = o.relu;
-    pe.Cog = Cog; pe.Cout_total = Cout_total; pe.OHW = g.OHW; pe.OW = g.OW; pe.M = g.M;
-    pe.dOHW = g.dOHW; pe.dOW = g.dOW;
-    pe.y_halo = o.y_halo; pe.y_wp = o.OW + 2 * o.y_halo; pe.y_plane = (int64_t)(o.OH + 2 * o.y_halo) * pe.y_wp;
-    pe.m_halo = o.m_halo; pe.m_wp = o.OW + 2 * o.m_halo; pe.m_plane = (int64_t)(o.OH + 2 * o.m_halo) * pe.m_wp;
+    const EpiConvNCHW::Params pe = make_epi(g, Cog, Cout_total, o);
     static bool attr_set = false;
     if (!attr_set) {
         const void* kern;
@@ -2585,12 +2585,7 @@ static int launch_conv_ring(const ConvGeom& g, const float* w, int64_t w_ld, int
                        CogP, nstages, planes, wsplit);
     VL_LAUNCH_CHECK();
     ConvRingParams pa{wsplit, CogP, nstages};
-    EpiConvNCHW::Params pe;
-    pe.y = o.y; pe.bias = o.bias; pe.mask = o.mask; pe.relu = o.relu;
-    pe.Cog = Cog; pe.Cout_total = Cout_total; pe.OHW = g.OHW; pe.OW = g.OW; pe.M = g.M;
-    pe.dOHW = g.dOHW; pe.dOW = g.dOW;
-    pe.y_halo = o.y_halo; pe.y_wp = o.OW + 2 * o.y_halo; pe.y_plane = (int64_t)(o.OH + 2 * o.y_halo) * pe.y_wp;
-    pe.m_halo = o.m_halo; pe.m_wp = o.OW + 2 * o.m_halo; pe.m_plane = (int64_t)(o.OH + 2 * o.m_halo) * pe.m_wp;
+    const EpiConvNCHW::Params pe = make_epi(g, Cog, Cout_total, o);
     const int OH = g.OHW / g.OW, OWp = (g.OW + 3) / 4 * 4, Mp = g.M / g.OW * OWp;
     const int tiles_i = ceil_div(Cog, BM), tiles_j = ceil_div(Mp, BN);
     dim3 grid(tiles_i * tiles_j, (unsigned)groups, 1);
@@ -2631,14 +2626,16 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
         if (Cog >= 96) return launch_conv_ring<128>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, wsplit, s);
         if (Cog >= 40 && Cog <= 64) return launch_conv_ring<64>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, wsplit, s);
     }
+    // the LDS-DMA kernels: padded layout, the weight tensor within one buffer resource
+    const bool dma_ok = PADDED && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged;
     // Few frames (one rank's shard of a multi-GPU job): the tile with the fewest padded rows can leave CUs idle or half of them
     // with two workgroups and the rest with one.  Per-CU load of a tile width = ceil(workgroups / CUs) x its rows; take the
     // LDS-DMA kernel (128 / 96 / 48 rows) with the smallest load, ties to the wider tile.  With many frames the widths agree
     // with the padded-row rule below (loads differ by the padding only), which then decides alone.
-    const int64_t px = ceil_div(g.M, 128), cus = device_cus(), ngrp = Cout_total / Cog;
+    const int64_t px = ceil_div(g.M, 128), cus = vl_device_cus(), ngrp = Cout_total / Cog;
     const bool few = px * ceil_div(Cog, 128) * ngrp < 8 * cus;        // under 8 workgroups per CU at the widest tile: quantisation matters
     // (the few-frames branch keeps the flat pixel order: its width pick and tail split count flat tiles)
-    if (PADDED && few && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged && !kConvNoLoadPick) {
+    if (dma_ok && few && !kConvNoLoadPick) {
         const int widths[3] = {128, 96, 48};
         auto pick = [&](int64_t pxt, int64_t& load) {                 // width with the smallest per-CU load for pxt pixel tiles
             int b = 0;
@@ -2691,17 +2688,16 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
     }
     if (w128 <= w96 && w128 <= w64) {
         // 128-wide tiles in the padded layout: the LDS-DMA kernel
-        if (PADDED && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged) {
+        if (dma_ok) {
             return launch_conv_dma<128>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
         }
         return launch_conv<128, 2, 2, PADDED>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
     }
     // 48-wide tiles beat the 64-wide ones whenever they waste fewer rows (conv2 dgrad: 48 channels per group)
-    if (PADDED && ceil_div(Cog, 48) * 48 < w64 && ceil_div(Cog, 48) * 48 < w96 &&
-        (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged)
+    if (dma_ok && ceil_div(Cog, 48) * 48 < w64 && ceil_div(Cog, 48) * 48 < w96)
         return launch_conv_dma<48>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
     if (w96 <= w64) {
-        if (PADDED && (int64_t)g.K * w_ld * 4 < MAX_BUF_BYTES && !kConvStaged)
+        if (dma_ok)
             return launch_conv_dma<96>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
         return launch_conv<96, 1, 4, PADDED>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s);
     }
@@ -2866,17 +2862,6 @@ static int launch_wgrad_dma(const vl_conv_desc* d, const ConvGeom& g, const floa
     return reduce_wgrad(d, dw, ws, splits, s);
 }
 
-static int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 static int wgrad_splits(const vl_conv_desc* d, int n) {
     const int64_t M = (int64_t)n * d->oh * d->ow;
     const int tiles = ceil_div(d->K, 128) * ceil_div(d->cog, d->cog % 128 == 0 ? 128 : 96) * d->groups;
@@ -2891,7 +2876,7 @@ static int wgrad_splits(const vl_conv_desc* d, int n) {
     const int rtiles = ceil_div(M, 64);
     static const int forced = vl_exp_env("VL_WGRAD_SPLITS") ? atoi(vl_exp_env("VL_WGRAD_SPLITS")) : 0;   // experiments: force the split count
     if (forced >= 1 && forced <= rtiles) return forced;      // (this function IS the ws_bytes query's split count too: one source)
-    const int per_xcd = device_cus() / 8 > 0 ? device_cus() / 8 : 1;
+    const int per_xcd = vl_device_cus() / 8 > 0 ? vl_device_cus() / 8 : 1;
     const int64_t slab_bytes = ((int64_t)d->K + 1) * d->cout * 4;
     int best = 1;
     int64_t best_cost = -1;
@@ -3177,7 +3162,7 @@ static int gemm_split_splits(int m, int n, int k, int slots) {
 extern "C" size_t vl_gemm_split_ws_bytes(int m, int n, int k) {
     if (m <= 0 || n <= 0 || k <= 0) return 0;
     const size_t st = (size_t)ceil_div(k, 16), mp = (size_t)ceil_div(m, 128) * 128, np = (size_t)ceil_div(n, 256) * 256;
-    const int splits = gemm_split_splits(m, n, k, 2 * device_cus());
+    const int splits = gemm_split_splits(m, n, k, 2 * vl_device_cus());
     return st * 24 * (mp + np) * 4 + (splits > 1 ? (size_t)splits * m * n * 4 : 0) + 4096;
 }
 
@@ -3195,7 +3180,7 @@ static int launch_gemm_split(int transa, int transb, int m, int n, int k, const 
                        transb ? ldb : (int64_t)1, k, n, Np, planes, ib);
     VL_LAUNCH_CHECK();
     const int tiles = (Mp / 128) * (Np / 256);
-    const int splits = gemm_split_splits(m, n, k, device_cus() * (math == 6 ? 1 : 2));
+    const int splits = gemm_split_splits(m, n, k, vl_device_cus() * (math == 6 ? 1 : 2));
     const int sps = ceil_div(nstages, splits);
     GemmSplitParams P{ia, ib, Mp, Np, nstages, sps, splits > 1 ? slabs : c, ldc, (int64_t)m * n, bias, relu_mask, relu, m, n, splits};
     const size_t lds = (size_t)3 * (planes * 2 * 2 + planes * 2 * 4) * 1024;      // 72 KB (108 KB with three planes)
@@ -3235,7 +3220,7 @@ extern "C" int vl_gemm(int transa, int transb, int m, int n, int k, const float*
     // was provided
     int splits = 1;
     static const int kWantPerCu = vl_exp_env("VL_GEMM_WANT") ? atoi(vl_exp_env("VL_GEMM_WANT")) : 3;   // experiments: workgroups per CU aimed at
-    const int want = kWantPerCu * device_cus();
+    const int want = kWantPerCu * vl_device_cus();
     if (ws && tiles < want && !kGemmNoSplit) {
         splits = ceil_div(want, tiles);
         const int maxs = k / 256 > 0 ? k / 256 : 1;
