@@ -424,6 +424,36 @@ int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state
 int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
                      const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream);
 
+/* ---- tiered update: per-range learning-rate multipliers, untouched gaps ------------------------------------------------------
+ * A tier table lists the half-open element ranges [begin, end) of the flat buffers that an update touches, each with the multiplier
+ * of its learning rate.  The table is sorted and disjoint, lies inside [0, count), has 1 .. VL_MAX_LR_TIERS entries and multipliers
+ * that are finite and > 0; anything else is refused on the host.  It is read on the host and travels BY VALUE in the launch arguments:
+ * the caller's array may be freed as soon as the call returns, and a captured step needs no device table.
+ * Elements outside every tier are neither loaded nor stored (w, g and Adam's m, v alike: they may hold anything, NaN included).
+ * Inside a tier with multiplier mult the arithmetic is that of the plain call with lr replaced by the fp32 product lr * mult (Adam:
+ * step size adam_lr * mult), so the tier's elements get, bit for bit, what the plain entry point gives on that sub-range with
+ * lr' = (float)(lr * mult).  sumsq and clip_norm mean what they mean there: ONE global norm, whatever the table.  One launch per call,
+ * with the plain call's grid.  The plain entry points above are the table {0, count, 1.0f} of the same kernels. */
+#define VL_MAX_LR_TIERS 16
+typedef struct vl_lr_tier {
+    int64_t begin, end;
+    float lr_mult;
+} vl_lr_tier;
+int vl_sgd_apply_tiers(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq,
+                       float gscale, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream);
+int vl_adam_apply_tiers(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
+                        const float* sumsq, float gscale, int step, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers,
+                        vl_stream_t stream);
+int vl_sgd_apply_tiers_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
+                          float gscale, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream);
+int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
+                           const float* sumsq, float gscale, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers,
+                           vl_stream_t stream);
+/* out[0] = sum g^2 over the elements inside the tiers (the multipliers are ignored; elements outside are not read); ws: float[1024].
+ * Two stages in a fixed order like vl_sumsq: the same bits from run to run.  Not the summation order of vl_sumsq: callers whose table
+ * is the single full range call vl_sumsq. */
+int vl_sumsq_tiers(const float* g, int64_t count, const vl_lr_tier* tiers, int n_tiers, float* out, float* ws, vl_stream_t stream);
+
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);
 /* ReluGrad in place: d[i] = y[i] > 0 ? d[i] : 0 (y = the ReLU's forward output, alexnet.py:228,248). */

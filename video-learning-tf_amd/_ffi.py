@@ -91,6 +91,11 @@ SIGNATURES = {
     "vl_step_state_set": (i32, [p, i64, f32, u32, p]),
     "vl_sgd_apply_st": (i32, [p, p, i64, p, f32, p, f32, p, p]),
     "vl_adam_apply_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p]),
+    "vl_sgd_apply_tiers": (i32, [p, p, i64, f32, f32, p, f32, p, p, i32, p]),
+    "vl_adam_apply_tiers": (i32, [p, p, p, p, i64, f32, f32, p, f32, i32, p, p, i32, p]),
+    "vl_sgd_apply_tiers_st": (i32, [p, p, i64, p, f32, p, f32, p, p, i32, p]),
+    "vl_adam_apply_tiers_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p, i32, p]),
+    "vl_sumsq_tiers": (i32, [p, i64, p, i32, p, p, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),
@@ -103,6 +108,14 @@ SIGNATURES = {
     "vl_fuse_n_grad": (i32, [p, i32, p, p, i64, i32, p]),
     "vl_relu_grad": (i32, [p, p, i64, p]),
 }
+
+
+class LrTier(C.Structure):
+    """vl_lr_tier (include/vltf.h)."""
+    _fields_ = [("begin", i64), ("end", i64), ("lr_mult", f32)]
+
+
+MAX_LR_TIERS = 16         # VL_MAX_LR_TIERS
 
 
 class VltfError(RuntimeError):

@@ -1877,6 +1877,57 @@ extern "C" int vl_softmax_xent_len(const float* logits, const int32_t* labels, f
 }
 
 // ---- global norm + SGD / Adam (train.py:199-222) ----------------------------------------------
+// ---- tier table (vltf.h: vl_lr_tier): the ranges of the flat buffer an update / a norm touches, by value in the launch arguments --
+struct tier_table {
+    vl_lr_tier t[VL_MAX_LR_TIERS];
+    int n;
+};
+
+// sorted, disjoint, inside [0, count), multipliers finite and > 0 (the kernels rely on it: an element outside every tier is never
+// addressed, and no element is addressed twice)
+static int tier_table_make(const char* who, const vl_lr_tier* tiers, int n_tiers, int64_t count, tier_table* out) {
+    VL_CHECK(tiers && n_tiers >= 1 && n_tiers <= VL_MAX_LR_TIERS, "%s: 1 .. %d tiers, got %d", who, VL_MAX_LR_TIERS, n_tiers);
+    int64_t prev = 0;
+    for (int k = 0; k < n_tiers; ++k) {
+        const vl_lr_tier& t = tiers[k];
+        VL_CHECK(t.begin >= prev && t.end > t.begin && t.end <= count,
+                 "%s: tier %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)t.begin,
+                 (long long)t.end, (long long)count);
+        VL_CHECK(t.lr_mult > 0.f && t.lr_mult <= 3.402823466e38f, "%s: tier %d: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
+        out->t[k] = t;
+        prev = t.end;
+    }
+    out->n = n_tiers;
+    return 0;
+}
+
+static tier_table tier_table_full(int64_t count) {
+    tier_table tt;
+    tt.t[0].begin = 0;
+    tt.t[0].end = count;
+    tt.t[0].lr_mult = 1.f;
+    tt.n = 1;
+    return tt;
+}
+
+// [begin, end) = scalar head [begin, v0) + 16-byte interior [v0, v1) + scalar tail [v1, end).  The interior exists where every one of the
+// arrays is 16-byte aligned at the same element: `phase` = (address / 4) mod 4 of element 0, < 0 when the arrays disagree.
+__device__ __forceinline__ int align_phase(const void* a, const void* b, const void* c, const void* d) {
+    const int pa = (int)(((uintptr_t)a >> 2) & 3);
+    const bool same = (!b || (int)(((uintptr_t)b >> 2) & 3) == pa) && (!c || (int)(((uintptr_t)c >> 2) & 3) == pa) &&
+                      (!d || (int)(((uintptr_t)d >> 2) & 3) == pa);
+    return same ? pa : -1;
+}
+__device__ __forceinline__ void tier_split(int64_t begin, int64_t end, int phase, int64_t& v0, int64_t& v1) {
+    if (phase < 0) {
+        v0 = v1 = end;
+        return;
+    }
+    v0 = begin + ((4 - (int)((begin + phase) & 3)) & 3);
+    if (v0 > end) v0 = end;
+    v1 = v0 + ((end - v0) & ~(int64_t)3);
+}
+
 __global__ void sumsq_stage1(const float* __restrict__ g, int64_t count, float* __restrict__ ws) {
     __shared__ float sm[4];
     float acc = 0.f;
@@ -1916,6 +1967,43 @@ extern "C" int vl_sumsq(const float* g, int64_t count, float* out, float* ws, in
     return 0;
 }
 
+// vl_sumsq over the elements inside the tiers only (the multipliers play no part).  A lane walks the tiers in table order -- head,
+// 16-byte interior, tail of each -- so the order of every partial sum is fixed by the table and the grid.
+__global__ void sumsq_tiers_stage1(const float* __restrict__ g, tier_table tt, float* __restrict__ ws) {
+    __shared__ float sm[4];
+    float acc = 0.f;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    const int phase = align_phase(g, nullptr, nullptr, nullptr);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) acc += g[i] * g[i];
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            const float4 v = g4[i];
+            acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) acc += g[i] * g[i];
+    }
+    acc = block_sum_256(acc, sm);
+    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+
+extern "C" int vl_sumsq_tiers(const float* g, int64_t count, const vl_lr_tier* tiers, int n_tiers, float* out, float* ws, vl_stream_t stream) {
+    VL_CHECK(g && out && ws && count > 0, "vl_sumsq_tiers: bad argument");
+    tier_table tt;
+    if (int rc = tier_table_make("vl_sumsq_tiers", tiers, n_tiers, count, &tt)) return rc;
+    int64_t inside = 0;
+    for (int k = 0; k < tt.n; ++k) inside += tt.t[k].end - tt.t[k].begin;
+    const int blocks = grid_for(inside / 4 + 1, 256, 1024);
+    hipLaunchKernelGGL(sumsq_tiers_stage1, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, tt, ws);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sumsq_stage2, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, blocks, out, 0);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 __device__ __forceinline__ float clip_scale(float clip_norm, const float* sumsq, float gscale) {
     if (clip_norm <= 0.f || !sumsq) return gscale;
     const float norm = gscale * sqrtf(sumsq[0]);
@@ -1924,39 +2012,91 @@ __device__ __forceinline__ float clip_scale(float clip_norm, const float* sumsq,
 
 // the update bodies, shared by the eager kernels and the step-state ones (vl_sgd_apply_st / vl_adam_apply_st): only where lr / the
 // Adam step size comes from differs, so a replayed update and the eager one get the same bits
-// (grid-stride start and step from the kernel, as dropout_fwd_body)
-__device__ __forceinline__ void sgd_apply_body(float* __restrict__ w, const float* __restrict__ g, int64_t count, float lr, float clip_norm,
-                                               const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
-    const float a = lr * clip_scale(clip_norm, sumsq, gscale);
-    for (int64_t i = i0; i < count; i += step)
-        w[i] -= a * g[i];
+// (grid-stride start and step from the kernel, as dropout_fwd_body).  One element function each, used by the scalar and the 16-byte
+// loops alike: an element's result does not depend on which loop reached it.
+// The rounding steps are spelled out (no contraction left to the compiler, which chose differently per loop): the forms are the
+// ones the one-loop kernels were built with, so every loop here -- and the plain entry points before there were tiers -- give the same bits.
+__device__ __forceinline__ float sgd_elem(float w, float g, float a) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(-a, g, w);
 }
 
-__device__ __forceinline__ void adam_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                int64_t count, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
-                                                int64_t i0, int64_t step) {
+__device__ __forceinline__ void sgd_apply_body(float* __restrict__ w, const float* __restrict__ g, const tier_table& tt, float lr, float clip_norm,
+                                               const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
     const float sc = clip_scale(clip_norm, sumsq, gscale);
-    for (int64_t i = i0; i < count; i += step) {
-        const float gi = g[i] * sc;
-        const float mi = 0.9f * m[i] + 0.1f * gi;
-        const float vi = 0.999f * v[i] + 0.001f * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        w[i] -= lr_t * mi / (sqrtf(vi) + 1e-8f);
+    const int phase = align_phase(w, g, nullptr, nullptr);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        const float a = (lr * tt.t[k].lr_mult) * sc;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) w[i] = sgd_elem(w[i], g[i], a);
+        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            float4 wv = w4[i];
+            const float4 gv = g4[i];
+            wv.x = sgd_elem(wv.x, gv.x, a);
+            wv.y = sgd_elem(wv.y, gv.y, a);
+            wv.z = sgd_elem(wv.z, gv.z, a);
+            wv.w = sgd_elem(wv.w, gv.w, a);
+            w4[i] = wv;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) w[i] = sgd_elem(w[i], g[i], a);
     }
 }
 
-__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t count, float lr, float clip_norm,
+__device__ __forceinline__ void adam_elem(float& w, float g, float& m, float& v, float sc, float lr_t) {
+#pragma clang fp contract(off)
+    const float gi = g * sc;
+    const float mi = __builtin_fmaf(0.9f, m, 0.1f * gi);
+    const float vi = __builtin_fmaf(0.999f, v, gi * (0.001f * gi));
+    m = mi;
+    v = vi;
+    w = w - (lr_t * mi) / (sqrtf(vi) + 1e-8f);
+}
+
+__device__ __forceinline__ void adam_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                const tier_table& tt, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                                int64_t i0, int64_t step) {
+    const float sc = clip_scale(clip_norm, sumsq, gscale);
+    const int phase = align_phase(w, g, m, v);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        const float lr_k = lr_t * tt.t[k].lr_mult;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) adam_elem(w[i], g[i], m[i], v[i], sc, lr_k);
+        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+        float4* __restrict__ m4 = reinterpret_cast<float4*>(m + v0);
+        float4* __restrict__ q4 = reinterpret_cast<float4*>(v + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            float4 wv = w4[i], mv = m4[i], qv = q4[i];
+            const float4 gv = g4[i];
+            adam_elem(wv.x, gv.x, mv.x, qv.x, sc, lr_k);
+            adam_elem(wv.y, gv.y, mv.y, qv.y, sc, lr_k);
+            adam_elem(wv.z, gv.z, mv.z, qv.z, sc, lr_k);
+            adam_elem(wv.w, gv.w, mv.w, qv.w, sc, lr_k);
+            m4[i] = mv;
+            q4[i] = qv;
+            w4[i] = wv;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) adam_elem(w[i], g[i], m[i], v[i], sc, lr_k);
+    }
+}
+
+__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, float lr, float clip_norm,
                                  const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;                                        // the step's results are invalid (vl_status_or): no update
-    sgd_apply_body(w, g, count, lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    sgd_apply_body(w, g, tt, lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void adam_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                  int64_t count, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                  tier_table tt, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
                                   const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;
-    adam_apply_body(w, g, m, v, count, lr_t, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    adam_apply_body(w, g, m, v, tt, lr_t, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // *dst |= first word of an LSTM cluster workspace (its sticky time-out word, lstm_cluster.hip): the optimizer's `skip` word of a step
@@ -1971,13 +2111,26 @@ extern "C" int vl_status_or(uint32_t* dst, const void* lstm_ws, int init, vl_str
     return 0;
 }
 
-extern "C" int vl_sgd_apply(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq, float gscale,
-                            const uint32_t* skip, vl_stream_t stream) {
-    VL_CHECK(w && g && count > 0, "vl_sgd_apply: bad argument");
-    hipLaunchKernelGGL(sgd_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, count, lr,
+static int sgd_apply_launch(float* w, const float* g, int64_t count, const tier_table& tt, float lr, float clip_norm, const float* sumsq,
+                            float gscale, const uint32_t* skip, vl_stream_t stream) {
+    hipLaunchKernelGGL(sgd_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, tt, lr,
                        clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vl_sgd_apply(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq, float gscale,
+                            const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && count > 0, "vl_sgd_apply: bad argument");
+    return sgd_apply_launch(w, g, count, tier_table_full(count), lr, clip_norm, sumsq, gscale, skip, stream);
+}
+
+extern "C" int vl_sgd_apply_tiers(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq, float gscale,
+                                  const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream) {
+    VL_CHECK(w && g && count > 0, "vl_sgd_apply_tiers: bad argument");
+    tier_table tt;
+    if (int rc = tier_table_make("vl_sgd_apply_tiers", tiers, n_tiers, count, &tt)) return rc;
+    return sgd_apply_launch(w, g, count, tt, lr, clip_norm, sumsq, gscale, skip, stream);
 }
 
 // Adam's bias-corrected step size at count `step` (TF: lr * sqrt(1 - beta2^t) / (1 - beta1^t)); host code, shared by vl_adam_apply and
@@ -1987,14 +2140,27 @@ static float adam_step_size(float lr, int step) {
     return (float)(lr * sqrt(b2t) / b1t);
 }
 
-extern "C" int vl_adam_apply(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
-                             const float* sumsq, float gscale, int step, const uint32_t* skip, vl_stream_t stream) {
-    VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply: bad argument");
-    const float lr_t = adam_step_size(lr, step);
-    hipLaunchKernelGGL(adam_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, count,
+static int adam_apply_launch(float* w, const float* g, float* m, float* v, int64_t count, const tier_table& tt, float lr_t, float clip_norm,
+                             const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    hipLaunchKernelGGL(adam_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, tt,
                        lr_t, clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vl_adam_apply(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
+                             const float* sumsq, float gscale, int step, const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply: bad argument");
+    return adam_apply_launch(w, g, m, v, count, tier_table_full(count), adam_step_size(lr, step), clip_norm, sumsq, gscale, skip, stream);
+}
+
+extern "C" int vl_adam_apply_tiers(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
+                                   const float* sumsq, float gscale, int step, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers,
+                                   vl_stream_t stream) {
+    VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply_tiers: bad argument");
+    tier_table tt;
+    if (int rc = tier_table_make("vl_adam_apply_tiers", tiers, n_tiers, count, &tt)) return rc;
+    return adam_apply_launch(w, g, m, v, count, tt, adam_step_size(lr, step), clip_norm, sumsq, gscale, skip, stream);
 }
 
 // ---- step state (vltf.h: vl_step_state): the scalars a replayed step reads from device memory -------------------------------
@@ -2018,36 +2184,63 @@ extern "C" int vl_step_state_set(vl_step_state* state, int64_t step, float lr, u
 }
 
 // the update kernels above with lr / Adam's step size read from the step state
-__global__ void sgd_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t count, const vl_step_state* __restrict__ st,
+__global__ void sgd_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, const vl_step_state* __restrict__ st,
                                     float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;
-    sgd_apply_body(w, g, count, st->lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    sgd_apply_body(w, g, tt, st->lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void adam_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                     int64_t count, const vl_step_state* __restrict__ st, float clip_norm, const float* __restrict__ sumsq,
+                                     tier_table tt, const vl_step_state* __restrict__ st, float clip_norm, const float* __restrict__ sumsq,
                                      float gscale, const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;
-    adam_apply_body(w, g, m, v, count, st->adam_lr, clip_norm, sumsq, gscale,
+    adam_apply_body(w, g, m, v, tt, st->adam_lr, clip_norm, sumsq, gscale,
                     (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-extern "C" int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
-                               float gscale, const uint32_t* skip, vl_stream_t stream) {
-    VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_st: bad argument");
-    hipLaunchKernelGGL(sgd_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, count, state,
+static int sgd_apply_st_launch(float* w, const float* g, int64_t count, const tier_table& tt, const vl_step_state* state, float clip_norm,
+                               const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    hipLaunchKernelGGL(sgd_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, tt, state,
                        clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
-                                const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
-    VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_st: bad argument");
-    hipLaunchKernelGGL(adam_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, count,
+static int adam_apply_st_launch(float* w, const float* g, float* m, float* v, int64_t count, const tier_table& tt, const vl_step_state* state,
+                                float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    hipLaunchKernelGGL(adam_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, tt,
                        state, clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
+                               float gscale, const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_st: bad argument");
+    return sgd_apply_st_launch(w, g, count, tier_table_full(count), state, clip_norm, sumsq, gscale, skip, stream);
+}
+
+extern "C" int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
+                                const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_st: bad argument");
+    return adam_apply_st_launch(w, g, m, v, count, tier_table_full(count), state, clip_norm, sumsq, gscale, skip, stream);
+}
+
+extern "C" int vl_sgd_apply_tiers_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
+                                     float gscale, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream) {
+    VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_tiers_st: bad argument");
+    tier_table tt;
+    if (int rc = tier_table_make("vl_sgd_apply_tiers_st", tiers, n_tiers, count, &tt)) return rc;
+    return sgd_apply_st_launch(w, g, count, tt, state, clip_norm, sumsq, gscale, skip, stream);
+}
+
+extern "C" int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
+                                      const float* sumsq, float gscale, const uint32_t* skip, const vl_lr_tier* tiers, int n_tiers,
+                                      vl_stream_t stream) {
+    VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_tiers_st: bad argument");
+    tier_table tt;
+    if (int rc = tier_table_make("vl_adam_apply_tiers_st", tiers, n_tiers, count, &tt)) return rc;
+    return adam_apply_st_launch(w, g, m, v, count, tt, state, clip_norm, sumsq, gscale, skip, stream);
 }
 
 __global__ void fill_kernel(float* __restrict__ p, int64_t count, float value) {

@@ -55,6 +55,8 @@ class NetConfig:
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
     conv_math: str = "f32"                      # "f32" | "bf16x3" | "bf16x6" | "bf16" (ops.set_conv_math: opt-in bf16-MFMA conv products)
     step_graph: bool = False                    # train_step_u8 / forward_u8 captured once per input key and replayed (LRCNEngine docstring)
+    lr_mult: Optional[float] = None             # train.lr_mult: learning-rate factor of the `modified` variables (finetune_plan); None = 1
+    train_from: Optional[str] = None            # first trainable dcnn layer (TRAIN_FROM): every dcnn layer before it is frozen
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -106,6 +108,140 @@ def param_specs(cfg: NetConfig):
     return specs
 
 
+# ---- fine-tuning plan: learning-rate tiers, frozen layers, exchange chunks (host only) ------------------------------------------
+TRAIN_FROM = ("conv1", "conv2", "conv3", "conv4", "conv5", "fc6", "fc7", "fc8", "classifier")
+FC6_CHUNKS = 4          # row blocks of the fc6 weight gradient = all-reduce chunks of the data-parallel exchange
+
+
+def dcnn_layers(cfg: NetConfig):
+    """Names of the dcnn layers the pipeline has, first to last (alexnet.py:60-280: the tower ends at frame_encoding_layer)."""
+    layers = [c[0] for c in CONV_LAYERS] + ["fc6"]
+    if cfg.frame_encoding_layer != "fc6":
+        layers.append("fc7")
+    if cfg.frame_encoding_layer not in ("fc6", "fc7"):
+        layers.append("fc8")
+    return layers
+
+
+def frozen_layers(cfg: NetConfig):
+    """The dcnn layers cfg.train_from freezes (every one before it; `classifier`: all of them).  Refuses a name the pipeline lacks."""
+    if cfg.train_from is None:
+        return []
+    layers = dcnn_layers(cfg)
+    if cfg.train_from not in TRAIN_FROM:
+        raise VltfError("train_from [%s] is not one of %s" % (cfg.train_from, ", ".join(TRAIN_FROM)))
+    if cfg.train_from == "classifier":
+        return layers
+    if cfg.train_from not in layers:
+        raise VltfError("train_from [%s]: with frame_encoding_layer [%s] the pipeline has no such layer (it has %s)" %
+                        (cfg.train_from, cfg.frame_encoding_layer, ", ".join(layers)))
+    return layers[:layers.index(cfg.train_from)]
+
+
+_REGULAR_LEAVES = {l + k for l in [c[0] for c in CONV_LAYERS] + ["fc6", "fc7"] for k in ("W", "b")}
+
+
+def is_regular(name):
+    """The reference's `train_regular` variables (alexnet.py:214,231,251): the dcnn's, whatever pipeline scope they carry, but fc8
+    (alexnet.py:280: re-initialised, so it learns with the modified ones).  Every other variable -- fc8, the LSTM's, the fc heads --
+    is `train_modified` and gets lr * lr_mult (train.py:180)."""
+    parts = name.split("/")
+    return len(parts) in (2, 3) and parts[-2] == "dcnn" and parts[-1] in _REGULAR_LEAVES
+
+
+def check_lr_mult(lr_mult):
+    """None -> 1.0; anything but a finite float > 0 is refused (layers are held fixed with train_from, not with a zero factor)."""
+    if lr_mult is None:
+        return 1.0
+    m = float(lr_mult)
+    if not (m > 0.0 and math.isfinite(m)):
+        raise VltfError("lr_mult must be a finite number > 0, got %r (use train_from to hold layers fixed)" % (lr_mult,))
+    return m
+
+
+def base_grad_chunks(cfg: NetConfig):
+    """[(offset, count)] of the flat gradient in the order backward completes them, for a model with nothing frozen (dp.py).
+    fc6W (85 % of the bytes) goes in FC6_CHUNKS row blocks, each reduced as soon as the GEMM that produces it is queued; also returns
+    those row blocks [(row0, row1)]."""
+    specs = param_specs(cfg)
+    offsets, off = {}, 0
+    for name, shp in specs:
+        offsets[name] = off
+        off += int(np.prod(shp))
+    total = off
+    first_conv = offsets["dcnn/conv5W"]
+    f6o = offsets["dcnn/fc6W"]
+    rows6 = dict(specs)["dcnn/fc6W"][0]
+    nch = max(1, min(FC6_CHUNKS, rows6 // 128))
+    edges = [(-(-rows6 * i // nch) + 127) // 128 * 128 if 0 < i < nch else (0 if i == 0 else rows6) for i in range(nch + 1)]
+    row_blocks = [(edges[i], edges[i + 1]) for i in range(nch) if edges[i + 1] > edges[i]]
+    chunks = [(0, f6o)] if f6o > 0 else []
+    for bi, (r0, r1) in enumerate(row_blocks):
+        lo, hi = f6o + r0 * FC_DIM, f6o + r1 * FC_DIM
+        if bi == len(row_blocks) - 1:
+            hi = first_conv                                   # fc6b rides with the last block
+        chunks.append((lo, hi - lo))
+    # conv5..conv3 (8.0 of the 9.3 MB of conv gradients) go out as soon as conv3's weight gradient is queued, while conv2 / conv1
+    # backward (40 % of the conv backward) still runs; only conv2 + conv1 (1.4 MB) are left for the end of the step
+    conv_lo = offsets["dcnn/conv2W"]
+    chunks.append((first_conv, conv_lo - first_conv))
+    chunks.append((conv_lo, total - conv_lo))
+    assert sum(c for _, c in chunks) == total and all(chunks[i][0] + chunks[i][1] == chunks[i + 1][0] for i in range(len(chunks) - 1))
+    return chunks, row_blocks
+
+
+@dataclass
+class TrainPlan:
+    tiers: list             # [(begin, end, lr_mult)]: the trainable ranges of the flat buffer, sorted, adjacent equal factors merged
+    frozen: list            # names of the variables that are never updated, in flat order
+    chunks: list            # [(offset, count)]: the data-parallel exchange, covering exactly the trainable ranges
+    total: int              # elements of the flat buffer
+
+    def full_range(self):
+        """One tier over everything with factor 1: the plain norm / update calls apply (and keep their bits)."""
+        return self.tiers == [(0, self.total, 1.0)]
+
+    def trainable_bytes(self):
+        return 4 * sum(c for _, c in self.chunks)
+
+
+def tier_plan(specs, frozen, lr_mult, base_chunks):
+    """The plan of any variable list: specs [(name, shape)] in flat order, frozen variable names, the factor of the modified
+    variables, and the exchange chunks of the unfrozen model.  A chunk keeps its boundaries wherever its range is still trainable and is
+    cut to the trainable part otherwise, in the same order: with nothing frozen the chunk list is base_chunks item for item."""
+    m = check_lr_mult(lr_mult)
+    frozen = set(frozen)
+    tiers, spans, off = [], [], 0
+    for name, shp in specs:
+        n = int(np.prod(shp))
+        if name not in frozen:
+            f = 1.0 if is_regular(name) else m
+            if tiers and tiers[-1][1] == off and tiers[-1][2] == f:
+                tiers[-1] = (tiers[-1][0], off + n, f)
+            else:
+                tiers.append((off, off + n, f))
+            if spans and spans[-1][1] == off:
+                spans[-1] = (spans[-1][0], off + n)
+            else:
+                spans.append((off, off + n))
+        off += n
+    chunks = []
+    for lo, cnt in base_chunks:
+        for a, b in spans:
+            x, y = max(lo, a), min(lo + cnt, b)
+            if y > x:
+                chunks.append((x, y - x))
+    return TrainPlan(tiers, [n for n, _ in specs if n in frozen], chunks, off)
+
+
+def finetune_plan(cfg: NetConfig):
+    """TrainPlan of a one-pipeline model from its config alone (no device): cfg.lr_mult sorts the variables into two learning-rate
+    tiers, cfg.train_from freezes the dcnn layers before it."""
+    layers = frozen_layers(cfg)
+    frozen = ["dcnn/%s%s" % (l, k) for l in layers for k in ("W", "b")]
+    return tier_plan(param_specs(cfg), frozen, cfg.lr_mult, base_grad_chunks(cfg)[0])
+
+
 def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
     """Reference initialisers: W ~ truncated_normal(sigma=0.05) re-drawn beyond 2 sigma, b = 0.1
     (alexnet.py:40-46, tf_util.py:44-45); LSTM kernel glorot-uniform, bias 0 (TF defaults).
@@ -140,7 +276,7 @@ class LRCNEngine:
     copies the caller's tensors into the buffers, writes the block (ops.step_state_set) and replays.  Its LSTM launches run on a
     workspace of their own (lstm_ws_graph) whose tag stream the engine keeps: graph_tag_next, advanced by the graph's span per
     replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe."""
-    FC6_CHUNKS = 4          # row blocks of the fc6 weight gradient = all-reduce chunks of the data-parallel exchange
+    FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
     def __init__(self, cfg: NetConfig, max_clips: int, device="cuda:0", training=True, dp=None, flat=None):
@@ -182,27 +318,17 @@ class LRCNEngine:
                 self.G[name] = self.g[off:off + n].view(shp)
             self.offsets[name] = (off, n)
             off += n
-        # data-parallel exchange: chunks of the flat gradient in the order backward completes them (dp.py).  fc6W (85 % of the
-        # bytes) goes in FC6_CHUNKS row blocks, each reduced as soon as the GEMM that produces it is queued.
-        first_conv = self.offsets["dcnn/conv5W"][0]
-        f6o, f6n = self.offsets["dcnn/fc6W"]
-        rows6 = self.specs[[n for n, _ in self.specs].index("dcnn/fc6W")][1][0]
-        nch = max(1, min(self.FC6_CHUNKS, rows6 // 128))
-        edges = [(-(-rows6 * i // nch) + 127) // 128 * 128 if 0 < i < nch else (0 if i == 0 else rows6) for i in range(nch + 1)]
-        self.fc6_row_blocks = [(edges[i], edges[i + 1]) for i in range(nch) if edges[i + 1] > edges[i]]
-        self.grad_chunks = [(0, f6o)] if f6o > 0 else []
-        for bi, (r0, r1) in enumerate(self.fc6_row_blocks):
-            lo, hi = f6o + r0 * FC_DIM, f6o + r1 * FC_DIM
-            if bi == len(self.fc6_row_blocks) - 1:
-                hi = first_conv                                   # fc6b rides with the last block
-            self.grad_chunks.append((lo, hi - lo))
-        # conv5..conv3 (8.0 of the 9.3 MB of conv gradients) go out as soon as conv3's weight gradient is queued, while conv2 / conv1
-        # backward (40 % of the conv backward) still runs; only conv2 + conv1 (1.4 MB) are left for the end of the step
-        conv_lo = self.offsets["dcnn/conv2W"][0]
-        self.grad_chunks.append((first_conv, conv_lo - first_conv))
-        self.grad_chunks.append((conv_lo, total - conv_lo))
-        assert sum(c for _, c in self.grad_chunks) == total and all(
-            self.grad_chunks[i][0] + self.grad_chunks[i][1] == self.grad_chunks[i + 1][0] for i in range(len(self.grad_chunks) - 1))
+        # learning-rate tiers, frozen layers and the data-parallel exchange's chunks (finetune_plan): with nothing frozen the chunks
+        # are those of base_grad_chunks, in the order backward completes them
+        self.fc6_row_blocks = base_grad_chunks(cfg)[1]
+        self.plan = finetune_plan(cfg)
+        self.grad_chunks = self.plan.chunks
+        cut = len(frozen_layers(cfg))                          # dcnn layers [0, cut) are frozen: conv1..conv5, fc6, (fc7), (fc8)
+        self.first_conv = min(cut, len(CONV_LAYERS))           # first trainable conv layer; 5: the conv stack is frozen
+        self.fc_trains = {l: i >= cut for i, l in enumerate(dcnn_layers(cfg))}
+        self.dcnn_trains = cut < len(dcnn_layers(cfg))         # False: no gradient goes down into the tower at all
+        if training and cfg.classifier != "none" and not self.plan.tiers:
+            raise VltfError("train_from [%s] leaves this model nothing to train" % cfg.train_from)
         if cfg.optimizer == "adam" and training:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
 
@@ -431,7 +557,8 @@ class LRCNEngine:
 
     def get_grads(self):
         torch.cuda.synchronize(self.dev)
-        return {n: self.G[n].detach().cpu().numpy().copy() for n, _ in self.specs}
+        frozen = set(self.plan.frozen)                  # their range of g is never written: it holds nothing to hand out
+        return {n: self.G[n].detach().cpu().numpy().copy() for n, _ in self.specs if n not in frozen}
 
     # ---- optimizer state (what tf.train.Saver() keeps besides the weights, feeder.py:201: Adam slots + beta powers) -------
     OPT_PREFIX = "__optimizer__/"
@@ -664,7 +791,10 @@ class LRCNEngine:
         self._frames_now = n
         D, C, H, T = cfg.encode_dim(), cfg.num_classes, cfg.lstm_hidden, self.T
         sw = self.small_ws
-        side = self._side_stream()
+        kconv = self.first_conv                      # first trainable conv layer: nothing is computed for the layers before it
+        self._next_chunk = 0
+        # a frozen conv stack leaves the second stream nothing to run beside: it is not forked
+        side = self._side_stream() if kconv < len(self.layers) else None
         if side is not None:
             # the flipped / transposed weights every dgrad reads, all layers now, on the second stream (idle until fc6): a transpose
             # in front of its dgrad sits on the backward's critical chain while the weight gradient on the other stream takes the CUs
@@ -672,7 +802,7 @@ class LRCNEngine:
             # dgrad / wgrad the host issues first made no difference)
             side.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(side):
-                for L in self.layers[1:]:
+                for L in self.layers[kconv + 1:]:      # (a layer's dgrad runs only where the layer below it trains)
                     L["conv"].wt_transpose(P["dcnn/%sW" % L["name"]], L["wt"])
                 self._wt_ready.record(side)          # the first dgrad waits for this (below), nothing else on the launch stream does
         main = torch.cuda.current_stream(self.dev)
@@ -738,7 +868,9 @@ class LRCNEngine:
                     ops.gemm(S["hprev"], S["dz"], G[pre + "kernel"][din:], H, 4 * H, n, transa=True, ws=ws)
                     ops.colsum(S["dz"], G[pre + "bias"], sws, n, 4 * H)
                 param_grads(lstm_grads)
-                if l == 0 and lk:
+                if l == 0 and not self.dcnn_trains:
+                    pass                                                              # frozen tower: nobody reads dfeat
+                elif l == 0 and lk:
                     a = self.k_act[:n * 4 * H].view(ops.kc8_shape(4 * H, n))
                     w = self.k_w[:D * 4 * H].view(ops.kc8_shape(4 * H, D))
                     ops.pack_kc8(S["dz"], a, 4 * H, n, 1, 4 * H)                      # (position column, channel frame) = dz[frame][column]
@@ -762,31 +894,40 @@ class LRCNEngine:
             if D != Co:
                 ops.gemm(self.fc_in, d, G["fc_convert_w"], D, Co, rows, transa=True)
                 ops.colsum(d, G["fc_convert_b"], sw, rows, Co)
-                ops.gemm(d, P["fc_convert_w"], target, rows, D, Co, transb=True, relu_mask=relu_mask)
-            else:
+                if self.dcnn_trains:
+                    ops.gemm(d, P["fc_convert_w"], target, rows, D, Co, transb=True, relu_mask=relu_mask)
+            elif self.dcnn_trains:
                 target[:rows].copy_(d[:rows])
                 if relu_mask is not None:        # no fc in between (a feature pipeline): the encode layer's ReluGrad applies here
                     ops.relu_grad(target, relu_mask, rows * D)
-            if self.early:
+            if self.early and self.dcnn_trains:
                 # ReluGrad of the encode layer applies per frame after un-fusing
                 ops.temporal_fusion_bwd(self.dfc_in, self.dfeat, b, T, D, self.ff_method)
                 if self.f8 is None:
                     ops.relu_grad(self.dfeat, self.feat, n * D)
-        # ---- fc8 / fc7 / fc6 (dfeat already carries the ReluGrad of the encode layer)
+        # ---- fc8 / fc7 / fc6 (dfeat already carries the ReluGrad of the encode layer).  A layer gets its parameter gradients where it
+        # trains and hands a gradient down where the layer below it trains; below the first trainable layer nothing is launched.
+        trains = self.fc_trains
         d = self.dfeat
-        if self.f8 is not None:
+        if self.f8 is not None and trains["fc8"]:
             ops.gemm(self.f7, d, G["dcnn/fc8W"], FC_DIM, C, n, transa=True, ws=self.ws)
             ops.colsum(d, G["dcnn/fc8b"], sw, n, C)
-            ops.gemm(d, P["dcnn/fc8W"], self.df7, n, FC_DIM, C, transb=True, relu_mask=self.f7, ws=self.ws)
+            if trains["fc7"]:
+                ops.gemm(d, P["dcnn/fc8W"], self.df7, n, FC_DIM, C, transb=True, relu_mask=self.f7, ws=self.ws)
             d = self.df7
-        if self.f7 is not None:
+        if self.f7 is not None and trains["fc7"]:
             ops.gemm(self.f6, d, G["dcnn/fc7W"], FC_DIM, FC_DIM, n, transa=True, ws=self.ws)
             ops.colsum(d, G["dcnn/fc7b"], sw, n, FC_DIM)
-            ops.gemm(d, P["dcnn/fc7W"], self.df6, n, FC_DIM, FC_DIM, transb=True, relu_mask=self.f6, ws=self.ws)
+            if trains["fc6"]:
+                ops.gemm(d, P["dcnn/fc7W"], self.df6, n, FC_DIM, FC_DIM, transb=True, relu_mask=self.f6, ws=self.ws)
             d = self.df6
         L5 = self.layers[-1]
         kc8 = self._fc6_kc8(n)
-        if kc8:
+        f6o = self.offsets["dcnn/fc6W"][0]
+        convs_train = kconv < len(self.layers)
+        if not trains["fc6"]:
+            param_grads(lambda ws, sws: self._issue(f6o))         # everything above fc6, from the stream its parameter gradients ran on
+        elif kc8:
             # bf16 path (one stream): weight gradient in one pass on the packed-operand kernel (the exchange chunks follow it)
             ops.colsum(d, G["dcnn/fc6b"], sw, n, FC_DIM)
             F = self.flat_dim
@@ -799,17 +940,16 @@ class LRCNEngine:
             else:
                 # the exchange starts here, as on the fp32 path: a row block of fc6W = a range of the packed operand's 8-row
                 # blocks (block edges are multiples of 128), each block's all-reduce issued right behind its product
-                chunks = iter(self.grad_chunks)
-                if self.offsets["dcnn/fc6W"][0] > 0:
-                    self.dp.reduce_async(self.g, *next(chunks))
+                self._issue(f6o)
                 for r0, r1 in self.fc6_row_blocks:
                     ops.gemm_kc8(a[r0 // 8:r1 // 8], b_, G["dcnn/fc6W"][r0:r1], r1 - r0, FC_DIM, n, ws=self.ws)
-                    self.dp.reduce_async(self.g, *next(chunks))
-            a = self.k_act[:n * FC_DIM].view(ops.kc8_shape(FC_DIM, n))
-            w = self.k_w.view(ops.kc8_shape(FC_DIM, F))
-            ops.pack_kc8(d, a, FC_DIM, n, 1, FC_DIM)                          # (position j, channel frame) = dfc6[frame][j]
-            ops.pack_kc8(P["dcnn/fc6W"], w, FC_DIM, F, 1, FC_DIM)             # (position j, channel f) = W[f][j]
-            ops.gemm_kc8(a, w, L5["dp"], n, F, FC_DIM, ws=self.ws)
+                    self._issue(self._fc6_block_end(r1))
+            if convs_train:
+                a = self.k_act[:n * FC_DIM].view(ops.kc8_shape(FC_DIM, n))
+                w = self.k_w.view(ops.kc8_shape(FC_DIM, F))
+                ops.pack_kc8(d, a, FC_DIM, n, 1, FC_DIM)                          # (position j, channel frame) = dfc6[frame][j]
+                ops.pack_kc8(P["dcnn/fc6W"], w, FC_DIM, F, 1, FC_DIM)             # (position j, channel f) = W[f][j]
+                ops.gemm_kc8(a, w, L5["dp"], n, F, FC_DIM, ws=self.ws)
         else:
             def fc6_grads(ws, sws, d=d):
                 ops.colsum(d, G["dcnn/fc6b"], sws, n, FC_DIM)
@@ -819,15 +959,14 @@ class LRCNEngine:
                 # the exchange starts here: everything produced so far, then fc6W block by block -- block i is on the wire
                 # (RCCL's stream, which waits for the stream these launches are on) while block i+1 is computed, and the whole 85 % of
                 # the bytes before the conv backward is far along
-                chunks = iter(self.grad_chunks)
-                if self.offsets["dcnn/fc6W"][0] > 0:
-                    self.dp.reduce_async(self.g, *next(chunks))
+                self._issue(f6o)
                 flat_p = L5["p"].view(self.N, self.flat_dim)
                 for r0, r1 in self.fc6_row_blocks:
                     ops.gemm(flat_p[:, r0:], d, G["dcnn/fc6W"][r0:r1], r1 - r0, FC_DIM, n, transa=True, lda=self.flat_dim)
-                    self.dp.reduce_async(self.g, *next(chunks))
+                    self._issue(self._fc6_block_end(r1))
             param_grads(fc6_grads)
-            ops.gemm(d, P["dcnn/fc6W"], L5["dp"], n, self.flat_dim, FC_DIM, transb=True, ws=self.ws)     # the chain: into pool5's gradient
+            if convs_train:
+                ops.gemm(d, P["dcnn/fc6W"], L5["dp"], n, self.flat_dim, FC_DIM, transb=True, ws=self.ws)     # the chain: into pool5's gradient
         # ---- conv stack, last to first
         if side is not None:
             main.wait_event(self._wt_ready)
@@ -837,7 +976,10 @@ class LRCNEngine:
             with torch.cuda.stream(side):
                 launch()
 
-        for li in reversed(range(len(self.layers))):
+        issue_at = max(kconv, 2)        # conv5 .. conv3 (or .. the first trainable layer) go out behind this layer's weight gradient
+        if convs_train:
+            issue_hi = sum(self.offsets["dcnn/%sb" % self.layers[issue_at]["name"]])      # flat offset behind that layer's gradients
+        for li in reversed(range(kconv, len(self.layers))):
             L = self.layers[li]
             name, conv = L["name"], L["conv"]
             x_in = self.layers[li - 1]["out"][:n] if li > 0 else self.x0[:n]
@@ -864,8 +1006,10 @@ class LRCNEngine:
                     ops.pack_c8(dy, L["dyb"][:n], L["dy_halo"], L["dy_halo"])
                 self._run(name + ".wgrad", conv.c8_wgrad, L["xb"][:n], L["dyb"][:n], G["dcnn/%sW" % name], self.ws)
                 ops.bias_grad_c8(L["dyb"][:n], G["dcnn/%sb" % name], sw, conv.cout, L["dy_halo"])
-                if self.dp is not None and name == "conv3":
-                    self.dp.reduce_async(self.g, *self.grad_chunks[-2])
+                if li == issue_at:
+                    self._issue(issue_hi)
+                if li == kconv:
+                    continue                          # the layer below is frozen: no input gradient
                 prev = self.layers[li - 1]
                 conv.c8_pack_w(P["dcnn/%sW" % name], L["wbt"], True)
                 if prev["pool"]:
@@ -879,21 +1023,21 @@ class LRCNEngine:
             last_on_main = side is not None and li == 0
             wws, wsw = (self.ws_side, self.small_ws_side) if (side is not None and not last_on_main) else (self.ws, sw)
 
-            def wgrad(name=name, conv=conv, x_in=x_in, dy=dy, wws=wws, wsw=wsw):
+            def wgrad(name=name, conv=conv, x_in=x_in, dy=dy, wws=wws, wsw=wsw, li=li):
                 if conv.fuses_bias():      # bias gradient comes out of the same pass over dy
                     self._run(name + ".wgrad", conv.wgrad, x_in, dy, G["dcnn/%sW" % name], wws, db=G["dcnn/%sb" % name])
                 else:
                     self._run(name + ".wgrad", conv.wgrad, x_in, dy, G["dcnn/%sW" % name], wws)
                     ops.bias_grad_nchw(dy, G["dcnn/%sb" % name], wsw)
-                if self.dp is not None and name == "conv3":
+                if li == issue_at:
                     # issued from the stream the weight gradients ran on: RCCL's stream waits for that stream only
-                    self.dp.reduce_async(self.g, *self.grad_chunks[-2])
+                    self._issue(issue_hi)
 
             if side is None or last_on_main:
                 wgrad()                               # (conv1's: the chain ends here -- beside what the second stream still holds)
             else:
                 on_side(wgrad)                        # beside this layer's dgrad / the next pool backward
-            if li > 0:
+            if li > kconv:
                 prev = self.layers[li - 1]
                 wt = self.wt
                 if side is not None:
@@ -906,8 +1050,23 @@ class LRCNEngine:
                     self._run(name + ".dgrad", conv.dgrad, dy, wt, prev["dy"][:n], relu_mask=prev["y"][:n])
         if side is not None:
             torch.cuda.current_stream(self.dev).wait_stream(side)
-        if self.dp is not None:
-            self.dp.reduce_async(self.g, *self.grad_chunks[-1])
+        self._issue(self.plan.total)
+
+    def _issue(self, hi):
+        """Data parallel: starts the exchange of every chunk of the plan not yet issued that ends at or before flat offset `hi`.  The
+        flat buffer is in the order backward produces the gradients, so the caller names the end of what the launches queued so far (on
+        the current stream) have written."""
+        if self.dp is None:
+            return
+        while self._next_chunk < len(self.grad_chunks) and sum(self.grad_chunks[self._next_chunk]) <= hi:
+            self.dp.reduce_async(self.g, *self.grad_chunks[self._next_chunk])
+            self._next_chunk += 1
+
+    def _fc6_block_end(self, r1):
+        """Flat offset behind the fc6W row block ending at row r1; fc6b rides with the last block."""
+        f6o, f6n = self.offsets["dcnn/fc6W"]
+        end = f6o + r1 * FC_DIM
+        return end if end < f6o + f6n else f6o + f6n + FC_DIM
 
     def _side_stream(self):
         """Second HIP stream of the backward pass, or None (VLTF_WGRAD_STREAM=0; the bf16 path).  Independent launches -- the dgrad
@@ -970,7 +1129,8 @@ class LRCNEngine:
         gradients to the exchange and apply the same update as every other rank."""
         if self.dp is None:
             raise VltfError("train_step_empty is a data-parallel call")
-        ops.fill(self.g, 0.0)
+        for lo, hi, _ in self.plan.tiers:                # (frozen ranges of g are never written, read or exchanged)
+            ops.fill(self.g[lo:hi], 0.0)
         ops.fill(self.stats, 0.0)
         for lo, cnt in self.grad_chunks:
             self.dp.reduce_async(self.g, lo, cnt)
@@ -979,16 +1139,28 @@ class LRCNEngine:
     def _finish_step(self, rows, lr, clip_norm, fetch):
         if self.dp is not None:
             self.dp.wait()
-        ops.sumsq(self.g, self.ss, self.small_ws)
+        tiers = None if self.plan.full_range() else self.plan.tiers      # None: the plain calls (one full-range tier, same bits)
+        if tiers is None:
+            ops.sumsq(self.g, self.ss, self.small_ws)
+        else:
+            ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
         self.step_count += 1
         # a step whose LSTM cluster launch timed out must not reach the weights -- also with fetch=False, where the host reads the
         # status only later: the optimizer launch drops the update on the device (ops.step_guard), check_status raises at the next fetch
         skip = ops.step_guard(self._skip, getattr(self, "lstm_ws", None), self.lstm_ws_graph)
         if self._tag_off is not None:             # captured: lr and Adam's step size from the step state (written before each replay)
-            if self.cfg.optimizer == "adam":
+            if self.cfg.optimizer == "adam" and tiers is not None:
+                ops.adam_apply_tiers_st(self.w, self.g, self.adam_m, self.adam_v, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
+            elif self.cfg.optimizer == "adam":
                 ops.adam_apply_st(self.w, self.g, self.adam_m, self.adam_v, self.state, clip_norm, self.ss, 1.0, skip=skip)
+            elif tiers is not None:
+                ops.sgd_apply_tiers_st(self.w, self.g, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
             else:
                 ops.sgd_apply_st(self.w, self.g, self.state, clip_norm, self.ss, 1.0, skip=skip)
+        elif tiers is not None and self.cfg.optimizer == "adam":
+            ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif tiers is not None:
+            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         elif self.cfg.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         else:

@@ -39,8 +39,8 @@ import numpy as np
 import torch
 
 from . import ops
-from ._ffi import VltfError
-from .engine import FORGET_BIAS, LRCNEngine, NetConfig, param_specs
+from ._ffi import MAX_LR_TIERS, VltfError
+from .engine import FORGET_BIAS, LRCNEngine, NetConfig, dcnn_layers, finetune_plan, frozen_layers, param_specs, tier_plan
 
 
 @dataclass
@@ -55,6 +55,7 @@ class PipelineSpec:
     lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state)
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
+    train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
 
 
 @dataclass
@@ -109,6 +110,8 @@ class PipeNode:
             raise VltfError("Undefined representation [%s]" % s.representation)
         if s.input_fusion not in (None, "avg", "maximum", "concat", "ibias"):
             raise VltfError("Unknown fusion method: [%s]" % s.input_fusion)               # tf_util.py:178-179
+        if s.train_from is not None and s.representation != "dcnn":
+            raise VltfError("pipeline [%s]: train_from freezes dcnn layers, the representation is [%s]" % (s.name, s.representation))
         self.cpv_out = srcs[-1].cpv            # model.py:44-59: `cpv` is the loop variable = the LAST input's, whatever the fusion does
         # ---- stage 0: the pipeline's main tensor after the optional input fusion: (dim, fpc, max rows) ----------------------------
         self.tower = None
@@ -126,8 +129,9 @@ class PipeNode:
                 raise VltfError("pipeline [%s]: the fused frame datasets differ in shape / frames per clip" % s.name)
             self.fpc = seq[0].fpc
             cfg = NetConfig(image_shape=shapes.pop(), num_classes=C, fpc=self.fpc, frame_encoding_layer=s.frame_encoding_layer,
-                            classifier="none", optimizer=g.optimizer, conv_math=g.conv_math)
+                            classifier="none", optimizer=g.optimizer, conv_math=g.conv_math, train_from=s.train_from)
             self.tower_cfg = cfg
+            self.tower_trains = len(frozen_layers(cfg)) < len(dcnn_layers(cfg))     # False: the tower's backward is never called
             self.x_dim, self.max_rows0 = cfg.encode_dim(), seq[0].max_rows
         elif self.fusion in ("avg", "maximum"):
             if len({(x.dim, x.max_rows) for x in srcs}) != 1:
@@ -278,7 +282,8 @@ class PipeNode:
         R0, D0 = self.max_rows0, self.x_dim
         # is a gradient w.r.t. the stage-0 tensor wanted?  (a pipeline input other than the LSTM's state vector)
         self.primary_pipe = self.tower is None and any(x.kind == "pipe" for x in self.srcs if x is not self.state_src)
-        self.wants_feat = self.tower is not None or self.rep_fc or self.primary_pipe     # ... w.r.t. the classifier's input?
+        # ... w.r.t. the classifier's input?  (not for a fully frozen tower: nobody would read it)
+        self.wants_feat = (self.tower is not None and self.tower_trains) or self.rep_fc or self.primary_pipe
         if self.tower is None and self.fusion:
             self.xf = buf(R0, D0)
         if self.rep_fc:
@@ -744,15 +749,18 @@ def model_specs(pipelines, datasets, num_classes):
 
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
-                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32"):
+                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
+        """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
+        freezes the first layers of its tower (engine.tier_plan)."""
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
-        self._plan(pipelines, datasets, num_classes, optimizer, dropout_keep_prob, conv_math)
+        self._plan(pipelines, datasets, num_classes, optimizer, dropout_keep_prob, conv_math, lr_mult)
         self._allocate()
 
-    def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32"):
-        """The graph and its variable list (self.nodes, self.specs): host logic only, no device (model_specs uses it alone)."""
+    def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
+        """The graph, its variable list and its training plan (self.nodes, self.specs, self.plan): host logic only, no device
+        (model_specs uses it alone)."""
         if not pipelines:
             raise VltfError("no pipeline defined")
         self.num_classes, self.optimizer, self.dropout_keep_prob, self.conv_math = int(num_classes), optimizer, float(dropout_keep_prob or 0.0), conv_math
@@ -804,6 +812,26 @@ class GraphEngine:
         dup = {n for n, _ in self.specs if [m for m, _ in self.specs].count(n) > 1}
         if dup:
             raise VltfError("Variable %s already exists" % sorted(dup)[0])
+        # ---- learning-rate tiers, frozen variables and the data-parallel chunks in the order backward completes them: per pipeline its
+        # head, then its tower's own chunk list
+        frozen, chunks, off = [], [], 0
+        for nd in order:
+            cnt = sum(int(np.prod(shp)) for _, shp in nd.head_specs())
+            if cnt:
+                chunks.append((off, cnt))
+            off += cnt
+            if nd.spec.representation == "dcnn":
+                tp = finetune_plan(nd.tower_cfg)
+                frozen += [nd.scope + n for n in tp.frozen]
+                chunks += [(off + lo, c) for lo, c in tp.chunks]
+                off += tp.total
+        self.lr_mult = lr_mult
+        self.plan = tier_plan(self.specs, frozen, lr_mult, chunks)
+        if not self.plan.tiers:
+            raise VltfError("the train_from settings leave this model nothing to train")
+        if len(self.plan.tiers) > MAX_LR_TIERS:
+            raise VltfError("this model needs %d learning-rate tiers (ranges of the flat parameter buffer with one factor, frozen ranges "
+                            "between them); the update kernels take %d" % (len(self.plan.tiers), MAX_LR_TIERS))
 
     def _allocate(self):
         order = list(reversed(self.nodes))
@@ -820,7 +848,8 @@ class GraphEngine:
             self.P.update(nd.P)
             self.G.update(nd.G)
         assert off == total
-        # data-parallel chunks in the order backward completes them: per pipeline its head, then its tower's own chunk list
+        # data-parallel chunks in the order backward completes them: per pipeline its head, then the chunk list its tower issues
+        # (= self.plan.chunks, which _plan derives from the configs alone)
         self.grad_chunks = []
         for nd in order:
             if nd.head_cnt:
@@ -868,7 +897,8 @@ class GraphEngine:
 
     def get_grads(self):
         self._sync()
-        return {n: self.G[n].detach().cpu().numpy().copy() for n, _ in self.specs}
+        frozen = set(self.plan.frozen)
+        return {n: self.G[n].detach().cpu().numpy().copy() for n, _ in self.specs if n not in frozen}
 
     OPT_PREFIX = LRCNEngine.OPT_PREFIX
     get_opt_state = LRCNEngine.get_opt_state
@@ -996,7 +1026,8 @@ class GraphEngine:
         """This rank's shard of the global batch is empty: contribute zeros to the exchange, apply the same update as the others."""
         if self.dp is None:
             raise VltfError("train_step_empty is a data-parallel call")
-        ops.fill(self.g, 0.0)
+        for lo, hi, _ in self.plan.tiers:
+            ops.fill(self.g[lo:hi], 0.0)
         ops.fill(self.stats, 0.0)
         for lo, cnt in self.grad_chunks:
             self.dp.reduce_async(self.g, lo, cnt)
@@ -1005,10 +1036,18 @@ class GraphEngine:
     def _finish_step(self, rows, lr, clip_norm, fetch):
         if self.dp is not None:
             self.dp.wait()
-        ops.sumsq(self.g, self.ss, self.small_ws)
+        tiers = None if self.plan.full_range() else self.plan.tiers      # LRCNEngine._finish_step
+        if tiers is None:
+            ops.sumsq(self.g, self.ss, self.small_ws)
+        else:
+            ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
         self.step_count += 1
         skip = ops.step_guard(self._skip, *[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])   # LRCNEngine._finish_step
-        if self.optimizer == "adam":
+        if tiers is not None and self.optimizer == "adam":
+            ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif tiers is not None:
+            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)

@@ -669,6 +669,53 @@ def adam_apply_st(w, g, m, v, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, sk
               stream())
 
 
+# ---- tiered update (vltf.h: vl_lr_tier): per-range learning-rate multipliers, gaps untouched --------------------------------------
+def _tiers(tiers):
+    """[(begin, end, lr_mult)] -> (vl_lr_tier array, count); the library validates the table."""
+    tiers = list(tiers)
+    arr = (_ffi.LrTier * max(len(tiers), 1))()
+    for k, (lo, hi, mult) in enumerate(tiers):
+        arr[k].begin, arr[k].end, arr[k].lr_mult = int(lo), int(hi), float(mult)
+    return arr, len(tiers)
+
+
+def sumsq_tiers(g, tiers, out, ws):
+    """out[0] = sum g^2 over the elements inside the tiers; elements outside are not read."""
+    _f32(g, out, ws)
+    if ws.numel() < 1024:
+        raise _ffi.VltfError("sumsq_tiers: workspace needs 1024 floats")
+    arr, n = _tiers(tiers)
+    _ffi.call("vl_sumsq_tiers", _p(g), g.numel(), arr, n, _p(out), _p(ws), stream())
+
+
+def sgd_apply_tiers(w, g, tiers, lr, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """sgd_apply over the tiers [(begin, end, lr_mult)] only, each with lr * lr_mult: one launch."""
+    _f32(w, g, sumsq_t)
+    arr, n = _tiers(tiers)
+    _ffi.call("vl_sgd_apply_tiers", _p(w), _p(g), w.numel(), lr, clip_norm, _p(sumsq_t), gscale, _skip_word(skip), arr, n, stream())
+
+
+def adam_apply_tiers(w, g, m, v, tiers, lr, step, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    _f32(w, g, m, v, sumsq_t)
+    arr, n = _tiers(tiers)
+    _ffi.call("vl_adam_apply_tiers", _p(w), _p(g), _p(m), _p(v), w.numel(), lr, clip_norm, _p(sumsq_t), gscale, step, _skip_word(skip),
+              arr, n, stream())
+
+
+def sgd_apply_tiers_st(w, g, tiers, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    _f32(w, g, sumsq_t)
+    arr, n = _tiers(tiers)
+    _ffi.call("vl_sgd_apply_tiers_st", _p(w), _p(g), w.numel(), _state(state), clip_norm, _p(sumsq_t), gscale, _skip_word(skip), arr, n,
+              stream())
+
+
+def adam_apply_tiers_st(w, g, m, v, tiers, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    _f32(w, g, m, v, sumsq_t)
+    arr, n = _tiers(tiers)
+    _ffi.call("vl_adam_apply_tiers_st", _p(w), _p(g), _p(m), _p(v), w.numel(), _state(state), clip_norm, _p(sumsq_t), gscale,
+              _skip_word(skip), arr, n, stream())
+
+
 def step_guard(skip, *lstm_workspaces):
     """skip[0] = 1 if a cluster-form LSTM launch on any of the workspaces has timed out since its status was last read (the word is
     sticky, lstm_seq_check reads and resets it), else 0 -- on the stream, no host round trip.  Hand `skip` to sgd_apply / adam_apply:

@@ -11,7 +11,7 @@ import torch
 
 from . import dp as dpmod
 from .defs_ import defs
-from .engine import LRCNEngine, NetConfig, init_params
+from .engine import LRCNEngine, NetConfig, init_params, is_regular
 from .parse_opts import parse_seq
 from .settings_ import Settings
 from .train import Train
@@ -52,7 +52,8 @@ def pipeline_net_config(settings, p, dataset):
               frame_encoding_layer=p.frame_encoding_layer, classifier=p.classifier or defs.classifier.fc,
               dropout_keep_prob=settings.get_dropout(), optimizer=settings.train.optimizer if settings.train else "sgd",
               conv_math=os.environ.get("VLTF_CONV_MATH", "f32"),     # "bf16x3": opt-in split-bf16 conv products (not a reference key)
-              step_graph=step_graph_requested())                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
+              step_graph=step_graph_requested(),                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
+              lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None))
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -86,7 +87,8 @@ def graph_config(settings, feeder, batch):
         specs.append(PipelineSpec(name=name, input=list(p.input), representation=p.representation,
                                   frame_encoding_layer=p.frame_encoding_layer, fc_output_dim=getattr(p, "fc_output_dim", None),
                                   classifier=p.classifier, lstm_params=tuple(p.lstm_params) if p.lstm_params else None,
-                                  frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None, input_fusion=p.input_fusion))
+                                  frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None, input_fusion=p.input_fusion,
+                                  train_from=getattr(p, "train_from", None)))
     infos, dsets = {}, {}
     for tag in sorted({i for sp in specs for i in sp.input if i not in settings.pipelines}):
         found = feeder.get_dataset_by_tag(tag)
@@ -317,7 +319,7 @@ def main(init_file, seed=0, device=None):
     else:
         engine = GraphEngine(specs, infos, settings.num_classes, device=dev_name, training=bool(settings.train), dp=gar,
                              optimizer=settings.train.optimizer if settings.train else "sgd", dropout_keep_prob=settings.get_dropout(),
-                             conv_math=os.environ.get("VLTF_CONV_MATH", "f32"))
+                             conv_math=os.environ.get("VLTF_CONV_MATH", "f32"), lr_mult=settings.train.lr_mult if settings.train else None)
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))
@@ -329,6 +331,13 @@ def main(init_file, seed=0, device=None):
             loaded = {scope + k: v for k, v in load_weights_file(pl.weights_file).items()}
             # fc8 is re-initialised (alexnet.py:273)
             params.update({k: v for k, v in loaded.items() if k in params and not k.startswith(scope + "dcnn/fc8")})
+    if settings.train and not engine.plan.full_range():
+        frozen = set(engine.plan.frozen)
+        if settings.train.lr_mult not in (None, 1.0):              # train.py:162
+            info("Setting up two-tier training with a factor of %s for layers: %s" %
+                 (settings.train.lr_mult, [n for n, _ in engine.specs if n not in frozen and not is_regular(n)]))
+        if frozen:
+            info("Frozen (train_from): %s" % [n for n, _ in engine.specs if n in frozen])
     engine.load_params(params)
     feeder.init_saveload(engine, settings.resume_file)
     if os.environ.get("VLTF_PREFETCH", "2") != "0":      # batches read + uploaded ahead of the loop (0 = the reference's synchronous feed)

@@ -87,10 +87,26 @@ class Settings:
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         network.input_shape = self.read_field(content, "input_shape", listify=True)
         network.input_fusion = self.read_field(content, "input_fusion", validate=defs.fusion_method)
+        network.train_from = self.read_train_from(content, network)
         unread = [x for x in content if x not in self.pipeline_field_cache]
         if unread:
             error("Undefined pipeline field(s):" + str(unread))
         return network
+
+    def read_train_from(self, content, network):
+        """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
+        before it keeps its weights; `classifier` freezes the whole dcnn (engine.frozen_layers)."""
+        layer = self.read_field(content, "train_from")
+        if layer in (None, "None"):
+            return None
+        if network.representation != defs.representation.dcnn:
+            error("train_from freezes dcnn layers, but the pipeline's representation is [%s]" % network.representation)
+        from .engine import NetConfig, VltfError, frozen_layers
+        try:
+            frozen_layers(NetConfig(frame_encoding_layer=network.frame_encoding_layer, train_from=str(layer)))
+        except VltfError as ex:
+            error(str(ex))
+        return str(layer)
 
     # ---- run block (settings_.py:210-366) -------------------------------------------------------------------
     def read_config(self, config, init_file):
@@ -126,9 +142,11 @@ class Settings:
                 t.batch_size, t.epochs = int(obj["batch_size"]), int(obj["epochs"])
                 t.optimizer = defs.check(obj["optimizer"], defs.optim)
                 t.base_lr = float(obj["base_lr"])
+                # two learning-rate tiers (train.py:152-197, whose own code is broken: SURVEY 2): the `modified` variables -- fc8, the
+                # LSTM, the fc heads -- learn with base_lr * lr_mult, the pretrained dcnn with base_lr (engine.is_regular)
                 t.lr_mult = float(obj["lr_mult"]) if obj.get("lr_mult") not in (None, "None") else None
-                if t.lr_mult is not None:
-                    error("Two-tier learning rates (lr_mult) are broken in the reference (train.py:152-197) and not built.")
+                if t.lr_mult is not None and not (t.lr_mult > 0 and t.lr_mult != float("inf")):
+                    error("lr_mult must be a finite number > 0, got [%s] (train_from holds layers fixed)" % obj["lr_mult"])
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
