@@ -454,6 +454,28 @@ int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float* v, int64_t
  * is the single full range call vl_sumsq. */
 int vl_sumsq_tiers(const float* g, int64_t count, const vl_lr_tier* tiers, int n_tiers, float* out, float* ws, vl_stream_t stream);
 
+/* ---- SGD with momentum / Nesterov: tf.train.MomentumOptimizer(lr, momentum, use_nesterov) -------------------------------------------
+ * (= torch.optim.SGD(momentum, dampening=0, nesterov)).  The learning rate stays OUTSIDE the accumulator, so a schedule that changes
+ * lr rescales no history; clipping and gscale scale the gradient BEFORE it is accumulated.  Per element, every step one fp32 rounding,
+ * in this order (no contraction is left to the compiler, and the scalar and 16-byte loops share the element function):
+ *     sc   = the clip scale of vl_sgd_apply (gscale * clip_norm / max(gscale*sqrt(*sumsq), clip_norm), or gscale)
+ *     gi   = g * sc
+ *     a'   = fma(momentum, a, gi)                      the accumulator `accum`, count floats, zero before the first step
+ *     w'   = fma(-lr_k, a', w)                         nesterov == 0
+ *     w'   = fma(-lr_k, fma(momentum, a', gi), w)      nesterov != 0
+ *     lr_k = (float)(lr * tier.lr_mult)                the tier changes lr only, never the accumulator
+ * tiers == NULL && n_tiers == 0 is the full range {0, count, 1.0f}; any other table obeys the rules above, and elements outside every
+ * tier are neither loaded nor stored (w, g and accum alike).  accum != NULL, 0 < momentum < 1 (momentum 0 is vl_sgd_apply's job: this
+ * rule at 0 does not round as that one does).  skip: as vl_sgd_apply (accum stays untouched too).  One launch, the grid of
+ * vl_sgd_apply; it moves 5 floats per element (reads w, g, accum; writes w, accum), all of the interior as 16-byte accesses.
+ * vl_momentum_apply_st: lr = state->lr; momentum and nesterov are constants of a run and stay launch arguments. */
+int vl_momentum_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov,
+                      float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                      const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream);
+int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
+                         int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                         const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream);
+
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);
 /* ReluGrad in place: d[i] = y[i] > 0 ? d[i] : 0 (y = the ReLU's forward output, alexnet.py:228,248). */

@@ -96,6 +96,8 @@ SIGNATURES = {
     "vl_sgd_apply_tiers_st": (i32, [p, p, i64, p, f32, p, f32, p, p, i32, p]),
     "vl_adam_apply_tiers_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p, i32, p]),
     "vl_sumsq_tiers": (i32, [p, i64, p, i32, p, p, p]),
+    "vl_momentum_apply": (i32, [p, p, p, i64, f32, f32, i32, f32, p, f32, p, p, i32, p]),
+    "vl_momentum_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),

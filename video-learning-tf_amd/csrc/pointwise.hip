@@ -2086,6 +2086,51 @@ __device__ __forceinline__ void adam_apply_body(float* __restrict__ w, const flo
     }
 }
 
+// tf.train.MomentumOptimizer: the accumulator takes the clipped gradient, lr stays outside it (vltf.h: vl_momentum_apply)
+__device__ __forceinline__ void momentum_elem(float& w, float g, float& a, float sc, float lr_k, float momentum, bool nesterov) {
+#pragma clang fp contract(off)
+    const float gi = g * sc;
+    const float ai = __builtin_fmaf(momentum, a, gi);
+    a = ai;
+    w = __builtin_fmaf(-lr_k, nesterov ? __builtin_fmaf(momentum, ai, gi) : ai, w);
+}
+
+__device__ __forceinline__ void momentum_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a,
+                                                    const tier_table& tt, float lr, float momentum, bool nesterov, float clip_norm,
+                                                    const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
+    const float sc = clip_scale(clip_norm, sumsq, gscale);
+    const int phase = align_phase(w, g, a, nullptr);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        const float lr_k = lr * tt.t[k].lr_mult;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
+        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+        float4* __restrict__ a4 = reinterpret_cast<float4*>(a + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            float4 wv = w4[i], av = a4[i];
+            const float4 gv = g4[i];
+            momentum_elem(wv.x, gv.x, av.x, sc, lr_k, momentum, nesterov);
+            momentum_elem(wv.y, gv.y, av.y, sc, lr_k, momentum, nesterov);
+            momentum_elem(wv.z, gv.z, av.z, sc, lr_k, momentum, nesterov);
+            momentum_elem(wv.w, gv.w, av.w, sc, lr_k, momentum, nesterov);
+            a4[i] = av;
+            w4[i] = wv;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
+    }
+}
+
+__global__ void momentum_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, tier_table tt, float lr,
+                                      float momentum, int nesterov, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                      const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    momentum_apply_body(w, g, a, tt, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                        (int64_t)gridDim.x * blockDim.x);
+}
+
 __global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, float lr, float clip_norm,
                                  const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
     if (skip && *skip) return;                                        // the step's results are invalid (vl_status_or): no update
@@ -2241,6 +2286,49 @@ extern "C" int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float*
     tier_table tt;
     if (int rc = tier_table_make("vl_adam_apply_tiers_st", tiers, n_tiers, count, &tt)) return rc;
     return adam_apply_st_launch(w, g, m, v, count, tt, state, clip_norm, sumsq, gscale, skip, stream);
+}
+
+// ---- momentum / Nesterov update (vltf.h: vl_momentum_apply): two entry points, a NULL table is the full range ---------------------
+__global__ void momentum_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, tier_table tt,
+                                         const vl_step_state* __restrict__ st, float momentum, int nesterov, float clip_norm,
+                                         const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    momentum_apply_body(w, g, a, tt, st->lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
+                        (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+static int momentum_args(const char* who, const float* w, const float* g, const float* accum, int64_t count, float momentum,
+                         const vl_lr_tier* tiers, int n_tiers, tier_table* tt) {
+    VL_CHECK(w && g && accum && count > 0, "%s: bad argument", who);
+    VL_CHECK(momentum > 0.f && momentum < 1.f, "%s: momentum must lie in (0, 1), got %g", who, (double)momentum);   // (NaN fails)
+    if (!tiers && n_tiers == 0) {
+        *tt = tier_table_full(count);
+        return 0;
+    }
+    return tier_table_make(who, tiers, n_tiers, count, tt);
+}
+
+extern "C" int vl_momentum_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov,
+                                 float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, const vl_lr_tier* tiers,
+                                 int n_tiers, vl_stream_t stream) {
+    tier_table tt;
+    if (int rc = momentum_args("vl_momentum_apply", w, g, accum, count, momentum, tiers, n_tiers, &tt)) return rc;
+    hipLaunchKernelGGL(momentum_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt, lr,
+                       momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
+                                    int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                                    const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream) {
+    VL_CHECK(state, "vl_momentum_apply_st: bad argument");
+    tier_table tt;
+    if (int rc = momentum_args("vl_momentum_apply_st", w, g, accum, count, momentum, tiers, n_tiers, &tt)) return rc;
+    hipLaunchKernelGGL(momentum_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt,
+                       state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
 }
 
 __global__ void fill_kernel(float* __restrict__ p, int64_t count, float value) {

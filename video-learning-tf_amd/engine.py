@@ -17,6 +17,7 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import contextlib
+import gc
 import os
 import time
 
@@ -57,6 +58,8 @@ class NetConfig:
     step_graph: bool = False                    # train_step_u8 / forward_u8 captured once per input key and replayed (LRCNEngine docstring)
     lr_mult: Optional[float] = None             # train.lr_mult: learning-rate factor of the `modified` variables (finetune_plan); None = 1
     train_from: Optional[str] = None            # first trainable dcnn layer (TRAIN_FROM): every dcnn layer before it is frozen
+    momentum: float = 0.0                       # train.momentum: tf.train.MomentumOptimizer's, in [0, 1); 0 = plain SGD (optimizer sgd only)
+    nesterov: bool = False                      # train.nesterov: use_nesterov of the same (needs momentum > 0)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -157,6 +160,20 @@ def check_lr_mult(lr_mult):
     if not (m > 0.0 and math.isfinite(m)):
         raise VltfError("lr_mult must be a finite number > 0, got %r (use train_from to hold layers fixed)" % (lr_mult,))
     return m
+
+
+def check_momentum(optimizer, momentum, nesterov):
+    """(momentum, nesterov) of an SGD run, None read as 0 / False.  Refused: momentum outside [0, 1), nesterov without momentum, either
+    with Adam (which keeps its own first moment)."""
+    m = 0.0 if momentum is None else float(momentum)
+    nesterov = bool(nesterov)
+    if not (0.0 <= m < 1.0):
+        raise VltfError("momentum must lie in [0, 1), got %r" % (momentum,))
+    if nesterov and m == 0.0:
+        raise VltfError("nesterov needs momentum > 0")
+    if optimizer == "adam" and (m > 0.0 or nesterov):
+        raise VltfError("momentum / nesterov belong to optimizer sgd; adam has its own first moment")
+    return m, nesterov
 
 
 def base_grad_chunks(cfg: NetConfig):
@@ -287,6 +304,7 @@ class LRCNEngine:
         if cfg.step_graph and dp is not None:
             raise VltfError("step_graph is refused with data parallelism: capturing the gradient exchange's collectives is unmeasured "
                             "on this stack")
+        self.momentum, self.nesterov = check_momentum(cfg.optimizer, cfg.momentum, cfg.nesterov)
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
         self.dev = torch.device(device)
@@ -331,6 +349,7 @@ class LRCNEngine:
             raise VltfError("train_from [%s] leaves this model nothing to train" % cfg.train_from)
         if cfg.optimizer == "adam" and training:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
+        self.mom = torch.zeros(total, device=dev) if self.momentum > 0.0 and training else None    # the momentum accumulator
 
         # ---- conv stack plan.  Tensors a conv gathers from (its x, and the dy its dgrad reads) are stored
         # with a zero halo equal to the conv's SAME padding, so the im2col gather is test-free (vltf.h).
@@ -570,6 +589,8 @@ class LRCNEngine:
         if self.cfg.optimizer == "adam" and self.training:
             st[self.OPT_PREFIX + "adam_m"] = self.adam_m.detach().cpu().numpy().copy()
             st[self.OPT_PREFIX + "adam_v"] = self.adam_v.detach().cpu().numpy().copy()
+        if self.mom is not None:
+            st[self.OPT_PREFIX + "momentum"] = self.mom.detach().cpu().numpy().copy()
         return st
 
     def load_opt_state(self, state, global_step=None):
@@ -582,16 +603,20 @@ class LRCNEngine:
             missing.append(key)
             if global_step is not None:
                 self.step_count = int(global_step)
+        slots = []
         if self.cfg.optimizer == "adam" and self.training:
-            for name, t in (("adam_m", self.adam_m), ("adam_v", self.adam_v)):
-                a = state.get(self.OPT_PREFIX + name)
-                if a is None:
-                    missing.append(self.OPT_PREFIX + name)
-                    continue
-                a = np.asarray(a, np.float32)
-                if a.shape != (t.numel(),):
-                    raise VltfError("optimizer state %s has shape %s, expected (%d,)" % (name, a.shape, t.numel()))
-                t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+            slots = [("adam_m", self.adam_m), ("adam_v", self.adam_v)]
+        elif self.mom is not None:
+            slots = [("momentum", self.mom)]
+        for name, t in slots:
+            a = state.get(self.OPT_PREFIX + name)
+            if a is None:
+                missing.append(self.OPT_PREFIX + name)
+                continue
+            a = np.asarray(a, np.float32)
+            if a.shape != (t.numel(),):
+                raise VltfError("optimizer state %s has shape %s, expected (%d,)" % (name, a.shape, t.numel()))
+            t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
         return missing
 
     def check_status(self):
@@ -1153,16 +1178,21 @@ class LRCNEngine:
                 ops.adam_apply_tiers_st(self.w, self.g, self.adam_m, self.adam_v, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
             elif self.cfg.optimizer == "adam":
                 ops.adam_apply_st(self.w, self.g, self.adam_m, self.adam_v, self.state, clip_norm, self.ss, 1.0, skip=skip)
+            elif self.mom is not None:
+                ops.momentum_apply_st(self.w, self.g, self.mom, self.state, self.momentum, self.nesterov, clip_norm, self.ss, 1.0,
+                                      skip=skip, tiers=tiers)
             elif tiers is not None:
                 ops.sgd_apply_tiers_st(self.w, self.g, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
             else:
                 ops.sgd_apply_st(self.w, self.g, self.state, clip_norm, self.ss, 1.0, skip=skip)
         elif tiers is not None and self.cfg.optimizer == "adam":
             ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
-        elif tiers is not None:
-            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         elif self.cfg.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.mom is not None:
+            ops.momentum_apply(self.w, self.g, self.mom, lr, self.momentum, self.nesterov, clip_norm, self.ss, 1.0, skip=skip, tiers=tiers)
+        elif tiers is not None:
+            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
         return self._fetch(rows, fetch)
@@ -1257,6 +1287,13 @@ class LRCNEngine:
         graph = torch.cuda.CUDAGraph()
         step_count = self.step_count
         self._tag_off = 0
+        # No finaliser may run inside the capture: releasing a conv or resize descriptor frees device tables (hipFree), which a thread-local
+        # capture on this thread does not allow -- it invalidates the capture.  Engines that sit in reference cycles (a GraphEngine and the
+        # towers it owns) are released by the cycle collector only, at a moment of its choosing: collect them now, and keep the collector
+        # off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 frames = inputs["frames"]
@@ -1271,6 +1308,8 @@ class LRCNEngine:
                     rows = self._forward(n, b, train=False)
             span = self._tag_off
         finally:
+            if gc_was_on:
+                gc.enable()
             self._tag_off = None
             self.step_count = step_count
         self.graph_capture_ms.append((time.perf_counter() - t0) * 1e3)

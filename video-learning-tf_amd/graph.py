@@ -40,7 +40,7 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import FORGET_BIAS, LRCNEngine, NetConfig, dcnn_layers, finetune_plan, frozen_layers, param_specs, tier_plan
+from .engine import FORGET_BIAS, LRCNEngine, NetConfig, check_momentum, dcnn_layers, finetune_plan, frozen_layers, param_specs, tier_plan
 
 
 @dataclass
@@ -749,9 +749,11 @@ def model_specs(pipelines, datasets, num_classes):
 
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
-                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
+                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
-        freezes the first layers of its tower (engine.tier_plan)."""
+        freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
+        (engine.check_momentum); 0 = plain SGD."""
+        self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
@@ -858,6 +860,7 @@ class GraphEngine:
                 self.grad_chunks += [(nd.tower_off + lo, cnt) for lo, cnt in nd.tower.grad_chunks]
         if optimizer == "adam" and training:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
+        self.mom = torch.zeros(total, device=dev) if self.momentum > 0.0 and training else None    # the momentum accumulator
         rows = self.last.max_rows
         self.stats = torch.zeros(2, device=dev)
         self.loss_rows = torch.zeros(2 * rows, device=dev)
@@ -1045,10 +1048,12 @@ class GraphEngine:
         skip = ops.step_guard(self._skip, *[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])   # LRCNEngine._finish_step
         if tiers is not None and self.optimizer == "adam":
             ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
-        elif tiers is not None:
-            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         elif self.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.mom is not None:
+            ops.momentum_apply(self.w, self.g, self.mom, lr, self.momentum, self.nesterov, clip_norm, self.ss, 1.0, skip=skip, tiers=tiers)
+        elif tiers is not None:
+            ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
         if not fetch:

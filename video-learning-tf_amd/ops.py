@@ -716,6 +716,30 @@ def adam_apply_tiers_st(w, g, m, v, tiers, state, clip_norm=0.0, sumsq_t=None, g
               _skip_word(skip), arr, n, stream())
 
 
+def _momentum_sizes(w, g, accum):
+    if g.numel() != w.numel() or (accum is not None and accum.numel() != w.numel()):
+        raise _ffi.VltfError("momentum_apply: w, g and accum must have one element count")
+
+
+def momentum_apply(w, g, accum, lr, momentum, nesterov=False, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None, tiers=None):
+    """SGD with momentum (tf.train.MomentumOptimizer; vltf.h: vl_momentum_apply): accum = momentum * accum + clipped g, then
+    w -= lr * accum (nesterov: lr * (clipped g + momentum * accum)).  tiers None: the whole buffer; else as sgd_apply_tiers."""
+    _f32(w, g, accum, sumsq_t)
+    _momentum_sizes(w, g, accum)
+    arr, n = (None, 0) if tiers is None else _tiers(tiers)
+    _ffi.call("vl_momentum_apply", _p(w), _p(g), _p(accum), w.numel(), lr, momentum, int(bool(nesterov)), clip_norm, _p(sumsq_t), gscale,
+              _skip_word(skip), arr, n, stream())
+
+
+def momentum_apply_st(w, g, accum, state, momentum, nesterov=False, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None, tiers=None):
+    """momentum_apply with lr read from the step state."""
+    _f32(w, g, accum, sumsq_t)
+    _momentum_sizes(w, g, accum)
+    arr, n = (None, 0) if tiers is None else _tiers(tiers)
+    _ffi.call("vl_momentum_apply_st", _p(w), _p(g), _p(accum), w.numel(), _state(state), momentum, int(bool(nesterov)), clip_norm,
+              _p(sumsq_t), gscale, _skip_word(skip), arr, n, stream())
+
+
 def step_guard(skip, *lstm_workspaces):
     """skip[0] = 1 if a cluster-form LSTM launch on any of the workspaces has timed out since its status was last read (the word is
     sticky, lstm_seq_check reads and resets it), else 0 -- on the stream, no host round trip.  Hand `skip` to sgd_apply / adam_apply:

@@ -53,7 +53,8 @@ def pipeline_net_config(settings, p, dataset):
               dropout_keep_prob=settings.get_dropout(), optimizer=settings.train.optimizer if settings.train else "sgd",
               conv_math=os.environ.get("VLTF_CONV_MATH", "f32"),     # "bf16x3": opt-in split-bf16 conv products (not a reference key)
               step_graph=step_graph_requested(),                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
-              lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None))
+              lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None),
+              momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False)
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -319,7 +320,9 @@ def main(init_file, seed=0, device=None):
     else:
         engine = GraphEngine(specs, infos, settings.num_classes, device=dev_name, training=bool(settings.train), dp=gar,
                              optimizer=settings.train.optimizer if settings.train else "sgd", dropout_keep_prob=settings.get_dropout(),
-                             conv_math=os.environ.get("VLTF_CONV_MATH", "f32"), lr_mult=settings.train.lr_mult if settings.train else None)
+                             conv_math=os.environ.get("VLTF_CONV_MATH", "f32"), lr_mult=settings.train.lr_mult if settings.train else None,
+                             momentum=settings.train.momentum if settings.train else 0.0,
+                             nesterov=settings.train.nesterov if settings.train else False)
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

@@ -19,6 +19,7 @@ class TrainSettings:
     batch_size, epochs, epoch_index = 100, 15, 0
     optimizer, base_lr, lr_mult = defs.optim.sgd, 0.001, None
     lr_decay, clip_norm, dropout_keep_prob = None, 0, 0.5
+    momentum, nesterov = 0.0, False
 
 
 class ValSettings:
@@ -141,12 +142,24 @@ class Settings:
                 t = self.train = TrainSettings()
                 t.batch_size, t.epochs = int(obj["batch_size"]), int(obj["epochs"])
                 t.optimizer = defs.check(obj["optimizer"], defs.optim)
+                if t.optimizer not in (defs.optim.sgd, defs.optim.adam):        # train.py:171,208 (rmsprop is a name without an update)
+                    error("Undefined optimizer %s" % t.optimizer)
                 t.base_lr = float(obj["base_lr"])
                 # two learning-rate tiers (train.py:152-197, whose own code is broken: SURVEY 2): the `modified` variables -- fc8, the
                 # LSTM, the fc heads -- learn with base_lr * lr_mult, the pretrained dcnn with base_lr (engine.is_regular)
                 t.lr_mult = float(obj["lr_mult"]) if obj.get("lr_mult") not in (None, "None") else None
                 if t.lr_mult is not None and not (t.lr_mult > 0 and t.lr_mult != float("inf")):
                     error("lr_mult must be a finite number > 0, got [%s] (train_from holds layers fixed)" % obj["lr_mult"])
+                # SGD with momentum (tf.train.MomentumOptimizer; the reference's `#momentum: 0.9`): absent / None = plain SGD
+                from .engine import VltfError, check_momentum
+                nesterov = obj.get("nesterov") if obj.get("nesterov") not in (None, "None") else False
+                if not isinstance(nesterov, bool):
+                    error("train.nesterov must be a boolean, got [%s]" % (nesterov,))
+                try:
+                    t.momentum, t.nesterov = check_momentum(
+                        t.optimizer, float(obj["momentum"]) if obj.get("momentum") not in (None, "None") else 0.0, nesterov)
+                except (VltfError, TypeError, ValueError) as ex:
+                    error("train.momentum / train.nesterov: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
