@@ -476,6 +476,30 @@ int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, 
                          int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
                          const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream);
 
+/* ---- L2 weight decay: the regulariser's gradient and both sums in the launch that was the global norm ---------------------------------
+ * loss_total = loss + sum_k (decay_k / 2) |w_k|^2 (tf.nn.l2_loss, Caffe weight_decay, torch.optim.SGD(weight_decay=)): the gradient
+ * every later stage sees -- the global-norm clip, SGD, momentum, Adam (so Adam gets coupled L2, not AdamW) -- is g + decay w.  This call
+ * REPLACES vl_sumsq / vl_sumsq_tiers in a step: it writes the regularised gradient over g IN PLACE and returns the two sums; the update
+ * entry points above then run unchanged on g, with out as their sumsq.
+ * The range table obeys the rules of vl_lr_tier: sorted, disjoint, inside [0, count), 1 .. VL_MAX_DECAY_RANGES entries; decay finite and
+ * >= 0; anything else is refused on the host with the entry's index in the message.  It is read on the host and travels BY VALUE in the
+ * launch arguments (64 x 24 bytes), so a captured step needs no device table.  Per element, no contraction left to the compiler, one
+ * element function for the scalar head / tail and the 16-byte interior:
+ *     decay_k > 0:   g' = fma(decay_k, w, g), stored;   out[0] += g' * g';   out[1] += ((0.5f * decay_k) * w) * w
+ *     decay_k == 0:  out[0] += g * g;   w is NOT loaded and g is NOT stored (biases cost one read, as in vl_sumsq_tiers)
+ *     outside every range: neither loaded nor stored (w and g may hold anything there, NaN included)
+ * out: float[2], out[0] = sum g'^2 over every range, out[1] = sum (decay_k / 2) w^2, both overwritten.  ws: float[2048].  Two stages in
+ * a fixed order (per-block partials, then one 256-thread block): the same bits from run to run, no float atomics.  w and g that
+ * disagree in 16-byte phase take the scalar loops.  g must be written afresh by every backward pass: a caller that accumulates into g
+ * across steps would decay it twice.  Over decayed elements the launch moves 3 floats each (reads w, g; writes g): vl_sgd_apply's traffic. */
+#define VL_MAX_DECAY_RANGES 64
+typedef struct vl_decay_range {
+    int64_t begin, end;
+    float decay;
+} vl_decay_range;
+int vl_l2_regularize(const float* w, float* g, int64_t count, const vl_decay_range* ranges, int n_ranges, float* out /* [2] */,
+                     float* ws /* float[2048] */, vl_stream_t stream);
+
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);
 /* ReluGrad in place: d[i] = y[i] > 0 ? d[i] : 0 (y = the ReLU's forward output, alexnet.py:228,248). */

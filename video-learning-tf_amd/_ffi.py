@@ -98,6 +98,7 @@ SIGNATURES = {
     "vl_sumsq_tiers": (i32, [p, i64, p, i32, p, p, p]),
     "vl_momentum_apply": (i32, [p, p, p, i64, f32, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_momentum_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p]),
+    "vl_l2_regularize": (i32, [p, p, i64, p, i32, p, p, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),
@@ -118,6 +119,14 @@ class LrTier(C.Structure):
 
 
 MAX_LR_TIERS = 16         # VL_MAX_LR_TIERS
+
+
+class DecayRange(C.Structure):
+    """vl_decay_range (include/vltf.h)."""
+    _fields_ = [("begin", i64), ("end", i64), ("decay", f32)]
+
+
+MAX_DECAY_RANGES = 64     # VL_MAX_DECAY_RANGES
 
 
 class VltfError(RuntimeError):

@@ -2004,6 +2004,128 @@ extern "C" int vl_sumsq_tiers(const float* g, int64_t count, const vl_lr_tier* t
     return 0;
 }
 
+// ---- L2 weight decay fused into the norm launch (vltf.h: vl_l2_regularize) ----------------------------------------------------------
+// g <- g + decay w in place, then the two sums of the regularised gradient and of the regulariser.  The table travels by value like
+// the tier table; a range with decay 0 (biases) is vl_sumsq_tiers' loop: g read once, w never loaded, g never stored.
+struct decay_table {
+    vl_decay_range r[VL_MAX_DECAY_RANGES];
+    int n;
+};
+
+static int decay_table_make(const char* who, const vl_decay_range* ranges, int n_ranges, int64_t count, decay_table* out) {
+    VL_CHECK(ranges && n_ranges >= 1 && n_ranges <= VL_MAX_DECAY_RANGES, "%s: 1 .. %d ranges, got %d", who, VL_MAX_DECAY_RANGES, n_ranges);
+    int64_t prev = 0;
+    for (int k = 0; k < n_ranges; ++k) {
+        const vl_decay_range& r = ranges[k];
+        VL_CHECK(r.begin >= prev && r.end > r.begin && r.end <= count,
+                 "%s: range %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
+                 (long long)r.end, (long long)count);
+        VL_CHECK(r.decay >= 0.f && r.decay <= 3.402823466e38f, "%s: range %d: decay must be finite and >= 0", who, k);   // (NaN fails both)
+        out->r[k] = r;
+        prev = r.end;
+    }
+    out->n = n_ranges;
+    return 0;
+}
+
+// one element function for the scalar and the 16-byte loops: an element's g' does not depend on the loop that reached it
+__device__ __forceinline__ void l2_elem(float w, float& g, float decay, float half_decay, float& ss, float& rs) {
+#pragma clang fp contract(off)
+    const float gi = __builtin_fmaf(decay, w, g);
+    g = gi;
+    ss = ss + gi * gi;
+    rs = rs + (half_decay * w) * w;
+}
+__device__ __forceinline__ void l2_elem4(const float4& w, float4& g, float decay, float half_decay, float& ss, float& rs) {
+    l2_elem(w.x, g.x, decay, half_decay, ss, rs);
+    l2_elem(w.y, g.y, decay, half_decay, ss, rs);
+    l2_elem(w.z, g.z, decay, half_decay, ss, rs);
+    l2_elem(w.w, g.w, decay, half_decay, ss, rs);
+}
+
+// ws[block] = the block's sum of g'^2, ws[1024 + block] = its sum of (decay / 2) w^2.  A lane walks the ranges in table order -- head,
+// 16-byte interior, tail of each -- so every partial sum's order is fixed by the table and the grid (sumsq_tiers_stage1).  (Measured
+// and dropped: two and four grid strides per pass of the interior with all loads issued first -- 106 and 109 us against 105 us for
+// this loop on 44.6 M floats)
+__global__ __launch_bounds__(256) void l2_regularize_stage1(const float* __restrict__ w, float* __restrict__ g, decay_table dt,
+                                                            float* __restrict__ ws) {
+    __shared__ float sm[4];
+    float ss = 0.f, rs = 0.f;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    const int phase = align_phase(w, g, nullptr, nullptr);
+    for (int k = 0; k < dt.n; ++k) {
+        const int64_t begin = dt.r[k].begin, end = dt.r[k].end;
+        const float decay = dt.r[k].decay, half_decay = 0.5f * decay;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        const int64_t nvec = (v1 - v0) / 4;
+        if (decay > 0.f) {
+            for (int64_t i = begin + i0; i < v0; i += step) {
+                float gi = g[i];
+                l2_elem(w[i], gi, decay, half_decay, ss, rs);
+                g[i] = gi;
+            }
+            const float4* __restrict__ w4 = reinterpret_cast<const float4*>(w + v0);
+            float4* __restrict__ g4 = reinterpret_cast<float4*>(g + v0);
+            for (int64_t i = i0; i < nvec; i += step) {
+                const float4 wv = w4[i];
+                float4 gv = g4[i];
+                l2_elem4(wv, gv, decay, half_decay, ss, rs);
+                g4[i] = gv;
+            }
+            for (int64_t j = v1 + i0; j < end; j += step) {
+                float gi = g[j];
+                l2_elem(w[j], gi, decay, half_decay, ss, rs);
+                g[j] = gi;
+            }
+        } else {
+            for (int64_t i = begin + i0; i < v0; i += step) ss += g[i] * g[i];
+            const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+            for (int64_t i = i0; i < nvec; i += step) {
+                const float4 v = g4[i];
+                ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
+            for (int64_t i = v1 + i0; i < end; i += step) ss += g[i] * g[i];
+        }
+    }
+    ss = block_sum_256(ss, sm);
+    rs = block_sum_256(rs, sm);
+    if (threadIdx.x == 0) {
+        ws[blockIdx.x] = ss;
+        ws[1024 + blockIdx.x] = rs;
+    }
+}
+
+__global__ __launch_bounds__(256) void l2_regularize_stage2(const float* __restrict__ ws, int nblocks, float* __restrict__ out) {
+    __shared__ float sm[4];
+    float ss = 0.f, rs = 0.f;
+    for (int i = threadIdx.x; i < nblocks; i += 256) {
+        ss += ws[i];
+        rs += ws[1024 + i];
+    }
+    ss = block_sum_256(ss, sm);
+    rs = block_sum_256(rs, sm);
+    if (threadIdx.x == 0) {
+        out[0] = ss;
+        out[1] = rs;
+    }
+}
+
+extern "C" int vl_l2_regularize(const float* w, float* g, int64_t count, const vl_decay_range* ranges, int n_ranges, float* out, float* ws,
+                                vl_stream_t stream) {
+    VL_CHECK(w && g && out && ws && count > 0, "vl_l2_regularize: bad argument");
+    decay_table dt;
+    if (int rc = decay_table_make("vl_l2_regularize", ranges, n_ranges, count, &dt)) return rc;
+    int64_t inside = 0;
+    for (int k = 0; k < dt.n; ++k) inside += dt.r[k].end - dt.r[k].begin;
+    const int blocks = grid_for(inside / 4 + 1, 256, 1024);
+    hipLaunchKernelGGL(l2_regularize_stage1, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, g, dt, ws);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(l2_regularize_stage2, dim3(1), dim3(256), 0, (hipStream_t)stream, ws, blocks, out);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 __device__ __forceinline__ float clip_scale(float clip_norm, const float* sumsq, float gscale) {
     if (clip_norm <= 0.f || !sumsq) return gscale;
     const float norm = gscale * sqrtf(sumsq[0]);

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._ffi import VltfError
+from ._ffi import MAX_DECAY_RANGES, VltfError
 
 # name, kh, kw, cout, stride, groups, lrn, pool        (alexnet.py:60-211)
 CONV_LAYERS = (
@@ -60,6 +60,7 @@ class NetConfig:
     train_from: Optional[str] = None            # first trainable dcnn layer (TRAIN_FROM): every dcnn layer before it is frozen
     momentum: float = 0.0                       # train.momentum: tf.train.MomentumOptimizer's, in [0, 1); 0 = plain SGD (optimizer sgd only)
     nesterov: bool = False                      # train.nesterov: use_nesterov of the same (needs momentum > 0)
+    weight_decay: float = 0.0                   # train.weight_decay: L2 coefficient of the trained weight tensors (decay_ranges); 0 = off
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -174,6 +175,43 @@ def check_momentum(optimizer, momentum, nesterov):
     if optimizer == "adam" and (m > 0.0 or nesterov):
         raise VltfError("momentum / nesterov belong to optimizer sgd; adam has its own first moment")
     return m, nesterov
+
+
+def check_weight_decay(weight_decay):
+    """The L2 coefficient of a run as a float, None read as 0 (off).  Refused: negative, NaN, infinite, not a number."""
+    if weight_decay is None:
+        return 0.0
+    if isinstance(weight_decay, (bool, str, bytes)) or not isinstance(weight_decay, (int, float, np.integer, np.floating)):
+        raise VltfError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
+    d = float(weight_decay)
+    if not (d >= 0.0 and math.isfinite(d)):
+        raise VltfError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
+    return d
+
+
+def decay_ranges(specs, plan, weight_decay):
+    """[(begin, end, decay)] for ops.l2_regularize: every trainable range of plan.tiers cut at the variable extents of specs, decay =
+    weight_decay for a variable of rank >= 2 (conv / fc weights, LSTM kernels, the fc heads) and 0 for rank 1 (every bias), adjacent
+    entries with one coefficient merged.  Frozen variables lie outside plan.tiers and so outside every entry: never read, never
+    written, not in the regulariser.  Host only."""
+    d = check_weight_decay(weight_decay)
+    out, off = [], 0
+    for _, shp in specs:
+        n = int(np.prod(shp))
+        c = d if len(shp) >= 2 else 0.0
+        for lo, hi, _ in plan.tiers:
+            a, b = max(lo, off), min(hi, off + n)
+            if b <= a:
+                continue
+            if out and out[-1][1] == a and out[-1][2] == c:
+                out[-1] = (out[-1][0], b, c)
+            else:
+                out.append((a, b, c))
+        off += n
+    if len(out) > MAX_DECAY_RANGES:
+        raise VltfError("this model needs %d weight-decay ranges (runs of weights and of biases in the flat parameter buffer, frozen "
+                        "ranges between them); the regulariser kernel takes %d" % (len(out), MAX_DECAY_RANGES))
+    return out
 
 
 def base_grad_chunks(cfg: NetConfig):
@@ -305,6 +343,7 @@ class LRCNEngine:
             raise VltfError("step_graph is refused with data parallelism: capturing the gradient exchange's collectives is unmeasured "
                             "on this stack")
         self.momentum, self.nesterov = check_momentum(cfg.optimizer, cfg.momentum, cfg.nesterov)
+        self.weight_decay = check_weight_decay(cfg.weight_decay)
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
         self.dev = torch.device(device)
@@ -516,6 +555,15 @@ class LRCNEngine:
         self.stats = torch.zeros(2, device=dev)
         self.loss_rows = torch.zeros(2 * self.rows_out, device=dev)     # per-row losses | hits (vl_softmax_xent workspace)
         self.ss = torch.zeros(1, device=dev)
+        # L2 weight decay: ops.l2_regularize takes the norm's place in _finish_step and returns {sum g'^2, regulariser}; the update calls
+        # and _fetch read the first word through self.ss.  Off: nothing is allocated, the norm calls are the ones of before.
+        self.decay, self.ss2 = None, None
+        if self.weight_decay > 0.0 and cfg.classifier == "none":
+            raise VltfError("a feature pipeline (classifier none) has no step of its own: give weight_decay to the GraphEngine it trains in")
+        if self.weight_decay > 0.0 and training:
+            self.decay = decay_ranges(self.specs, self.plan, self.weight_decay)
+            self.ss2 = torch.zeros(2, device=dev)
+            self.ss = self.ss2[:1]
         self._skip = torch.zeros(1, dtype=torch.int32, device=dev)      # ops.step_guard: the optimizer launch's skip word
         self.probe, self.probe_events = None, []
         self._resizers = {}
@@ -1165,7 +1213,9 @@ class LRCNEngine:
         if self.dp is not None:
             self.dp.wait()
         tiers = None if self.plan.full_range() else self.plan.tiers      # None: the plain calls (one full-range tier, same bits)
-        if tiers is None:
+        if self.decay is not None:                # g <- g + decay w in place; self.ss = self.ss2[:1] is the regularised gradient's norm
+            ops.l2_regularize(self.w, self.g, self.decay, self.ss2, self.small_ws)
+        elif tiers is None:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
@@ -1203,8 +1253,11 @@ class LRCNEngine:
         torch.cuda.synchronize(self.dev)
         self.check_status()
         st = self.stats.cpu().numpy()
-        return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "grad_norm": math.sqrt(float(self.ss.item())),
-                "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "grad_norm": math.sqrt(float(self.ss.item())),
+               "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        if self.ss2 is not None:                  # the regulariser at the weights the forward pass used; `loss` stays the data loss
+            out["reg_loss"] = float(self.ss2[1].item())
+        return out
 
     def _rows_for(self, b, n):
         if self.cfg.classifier == "lstm":

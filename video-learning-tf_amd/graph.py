@@ -40,7 +40,8 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import FORGET_BIAS, LRCNEngine, NetConfig, check_momentum, dcnn_layers, finetune_plan, frozen_layers, param_specs, tier_plan
+from .engine import (FORGET_BIAS, LRCNEngine, NetConfig, check_momentum, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan,
+                     frozen_layers, param_specs, tier_plan)
 
 
 @dataclass
@@ -749,15 +750,18 @@ def model_specs(pipelines, datasets, num_classes):
 
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
-                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False):
+                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
-        (engine.check_momentum); 0 = plain SGD."""
+        (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
+        pipeline (engine.decay_ranges); 0 = off."""
         self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)
+        self.weight_decay = check_weight_decay(weight_decay)
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
         self._plan(pipelines, datasets, num_classes, optimizer, dropout_keep_prob, conv_math, lr_mult)
+        self.decay = decay_ranges(self.specs, self.plan, self.weight_decay) if self.weight_decay > 0.0 and training else None
         self._allocate()
 
     def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
@@ -865,6 +869,10 @@ class GraphEngine:
         self.stats = torch.zeros(2, device=dev)
         self.loss_rows = torch.zeros(2 * rows, device=dev)
         self.ss = torch.zeros(1, device=dev)
+        self.ss2 = None
+        if self.decay is not None:                # L2 weight decay (LRCNEngine.__init__): {sum g'^2, regulariser}, self.ss its first word
+            self.ss2 = torch.zeros(2, device=dev)
+            self.ss = self.ss2[:1]
         self._skip = torch.zeros(1, dtype=torch.int32, device=dev)      # ops.step_guard: the optimizer launch's skip word
         self.small_ws = torch.empty(64 * 1024, device=dev)
         self._queued, self._pending_lstm = [], 0
@@ -1040,7 +1048,9 @@ class GraphEngine:
         if self.dp is not None:
             self.dp.wait()
         tiers = None if self.plan.full_range() else self.plan.tiers      # LRCNEngine._finish_step
-        if tiers is None:
+        if self.decay is not None:
+            ops.l2_regularize(self.w, self.g, self.decay, self.ss2, self.small_ws)
+        elif tiers is None:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
@@ -1061,8 +1071,11 @@ class GraphEngine:
         self._sync()
         self.check_status()
         st = self.stats.cpu().numpy()
-        return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1),
-                "grad_norm": math.sqrt(float(self.ss.item())), "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1),
+               "grad_norm": math.sqrt(float(self.ss.item())), "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        if self.ss2 is not None:
+            out["reg_loss"] = float(self.ss2[1].item())
+        return out
 
 
 class _TowerReduce:

@@ -688,6 +688,24 @@ def sumsq_tiers(g, tiers, out, ws):
     _ffi.call("vl_sumsq_tiers", _p(g), g.numel(), arr, n, _p(out), _p(ws), stream())
 
 
+def l2_regularize(w, g, ranges, out, ws):
+    """L2 weight decay in the norm's launch (vltf.h: vl_l2_regularize).  ranges = [(begin, end, decay)]: inside a range with decay > 0
+    g becomes g + decay * w IN PLACE; out[0] = sum of the regularised g^2 over every range, out[1] = sum (decay / 2) w^2.  A range with
+    decay 0 is only summed (w not read, g not written); elements outside every range are not touched."""
+    _f32(w, g, out, ws)
+    if g.numel() != w.numel():
+        raise _ffi.VltfError("l2_regularize: w and g must have one element count")
+    if out.numel() < 2:
+        raise _ffi.VltfError("l2_regularize: out needs 2 floats")
+    if ws.numel() < 2048:
+        raise _ffi.VltfError("l2_regularize: workspace needs 2048 floats")
+    ranges = list(ranges)
+    arr = (_ffi.DecayRange * max(len(ranges), 1))()
+    for k, (lo, hi, decay) in enumerate(ranges):
+        arr[k].begin, arr[k].end, arr[k].decay = int(lo), int(hi), float(decay)
+    _ffi.call("vl_l2_regularize", _p(w), _p(g), w.numel(), arr, len(ranges), _p(out), _p(ws), stream())
+
+
 def sgd_apply_tiers(w, g, tiers, lr, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
     """sgd_apply over the tiers [(begin, end, lr_mult)] only, each with lr * lr_mult: one launch."""
     _f32(w, g, sumsq_t)

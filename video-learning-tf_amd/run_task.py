@@ -54,7 +54,8 @@ def pipeline_net_config(settings, p, dataset):
               conv_math=os.environ.get("VLTF_CONV_MATH", "f32"),     # "bf16x3": opt-in split-bf16 conv products (not a reference key)
               step_graph=step_graph_requested(),                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
               lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None),
-              momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False)
+              momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False,
+              weight_decay=settings.train.weight_decay if settings.train else 0.0)
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -205,7 +206,10 @@ def do_train(settings, train, feeder, engine):
             if min_train_loss[0] > batch_loss:
                 min_train_loss = (batch_loss, settings.global_step)
             nats = batch_loss / math.log(settings.num_classes)
-            info("Learning rate %2.8f, global step: %d, batch loss/nats : %2.5f / %2.3f " % (learning_rate, settings.global_step, batch_loss, nats))
+            # (weight decay: `batch loss` stays the data loss, the lambda-weighted L2 term is logged beside it)
+            reg = "+ L2 regulariser : %2.6f" % train.last["reg_loss"] if "reg_loss" in train.last else ""
+            info("Learning rate %2.8f, global step: %d, batch loss/nats : %2.5f / %2.3f %s" %
+                 (learning_rate, settings.global_step, batch_loss, nats, reg))
             info("Dataset global step %d, epoch index %d, batch sizes %s, batch index train %d" %
                  (settings.global_step, settings.train.epoch_index + 1, str(feeder.get_batch_sizes()), feeder.get_batch_index()))
             if feeder.should_save(run_batch_count):
@@ -322,7 +326,8 @@ def main(init_file, seed=0, device=None):
                              optimizer=settings.train.optimizer if settings.train else "sgd", dropout_keep_prob=settings.get_dropout(),
                              conv_math=os.environ.get("VLTF_CONV_MATH", "f32"), lr_mult=settings.train.lr_mult if settings.train else None,
                              momentum=settings.train.momentum if settings.train else 0.0,
-                             nesterov=settings.train.nesterov if settings.train else False)
+                             nesterov=settings.train.nesterov if settings.train else False,
+                             weight_decay=settings.train.weight_decay if settings.train else 0.0)
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

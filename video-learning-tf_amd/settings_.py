@@ -20,6 +20,7 @@ class TrainSettings:
     optimizer, base_lr, lr_mult = defs.optim.sgd, 0.001, None
     lr_decay, clip_norm, dropout_keep_prob = None, 0, 0.5
     momentum, nesterov = 0.0, False
+    weight_decay = 0.0
 
 
 class ValSettings:
@@ -160,6 +161,18 @@ class Settings:
                         t.optimizer, float(obj["momentum"]) if obj.get("momentum") not in (None, "None") else 0.0, nesterov)
                 except (VltfError, TypeError, ValueError) as ex:
                     error("train.momentum / train.nesterov: %s" % ex)
+                # L2 weight decay of the trained weight tensors (engine.decay_ranges): absent / None = off
+                from .engine import check_weight_decay
+                wd = obj.get("weight_decay")
+                if isinstance(wd, str) and wd != "None":         # YAML reads 5e-4 (no dot) and nan / inf as strings
+                    try:
+                        wd = float(wd)
+                    except ValueError:
+                        pass
+                try:
+                    t.weight_decay = check_weight_decay(None if wd == "None" else wd)
+                except VltfError as ex:
+                    error("train.weight_decay: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
