@@ -418,6 +418,10 @@ int vl_status_or(uint32_t* dst, const void* lstm_ws, int init, vl_stream_t strea
  * replayed update must equal the eager one bit for bit).  step >= 0. */
 size_t vl_step_state_bytes(void);
 int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag_origin, vl_stream_t stream);
+/* The same for a micro-step of an accumulated update (vl_grad_accumulate): state->step = draw_step, the dropout seed's input, while
+ * adam_lr comes from update_step by the code above.  vl_step_state_set(s, step, ...) is vl_step_state_set_micro(s, step, step, ...). */
+int vl_step_state_set_micro(vl_step_state* state, int64_t update_step, int64_t draw_step, float lr, uint32_t tag_origin,
+                            vl_stream_t stream);
 /* vl_sgd_apply with lr = state->lr; vl_adam_apply with the step size state->adam_lr (= count state->step + 1). */
 int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
                     float gscale, const uint32_t* skip, vl_stream_t stream);
@@ -491,7 +495,7 @@ int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, 
  * out: float[2], out[0] = sum g'^2 over every range, out[1] = sum (decay_k / 2) w^2, both overwritten.  ws: float[2048].  Two stages in
  * a fixed order (per-block partials, then one 256-thread block): the same bits from run to run, no float atomics.  w and g that
  * disagree in 16-byte phase take the scalar loops.  g must be written afresh by every backward pass: a caller that accumulates into g
- * across steps would decay it twice.  Over decayed elements the launch moves 3 floats each (reads w, g; writes g): vl_sgd_apply's traffic. */
+ * across steps would decay it twice (vl_grad_accumulate below: the engines regularise only the final sum of an accumulated update).  Over decayed elements the launch moves 3 floats each (reads w, g; writes g): vl_sgd_apply's traffic. */
 #define VL_MAX_DECAY_RANGES 64
 typedef struct vl_decay_range {
     int64_t begin, end;
@@ -499,6 +503,19 @@ typedef struct vl_decay_range {
 } vl_decay_range;
 int vl_l2_regularize(const float* w, float* g, int64_t count, const vl_decay_range* ranges, int n_ranges, float* out /* [2] */,
                      float* ws /* float[2048] */, vl_stream_t stream);
+
+/* ---- gradient accumulation: k micro-batches per update, one ranged launch per micro-step ------------------------------------------------
+ * mode 0 (store): acc = g, the first micro-step (no fill is ever needed);  mode 1 (add): acc = acc + g;  mode 2 (final): g = acc + g,
+ * acc left as it is.  One fp32 add per element, the same element function for the scalar head / tail and the 16-byte interior: the
+ * result is bit for bit the IEEE single sum, and an update's gradient is ((g1 + g2) + g3) + ... in call order, the same from run to run.
+ * The range table obeys the rules of vl_lr_tier (sorted, disjoint, inside [0, count), 1 .. VL_MAX_LR_TIERS entries; lr_mult must be valid
+ * and is ignored, as in vl_sumsq_tiers); ranges == NULL && n_ranges == 0 is the full range.  It travels BY VALUE in the launch arguments.
+ * Elements outside every range are neither loaded nor stored, in acc and in g alike (they may hold NaN).  acc and g that disagree in
+ * 16-byte phase take the scalar loops.  One launch, the grid of vl_sgd_apply; per element in range it moves 2 floats (store) or 3 (add,
+ * final), i.e. vl_sgd_apply's traffic.  Refused on the host: a null pointer, count <= 0, an unknown mode, a bad table.
+ * This is the accumulating caller vl_l2_regularize warns about: the engines regularise only the FINAL sum (mode 2 first, then
+ * vl_l2_regularize on g, once per update), so the decay enters once however many micro-steps there were. */
+int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode, const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream);
 
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);

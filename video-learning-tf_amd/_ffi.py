@@ -89,6 +89,7 @@ SIGNATURES = {
     "vl_status_or": (i32, [p, p, i32, p]),
     "vl_step_state_bytes": (sz, []),
     "vl_step_state_set": (i32, [p, i64, f32, u32, p]),
+    "vl_step_state_set_micro": (i32, [p, i64, i64, f32, u32, p]),
     "vl_sgd_apply_st": (i32, [p, p, i64, p, f32, p, f32, p, p]),
     "vl_adam_apply_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p]),
     "vl_sgd_apply_tiers": (i32, [p, p, i64, f32, f32, p, f32, p, p, i32, p]),
@@ -99,6 +100,7 @@ SIGNATURES = {
     "vl_momentum_apply": (i32, [p, p, p, i64, f32, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_momentum_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_l2_regularize": (i32, [p, p, i64, p, i32, p, p, p]),
+    "vl_grad_accumulate": (i32, [p, p, i64, i32, p, i32, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),

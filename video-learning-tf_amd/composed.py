@@ -77,7 +77,8 @@ class ComposedEngine(GraphEngine):
         pipes, datasets = two_pipelines(enc_cfg, head, max_clips, scopes)
         super().__init__(pipes, datasets, head.num_classes, device, training, dp, optimizer=enc_cfg.optimizer,
                          dropout_keep_prob=head.dropout_keep_prob or enc_cfg.dropout_keep_prob, conv_math=enc_cfg.conv_math,
-                         momentum=enc_cfg.momentum, nesterov=enc_cfg.nesterov, weight_decay=enc_cfg.weight_decay)
+                         momentum=enc_cfg.momentum, nesterov=enc_cfg.nesterov, weight_decay=enc_cfg.weight_decay,
+                         accumulate=enc_cfg.accumulate)
         self.enc_cfg = enc_cfg
         self.Ts = self.last.fpc                  # steps the second LSTM runs (one more under ibias)
 
@@ -92,9 +93,10 @@ class ComposedEngine(GraphEngine):
         return GraphEngine.forward(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize), seq_len=seq_len)
 
     def train_step(self, frames_u8, words, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                   fetch=True, global_rows=None, resize=None, seq_len=None):
+                   fetch=True, global_rows=None, resize=None, seq_len=None, micro=None):
         """sess.run([.., loss, .., optimizer], fdict): labels int32 one-hot [rows, classes], rows = clips (fusion avg | last |
         state) or clips * steps (fusion reshape: one row per time step, clip-major).  seq_len: e.g. {"dec": caption lengths}: the
-        padded word steps stay out of the loss (GraphEngine.train_step)."""
+        padded word steps stay out of the loss (GraphEngine.train_step).  micro = (i, k): micro-step i of an accumulated update
+        (enc_cfg.accumulate >= k)."""
         return GraphEngine.train_step(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize), onehot, lr,
-                                      clip_norm, fetch, global_rows, seq_len=seq_len)
+                                      clip_norm, fetch, global_rows, seq_len=seq_len, micro=micro)

@@ -2342,12 +2342,24 @@ __global__ void step_state_set_kernel(vl_step_state* __restrict__ st, int64_t st
 
 extern "C" size_t vl_step_state_bytes(void) { return sizeof(vl_step_state); }
 
-extern "C" int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag_origin, vl_stream_t stream) {
-    VL_CHECK(state && step >= 0 && step < INT32_MAX, "vl_step_state_set: bad argument");
-    hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, step, lr, tag_origin,
-                       adam_step_size(lr, (int)step + 1));
+// update_step: the count behind Adam's step size; draw_step: what state->step holds, the dropout seed's input.  They differ only under
+// gradient accumulation, where the micro-steps of one update draw different masks.
+static int step_state_write(const char* who, vl_step_state* state, int64_t update_step, int64_t draw_step, float lr, uint32_t tag_origin,
+                            vl_stream_t stream) {
+    VL_CHECK(state && update_step >= 0 && update_step < INT32_MAX && draw_step >= 0, "%s: bad argument", who);
+    hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, draw_step, lr, tag_origin,
+                       adam_step_size(lr, (int)update_step + 1));
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag_origin, vl_stream_t stream) {
+    return step_state_write("vl_step_state_set", state, step, step, lr, tag_origin, stream);
+}
+
+extern "C" int vl_step_state_set_micro(vl_step_state* state, int64_t update_step, int64_t draw_step, float lr, uint32_t tag_origin,
+                                       vl_stream_t stream) {
+    return step_state_write("vl_step_state_set_micro", state, update_step, draw_step, lr, tag_origin, stream);
 }
 
 // the update kernels above with lr / Adam's step size read from the step state
@@ -2449,6 +2461,70 @@ extern "C" int vl_momentum_apply_st(float* w, const float* g, float* accum, int6
     if (int rc = momentum_args("vl_momentum_apply_st", w, g, accum, count, momentum, tiers, n_tiers, &tt)) return rc;
     hipLaunchKernelGGL(momentum_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt,
                        state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- gradient accumulation over micro-batches (vltf.h: vl_grad_accumulate) ------------------------------------------------------------
+// MODE 0: acc = g.  MODE 1: acc = acc + g.  MODE 2: g = acc + g (acc stays).  One fp32 add per element, shared by the scalar head / tail
+// and the 16-byte interior; the ranges are walked as in sgd_apply_body, so an element outside every range is never addressed.
+__device__ __forceinline__ float acc_elem(float a, float g) {
+#pragma clang fp contract(off)
+    return a + g;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ g, tier_table tt) {
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    const int phase = align_phase(acc, g, nullptr, nullptr);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) {
+            if (MODE == 0) acc[i] = g[i];
+            else if (MODE == 1) acc[i] = acc_elem(acc[i], g[i]);
+            else g[i] = acc_elem(acc[i], g[i]);
+        }
+        float4* __restrict__ a4 = reinterpret_cast<float4*>(acc + v0);
+        float4* __restrict__ g4 = reinterpret_cast<float4*>(g + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            const float4 gv = g4[i];
+            if (MODE == 0) {
+                a4[i] = gv;
+            } else {
+                const float4 av = a4[i];
+                float4 r;
+                r.x = acc_elem(av.x, gv.x);
+                r.y = acc_elem(av.y, gv.y);
+                r.z = acc_elem(av.z, gv.z);
+                r.w = acc_elem(av.w, gv.w);
+                if (MODE == 1) a4[i] = r;
+                else g4[i] = r;
+            }
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) {
+            if (MODE == 0) acc[i] = g[i];
+            else if (MODE == 1) acc[i] = acc_elem(acc[i], g[i]);
+            else g[i] = acc_elem(acc[i], g[i]);
+        }
+    }
+}
+
+extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode, const vl_lr_tier* ranges, int n_ranges,
+                                  vl_stream_t stream) {
+    VL_CHECK(acc && g && count > 0, "vl_grad_accumulate: bad argument");
+    VL_CHECK(mode >= 0 && mode <= 2, "vl_grad_accumulate: mode must be 0 (store), 1 (add) or 2 (final), got %d", mode);
+    tier_table tt;
+    if (!ranges && n_ranges == 0) {
+        tt = tier_table_full(count);
+    } else if (int rc = tier_table_make("vl_grad_accumulate", ranges, n_ranges, count, &tt)) {
+        return rc;
+    }
+    const dim3 grid(grid_for(count, 256, 4096)), block(256);
+    if (mode == 0) hipLaunchKernelGGL(grad_accumulate_kernel<0>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
+    else if (mode == 1) hipLaunchKernelGGL(grad_accumulate_kernel<1>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<2>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
     VL_LAUNCH_CHECK();
     return 0;
 }

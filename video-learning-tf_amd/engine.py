@@ -61,6 +61,7 @@ class NetConfig:
     momentum: float = 0.0                       # train.momentum: tf.train.MomentumOptimizer's, in [0, 1); 0 = plain SGD (optimizer sgd only)
     nesterov: bool = False                      # train.nesterov: use_nesterov of the same (needs momentum > 0)
     weight_decay: float = 0.0                   # train.weight_decay: L2 coefficient of the trained weight tensors (decay_ranges); 0 = off
+    accumulate: int = 1                         # train.accumulate: most micro-batches one update may sum (train_step_*(micro=(i, k))); 1 = off
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -187,6 +188,72 @@ def check_weight_decay(weight_decay):
     if not (d >= 0.0 and math.isfinite(d)):
         raise VltfError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
     return d
+
+
+def check_accumulate(accumulate):
+    """The micro-batches per update of a run as an int, None read as 1 (off).  Refused: bools, strings, floats that are not whole,
+    values < 1."""
+    if accumulate is None:
+        return 1
+    bad = isinstance(accumulate, (bool, np.bool_, str, bytes)) or not isinstance(accumulate, (int, float, np.integer, np.floating))
+    if bad or not math.isfinite(accumulate) or accumulate != int(accumulate) or int(accumulate) < 1:
+        raise VltfError("accumulate must be a whole number >= 1, got %r" % (accumulate,))
+    return int(accumulate)
+
+
+class MicroSequence:
+    """The order of the micro-steps of accumulated updates, shared by both engines: train_step_*(micro=(i, k)) calls must come as
+    (0, k), (1, k) .. (k - 1, k) with k <= limit; micro=None is the plain step and stands alone.  Anything else is refused, and a
+    refusal abandons the group in progress: the next call must start one.  `rows` sums the rows of a group's calls on the host."""
+
+    def __init__(self, limit):
+        self.limit, self.next, self.rows = limit, None, 0
+
+    def reset(self):
+        self.next = None
+
+    def open(self):
+        """A group has begun and has not seen its final micro-step."""
+        return self.next is not None
+
+    def enter(self, micro):
+        """Checks the call against the sequence and advances it; returns None (plain step) or (i, k)."""
+        pending, self.next = self.next, None
+        if micro is None:
+            if pending is not None:
+                raise VltfError("a plain step inside an accumulated update: micro-step %d of %d was due (the group is abandoned)" % pending)
+            return None
+        try:
+            i, k = micro
+            ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (i, k))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise VltfError("micro must be (i, k), two ints, got %r" % (micro,))
+        i, k = int(i), int(k)
+        if not (0 <= i < k <= self.limit):
+            raise VltfError("micro = (%d, %d): need 0 <= i < k <= accumulate = %d" % (i, k, self.limit))
+        if (i, k) != (pending or (0, k)):
+            raise VltfError("micro = (%d, %d) is out of sequence: %s was due (the group is abandoned; start again at i = 0)" %
+                            (i, k, "(%d, %d)" % pending if pending else "the first micro-step (0, k)"))
+        if i < k - 1:
+            self.next = (i + 1, k)
+        return i, k
+
+    def add_rows(self, mi, rows):
+        """Rows of the update so far, this call's included."""
+        if mi is None:
+            return rows
+        self.rows = rows + (self.rows if mi[0] else 0)
+        return self.rows
+
+    @staticmethod
+    def role(mi):
+        """(launch sequence of the call, k): the micro part of a captured step's key."""
+        if mi is None or mi[1] == 1:
+            return "single", 1
+        i, k = mi
+        return ("first" if i == 0 else "last" if i == k - 1 else "middle"), k
 
 
 def decay_ranges(specs, plan, weight_decay):
@@ -330,7 +397,9 @@ class LRCNEngine:
     and the dropout seed, the origin of its LSTM exchange tags) from a device block (vl_step_state): before each replay the host
     copies the caller's tensors into the buffers, writes the block (ops.step_state_set) and replays.  Its LSTM launches run on a
     workspace of their own (lstm_ws_graph) whose tag stream the engine keeps: graph_tag_next, advanced by the graph's span per
-    replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe."""
+    replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe.
+    With NetConfig.accumulate > 1 the key also holds the micro-step's role (first / middle / last / single) and k: three launch sequences,
+    three graphs; the state's count is then the dropout draw index and Adam's step size follows step_count (ops.step_state_set_micro)."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -344,6 +413,7 @@ class LRCNEngine:
                             "on this stack")
         self.momentum, self.nesterov = check_momentum(cfg.optimizer, cfg.momentum, cfg.nesterov)
         self.weight_decay = check_weight_decay(cfg.weight_decay)
+        self.accumulate = check_accumulate(cfg.accumulate)
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
         self.dev = torch.device(device)
@@ -389,6 +459,11 @@ class LRCNEngine:
         if cfg.optimizer == "adam" and training:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
         self.mom = torch.zeros(total, device=dev) if self.momentum > 0.0 and training else None    # the momentum accumulator
+        # gradient accumulation (train_step_*(micro=(i, k))): the running sum of an update's micro-step gradients.  Written by the first
+        # micro-step's store over plan.tiers, so it needs no fill; frozen ranges are never touched.  Allocated here, never in a capture.
+        self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None
+        self.micro = MicroSequence(self.accumulate)
+        self._mi = None                       # the (i, k) of the train step being issued; None: a plain step
 
         # ---- conv stack plan.  Tensors a conv gathers from (its x, and the dy its dgrad reads) are stored
         # with a zero halo equal to the conv's SAME padding, so the im2col gather is test-free (vltf.h).
@@ -632,6 +707,9 @@ class LRCNEngine:
 
     def get_opt_state(self):
         """{reserved name: array} to store beside the weights; step_count drives Adam's bias correction and the dropout seed."""
+        if self.micro.open():
+            self.micro.reset()
+            raise VltfError("optimizer state is taken at update boundaries only: an accumulated update is in progress (it is abandoned)")
         torch.cuda.synchronize(self.dev)
         st = {self.OPT_PREFIX + "step_count": np.array([self.step_count], np.int64)}
         if self.cfg.optimizer == "adam" and self.training:
@@ -671,7 +749,11 @@ class LRCNEngine:
         """Raises when a cluster-form LSTM launch since the last check timed out (ops.lstm_seq_check: the flag is sticky over the
         launches of a step and reset here).  Synchronises; called wherever results are fetched to the host."""
         if getattr(self, "lstm_ws", None) is not None:
-            ops.lstm_seq_check(self.lstm_ws, self.lstm_ws_graph)
+            try:
+                ops.lstm_seq_check(self.lstm_ws, self.lstm_ws_graph)
+            except VltfError:
+                self.micro.reset()            # an accumulated update in progress holds an invalid gradient: it is abandoned
+                raise
 
     def logits_host(self, rows=None):
         torch.cuda.synchronize(self.dev)
@@ -820,7 +902,7 @@ class LRCNEngine:
                 v = self.dropped
             elif self._dropout:
                 ops.dropout_fwd(v[:r], self.dropped[:r], self.drop_mask[:r], cfg.dropout_keep_prob,
-                                (self.step_count << 20) ^ 0x5DEECE66D)
+                                (self._draw_index() << 20) ^ 0x5DEECE66D)
                 v = self.dropped
             self._v = v
             if H != C:
@@ -1125,14 +1207,29 @@ class LRCNEngine:
             torch.cuda.current_stream(self.dev).wait_stream(side)
         self._issue(self.plan.total)
 
+    def _draw_index(self, mi=None):
+        """What the dropout seed is formed from: the micro-steps of one update draw different masks; with accumulate 1 the step count.
+        mi: the micro-step (default: the one being issued)."""
+        mi = mi if mi is not None else self._mi
+        return self.step_count * self.accumulate + (mi[0] if mi is not None else 0)
+
+    def _acc_tiers(self):
+        return None if self.plan.full_range() else self.plan.tiers
+
     def _issue(self, hi):
         """Data parallel: starts the exchange of every chunk of the plan not yet issued that ends at or before flat offset `hi`.  The
         flat buffer is in the order backward produces the gradients, so the caller names the end of what the launches queued so far (on
         the current stream) have written."""
         if self.dp is None:
             return
+        mi = self._mi
+        if mi is not None and mi[0] < mi[1] - 1:
+            return                                # a non-final micro-step: the exchange happens once per update
         while self._next_chunk < len(self.grad_chunks) and sum(self.grad_chunks[self._next_chunk]) <= hi:
-            self.dp.reduce_async(self.g, *self.grad_chunks[self._next_chunk])
+            lo, cnt = self.grad_chunks[self._next_chunk]
+            if mi is not None and mi[1] > 1:      # the final micro-step: g = gacc + g over the chunk, right before it goes out
+                ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, [(lo, lo + cnt, 1.0)])
+            self.dp.reduce_async(self.g, lo, cnt)
             self._next_chunk += 1
 
     def _fc6_block_end(self, r1):
@@ -1181,33 +1278,58 @@ class LRCNEngine:
         ops.maxpool_bwd(L["dp"][:n], L["arg"][:n], dx, relu_mask=relu_mask, hwc=L["hwc"], dy_halo=L["p_halo"], dx_halo=dx_halo)
 
     # ---- train step ----------------------------------------------------------------------------
-    def _train(self, n, b, onehot, lr, clip_norm, fetch, global_rows=None):
+    def _train(self, n, b, onehot, lr, clip_norm, fetch, global_rows=None, mi=None):
+        """mi: None, or the (i, k) MicroSequence.enter admitted (micro-step i of an update of k)."""
         if not self.training:
             raise VltfError("engine was built with training=False")
         if self.cfg.classifier == "none":
             raise VltfError("a feature pipeline (classifier none) has no loss of its own: it trains inside a GraphEngine")
         if onehot.dtype != torch.int32 or tuple(onehot.shape) != (self._rows_for(b, n), self.cfg.num_classes):
             raise VltfError("labels must be int32 one-hot of shape (%d, %d)" % (self._rows_for(b, n), self.cfg.num_classes))
-        rows = self._forward(n, b, train=True)
-        world = self.dp.world if self.dp is not None else 1
-        ops.fill(self.stats, 0.0)
-        # mean over the GLOBAL batch (train.py:123): each rank scales its rows by 1/global_rows and the all-reduce sums.
-        # global_rows defaults to rows*world (equal shards); a workflow with ragged shards passes the true count.
-        ops.softmax_xent(self.logits[:rows], onehot, self.dlogits, self.stats, 1.0 / (global_rows or rows * world), self.loss_rows)
-        self._backward(n, b)
-        return self._finish_step(rows, lr, clip_norm, fetch)
+        self._mi = mi
+        try:
+            rows = self._forward(n, b, train=True)
+            world = self.dp.world if self.dp is not None else 1
+            i, k = mi if mi is not None else (0, 1)
+            if i == 0:                            # loss_sum / correct sum on the device over the micro-steps of an update
+                ops.fill(self.stats, 0.0)
+            # mean over the GLOBAL batch (train.py:123): each rank scales its rows by 1/global_rows and the all-reduce sums.
+            # global_rows defaults to rows*world*k (equal shards, equal micro-batches); a workflow with ragged shards or unequal
+            # micro-batches passes the true count of the whole update on every call.
+            ops.softmax_xent(self.logits[:rows], onehot, self.dlogits, self.stats, 1.0 / (global_rows or rows * world * k), self.loss_rows)
+            self._backward(n, b)
+        finally:
+            self._mi = None
+        total_rows = self.micro.add_rows(mi, rows)
+        if i < k - 1:                             # not the update's last micro-step: g joins the running sum, nothing else happens
+            ops.grad_accumulate(self.gacc, self.g, ops.ACC_STORE if i == 0 else ops.ACC_ADD, self._acc_tiers())
+            return self._fetch(total_rows, fetch, partial=True)
+        if k > 1 and self.dp is None:             # (data parallel: _issue added each chunk before it went out)
+            ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, self._acc_tiers())
+        return self._finish_step(total_rows, lr, clip_norm, fetch)
 
-    def train_step_empty(self, lr, clip_norm=0.0, fetch=True):
+    def train_step_empty(self, lr, clip_norm=0.0, fetch=True, micro=None):
         """This rank's shard of the global batch is empty (fewer videos than ranks in a short last batch): contribute zero
-        gradients to the exchange and apply the same update as every other rank."""
+        gradients to the exchange and apply the same update as every other rank.  As a micro-step it adds nothing to the update's sum."""
         if self.dp is None:
             raise VltfError("train_step_empty is a data-parallel call")
+        mi = self.micro.enter(micro)
+        i, k = mi if mi is not None else (0, 1)
+        if i == 0:
+            ops.fill(self.stats, 0.0)
+        total_rows = self.micro.add_rows(mi, 0)
+        if i < k - 1:
+            if i == 0:                            # the group's sum must be defined for the micro-steps that follow
+                for lo, hi, _ in self.plan.tiers:
+                    ops.fill(self.gacc[lo:hi], 0.0)
+            return self._fetch(total_rows, fetch, partial=True)
         for lo, hi, _ in self.plan.tiers:                # (frozen ranges of g are never written, read or exchanged)
             ops.fill(self.g[lo:hi], 0.0)
-        ops.fill(self.stats, 0.0)
         for lo, cnt in self.grad_chunks:
+            if k > 1:
+                ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, [(lo, lo + cnt, 1.0)])
             self.dp.reduce_async(self.g, lo, cnt)
-        return self._finish_step(0, lr, clip_norm, fetch)
+        return self._finish_step(total_rows, lr, clip_norm, fetch)
 
     def _finish_step(self, rows, lr, clip_norm, fetch):
         if self.dp is not None:
@@ -1247,12 +1369,16 @@ class LRCNEngine:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
         return self._fetch(rows, fetch)
 
-    def _fetch(self, rows, fetch):
+    def _fetch(self, rows, fetch, partial=False):
+        """partial: a micro-step before the update's last -- the running sums of the update so far, no norm yet."""
         if not fetch:
             return None
         torch.cuda.synchronize(self.dev)
         self.check_status()
         st = self.stats.cpu().numpy()
+        if partial:
+            return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows, "loss_sum": float(st[0]),
+                    "correct": float(st[1])}
         out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "grad_norm": math.sqrt(float(self.ss.item())),
                "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
         if self.ss2 is not None:                  # the regulariser at the weights the forward pass used; `loss` stays the data loss
@@ -1265,35 +1391,50 @@ class LRCNEngine:
         return b if (self.early or self.late) else n
 
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                      fetch=True, global_rows=None, resize=None):
-        """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44)."""
-        if self.step_graph:
-            done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
-                                         global_rows)
-            if done:
-                return out
-        n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
-        return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows)
+                      fetch=True, global_rows=None, resize=None, micro=None):
+        """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44).
+        micro = (i, k): micro-step i of an update that sums k of them (k <= cfg.accumulate), called in order i = 0 .. k - 1.  Only the
+        last one exchanges, regularises, clips and updates, with its lr; the others return the running loss of the update and no
+        grad_norm.  The loss is scaled by 1 / (rows * world * k) unless global_rows gives the rows of the whole update."""
+        mi = self.micro.enter(micro)
+        try:
+            if self.step_graph:
+                done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
+                                             global_rows, mi)
+                if done:
+                    return out
+            n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
+            return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
+        except VltfError:
+            self.micro.reset()
+            raise
 
-    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True):
-        n, b = self.feed_f32_nhwc(frames_nhwc)
-        return self._train(n, b, onehot, lr, clip_norm, fetch)
+    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None):
+        mi = self.micro.enter(micro)
+        try:
+            n, b = self.feed_f32_nhwc(frames_nhwc)
+            return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
+        except VltfError:
+            self.micro.reset()
+            raise
 
     # ---- captured steps (NetConfig.step_graph, class docstring) ---------------------------------------------------------------
     def _graph_step(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot=None, lr=0.0, clip_norm=0.0, fetch=True,
-                    global_rows=None):
+                    global_rows=None, mi=None):
         """(True, the call's result) when the call was replayed; (False, None) when it runs eagerly (the first call of its key)."""
         rz = tuple((tuple(int(v) for v in s_), tuple(int(v) for v in d_)) for s_, d_ in (resize or ()))
         key = ("train" if train else "forward", int(frames_u8.shape[0]), tuple(frames_u8.shape[1:]), rz, crop_y is not None,
                crop_x is not None, mirror is not None, mean_bgr is not None, float(clip_norm) if train else None,
                global_rows if train else None, self.cfg.dropout_keep_prob if train else None)
+        if train and self.accumulate > 1:     # first / middle / last micro-steps are different launch sequences: a graph each
+            key += MicroSequence.role(mi)
         g = self._graphs.get(key)
         if g is None:
             if key not in self._graph_warm:   # warm-up: one-time set-up (function attributes, tables, resizers, side-stream buffers)
                 self._graph_warm.add(key)
                 return False, None
             g = self._graphs[key] = self._capture(train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm,
-                                                  global_rows)
+                                                  global_rows, mi)
         for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x), ("mirror", mirror), ("onehot", onehot)):
             dst = g["inputs"].get(name)
             if dst is None:
@@ -1304,13 +1445,20 @@ class LRCNEngine:
             dst.copy_(t)
         if mean_bgr is not None:
             self.mean_dev.copy_(torch.as_tensor(np.asarray(mean_bgr, np.float32)), non_blocking=True)
-        ops.step_state_set(self.state, self.step_count, lr, self._graph_tag_origin(g["span"]))
+        draw = self._draw_index(mi)
+        if draw == self.step_count:
+            ops.step_state_set(self.state, self.step_count, lr, self._graph_tag_origin(g["span"]))
+        else:                                     # accumulation: the dropout seed follows the draw index, Adam's step size the update count
+            ops.step_state_set_micro(self.state, self.step_count, draw, lr, self._graph_tag_origin(g["span"]))
         g["graph"].replay()
         self._rows = g["rows"]
         if not train:
             return True, self.logits[:g["rows"]]
+        total_rows = self.micro.add_rows(mi, g["rows"])
+        if mi is not None and mi[0] < mi[1] - 1:
+            return True, self._fetch(total_rows, fetch, partial=True)
         self.step_count += 1
-        return True, self._fetch(g["rows"], fetch)
+        return True, self._fetch(total_rows, fetch)
 
     def _graph_tag_origin(self, span):
         """Tag origin of the next replay on lstm_ws_graph (its launches use origin + 1 .. origin + span - 1).  Past the limit the exchange
@@ -1322,7 +1470,7 @@ class LRCNEngine:
         self.graph_tag_next += span
         return origin
 
-    def _capture(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm, global_rows):
+    def _capture(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm, global_rows, mi=None):
         """Captures one call over static input buffers.  Nothing runs and no host state moves: the replay that follows is the step."""
         t0 = time.perf_counter()
         inputs = {name: torch.empty_like(t) for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x),
@@ -1338,7 +1486,7 @@ class LRCNEngine:
             chain.append((rs, torch.empty((n, rs.oh, rs.ow, 3), dtype=torch.uint8, device=self.dev),
                           torch.empty(need, dtype=torch.uint8, device=self.dev) if need else None))
         graph = torch.cuda.CUDAGraph()
-        step_count = self.step_count
+        step_count, acc_rows = self.step_count, self.micro.rows
         self._tag_off = 0
         # No finaliser may run inside the capture: releasing a conv or resize descriptor frees device tables (hipFree), which a thread-local
         # capture on this thread does not allow -- it invalidates the capture.  Engines that sit in reference cycles (a GraphEngine and the
@@ -1355,7 +1503,7 @@ class LRCNEngine:
                 self._feed_dev(frames, n, b, self.mean_dev if mean_bgr is not None else None, inputs.get("crop_y"), inputs.get("crop_x"),
                                inputs.get("mirror"))
                 if train:
-                    self._train(n, b, inputs["onehot"], 0.0, clip_norm, False, global_rows)
+                    self._train(n, b, inputs["onehot"], 0.0, clip_norm, False, global_rows, mi)
                     rows = self._rows
                 else:
                     rows = self._forward(n, b, train=False)
@@ -1364,6 +1512,6 @@ class LRCNEngine:
             if gc_was_on:
                 gc.enable()
             self._tag_off = None
-            self.step_count = step_count
+            self.step_count, self.micro.rows = step_count, acc_rows
         self.graph_capture_ms.append((time.perf_counter() - t0) * 1e3)
         return dict(graph=graph, inputs=inputs, rows=rows, span=span, resize_buffers=[(dst, tmp) for _, dst, tmp in chain])

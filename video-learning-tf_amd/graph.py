@@ -40,8 +40,8 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, NetConfig, check_momentum, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan,
-                     frozen_layers, param_specs, tier_plan)
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_momentum, check_weight_decay,
+                     dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
 
 
 @dataclass
@@ -440,7 +440,7 @@ class PipeNode:
                     self.x0_others[i][:n].copy_(tw.x0[:n])
             if len(seq) > 1:                   # mean / maximum over the list (the zero halo stays zero under both)
                 ops.fuse_n([t[:n] for t in self.x0_others] + [tw.x0[:n]], tw.x0[:n], self.fusion, count=tw.x0[:n].numel())
-            tw.step_count = g.step_count
+            tw.step_count = g._draw_index()        # (the tower's dropout seed; its own accumulate is 1)
             tw._forward(n, b, train)
             self._nb = (n, b)
             x, rows = tw.logits, n
@@ -552,7 +552,7 @@ class PipeNode:
         self._dropout = train and g.dropout_keep_prob > 0 and self.lfusion != "state"       # lstm.py:80-93
         if self._dropout:
             ops.dropout_fwd(v[:r], self.dropped[:r], self.drop_mask[:r], g.dropout_keep_prob,
-                            (g.step_count << 20) ^ (0x2545F4914F6CDD1D + 0x9E3779B9 * self.index))
+                            (g._draw_index() << 20) ^ (0x2545F4914F6CDD1D + 0x9E3779B9 * self.index))
             v = self.dropped
         self._v = v
         if H != C:
@@ -750,11 +750,15 @@ def model_specs(pipelines, datasets, num_classes):
 
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
-                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0):
+                 optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
+                 accumulate=1):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
-        pipeline (engine.decay_ranges); 0 = off."""
+        pipeline (engine.decay_ranges); 0 = off.  accumulate: the most micro-batches one update may sum, train_step(micro=(i, k))
+        (engine.check_accumulate, LRCNEngine.train_step_u8); 1 = off."""
+        self.accumulate = check_accumulate(accumulate)
+        self.micro, self._mi = MicroSequence(self.accumulate), None
         self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)
         self.weight_decay = check_weight_decay(weight_decay)
         self.dev = torch.device(device)
@@ -865,6 +869,7 @@ class GraphEngine:
         if optimizer == "adam" and training:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
         self.mom = torch.zeros(total, device=dev) if self.momentum > 0.0 and training else None    # the momentum accumulator
+        self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None   # LRCNEngine.__init__: the running sum
         rows = self.last.max_rows
         self.stats = torch.zeros(2, device=dev)
         self.loss_rows = torch.zeros(2 * rows, device=dev)
@@ -921,7 +926,14 @@ class GraphEngine:
         return self
 
     def check_status(self):
-        ops.lstm_seq_check(*[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])
+        try:
+            ops.lstm_seq_check(*[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])
+        except VltfError:
+            self.micro.reset()                # LRCNEngine.check_status: an accumulated update in progress is abandoned
+            raise
+
+    _draw_index = LRCNEngine._draw_index
+    _acc_tiers = LRCNEngine._acc_tiers
 
     def logits_host(self):
         self._sync()
@@ -975,26 +987,41 @@ class GraphEngine:
         rows = self._forward(feeds, train=False)
         return self.last.out[:rows]
 
-    def train_step(self, feeds, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, seq_len=None):
+    def train_step(self, feeds, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, seq_len=None, micro=None):
         """sess.run([.., loss, .., optimizer], fdict): labels int32 one-hot [rows, classes] for the LAST pipeline's rows.
         seq_len as in forward; when the last pipeline has lengths and fusion `reshape`, loss and accuracy are means over the
-        n_valid = sum(lengths) live rows (labels still hold every row) and the returned `rows` is n_valid."""
+        n_valid = sum(lengths) live rows (labels still hold every row) and the returned `rows` is n_valid.
+        micro = (i, k): micro-step i of an update that sums k of them (LRCNEngine.train_step_u8); with a masked loss global_rows is then
+        the live rows of the whole update (default n_valid * k)."""
+        mi = self.micro.enter(micro)
+        try:
+            return self._train_step(feeds, onehot, lr, clip_norm, fetch, global_rows, seq_len, mi)
+        except VltfError:
+            self.micro.reset()
+            raise
+        finally:
+            self._mi = None
+
+    def _train_step(self, feeds, onehot, lr, clip_norm, fetch, global_rows, seq_len, mi):
         if not self.training:
             raise VltfError("engine was built with training=False")
+        i, k = mi if mi is not None else (0, 1)
         n_valid = self._set_seq_len(seq_len, feeds)
-        if n_valid is not None and global_rows is not None:
+        if n_valid is not None and global_rows is not None and k == 1:
             raise VltfError("global_rows is the data-parallel row count; a loss masked by seq_len takes its own live-row count")
+        self._mi = mi
         rows = self._forward(feeds, train=True)
         if onehot.dtype != torch.int32 or tuple(onehot.shape) != (rows, self.num_classes):
             raise VltfError("labels must be int32 one-hot of shape (%d, %d)" % (rows, self.num_classes))
         world = self.dp.world if self.dp is not None else 1
-        ops.fill(self.stats, 0.0)
+        if i == 0:                                # loss_sum / correct sum on the device over the micro-steps of an update
+            ops.fill(self.stats, 0.0)
         last = self.last
         if n_valid is not None:       # padded steps are kept out of the loss (non_padding_index, dataset_.py:327-383)
-            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / n_valid, self.loss_rows, seq_len=last.seq_len,
-                             T=last.fpc)
+            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or n_valid * k), self.loss_rows,
+                             seq_len=last.seq_len, T=last.fpc)
         else:
-            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or rows * world), self.loss_rows)
+            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or rows * world * k), self.loss_rows)
         # backward, last pipeline first.  RCCL chunks are held back while an LSTM backward launch is still to come: the cluster
         # form of the recurrence needs every CU and must not spin under an all-reduce kernel that holds some (vl_lstm_seq_status)
         self._pending_lstm = sum(1 for nd in self.nodes if nd.cls == "lstm")
@@ -1004,7 +1031,23 @@ class GraphEngine:
         for nd in reversed(self.nodes):
             nd.backward()
         self._flush()
-        return self._finish_step(rows if n_valid is None else n_valid, lr, clip_norm, fetch)
+        total_rows = self.micro.add_rows(mi, rows if n_valid is None else n_valid)
+        if i < k - 1:                             # LRCNEngine._train: g joins the running sum, nothing else happens
+            ops.grad_accumulate(self.gacc, self.g, ops.ACC_STORE if i == 0 else ops.ACC_ADD, self._acc_tiers())
+            return self._fetch(total_rows, fetch, partial=True)
+        if k > 1 and self.dp is None:             # (data parallel: _exchange added each chunk before it went out)
+            ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, self._acc_tiers())
+        return self._finish_step(total_rows, lr, clip_norm, fetch)
+
+    def _exchange(self, off, cnt):
+        """One chunk of the flat gradient goes out.  A non-final micro-step exchanges nothing; the final one of k > 1 first adds the
+        running sum over the chunk, on the current stream (LRCNEngine._issue)."""
+        mi = self._mi
+        if mi is not None and mi[0] < mi[1] - 1:
+            return
+        if mi is not None and mi[1] > 1:
+            ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, [(off, off + cnt, 1.0)])
+        self.dp.reduce_async(self.g, off, cnt)
 
     def _reduce(self, off, cnt):
         if self.dp is None or cnt == 0:
@@ -1012,11 +1055,11 @@ class GraphEngine:
         if self._pending_lstm > 0:
             self._queued.append((off, cnt))
         else:
-            self.dp.reduce_async(self.g, off, cnt)
+            self._exchange(off, cnt)
 
     def _flush(self):
         for off, cnt in self._queued:
-            self.dp.reduce_async(self.g, off, cnt)
+            self._exchange(off, cnt)
         self._queued = []
 
     def _head_done(self, nd):
@@ -1033,16 +1076,28 @@ class GraphEngine:
     def _tower_dp(self, nd):
         return _TowerReduce(self, nd.tower_off) if self.dp is not None else None
 
-    def train_step_empty(self, lr, clip_norm=0.0, fetch=True):
-        """This rank's shard of the global batch is empty: contribute zeros to the exchange, apply the same update as the others."""
+    def train_step_empty(self, lr, clip_norm=0.0, fetch=True, micro=None):
+        """This rank's shard of the global batch is empty: contribute zeros to the exchange, apply the same update as the others
+        (as a micro-step: add nothing to the update's sum, LRCNEngine.train_step_empty)."""
         if self.dp is None:
             raise VltfError("train_step_empty is a data-parallel call")
+        mi = self.micro.enter(micro)
+        i, k = mi if mi is not None else (0, 1)
+        if i == 0:
+            ops.fill(self.stats, 0.0)
+        total_rows = self.micro.add_rows(mi, 0)
+        if i < k - 1:
+            if i == 0:
+                for lo, hi, _ in self.plan.tiers:
+                    ops.fill(self.gacc[lo:hi], 0.0)
+            return self._fetch(total_rows, fetch, partial=True)
         for lo, hi, _ in self.plan.tiers:
             ops.fill(self.g[lo:hi], 0.0)
-        ops.fill(self.stats, 0.0)
         for lo, cnt in self.grad_chunks:
+            if k > 1:
+                ops.grad_accumulate(self.gacc, self.g, ops.ACC_FINAL, [(lo, lo + cnt, 1.0)])
             self.dp.reduce_async(self.g, lo, cnt)
-        return self._finish_step(0, lr, clip_norm, fetch)
+        return self._finish_step(total_rows, lr, clip_norm, fetch)
 
     def _finish_step(self, rows, lr, clip_norm, fetch):
         if self.dp is not None:
@@ -1066,11 +1121,18 @@ class GraphEngine:
             ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
+        return self._fetch(rows, fetch)
+
+    def _fetch(self, rows, fetch, partial=False):
+        """partial: a micro-step before the update's last -- the running sums of the update so far, no norm yet."""
         if not fetch:
             return None
         self._sync()
         self.check_status()
         st = self.stats.cpu().numpy()
+        if partial:
+            return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows, "loss_sum": float(st[0]),
+                    "correct": float(st[1])}
         out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1),
                "grad_norm": math.sqrt(float(self.ss.item())), "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
         if self.ss2 is not None:

@@ -656,6 +656,12 @@ def step_state_set(state, step, lr, tag_origin):
     _ffi.call("vl_step_state_set", _state(state), int(step), lr, int(tag_origin), stream())
 
 
+def step_state_set_micro(state, update_step, draw_step, lr, tag_origin):
+    """step_state_set for a micro-step of an accumulated update: the state's count (the dropout seed's input) = draw_step, Adam's step
+    size that of count update_step + 1 (vl_step_state_set_micro)."""
+    _ffi.call("vl_step_state_set_micro", _state(state), int(update_step), int(draw_step), lr, int(tag_origin), stream())
+
+
 def sgd_apply_st(w, g, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
     """sgd_apply with lr read from the step state."""
     _f32(w, g, sumsq_t)
@@ -704,6 +710,23 @@ def l2_regularize(w, g, ranges, out, ws):
     for k, (lo, hi, decay) in enumerate(ranges):
         arr[k].begin, arr[k].end, arr[k].decay = int(lo), int(hi), float(decay)
     _ffi.call("vl_l2_regularize", _p(w), _p(g), w.numel(), arr, len(ranges), _p(out), _p(ws), stream())
+
+
+ACC_STORE, ACC_ADD, ACC_FINAL = 0, 1, 2
+
+
+def grad_accumulate(acc, g, mode, ranges=None):
+    """Gradient accumulation (vltf.h: vl_grad_accumulate).  mode ACC_STORE: acc = g; ACC_ADD: acc = acc + g; ACC_FINAL: g = acc + g.
+    ranges = [(begin, end, lr_mult)] (plan.tiers; the factor is ignored) or None for everything; elements outside every range are
+    not touched in either buffer.  One launch."""
+    _f32(acc, g)
+    if acc.numel() != g.numel():
+        raise _ffi.VltfError("grad_accumulate: acc and g must have one element count")
+    if ranges is None:
+        arr, n = None, 0
+    else:
+        arr, n = _tiers(ranges)
+    _ffi.call("vl_grad_accumulate", _p(acc), _p(g), g.numel(), int(mode), arr, n, stream())
 
 
 def sgd_apply_tiers(w, g, tiers, lr, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):

@@ -55,7 +55,8 @@ def pipeline_net_config(settings, p, dataset):
               step_graph=step_graph_requested(),                   # VLTF_STEP_GRAPH=1: captured train / forward steps (not a reference key)
               lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None),
               momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False,
-              weight_decay=settings.train.weight_decay if settings.train else 0.0)
+              weight_decay=settings.train.weight_decay if settings.train else 0.0,
+              accumulate=settings.train.accumulate if settings.train else 1)
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -186,7 +187,12 @@ def do_train(settings, train, feeder, engine):
     """run_task.py:25-81."""
     run_batch_count, min_train_loss = 0, (1000, -1)
     fed_clips, fed_time = 0, 0.0          # feed + step time of every batch but the first (checkpoint writes excluded)
+    save_due, saved_at, updates = False, -1, 0      # gradient accumulation: a save that falls inside a group waits for the group's end
+    accumulate = getattr(train, "accumulate", 1)
     info("Starting train")
+    if accumulate > 1:
+        info("Gradient accumulation: %d batches of %d videos = %d videos per update (all ranks together); global step counts batches" %
+             (accumulate, settings.train.batch_size, accumulate * settings.train.batch_size))
     for _ in range(settings.train.epoch_index, settings.train.epochs):
         while feeder.loop():
             tic = time.perf_counter()
@@ -212,7 +218,14 @@ def do_train(settings, train, feeder, engine):
                  (learning_rate, settings.global_step, batch_loss, nats, reg))
             info("Dataset global step %d, epoch index %d, batch sizes %s, batch index train %d" %
                  (settings.global_step, settings.train.epoch_index + 1, str(feeder.get_batch_sizes()), feeder.get_batch_index()))
-            if feeder.should_save(run_batch_count):
+            group_done = accumulate == 1 or train.group_done
+            if accumulate > 1 and group_done:
+                updates += 1
+                info("Update %d closed at global step %d: %d rows, loss %2.5f, gradient norm %2.5f" %
+                     (updates, settings.global_step, train.last["rows"], batch_loss, train.last.get("grad_norm", float("nan"))))
+            save_due = save_due or feeder.should_save(run_batch_count)
+            if save_due and group_done:
+                save_due, saved_at = False, run_batch_count
                 feeder.save(engine, "ep_%d_btch_%d_gs_%d" % (1 + settings.train.epoch_index, feeder.get_batch_index(), settings.global_step),
                             settings.global_step)
         info("Epoch [%d] training run complete." % (1 + settings.train.epoch_index) if run_batch_count > 0 else
@@ -222,7 +235,7 @@ def do_train(settings, train, feeder, engine):
     info("Minimum training loss: %2.2f on global index %d" % (min_train_loss[0], min_train_loss[1]))
     if fed_time > 0:
         info("Training throughput: %.1f clips/s over %d batches (input feed + train step)" % (fed_clips / fed_time, run_batch_count - 1))
-    if run_batch_count > 0 and not feeder.should_save(run_batch_count):
+    if run_batch_count > 0 and saved_at != run_batch_count:
         info("Saving model checkpoint out of turn, since training's finished.")
         feeder.save(engine, "ep_%d_btch_%d_gs_%d" % (1 + settings.train.epoch_index, feeder.get_num_batches(), settings.global_step),
                     settings.global_step)
@@ -327,7 +340,8 @@ def main(init_file, seed=0, device=None):
                              conv_math=os.environ.get("VLTF_CONV_MATH", "f32"), lr_mult=settings.train.lr_mult if settings.train else None,
                              momentum=settings.train.momentum if settings.train else 0.0,
                              nesterov=settings.train.nesterov if settings.train else False,
-                             weight_decay=settings.train.weight_decay if settings.train else 0.0)
+                             weight_decay=settings.train.weight_decay if settings.train else 0.0,
+                             accumulate=settings.train.accumulate if settings.train else 1)
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

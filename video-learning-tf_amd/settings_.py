@@ -21,6 +21,7 @@ class TrainSettings:
     lr_decay, clip_norm, dropout_keep_prob = None, 0, 0.5
     momentum, nesterov = 0.0, False
     weight_decay = 0.0
+    accumulate = 1
 
 
 class ValSettings:
@@ -173,6 +174,13 @@ class Settings:
                     t.weight_decay = check_weight_decay(None if wd == "None" else wd)
                 except VltfError as ex:
                     error("train.weight_decay: %s" % ex)
+                # gradient accumulation: `accumulate` consecutive batches of an epoch make one update (train.accumulate_groups); batch_size
+                # stays what one call feeds.  absent / None = 1
+                from .engine import check_accumulate
+                try:
+                    t.accumulate = check_accumulate(None if obj.get("accumulate") == "None" else obj.get("accumulate"))
+                except VltfError as ex:
+                    error("train.accumulate: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:

@@ -46,14 +46,50 @@ def precompute_learning_rates(settings, num_batches):
     return lrs
 
 
+def accumulate_groups(num_batches, k, start_batch=0):
+    """[(first, last)] batch indices of an epoch, inclusive: the groups of k consecutive batches that make one update each, from
+    start_batch on.  Groups never span epochs, so the last one may be short.  start_batch must be where a group begins (checkpoints are
+    written at group ends only, so a resume lands there); num_batches itself (a finished epoch) gives no group."""
+    if k < 1 or num_batches < 0 or not (0 <= start_batch <= num_batches):
+        raise ValueError("accumulate_groups(%r, %r, %r): need k >= 1 and 0 <= start_batch <= num_batches" % (num_batches, k, start_batch))
+    if start_batch % k and start_batch != num_batches:
+        raise ValueError("batch %d does not begin a group of %d batches: a run with accumulate %d resumes at a multiple of %d only" %
+                         (start_batch, k, k, k))
+    return [(first, min(first + k, num_batches) - 1) for first in range(start_batch, num_batches, k)]
+
+
 class Train:
-    """train.py:112-149: owns the LR table and global_step; run_step is the train sess.run."""
+    """train.py:112-149: owns the LR table and global_step; run_step is the train sess.run.
+    train.accumulate k > 1: the batches of an epoch go to the engine in groups (accumulate_groups) as the micro-steps of one update.
+    global_step, the learning-rate table and the checkpoint names keep counting BATCHES; the update takes the lr of its last batch."""
 
     def __init__(self, settings, feeder, engine):
         self.engine = engine
         self.learning_rates = precompute_learning_rates(settings, feeder.get_num_batches())
         self.global_step = settings.global_step
         self.clip_norm = float(settings.train.clip_norm or 0)
+        self.accumulate = int(getattr(settings.train, "accumulate", 1) or 1)
+        self._group, self._group_clips = None, 0
+        self.group_done = True                  # the last run_step closed an update: a checkpoint may be written
+
+    def _micro(self, fdict):
+        """-> (micro, clips of the whole group over all ranks) of the batch in fdict; (None, None) without accumulation.  The group's
+        clips come from the dataset's batch list before its first step, so a short last batch inside a group still gives the exact
+        mean over the group."""
+        if self.accumulate == 1:
+            return None, None
+        d = fdict["dataset"]
+        pos = fdict["batch_index"] - 1           # (the dataset's index has already moved past this batch)
+        if self._group is None or not (self._group[0] <= pos <= self._group[1]):
+            try:
+                self._group = accumulate_groups(len(d.batches), self.accumulate, pos)[0]
+            except (ValueError, IndexError) as ex:
+                error("train.accumulate: %s" % ex)
+            first, last = self._group
+            self._group_clips = sum(d.clips_per_video[first * d.batch_size:(last + 1) * d.batch_size])
+        first, last = self._group
+        self.group_done = pos == last
+        return (pos - first, last - first + 1), self._group_clips
 
     def run_step(self, fdict, others=None):
         """-> (loss, current_lr, global_step) like sess.run([.., loss, current_lr, global_step, optimizer]).
@@ -71,19 +107,24 @@ class Train:
         if dpg is not None and fdict.get("global_clips") is not None:
             # per-frame head (classifier fc, no frame fusion): one logits row per frame -> global rows = global clips * fpc
             grows = fdict["global_clips"] * (1 if per_clip else eng.cfg.fpc)
+        micro, group_clips = self._micro(fdict)
+        kw = {}
+        if micro is not None:                    # the loss is the mean over the rows of the whole update, on every one of its calls
+            grows = group_clips * (1 if per_clip else eng.cfg.fpc)
+            kw = dict(micro=micro)
         if len(fdict["labels"]) == 0:
-            out = eng.train_step_empty(lr, self.clip_norm)
+            out = eng.train_step_empty(lr, self.clip_norm, **kw)
         elif "device" in fdict:          # uploaded ahead of time by the feeder's BatchPrefetcher: wait for the copy on the stream
             torch.cuda.current_stream(dev).wait_event(fdict["ready"])
             t = fdict["device"]
             out = eng.train_step_u8(t["frames_u8"], t["labels"], lr, self.clip_norm, fdict["mean_bgr"], t["crop_y"], t["crop_x"],
-                                    t["mirror"], global_rows=grows, resize=fdict.get("resize"))
+                                    t["mirror"], global_rows=grows, resize=fdict.get("resize"), **kw)
         else:
             out = eng.train_step_u8(torch.from_numpy(fdict["frames_u8"]).to(dev, non_blocking=True),
                                     torch.from_numpy(fdict["labels"]).to(dev),
                                     lr, self.clip_norm, fdict["mean_bgr"],
                                     torch.from_numpy(fdict["crop_y"]).to(dev), torch.from_numpy(fdict["crop_x"]).to(dev),
-                                    torch.from_numpy(fdict["mirror"]).to(dev), global_rows=grows, resize=fdict.get("resize"))
+                                    torch.from_numpy(fdict["mirror"]).to(dev), global_rows=grows, resize=fdict.get("resize"), **kw)
         if dpg is not None:              # log the global-batch loss, not the shard's
             tot = dpg.sum_scalars(torch.tensor([out["loss_sum"], out["correct"], float(out["rows"])], device=dev, dtype=torch.float64))
             tot = tot.cpu().numpy()
@@ -106,13 +147,19 @@ class Train:
         if eng.dp is not None and fdict.get("global_clips") is not None and len(fdict["labels"]):
             # rows of the GLOBAL batch: the main dataset's global clips times this model's logits rows per main clip
             grows = fdict["global_clips"] * len(labels) // len(fdict["labels"])
+        micro, group_clips = self._micro(fdict)
+        kw = {}
+        if micro is not None:
+            kw = dict(micro=micro)
+            if len(fdict["labels"]):
+                grows = group_clips * len(labels) // len(fdict["labels"])
         if len(labels) == 0:                 # this rank's shard of a short last batch is empty
-            out = eng.train_step_empty(lr, self.clip_norm)
+            out = eng.train_step_empty(lr, self.clip_norm, **kw)
         else:
             fdicts = dict(others)
             fdicts[defs.dataset_tag.main] = fdict
             out = eng.train_step(graph_feeds(fdicts, sorted(fdicts), dev), torch.from_numpy(np.ascontiguousarray(labels)).to(dev), lr,
-                                 self.clip_norm, global_rows=grows)
+                                 self.clip_norm, global_rows=grows, **kw)
         if eng.dp is not None:
             tot = eng.dp.sum_scalars(torch.tensor([out["loss_sum"], out["correct"], float(out["rows"])], device=dev, dtype=torch.float64))
             tot = tot.cpu().numpy()
