@@ -379,6 +379,18 @@ int vl_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, int64_t coun
 int vl_dropout_fwd_st(const float* x, float* y, uint8_t* mask, int64_t count, float keep, const vl_step_state* state,
                       vl_stream_t stream);
 
+/* ---- dropout on the ReLU'd fc layers of the tower (Caffe AlexNet's drop6 / drop7), in place, no mask buffer ----------------------
+ * y[e] = kept(e) ? y[e] / keep : 0 over `count` floats, any count >= 1, any 4-byte aligned pointer (16-byte accesses over the part
+ * of the range that is 16-byte aligned, scalar head and tail).  kept(e) is a function of (seed, salt, e) alone, e counted from the
+ * pointer given:   s = seed ^ splitmix64(0xFC00 + salt);  h = splitmix64(s ^ splitmix64(e));  kept = (h >> 40) * 2^-24 < keep
+ * (splitmix64: the generator of vl_dropout_fwd; the salt separates the layers' and towers' masks from each other and from
+ * vl_dropout_fwd's, which uses the bare seed).  y being a ReLU output, y > 0 afterwards means "ReLU active and kept": */
+int vl_fc_dropout_fwd(float* y, int64_t count, float keep, uint64_t seed, uint32_t salt, vl_stream_t stream);
+/* The same with seed = (state->step << 20) ^ 0x5DEECE66D, read from the step state when the kernel runs (as vl_dropout_fwd_st). */
+int vl_fc_dropout_fwd_st(float* y, int64_t count, float keep, const vl_step_state* state, uint32_t salt, vl_stream_t stream);
+/* ... so ReluGrad and the dropout's gradient are one pass over the dropped output: d[e] = y[e] > 0 ? d[e] / keep : 0, in place. */
+int vl_relu_dropout_grad(float* d, const float* y, int64_t count, float keep, vl_stream_t stream);
+
 /* ---- loss: mean_b softmax_cross_entropy_with_logits (train.py:120-123) + accuracy (142-149) ----
  * labels: int32 one/multi-hot [batch][classes] (the reference's labels placeholder, train.py:117).
  * dlogits = (softmax - labels) * grad_scale   (grad_scale = 1/global_batch); may be NULL.

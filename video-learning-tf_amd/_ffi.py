@@ -81,6 +81,9 @@ SIGNATURES = {
     "vl_dropout_fwd": (i32, [p, p, p, i64, f32, u64, p]),
     "vl_dropout_bwd": (i32, [p, p, p, i64, f32, p]),
     "vl_dropout_fwd_st": (i32, [p, p, p, i64, f32, p, p]),
+    "vl_fc_dropout_fwd": (i32, [p, i64, f32, u64, u32, p]),
+    "vl_fc_dropout_fwd_st": (i32, [p, i64, f32, p, u32, p]),
+    "vl_relu_dropout_grad": (i32, [p, p, i64, f32, p]),
     "vl_softmax_xent": (i32, [p, p, p, p, p, i32, i32, f32, p]),
     "vl_softmax_xent_len": (i32, [p, p, p, p, p, i32, i32, f32, p, i32, p]),
     "vl_sumsq": (i32, [p, i64, p, p, i32, p]),

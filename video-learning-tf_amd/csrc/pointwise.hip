@@ -2546,6 +2546,103 @@ extern "C" int vl_relu_grad(float* d, const float* y, int64_t count, vl_stream_t
     return 0;
 }
 
+// ---- dropout on the ReLU'd fc layers of the tower (fc6 / fc7), in place, no mask buffer (vltf.h: vl_fc_dropout_fwd) -----------------
+// The draw of element e is a function of (seed, salt, e) alone: the scalar head / tail and the 16-byte interior call one element
+// function with the element's index relative to the pointer given, so neither the launch geometry nor the alignment changes a mask.
+__device__ __forceinline__ uint64_t fc_dropout_stream(uint64_t seed, uint32_t salt) {
+    return seed ^ splitmix64(0xFC00ull + (uint64_t)salt);
+}
+
+__device__ __forceinline__ float fc_dropout_elem(float y, uint64_t s, int64_t e, float keep) {
+#pragma clang fp contract(off)
+    const uint64_t h = splitmix64(s ^ splitmix64((uint64_t)e));
+    const float uni = (float)(h >> 40) * (1.0f / 16777216.0f);
+    return uni < keep ? y / keep : 0.f;
+}
+
+__device__ __forceinline__ void fc_dropout_body(float* __restrict__ y, int64_t count, float keep, uint64_t s, int64_t i0, int64_t step) {
+    int64_t v0, v1;
+    tier_split(0, count, align_phase(y, nullptr, nullptr, nullptr), v0, v1);
+    for (int64_t e = i0; e < v0; e += step) y[e] = fc_dropout_elem(y[e], s, e, keep);
+    float4* __restrict__ y4 = reinterpret_cast<float4*>(y + v0);
+    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+        const int64_t e = v0 + 4 * i;
+        float4 v = y4[i];
+        v.x = fc_dropout_elem(v.x, s, e, keep);
+        v.y = fc_dropout_elem(v.y, s, e + 1, keep);
+        v.z = fc_dropout_elem(v.z, s, e + 2, keep);
+        v.w = fc_dropout_elem(v.w, s, e + 3, keep);
+        y4[i] = v;
+    }
+    for (int64_t e = v1 + i0; e < count; e += step) y[e] = fc_dropout_elem(y[e], s, e, keep);
+}
+
+__global__ __launch_bounds__(256) void fc_dropout_fwd_kernel(float* __restrict__ y, int64_t count, float keep, uint64_t seed, uint32_t salt) {
+    fc_dropout_body(y, count, keep, fc_dropout_stream(seed, salt), (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                    (int64_t)gridDim.x * blockDim.x);
+}
+
+// the seed as vl_dropout_fwd_st forms it, from the step state when the kernel runs (a replayed step's own count)
+__global__ __launch_bounds__(256) void fc_dropout_fwd_st_kernel(float* __restrict__ y, int64_t count, float keep,
+                                                                const vl_step_state* __restrict__ st, uint32_t salt) {
+    fc_dropout_body(y, count, keep, fc_dropout_stream(((uint64_t)st->step << 20) ^ 0x5DEECE66Dull, salt),
+                    (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// a lane takes 4 elements per pass: the grid covers 4 * 256 * VL_FC_DROPOUT_GRID_CAP elements before its loop turns
+#define VL_FC_DROPOUT_GRID_CAP 4096
+
+extern "C" int vl_fc_dropout_fwd(float* y, int64_t count, float keep, uint64_t seed, uint32_t salt, vl_stream_t stream) {
+    VL_CHECK(y && ((uintptr_t)y & 3) == 0 && count > 0 && keep > 0.f && keep <= 1.f, "vl_fc_dropout_fwd: bad argument");
+    hipLaunchKernelGGL(fc_dropout_fwd_kernel, dim3(grid_for((count + 3) / 4, 256, VL_FC_DROPOUT_GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, y, count, keep, seed, salt);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_fc_dropout_fwd_st(float* y, int64_t count, float keep, const vl_step_state* state, uint32_t salt,
+                                    vl_stream_t stream) {
+    VL_CHECK(y && ((uintptr_t)y & 3) == 0 && state && count > 0 && keep > 0.f && keep <= 1.f, "vl_fc_dropout_fwd_st: bad argument");
+    hipLaunchKernelGGL(fc_dropout_fwd_st_kernel, dim3(grid_for((count + 3) / 4, 256, VL_FC_DROPOUT_GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, y, count, keep, state, salt);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ReluGrad and the dropout's gradient in one: y is the dropped ReLU output, > 0 exactly where the ReLU was active and the draw kept
+__device__ __forceinline__ float relu_dropout_grad_elem(float d, float y, float keep) {
+#pragma clang fp contract(off)
+    return y > 0.f ? d / keep : 0.f;
+}
+
+__global__ __launch_bounds__(256) void relu_dropout_grad_kernel(float* __restrict__ d, const float* __restrict__ y, int64_t count, float keep) {
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    int64_t v0, v1;
+    tier_split(0, count, align_phase(d, y, nullptr, nullptr), v0, v1);
+    for (int64_t e = i0; e < v0; e += step) d[e] = relu_dropout_grad_elem(d[e], y[e], keep);
+    float4* __restrict__ d4 = reinterpret_cast<float4*>(d + v0);
+    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + v0);
+    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+        float4 dv = d4[i];
+        const float4 yv = y4[i];
+        dv.x = relu_dropout_grad_elem(dv.x, yv.x, keep);
+        dv.y = relu_dropout_grad_elem(dv.y, yv.y, keep);
+        dv.z = relu_dropout_grad_elem(dv.z, yv.z, keep);
+        dv.w = relu_dropout_grad_elem(dv.w, yv.w, keep);
+        d4[i] = dv;
+    }
+    for (int64_t e = v1 + i0; e < count; e += step) d[e] = relu_dropout_grad_elem(d[e], y[e], keep);
+}
+
+extern "C" int vl_relu_dropout_grad(float* d, const float* y, int64_t count, float keep, vl_stream_t stream) {
+    VL_CHECK(d && y && (((uintptr_t)d | (uintptr_t)y) & 3) == 0 && count > 0 && keep > 0.f && keep <= 1.f,
+             "vl_relu_dropout_grad: bad argument");
+    hipLaunchKernelGGL(relu_dropout_grad_kernel, dim3(grid_for((count + 3) / 4, 256, VL_FC_DROPOUT_GRID_CAP)), dim3(256), 0,
+                       (hipStream_t)stream, d, y, count, keep);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int vl_fill(float* p, int64_t count, float value, vl_stream_t stream) {
     VL_CHECK(p && count > 0, "vl_fill: bad argument");
     hipLaunchKernelGGL(fill_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, p, count, value);

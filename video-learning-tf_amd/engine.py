@@ -62,6 +62,8 @@ class NetConfig:
     nesterov: bool = False                      # train.nesterov: use_nesterov of the same (needs momentum > 0)
     weight_decay: float = 0.0                   # train.weight_decay: L2 coefficient of the trained weight tensors (decay_ranges); 0 = off
     accumulate: int = 1                         # train.accumulate: most micro-batches one update may sum (train_step_*(micro=(i, k))); 1 = off
+    fc_dropout_keep_prob: float = 0.0           # train.fc_dropout_keep_prob: dropout on relu(fc6) / relu(fc7) (Caffe's drop6 / drop7); 0 = off
+    fc_dropout_salt: int = 0                    # which mask stream this tower draws from (fc_dropout_salt): a GraphEngine numbers its towers
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -188,6 +190,34 @@ def check_weight_decay(weight_decay):
     if not (d >= 0.0 and math.isfinite(d)):
         raise VltfError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
     return d
+
+
+def check_fc_dropout(keep_prob):
+    """The keep probability of the fc6 / fc7 dropout as a float, None or 0 read as 0 (off).  Accepted: (0, 1]; 1 launches nothing.
+    Refused: negative, above 1, NaN, infinite, not a number."""
+    if keep_prob is None:
+        return 0.0
+    if isinstance(keep_prob, (bool, str, bytes)) or not isinstance(keep_prob, (int, float, np.integer, np.floating)):
+        raise VltfError("fc_dropout_keep_prob must be a number in [0, 1] (0 = off), got %r" % (keep_prob,))
+    k = float(keep_prob)
+    if not (0.0 <= k <= 1.0):                     # (NaN fails both)
+        raise VltfError("fc_dropout_keep_prob must be a number in [0, 1] (0 = off), got %r" % (keep_prob,))
+    return k
+
+
+def dropout_seed(draw_index):
+    """The seed of every dropout launch of the step with this draw index (LRCNEngine._draw_index); the _st launches of a captured
+    step form the same value on the device from the step state's count."""
+    return (int(draw_index) << 20) ^ 0x5DEECE66D
+
+
+FC_DROPOUT_LAYERS = ("fc6", "fc7")
+
+
+def fc_dropout_salt(cfg: NetConfig, layer):
+    """The salt of one fc layer's masks (vl_fc_dropout_fwd): fc6 and fc7 of one tower differ in the low bit, towers in the bits above
+    it (cfg.fc_dropout_salt: 0 for an LRCNEngine of its own, 1 + the node index inside a GraphEngine)."""
+    return ((int(cfg.fc_dropout_salt) << 1) | FC_DROPOUT_LAYERS.index(layer)) & 0xFFFFFFFF
 
 
 def check_accumulate(accumulate):
@@ -414,6 +444,7 @@ class LRCNEngine:
         self.momentum, self.nesterov = check_momentum(cfg.optimizer, cfg.momentum, cfg.nesterov)
         self.weight_decay = check_weight_decay(cfg.weight_decay)
         self.accumulate = check_accumulate(cfg.accumulate)
+        self.fc_keep = check_fc_dropout(cfg.fc_dropout_keep_prob)      # 0: off; 1: on paper only, nothing is launched
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
         self.dev = torch.device(device)
@@ -858,8 +889,13 @@ class LRCNEngine:
             ops.gemm_kc8(a, w, self.f6, n, FC_DIM, F, bias=P["dcnn/fc6b"], relu=True, ws=self.ws)
         else:
             ops.gemm(x, P["dcnn/fc6W"], self.f6, n, FC_DIM, self.flat_dim, bias=P["dcnn/fc6b"], relu=True, ws=self.ws)
+        self._fc_drop = train and 0.0 < self.fc_keep < 1.0      # this pass dropped f6 / f7: their ReluGrad sites divide by keep
+        if self._fc_drop:
+            self._fc_dropout("fc6", self.f6[:n])
         if self.f7 is not None:
             ops.gemm(self.f6, P["dcnn/fc7W"], self.f7, n, FC_DIM, FC_DIM, bias=P["dcnn/fc7b"], relu=True, ws=self.ws)
+            if self._fc_drop:
+                self._fc_dropout("fc7", self.f7[:n])
         if self.f8 is not None:
             ops.gemm(self.f7, P["dcnn/fc8W"], self.f8, n, cfg.num_classes, FC_DIM, bias=P["dcnn/fc8b"], ws=self.ws)
         D, C, H, T = cfg.encode_dim(), cfg.num_classes, cfg.lstm_hidden, self.T
@@ -1032,10 +1068,11 @@ class LRCNEngine:
                     ops.pack_kc8(K, w, 4 * H, D, 1, 4 * H)                            # (position column, channel j) = K[j][column]
                     ops.gemm_kc8(a, w, self.dfeat, n, D, 4 * H, ws=self.ws)
                     if self.f8 is None:
-                        ops.relu_grad(self.dfeat, self.feat, n * D)                   # ReluGrad of fc6 / fc7
+                        self._relu_grad(self.dfeat, self.feat, n * D)                 # ReluGrad of fc6 / fc7
                 elif l == 0:
                     relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
-                    ops.gemm(S["dz"], K, self.dfeat, n, D, 4 * H, transb=True, ldb=4 * H, relu_mask=relu_mask, ws=self.ws)
+                    ops.gemm(S["dz"], K, self.dfeat, n, D, 4 * H, transb=True, ldb=4 * H, relu_mask=self._fused_mask(relu_mask), ws=self.ws)
+                    self._relu_grad_behind(self.dfeat, relu_mask, n * D)
                 else:
                     ops.gemm(S["dz"], K, self.lstm[l - 1]["dout"], n, H, 4 * H, transb=True, ldb=4 * H, ws=self.ws)
         else:
@@ -1050,16 +1087,17 @@ class LRCNEngine:
                 ops.gemm(self.fc_in, d, G["fc_convert_w"], D, Co, rows, transa=True)
                 ops.colsum(d, G["fc_convert_b"], sw, rows, Co)
                 if self.dcnn_trains:
-                    ops.gemm(d, P["fc_convert_w"], target, rows, D, Co, transb=True, relu_mask=relu_mask)
+                    ops.gemm(d, P["fc_convert_w"], target, rows, D, Co, transb=True, relu_mask=self._fused_mask(relu_mask))
+                    self._relu_grad_behind(target, relu_mask, rows * D)
             elif self.dcnn_trains:
                 target[:rows].copy_(d[:rows])
                 if relu_mask is not None:        # no fc in between (a feature pipeline): the encode layer's ReluGrad applies here
-                    ops.relu_grad(target, relu_mask, rows * D)
+                    self._relu_grad(target, relu_mask, rows * D)
             if self.early and self.dcnn_trains:
                 # ReluGrad of the encode layer applies per frame after un-fusing
                 ops.temporal_fusion_bwd(self.dfc_in, self.dfeat, b, T, D, self.ff_method)
                 if self.f8 is None:
-                    ops.relu_grad(self.dfeat, self.feat, n * D)
+                    self._relu_grad(self.dfeat, self.feat, n * D)
         # ---- fc8 / fc7 / fc6 (dfeat already carries the ReluGrad of the encode layer).  A layer gets its parameter gradients where it
         # trains and hands a gradient down where the layer below it trains; below the first trainable layer nothing is launched.
         trains = self.fc_trains
@@ -1068,13 +1106,15 @@ class LRCNEngine:
             ops.gemm(self.f7, d, G["dcnn/fc8W"], FC_DIM, C, n, transa=True, ws=self.ws)
             ops.colsum(d, G["dcnn/fc8b"], sw, n, C)
             if trains["fc7"]:
-                ops.gemm(d, P["dcnn/fc8W"], self.df7, n, FC_DIM, C, transb=True, relu_mask=self.f7, ws=self.ws)
+                ops.gemm(d, P["dcnn/fc8W"], self.df7, n, FC_DIM, C, transb=True, relu_mask=self._fused_mask(self.f7), ws=self.ws)
+                self._relu_grad_behind(self.df7, self.f7, n * FC_DIM)
             d = self.df7
         if self.f7 is not None and trains["fc7"]:
             ops.gemm(self.f6, d, G["dcnn/fc7W"], FC_DIM, FC_DIM, n, transa=True, ws=self.ws)
             ops.colsum(d, G["dcnn/fc7b"], sw, n, FC_DIM)
             if trains["fc6"]:
-                ops.gemm(d, P["dcnn/fc7W"], self.df6, n, FC_DIM, FC_DIM, transb=True, relu_mask=self.f6, ws=self.ws)
+                ops.gemm(d, P["dcnn/fc7W"], self.df6, n, FC_DIM, FC_DIM, transb=True, relu_mask=self._fused_mask(self.f6), ws=self.ws)
+                self._relu_grad_behind(self.df6, self.f6, n * FC_DIM)
             d = self.df6
         L5 = self.layers[-1]
         kc8 = self._fc6_kc8(n)
@@ -1206,6 +1246,31 @@ class LRCNEngine:
         if side is not None:
             torch.cuda.current_stream(self.dev).wait_stream(side)
         self._issue(self.plan.total)
+
+    # ---- dropout on relu(fc6) / relu(fc7) (cfg.fc_dropout_keep_prob) ------------------------------------------------------------
+    # In place and mask-free: a dropped output is > 0 exactly where the ReLU was active and the draw kept, so the ReluGrad sites of
+    # f6 / f7 keep reading the same tensor and only gain the division by keep (vl_relu_dropout_grad).
+    def _fc_dropout(self, layer, y):
+        salt = fc_dropout_salt(self.cfg, layer)
+        if self._tag_off is not None:             # captured: the seed follows the step state's count
+            ops.fc_dropout_fwd_st(y, self.fc_keep, self.state, salt)
+        else:
+            ops.fc_dropout_fwd(y, self.fc_keep, dropout_seed(self._draw_index()), salt)
+
+    def _relu_grad(self, d, y, count):
+        """ReluGrad of f6 / f7 on its own launch; after a forward pass that dropped them, with the dropout's gradient."""
+        if self._fc_drop:
+            ops.relu_dropout_grad(d, y, self.fc_keep, count)
+        else:
+            ops.relu_grad(d, y, count)
+
+    def _fused_mask(self, relu_mask):
+        """The relu_mask= a GEMM epilogue gets: after a forward pass that dropped f6 / f7 none -- _relu_grad_behind follows the GEMM."""
+        return None if self._fc_drop else relu_mask
+
+    def _relu_grad_behind(self, d, relu_mask, count):
+        if self._fc_drop and relu_mask is not None:
+            ops.relu_dropout_grad(d, relu_mask, self.fc_keep, count)
 
     def _draw_index(self, mi=None):
         """What the dropout seed is formed from: the micro-steps of one update draw different masks; with accumulate 1 the step count.

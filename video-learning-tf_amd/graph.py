@@ -40,8 +40,8 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_momentum, check_weight_decay,
-                     dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_fc_dropout, check_momentum,
+                     check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
 
 
 @dataclass
@@ -130,7 +130,8 @@ class PipeNode:
                 raise VltfError("pipeline [%s]: the fused frame datasets differ in shape / frames per clip" % s.name)
             self.fpc = seq[0].fpc
             cfg = NetConfig(image_shape=shapes.pop(), num_classes=C, fpc=self.fpc, frame_encoding_layer=s.frame_encoding_layer,
-                            classifier="none", optimizer=g.optimizer, conv_math=g.conv_math, train_from=s.train_from)
+                            classifier="none", optimizer=g.optimizer, conv_math=g.conv_math, train_from=s.train_from,
+                            fc_dropout_keep_prob=getattr(g, "fc_dropout_keep_prob", 0.0), fc_dropout_salt=1 + index)
             self.tower_cfg = cfg
             self.tower_trains = len(frozen_layers(cfg)) < len(dcnn_layers(cfg))     # False: the tower's backward is never called
             self.x_dim, self.max_rows0 = cfg.encode_dim(), seq[0].max_rows
@@ -751,12 +752,15 @@ def model_specs(pipelines, datasets, num_classes):
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
-                 accumulate=1):
+                 accumulate=1, fc_dropout_keep_prob=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
         pipeline (engine.decay_ranges); 0 = off.  accumulate: the most micro-batches one update may sum, train_step(micro=(i, k))
-        (engine.check_accumulate, LRCNEngine.train_step_u8); 1 = off."""
+        (engine.check_accumulate, LRCNEngine.train_step_u8); 1 = off.  fc_dropout_keep_prob: dropout on relu(fc6) / relu(fc7) of every
+        dcnn tower in a training forward (engine.check_fc_dropout), each tower under a salt of its own (1 + its node index: two towers
+        draw different masks at one step; data-parallel ranks are not salted, as with the heads' dropout); 0 = off."""
+        self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
         self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)

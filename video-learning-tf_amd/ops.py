@@ -592,6 +592,28 @@ def dropout_bwd(dy, mask, dx, keep):
     _ffi.call("vl_dropout_bwd", _p(dy), _p(mask), _p(dx), dy.numel(), keep, stream())
 
 
+FC_DROPOUT_GRID_SPAN = 4 * 256 * 4096     # elements one pass of the fc-dropout launches' grid covers (VL_FC_DROPOUT_GRID_CAP)
+
+
+def fc_dropout_fwd(y, keep, seed, salt):
+    """Dropout of a ReLU'd fc output in place, no mask kept (vl_fc_dropout_fwd): element e of y is kept iff the draw of (seed, salt,
+    e) falls below keep, and divided by keep."""
+    _f32(y); _dense(y)
+    _ffi.call("vl_fc_dropout_fwd", _p(y), y.numel(), keep, int(seed), int(salt), stream())
+
+
+def fc_dropout_fwd_st(y, keep, state, salt):
+    """fc_dropout_fwd with the seed formed on the device from the step state's count (vl_fc_dropout_fwd_st)."""
+    _f32(y); _dense(y)
+    _ffi.call("vl_fc_dropout_fwd_st", _p(y), y.numel(), keep, _state(state), int(salt), stream())
+
+
+def relu_dropout_grad(d, y, keep, count=None):
+    """d = y > 0 ? d / keep : 0 in place: ReluGrad and the dropout gradient of an output fc_dropout_fwd dropped (vl_relu_dropout_grad)."""
+    _f32(d, y); _dense(d, y)
+    _ffi.call("vl_relu_dropout_grad", _p(d), _p(y), d.numel() if count is None else int(count), keep, stream())
+
+
 # ---- loss / optimizer ----------------------------------------------------------------------------
 def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None, seq_len=None, T=None):
     """rows: float32 workspace of >= 2*batch elements (per-row losses and hits); without it one workgroup walks the batch.

@@ -56,7 +56,7 @@ def pipeline_net_config(settings, p, dataset):
               lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None),
               momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False,
               weight_decay=settings.train.weight_decay if settings.train else 0.0,
-              accumulate=settings.train.accumulate if settings.train else 1)
+              accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout())
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -341,7 +341,8 @@ def main(init_file, seed=0, device=None):
                              momentum=settings.train.momentum if settings.train else 0.0,
                              nesterov=settings.train.nesterov if settings.train else False,
                              weight_decay=settings.train.weight_decay if settings.train else 0.0,
-                             accumulate=settings.train.accumulate if settings.train else 1)
+                             accumulate=settings.train.accumulate if settings.train else 1,
+                             fc_dropout_keep_prob=settings.get_fc_dropout())
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

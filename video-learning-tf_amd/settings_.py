@@ -22,6 +22,7 @@ class TrainSettings:
     momentum, nesterov = 0.0, False
     weight_decay = 0.0
     accumulate = 1
+    fc_dropout_keep_prob = 0.0
 
 
 class ValSettings:
@@ -42,6 +43,10 @@ class Settings:
 
     def get_dropout(self):
         return self.train.dropout_keep_prob if self.phase == defs.phase.train else 0.0
+
+    def get_fc_dropout(self):
+        """train.fc_dropout_keep_prob (dropout on relu(fc6) / relu(fc7) of the dcnn towers); 0 = off, and outside the train phase."""
+        return self.train.fc_dropout_keep_prob if self.phase == defs.phase.train else 0.0
 
     # ---- pipelines (settings_.py:134-208) ---------------------------------------------------------------
     def read_field(self, config, fieldname, validate=None, required=False, listify=False):
@@ -181,6 +186,18 @@ class Settings:
                     t.accumulate = check_accumulate(None if obj.get("accumulate") == "None" else obj.get("accumulate"))
                 except VltfError as ex:
                     error("train.accumulate: %s" % ex)
+                # dropout on the ReLU'd fc layers of the AlexNet towers (Caffe's drop6 / drop7; engine.check_fc_dropout): absent / None = off
+                from .engine import check_fc_dropout
+                fk = obj.get("fc_dropout_keep_prob")
+                if isinstance(fk, str) and fk != "None":         # a quoted number; nan / inf come as strings too
+                    try:
+                        fk = float(fk)
+                    except ValueError:
+                        pass
+                try:
+                    t.fc_dropout_keep_prob = check_fc_dropout(None if fk == "None" else fk)
+                except VltfError as ex:
+                    error("train.fc_dropout_keep_prob: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
