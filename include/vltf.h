@@ -529,6 +529,40 @@ int vl_l2_regularize(const float* w, float* g, int64_t count, const vl_decay_ran
  * vl_l2_regularize on g, once per update), so the decay enters once however many micro-steps there were. */
 int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode, const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream);
 
+/* ---- per-variable gradient and weight statistics: one segmented, fixed-order reduction over the flat buffers -------------------------------
+ * One launch returns a row of statistics per segment (= per variable), whether the segment is fc6W or a 96-float bias.  READ-ONLY on w
+ * and g.  The segment table obeys the rules of vl_lr_tier: sorted, disjoint, inside [0, count), 1 .. VL_MAX_STAT_SEGMENTS entries, each of
+ * 1 .. 2^32 - 1 elements; anything else is refused on the host with the entry's index in the message.  It is read on the host and travels BY
+ * VALUE in the launch arguments together with each segment's first chunk index, so a captured step needs no device table.  Elements outside
+ * every segment are neither loaded nor stored (they may hold NaN; frozen ranges of g do).
+ * Per element x of w and of g:  finite -> sum += (double)x, sumsq += (double)x * (double)x (the square is exact), min / max;  NaN or +-Inf ->
+ * counted in *_nonfinite and left out of the sums and of min / max.  A denormal is finite and is not zero; g_zero counts +0 and -0.  Every
+ * sum of a segment of N elements is within N 2^-53 sum|term| of the exact sum; min, max and the counts are exact (of +0 and -0 the
+ * minimum is -0 and the maximum +0).
+ * Order: a segment is cut into chunks of VL_STAT_CHUNK elements (chunks never span segments, a segment's last chunk is short).  Stage 1:
+ * one workgroup per chunk finds its segment by a uniform scan of the table and writes one partial row to ws.  The element at index j of its
+ * chunk is added, in order of j, to accumulator j mod 1024 of that chunk, and the 1024 accumulators are reduced in a fixed tree: where a
+ * 16-byte load happens to begin plays no part.  Stage 2: one workgroup per segment reduces the segment's rows in a fixed order into out[s].
+ * So the result is the same bits from run to run and depends on the table and on VL_STAT_CHUNK alone -- not on a grid size, not on the
+ * pointers' alignment; no float atomics.  Interior elements are read as 16-byte loads where w and g agree in 16-byte phase, else by the
+ * same element function through 4-byte loads.  The launch reads w and g once inside the segments: 8 bytes per element.
+ * out: device, [n_segs], every byte overwritten.  ws: device, vl_tensor_stats_ws_bytes(segs, n_segs) bytes (one row per chunk; 0 when the
+ * table would be refused), overwritten; 8-byte aligned like out.  Nothing needs zeroing first. */
+#define VL_MAX_STAT_SEGMENTS 64
+#define VL_STAT_CHUNK 16384
+typedef struct vl_stat_segment {
+    int64_t begin, end;
+} vl_stat_segment;
+typedef struct vl_tensor_stat {
+    double g_sum, g_sumsq, w_sum, w_sumsq;
+    float g_min, g_max, w_min, w_max;
+    uint32_t g_nonfinite, w_nonfinite, g_zero;
+    uint32_t reserved;
+} vl_tensor_stat;
+size_t vl_tensor_stats_ws_bytes(const vl_stat_segment* segs, int n_segs);
+int vl_tensor_stats(const float* w, const float* g, int64_t count, const vl_stat_segment* segs, int n_segs, vl_tensor_stat* out,
+                    void* ws, size_t ws_bytes, vl_stream_t stream);
+
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);
 /* ReluGrad in place: d[i] = y[i] > 0 ? d[i] : 0 (y = the ReLU's forward output, alexnet.py:228,248). */

@@ -104,6 +104,8 @@ SIGNATURES = {
     "vl_momentum_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_l2_regularize": (i32, [p, p, i64, p, i32, p, p, p]),
     "vl_grad_accumulate": (i32, [p, p, i64, i32, p, i32, p]),
+    "vl_tensor_stats_ws_bytes": (sz, [p, i32]),
+    "vl_tensor_stats": (i32, [p, p, i64, p, i32, p, p, sz, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),
@@ -132,6 +134,22 @@ class DecayRange(C.Structure):
 
 
 MAX_DECAY_RANGES = 64     # VL_MAX_DECAY_RANGES
+
+
+class StatSegment(C.Structure):
+    """vl_stat_segment (include/vltf.h)."""
+    _fields_ = [("begin", i64), ("end", i64)]
+
+
+class TensorStat(C.Structure):
+    """vl_tensor_stat (include/vltf.h): 64 bytes, one per segment."""
+    _fields_ = [("g_sum", C.c_double), ("g_sumsq", C.c_double), ("w_sum", C.c_double), ("w_sumsq", C.c_double),
+                ("g_min", f32), ("g_max", f32), ("w_min", f32), ("w_max", f32),
+                ("g_nonfinite", u32), ("w_nonfinite", u32), ("g_zero", u32), ("reserved", u32)]
+
+
+MAX_STAT_SEGMENTS = 64    # VL_MAX_STAT_SEGMENTS
+STAT_CHUNK = 16384        # VL_STAT_CHUNK
 
 
 class VltfError(RuntimeError):

@@ -2529,6 +2529,252 @@ extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode,
     return 0;
 }
 
+// ---- per-variable gradient / weight statistics (vltf.h: vl_tensor_stats) ----------------------------------------------------------------
+// A segmented two-stage reduction in fp64.  The order is a property of the table alone: element j of a chunk goes, in order of j, into
+// accumulator j mod 1024 of its chunk ("slot"), the slots are summed in a fixed tree, the chunk rows of a segment likewise.  A thread
+// reads the 16-byte vectors v = t, t + 256, ... of its chunk counted from the aligned address at or before the chunk's first element,
+// r = 0 .. 3 elements earlier: component c of vector v is element j = 4 v + c - r, so (thread, component) always feeds slot
+// (4 t + c - r) mod 1024 and where the vectors begin changes only WHO holds a slot, never what is added to it or in which order.
+constexpr int STAT_SLOTS = 1024;
+static_assert(sizeof(vl_tensor_stat) == 64, "vl_tensor_stat is 64 bytes");
+static_assert((VL_STAT_CHUNK & (VL_STAT_CHUNK - 1)) == 0 && VL_STAT_CHUNK % STAT_SLOTS == 0, "VL_STAT_CHUNK: a power of two, whole slot rounds");
+
+struct stat_table {
+    vl_stat_segment seg[VL_MAX_STAT_SEGMENTS];
+    int first[VL_MAX_STAT_SEGMENTS + 1];      // a segment's first chunk index; first[n] = the chunks of the whole table
+    int n;
+};
+
+// count < 0: the bound of the buffers is not known (vl_tensor_stats_ws_bytes)
+static int stat_table_make(const char* who, const vl_stat_segment* segs, int n_segs, int64_t count, stat_table* out) {
+    VL_CHECK(segs && n_segs >= 1 && n_segs <= VL_MAX_STAT_SEGMENTS, "%s: 1 .. %d segments, got %d", who, VL_MAX_STAT_SEGMENTS, n_segs);
+    int64_t prev = 0;
+    int chunks = 0;
+    for (int k = 0; k < n_segs; ++k) {
+        const vl_stat_segment& s = segs[k];
+        VL_CHECK(s.begin >= prev && s.end > s.begin && (count < 0 || s.end <= count),
+                 "%s: segment %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)s.begin,
+                 (long long)s.end, (long long)count);
+        VL_CHECK(s.end - s.begin <= 0xFFFFFFFFll, "%s: segment %d has %lld elements, more than 2^32 - 1", who, k, (long long)(s.end - s.begin));
+        out->seg[k] = s;
+        out->first[k] = chunks;
+        chunks += (int)((s.end - s.begin + VL_STAT_CHUNK - 1) / VL_STAT_CHUNK);
+        prev = s.end;
+    }
+    out->first[n_segs] = chunks;
+    out->n = n_segs;
+    return 0;
+}
+
+// floats as ints of the same order, -0 below +0: min / max of the keys are exact and do not depend on the order of the operands
+constexpr int STAT_KEY_PINF = 0x7f800000, STAT_KEY_NINF = (int)0x807fffffu;
+__device__ __forceinline__ int stat_key(float x) {
+    const int k = __float_as_int(x);
+    return k ^ ((k >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float stat_unkey(int k) { return __int_as_float(k ^ ((k >> 31) & 0x7fffffff)); }
+
+struct stat_acc {
+    double d[4];              // g_sum, g_sumsq, w_sum, w_sumsq
+    int mn[2], mx[2];         // keys of g / w min and max
+    uint32_t cnt[3];          // g_nonfinite, w_nonfinite, g_zero
+};
+__device__ __forceinline__ void stat_acc_init(stat_acc& a) {
+    a.d[0] = a.d[1] = a.d[2] = a.d[3] = 0.0;
+    a.mn[0] = a.mn[1] = STAT_KEY_PINF;
+    a.mx[0] = a.mx[1] = STAT_KEY_NINF;
+    a.cnt[0] = a.cnt[1] = a.cnt[2] = 0u;
+}
+
+// one element function for the 4-byte and the 16-byte loads.  Finite, zero and the order keys are read off the bits, so no denormal mode
+// plays a part; a non-finite element adds +0 to the sums and the neutral key to min / max.
+__device__ __forceinline__ void stat_elem(float w, float g, double& gs, double& gq, double& wsum, double& wq, stat_acc& a) {
+    const int gb = __float_as_int(g), wb = __float_as_int(w);
+    const bool gf = (gb & 0x7f800000) != 0x7f800000, wf = (wb & 0x7f800000) != 0x7f800000;
+    const double gd = gf ? (double)g : 0.0, wd = wf ? (double)w : 0.0;
+    gs += gd;
+    gq = __builtin_fma(gd, gd, gq);           // the product of two fp32 values is exact in fp64: one rounding, that of the sum
+    wsum += wd;
+    wq = __builtin_fma(wd, wd, wq);
+    const int gk = stat_key(g), wk = stat_key(w);
+    a.mn[0] = min(a.mn[0], gf ? gk : STAT_KEY_PINF);
+    a.mx[0] = max(a.mx[0], gf ? gk : STAT_KEY_NINF);
+    a.mn[1] = min(a.mn[1], wf ? wk : STAT_KEY_PINF);
+    a.mx[1] = max(a.mx[1], wf ? wk : STAT_KEY_NINF);
+    a.cnt[0] += gf ? 0u : 1u;
+    a.cnt[1] += wf ? 0u : 1u;
+    a.cnt[2] += (gb & 0x7fffffff) == 0 ? 1u : 0u;
+}
+
+// every lane of the block ends with the block's totals: xor butterfly inside a wave, then the four waves in wave order
+__device__ __forceinline__ void stat_block_reduce(stat_acc& a, double* smd /* [16] */, int* smi /* [28] */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a.d[q] += __shfl_xor(a.d[q], o, 64);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            a.mn[q] = min(a.mn[q], __shfl_xor(a.mn[q], o, 64));
+            a.mx[q] = max(a.mx[q], __shfl_xor(a.mx[q], o, 64));
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a.cnt[q] += (uint32_t)__shfl_xor((int)a.cnt[q], o, 64);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+        for (int q = 0; q < 4; ++q) smd[wv * 4 + q] = a.d[q];
+        for (int q = 0; q < 2; ++q) {
+            smi[wv * 7 + q] = a.mn[q];
+            smi[wv * 7 + 2 + q] = a.mx[q];
+        }
+        for (int q = 0; q < 3; ++q) smi[wv * 7 + 4 + q] = (int)a.cnt[q];
+    }
+    __syncthreads();
+    for (int q = 0; q < 4; ++q) a.d[q] = ((smd[q] + smd[4 + q]) + smd[8 + q]) + smd[12 + q];
+    for (int q = 0; q < 2; ++q) {
+        a.mn[q] = min(min(smi[q], smi[7 + q]), min(smi[14 + q], smi[21 + q]));
+        a.mx[q] = max(max(smi[2 + q], smi[9 + q]), max(smi[16 + q], smi[23 + q]));
+    }
+    for (int q = 0; q < 3; ++q) a.cnt[q] = (uint32_t)smi[4 + q] + (uint32_t)smi[11 + q] + (uint32_t)smi[18 + q] + (uint32_t)smi[25 + q];
+    __syncthreads();
+}
+
+__device__ __forceinline__ void stat_row_store(vl_tensor_stat* row, const stat_acc& a) {
+    vl_tensor_stat r;
+    r.g_sum = a.d[0];
+    r.g_sumsq = a.d[1];
+    r.w_sum = a.d[2];
+    r.w_sumsq = a.d[3];
+    r.g_min = stat_unkey(a.mn[0]);
+    r.g_max = stat_unkey(a.mx[0]);
+    r.w_min = stat_unkey(a.mn[1]);
+    r.w_max = stat_unkey(a.mx[1]);
+    r.g_nonfinite = a.cnt[0];
+    r.w_nonfinite = a.cnt[1];
+    r.g_zero = a.cnt[2];
+    r.reserved = 0u;
+    *row = r;
+}
+
+// one workgroup per chunk -> ws[chunk]
+__global__ __launch_bounds__(256) void tensor_stats_stage1(const float* __restrict__ w, const float* __restrict__ g, stat_table st,
+                                                           vl_tensor_stat* __restrict__ ws) {
+    __shared__ double sl[4][STAT_SLOTS];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int s = 0;
+    for (int k = 1; k < st.n; ++k)
+        if (st.first[k] <= b) s = k;
+    const int64_t cb = st.seg[s].begin + (int64_t)(b - st.first[s]) * VL_STAT_CHUNK;
+    const int64_t rest = st.seg[s].end - cb;
+    const int len = rest < VL_STAT_CHUNK ? (int)rest : VL_STAT_CHUNK;
+    const int phase = align_phase(w, g, nullptr, nullptr);
+    const int r = phase < 0 ? 0 : (int)((cb + phase) & 3);
+    const int64_t base = cb - r;              // the element of vector 0, component 0: 16-byte aligned in w and in g when phase >= 0
+    const int nv = (len + r + 3) >> 2;
+    double gs[4] = {0.0, 0.0, 0.0, 0.0}, gq[4] = {0.0, 0.0, 0.0, 0.0}, wsum[4] = {0.0, 0.0, 0.0, 0.0}, wq[4] = {0.0, 0.0, 0.0, 0.0};
+    stat_acc a;
+    stat_acc_init(a);
+    constexpr int U = 4;
+    for (int v0 = t; v0 < nv; v0 += 256 * U) {
+        if (phase >= 0 && 4 * v0 >= r && 4 * (v0 + 256 * (U - 1)) + 4 - r <= len) {      // U whole vectors: every load issued first
+            float4 wv[U], gv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                wv[u] = *reinterpret_cast<const float4*>(w + base + 4 * (int64_t)(v0 + 256 * u));
+                gv[u] = *reinterpret_cast<const float4*>(g + base + 4 * (int64_t)(v0 + 256 * u));
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                stat_elem(wv[u].x, gv[u].x, gs[0], gq[0], wsum[0], wq[0], a);
+                stat_elem(wv[u].y, gv[u].y, gs[1], gq[1], wsum[1], wq[1], a);
+                stat_elem(wv[u].z, gv[u].z, gs[2], gq[2], wsum[2], wq[2], a);
+                stat_elem(wv[u].w, gv[u].w, gs[3], gq[3], wsum[3], wq[3], a);
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int v = v0 + 256 * u;
+            if (v >= nv) break;
+            const int j0 = 4 * v - r;         // the chunk index of component 0
+            const int64_t e = base + 4 * (int64_t)v;
+            if (phase >= 0 && j0 >= 0 && j0 + 4 <= len) {
+                const float4 wv = *reinterpret_cast<const float4*>(w + e), gv = *reinterpret_cast<const float4*>(g + e);
+                stat_elem(wv.x, gv.x, gs[0], gq[0], wsum[0], wq[0], a);
+                stat_elem(wv.y, gv.y, gs[1], gq[1], wsum[1], wq[1], a);
+                stat_elem(wv.z, gv.z, gs[2], gq[2], wsum[2], wq[2], a);
+                stat_elem(wv.w, gv.w, gs[3], gq[3], wsum[3], wq[3], a);
+            } else {                          // the chunk's head or tail, or w and g disagree in phase: only elements of the chunk are addressed
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (j0 + c >= 0 && j0 + c < len) stat_elem(w[e + c], g[e + c], gs[c], gq[c], wsum[c], wq[c], a);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int slot = (4 * t + c - r) & (STAT_SLOTS - 1);
+        sl[0][slot] = gs[c];
+        sl[1][slot] = gq[c];
+        sl[2][slot] = wsum[c];
+        sl[3][slot] = wq[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a.d[q] = ((sl[q][4 * t] + sl[q][4 * t + 1]) + sl[q][4 * t + 2]) + sl[q][4 * t + 3];
+    __syncthreads();
+    stat_block_reduce(a, &sl[0][0], reinterpret_cast<int*>(&sl[1][0]));
+    if (t == 0) stat_row_store(ws + b, a);
+}
+
+// one workgroup per segment: its chunk rows in the order row t, t + 256, ... per thread, then the block's tree -> out[segment]
+__global__ __launch_bounds__(256) void tensor_stats_stage2(const vl_tensor_stat* __restrict__ ws, stat_table st,
+                                                           vl_tensor_stat* __restrict__ out) {
+    __shared__ double smd[16];
+    __shared__ int smi[28];
+    const int s = blockIdx.x;
+    stat_acc a;
+    stat_acc_init(a);
+    for (int i = st.first[s] + (int)threadIdx.x; i < st.first[s + 1]; i += 256) {
+        const vl_tensor_stat r = ws[i];
+        a.d[0] += r.g_sum;
+        a.d[1] += r.g_sumsq;
+        a.d[2] += r.w_sum;
+        a.d[3] += r.w_sumsq;
+        a.mn[0] = min(a.mn[0], stat_key(r.g_min));
+        a.mx[0] = max(a.mx[0], stat_key(r.g_max));
+        a.mn[1] = min(a.mn[1], stat_key(r.w_min));
+        a.mx[1] = max(a.mx[1], stat_key(r.w_max));
+        a.cnt[0] += r.g_nonfinite;
+        a.cnt[1] += r.w_nonfinite;
+        a.cnt[2] += r.g_zero;
+    }
+    stat_block_reduce(a, smd, smi);
+    if (threadIdx.x == 0) stat_row_store(out + s, a);
+}
+
+extern "C" size_t vl_tensor_stats_ws_bytes(const vl_stat_segment* segs, int n_segs) {
+    stat_table st;
+    if (stat_table_make("vl_tensor_stats_ws_bytes", segs, n_segs, -1, &st)) return 0;
+    return (size_t)st.first[st.n] * sizeof(vl_tensor_stat);
+}
+
+extern "C" int vl_tensor_stats(const float* w, const float* g, int64_t count, const vl_stat_segment* segs, int n_segs, vl_tensor_stat* out,
+                               void* ws, size_t ws_bytes, vl_stream_t stream) {
+    VL_CHECK(w && g && out && ws && count > 0, "vl_tensor_stats: bad argument");
+    VL_CHECK((((uintptr_t)w | (uintptr_t)g) & 3) == 0 && (((uintptr_t)out | (uintptr_t)ws) & 7) == 0, "vl_tensor_stats: misaligned pointer");
+    stat_table st;
+    if (int rc = stat_table_make("vl_tensor_stats", segs, n_segs, count, &st)) return rc;
+    const size_t need = (size_t)st.first[st.n] * sizeof(vl_tensor_stat);
+    VL_CHECK(ws_bytes >= need, "vl_tensor_stats: the workspace has %zu bytes, this table needs %zu (vl_tensor_stats_ws_bytes)", ws_bytes, need);
+    hipLaunchKernelGGL(tensor_stats_stage1, dim3(st.first[st.n]), dim3(256), 0, (hipStream_t)stream, w, g, st,
+                       reinterpret_cast<vl_tensor_stat*>(ws));
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tensor_stats_stage2, dim3(st.n), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const vl_tensor_stat*>(ws), st, out);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void fill_kernel(float* __restrict__ p, int64_t count, float value) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) p[i] = value;
 }

@@ -12,6 +12,7 @@ Activations are NCHW; parameters keep the reference's layouts and TF variable na
 classifier -> fc -> conv5..conv1, i.e. the order backward produces gradients, so the
 data-parallel all-reduce of the first (large: fc6 = 85 % of bytes) bucket overlaps the conv backward.
 """
+import collections
 import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -64,6 +65,7 @@ class NetConfig:
     accumulate: int = 1                         # train.accumulate: most micro-batches one update may sum (train_step_*(micro=(i, k))); 1 = off
     fc_dropout_keep_prob: float = 0.0           # train.fc_dropout_keep_prob: dropout on relu(fc6) / relu(fc7) (Caffe's drop6 / drop7); 0 = off
     fc_dropout_salt: int = 0                    # which mask stream this tower draws from (fc_dropout_salt): a GraphEngine numbers its towers
+    tensor_stats_interval: int = 0              # logging.tensor_stats_interval: per-variable statistics every N updates (stat_segments); 0 = off
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -231,6 +233,16 @@ def check_accumulate(accumulate):
     return int(accumulate)
 
 
+def check_tensor_stats_interval(interval):
+    """Updates between two per-variable statistics launches as an int, None or 0 read as 0 (off).  Refused: bools, strings, floats,
+    negative values -- anything but a whole number >= 1."""
+    if interval is None:
+        return 0
+    if isinstance(interval, (bool, np.bool_)) or not isinstance(interval, (int, np.integer)) or int(interval) < 0:
+        raise VltfError("tensor_stats_interval must be an integer >= 1 (None or 0 = off), got %r" % (interval,))
+    return int(interval)
+
+
 class MicroSequence:
     """The order of the micro-steps of accumulated updates, shared by both engines: train_step_*(micro=(i, k)) calls must come as
     (0, k), (1, k) .. (k - 1, k) with k <= limit; micro=None is the plain step and stands alone.  Anything else is refused, and a
@@ -309,6 +321,54 @@ def decay_ranges(specs, plan, weight_decay):
         raise VltfError("this model needs %d weight-decay ranges (runs of weights and of biases in the flat parameter buffer, frozen "
                         "ranges between them); the regulariser kernel takes %d" % (len(out), MAX_DECAY_RANGES))
     return out
+
+
+def stat_segments(specs, plan):
+    """[(name, begin, end)] for ops.tensor_stats: every variable of specs that lies inside plan.tiers, in flat order, one segment per
+    variable, nothing merged.  Frozen variables lie outside plan.tiers and are absent: their range of g is never read.  Host only."""
+    out, off = [], 0
+    for name, shp in specs:
+        n = int(np.prod(shp))
+        if n > 0 and any(lo <= off and off + n <= hi for lo, hi, _ in plan.tiers):
+            out.append((name, off, off + n))
+        off += n
+    return out
+
+
+def clip_scale_of(sumsq, clip_norm):
+    """The factor the update applies to the gradient: clip_norm / max(sqrt(sumsq), clip_norm), or 1 without a clip."""
+    if not clip_norm or clip_norm <= 0.0:
+        return 1.0
+    return float(clip_norm) / max(math.sqrt(sumsq), float(clip_norm))
+
+
+def tensor_stats_report(segments, rows, tiers, lr, clip_norm, sumsq):
+    """(OrderedDict {name: {...}}, grads_norm_mean) from the rows of ops.tensor_stats (ops.STAT_DTYPE records or mappings with those
+    fields), one per entry of segments [(name, begin, end)].  tiers: plan.tiers, whose factor is the variable's lr_mult; lr, clip_norm
+    and sumsq (the global sum of squares the update reads) are those of the step.  mean and std are over the finite elements; std =
+    sqrt(max(sumsq / n - mean^2, 0)).  sgd_update_ratio = lr * lr_mult * clip_scale * grad_norm / weight_norm is the plain-SGD figure
+    whatever the optimizer, None when weight_norm is 0.  grads_norm_mean is the mean over the variables of clip_scale * grad_norm (the
+    reference's `grads_norm`, train.py:215-222, taken of the clipped gradients).  Host only."""
+    scale = clip_scale_of(sumsq, clip_norm)
+    out, norms = collections.OrderedDict(), []
+    for (name, lo, hi), r in zip(segments, rows):
+        n = hi - lo
+        mult = next((float(m) for a, b, m in tiers if a <= lo and hi <= b), 1.0)
+        d = {}
+        for key, p, bad in (("grad", "g", int(r["g_nonfinite"])), ("weight", "w", int(r["w_nonfinite"]))):
+            s, q, fin = float(r[p + "_sum"]), float(r[p + "_sumsq"]), n - bad
+            mean = s / fin if fin else float("nan")
+            d[key + "_norm"] = math.sqrt(q)
+            d[key + "_mean"] = mean
+            d[key + "_std"] = math.sqrt(max(q / fin - mean * mean, 0.0)) if fin else float("nan")
+            d[key + "_min"], d[key + "_max"] = float(r[p + "_min"]), float(r[p + "_max"])
+            d[key + "_nonfinite"] = bad
+        d["grad_zero_fraction"] = int(r["g_zero"]) / n
+        d["lr_mult"] = mult
+        d["sgd_update_ratio"] = lr * mult * scale * d["grad_norm"] / d["weight_norm"] if d["weight_norm"] > 0.0 else None
+        out[name] = d
+        norms.append(scale * d["grad_norm"])
+    return out, (sum(norms) / len(norms) if norms else float("nan"))
 
 
 def base_grad_chunks(cfg: NetConfig):
@@ -429,7 +489,8 @@ class LRCNEngine:
     workspace of their own (lstm_ws_graph) whose tag stream the engine keeps: graph_tag_next, advanced by the graph's span per
     replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe.
     With NetConfig.accumulate > 1 the key also holds the micro-step's role (first / middle / last / single) and k: three launch sequences,
-    three graphs; the state's count is then the dropout draw index and Adam's step size follows step_count (ops.step_state_set_micro)."""
+    three graphs; the state's count is then the dropout draw index and Adam's step size follows step_count (ops.step_state_set_micro).
+    With NetConfig.tensor_stats_interval > 0 the key also holds whether the update is a stats step (_stats_due): two launch sequences."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -670,6 +731,10 @@ class LRCNEngine:
             self.decay = decay_ranges(self.specs, self.plan, self.weight_decay)
             self.ss2 = torch.zeros(2, device=dev)
             self.ss = self.ss2[:1]
+        if check_tensor_stats_interval(cfg.tensor_stats_interval) > 0 and cfg.classifier == "none":
+            raise VltfError("a feature pipeline (classifier none) has no step of its own: give tensor_stats_interval to the GraphEngine "
+                            "it trains in")
+        self._stats_setup(cfg.tensor_stats_interval)
         self._skip = torch.zeros(1, dtype=torch.int32, device=dev)      # ops.step_guard: the optimizer launch's skip word
         self.probe, self.probe_events = None, []
         self._resizers = {}
@@ -732,6 +797,58 @@ class LRCNEngine:
         torch.cuda.synchronize(self.dev)
         frozen = set(self.plan.frozen)                  # their range of g is never written: it holds nothing to hand out
         return {n: self.G[n].detach().cpu().numpy().copy() for n, _ in self.specs if n not in frozen}
+
+    # ---- per-variable statistics (tensor_stats_interval; shared with GraphEngine) --------------------------------------------------------
+    def _stats_setup(self, interval):
+        """Off (None / 0, or an engine that does not train): nothing is allocated and no launch, graph key or result key changes.  On:
+        one segment per trained variable (stat_segments), the rows and the chunk workspace of ops.tensor_stats and a word that keeps the
+        stats step's global sum of squares -- allocated here, never inside a capture."""
+        self.tensor_stats_interval = check_tensor_stats_interval(interval)
+        self.stat_segs, self._stats_meta, self._stats_last = None, None, None
+        if self.tensor_stats_interval > 0 and self.training:
+            self.stat_segs = stat_segments(self.specs, self.plan)
+            self.stat_out = torch.empty(len(self.stat_segs) * ops.STAT_ROW_BYTES, dtype=torch.uint8, device=self.dev)
+            self.stat_ws = torch.empty(ops.tensor_stats_ws_bytes(self.stat_segs), dtype=torch.uint8, device=self.dev)
+            self.stat_ss = torch.zeros(1, device=self.dev)
+
+    def _stats_due(self):
+        """The update about to be applied (0-based index step_count) is a stats step."""
+        return self.stat_segs is not None and self.step_count % self.tensor_stats_interval == 0
+
+    def _stats_launch(self, lr, clip_norm):
+        """_finish_step, between the norm and the update: g is what the optimizer is about to consume (reduced over the ranks, summed over
+        the micro-steps, regularised, not yet clipped), w what the forward pass used.  Read-only, so the skip word does not concern it."""
+        ops.tensor_stats(self.w, self.g, self.stat_segs, self.stat_out, self.stat_ws)
+        self.stat_ss.copy_(self.ss)               # the next step's norm overwrites self.ss; a caller with fetch=False may look later
+        self._stats_note(lr, clip_norm)
+
+    def _stats_note(self, lr, clip_norm):
+        """Host side of a stats step: rows wait on the device for _stats_collect (a replayed step calls this with the replay's lr)."""
+        self._stats_meta = dict(update=self.step_count, lr=float(lr), clip_norm=float(clip_norm or 0.0))
+
+    def _stats_collect(self):
+        """Reads the rows of the last stats step (the caller has synchronised) and derives the report."""
+        meta, self._stats_meta = self._stats_meta, None
+        rows = ops.stat_rows(self.stat_out, len(self.stat_segs))
+        ss = float(self.stat_ss.item())
+        stats, mean = tensor_stats_report(self.stat_segs, rows, self.plan.tiers, meta["lr"], meta["clip_norm"], ss)
+        self._stats_last = dict(update=meta["update"], tensor_stats=stats, grads_norm_mean=mean)
+        return self._stats_last
+
+    def _stats_result(self, out):
+        """_fetch: the step just finished was a stats step -> its result gains tensor_stats and grads_norm_mean."""
+        if self._stats_meta is not None and self._stats_meta["update"] == self.step_count - 1:
+            st = self._stats_collect()
+            out["tensor_stats"], out["grads_norm_mean"] = st["tensor_stats"], st["grads_norm_mean"]
+        return out
+
+    def tensor_stats(self):
+        """The most recent stats step's {variable name: {...}} (tensor_stats_report), or None.  After a step with fetch=False it
+        synchronises first."""
+        if self._stats_meta is not None:
+            torch.cuda.synchronize(self.dev)
+            self._stats_collect()
+        return None if self._stats_last is None else self._stats_last["tensor_stats"]
 
     # ---- optimizer state (what tf.train.Saver() keeps besides the weights, feeder.py:201: Adam slots + beta powers) -------
     OPT_PREFIX = "__optimizer__/"
@@ -1406,6 +1523,8 @@ class LRCNEngine:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
+        if self._stats_due():
+            self._stats_launch(lr, clip_norm)
         self.step_count += 1
         # a step whose LSTM cluster launch timed out must not reach the weights -- also with fetch=False, where the host reads the
         # status only later: the optimizer launch drops the update on the device (ops.step_guard), check_status raises at the next fetch
@@ -1448,7 +1567,7 @@ class LRCNEngine:
                "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
         if self.ss2 is not None:                  # the regulariser at the weights the forward pass used; `loss` stays the data loss
             out["reg_loss"] = float(self.ss2[1].item())
-        return out
+        return self._stats_result(out)
 
     def _rows_for(self, b, n):
         if self.cfg.classifier == "lstm":
@@ -1493,6 +1612,10 @@ class LRCNEngine:
                global_rows if train else None, self.cfg.dropout_keep_prob if train else None)
         if train and self.accumulate > 1:     # first / middle / last micro-steps are different launch sequences: a graph each
             key += MicroSequence.role(mi)
+        final = mi is None or mi[0] == mi[1] - 1
+        stats = train and final and self._stats_due()
+        if train and self.stat_segs is not None:  # a stats step and a plain step are different launch sequences too
+            key += (stats,)
         g = self._graphs.get(key)
         if g is None:
             if key not in self._graph_warm:   # warm-up: one-time set-up (function attributes, tables, resizers, side-stream buffers)
@@ -1522,6 +1645,8 @@ class LRCNEngine:
         total_rows = self.micro.add_rows(mi, g["rows"])
         if mi is not None and mi[0] < mi[1] - 1:
             return True, self._fetch(total_rows, fetch, partial=True)
+        if stats:
+            self._stats_note(lr, clip_norm)
         self.step_count += 1
         return True, self._fetch(total_rows, fetch)
 

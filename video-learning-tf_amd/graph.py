@@ -752,14 +752,16 @@ def model_specs(pipelines, datasets, num_classes):
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
-                 accumulate=1, fc_dropout_keep_prob=0.0):
+                 accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
         pipeline (engine.decay_ranges); 0 = off.  accumulate: the most micro-batches one update may sum, train_step(micro=(i, k))
         (engine.check_accumulate, LRCNEngine.train_step_u8); 1 = off.  fc_dropout_keep_prob: dropout on relu(fc6) / relu(fc7) of every
         dcnn tower in a training forward (engine.check_fc_dropout), each tower under a salt of its own (1 + its node index: two towers
-        draw different masks at one step; data-parallel ranks are not salted, as with the heads' dropout); 0 = off."""
+        draw different masks at one step; data-parallel ranks are not salted, as with the heads' dropout); 0 = off.
+        tensor_stats_interval: per-variable gradient / weight statistics every N updates (engine.stat_segments over this engine's
+        variable list, `<pipeline>/<tf name>` in a scoped model; LRCNEngine._stats_launch); None / 0 = off."""
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
@@ -771,6 +773,7 @@ class GraphEngine:
         self._plan(pipelines, datasets, num_classes, optimizer, dropout_keep_prob, conv_math, lr_mult)
         self.decay = decay_ranges(self.specs, self.plan, self.weight_decay) if self.weight_decay > 0.0 and training else None
         self._allocate()
+        self._stats_setup(tensor_stats_interval)
 
     def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
         """The graph, its variable list and its training plan (self.nodes, self.specs, self.plan): host logic only, no device
@@ -938,6 +941,9 @@ class GraphEngine:
 
     _draw_index = LRCNEngine._draw_index
     _acc_tiers = LRCNEngine._acc_tiers
+    _stats_setup, _stats_due, _stats_launch, _stats_note = (LRCNEngine._stats_setup, LRCNEngine._stats_due, LRCNEngine._stats_launch,
+                                                            LRCNEngine._stats_note)
+    _stats_collect, _stats_result, tensor_stats = LRCNEngine._stats_collect, LRCNEngine._stats_result, LRCNEngine.tensor_stats
 
     def logits_host(self):
         self._sync()
@@ -1113,6 +1119,8 @@ class GraphEngine:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
+        if self._stats_due():
+            self._stats_launch(lr, clip_norm)
         self.step_count += 1
         skip = ops.step_guard(self._skip, *[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])   # LRCNEngine._finish_step
         if tiers is not None and self.optimizer == "adam":
@@ -1141,7 +1149,7 @@ class GraphEngine:
                "grad_norm": math.sqrt(float(self.ss.item())), "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
         if self.ss2 is not None:
             out["reg_loss"] = float(self.ss2[1].item())
-        return out
+        return self._stats_result(out)
 
 
 class _TowerReduce:

@@ -2,6 +2,7 @@
 only: every wrapper passes ``data_ptr()`` and the current HIP stream; no torch math runs here."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _ffi
@@ -732,6 +733,83 @@ def l2_regularize(w, g, ranges, out, ws):
     for k, (lo, hi, decay) in enumerate(ranges):
         arr[k].begin, arr[k].end, arr[k].decay = int(lo), int(hi), float(decay)
     _ffi.call("vl_l2_regularize", _p(w), _p(g), w.numel(), arr, len(ranges), _p(out), _p(ws), stream())
+
+
+# ---- per-variable statistics (vltf.h: vl_tensor_stats) ------------------------------------------------------------------------------
+STAT_CHUNK, MAX_STAT_SEGMENTS = _ffi.STAT_CHUNK, _ffi.MAX_STAT_SEGMENTS
+STAT_ROW_BYTES = 64
+# a vl_tensor_stat row as numpy reads it from the bytes of `out`
+STAT_DTYPE = np.dtype([("g_sum", "<f8"), ("g_sumsq", "<f8"), ("w_sum", "<f8"), ("w_sumsq", "<f8"),
+                       ("g_min", "<f4"), ("g_max", "<f4"), ("w_min", "<f4"), ("w_max", "<f4"),
+                       ("g_nonfinite", "<u4"), ("w_nonfinite", "<u4"), ("g_zero", "<u4"), ("reserved", "<u4")])
+
+
+def _stat_segments(segments):
+    """[(begin, end)] or [(name, begin, end)] -> [(begin, end)]."""
+    return [(int(s[-2]), int(s[-1])) for s in segments]
+
+
+def stat_chunk_plan(segments):
+    """(first chunk index of every segment, chunks of the table): a segment is cut into chunks of STAT_CHUNK elements, the last one
+    short, and chunks never span segments.  Host only; the library derives the same plan from the table it is handed."""
+    first, chunks = [], 0
+    for lo, hi in _stat_segments(segments):
+        first.append(chunks)
+        chunks += -(-(hi - lo) // STAT_CHUNK)
+    return first, chunks
+
+
+def _stat_slices(segments):
+    segs = _stat_segments(segments)
+    if not segs:
+        raise _ffi.VltfError("tensor_stats: the segment table is empty")
+    return [segs[i:i + MAX_STAT_SEGMENTS] for i in range(0, len(segs), MAX_STAT_SEGMENTS)]
+
+
+def _stat_array(segs):
+    arr = (_ffi.StatSegment * len(segs))()
+    for k, (lo, hi) in enumerate(segs):
+        arr[k].begin, arr[k].end = lo, hi
+    return arr
+
+
+def tensor_stats_ws_bytes(segments):
+    """Bytes of workspace tensor_stats needs for this table: the largest requirement over its slices of MAX_STAT_SEGMENTS entries.
+    Host only.  A table the library refuses raises."""
+    need = 0
+    for segs in _stat_slices(segments):
+        n = int(_ffi.lib().vl_tensor_stats_ws_bytes(_stat_array(segs), len(segs)))
+        if n == 0:
+            raise _ffi.VltfError("tensor_stats_ws_bytes: %s" % (_ffi.lib().vl_last_error() or b"bad segment table").decode())
+        need = max(need, n)
+    return need
+
+
+def tensor_stats(w, g, segments, out, ws):
+    """One row of statistics per segment of the flat buffers w and g (vltf.h: vl_tensor_stats); read-only on both.  segments =
+    [(begin, end)] or [(name, begin, end)], any number: ceil(n / MAX_STAT_SEGMENTS) launches over consecutive slices of the table and
+    of out.  out: uint8 device tensor of STAT_ROW_BYTES per segment (stat_rows reads it), ws: uint8 device tensor of
+    tensor_stats_ws_bytes(segments); both are overwritten, neither needs zeroing."""
+    _f32(w, g)
+    if g.numel() != w.numel():
+        raise _ffi.VltfError("tensor_stats: w and g must have one element count")
+    slices = _stat_slices(segments)
+    total = sum(len(s) for s in slices)
+    for t, what in ((out, "out"), (ws, "ws")):
+        if t is None or not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise _ffi.VltfError("tensor_stats: %s must be a contiguous CUDA/HIP uint8 tensor" % what)
+    if out.numel() < total * STAT_ROW_BYTES:
+        raise _ffi.VltfError("tensor_stats: out needs %d bytes (%d per segment), has %d" % (total * STAT_ROW_BYTES, STAT_ROW_BYTES, out.numel()))
+    done = 0
+    for segs in slices:
+        _ffi.call("vl_tensor_stats", _p(w), _p(g), w.numel(), _stat_array(segs), len(segs), out.data_ptr() + done * STAT_ROW_BYTES, _p(ws),
+                  ws.numel(), stream())
+        done += len(segs)
+
+
+def stat_rows(out, n):
+    """The first n rows of a tensor_stats `out` on the host, as a numpy array of STAT_DTYPE (synchronises through the copy)."""
+    return out[:n * STAT_ROW_BYTES].cpu().numpy().view(STAT_DTYPE).copy()
 
 
 ACC_STORE, ACC_ADD, ACC_FINAL = 0, 1, 2

@@ -56,7 +56,8 @@ def pipeline_net_config(settings, p, dataset):
               lr_mult=settings.train.lr_mult if settings.train else None, train_from=getattr(p, "train_from", None),
               momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False,
               weight_decay=settings.train.weight_decay if settings.train else 0.0,
-              accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout())
+              accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout(),
+              tensor_stats_interval=settings.get_tensor_stats_interval())
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -214,6 +215,8 @@ def do_train(settings, train, feeder, engine):
             nats = batch_loss / math.log(settings.num_classes)
             # (weight decay: `batch loss` stays the data loss, the lambda-weighted L2 term is logged beside it)
             reg = "+ L2 regulariser : %2.6f" % train.last["reg_loss"] if "reg_loss" in train.last else ""
+            if "grads_norm_mean" in train.last:      # a stats step (logging.tensor_stats_interval): the reference's `grads_norm` summary
+                reg += " gradient norm : %.8g, mean per variable : %.8g" % (train.last["grad_norm"], train.last["grads_norm_mean"])
             info("Learning rate %2.8f, global step: %d, batch loss/nats : %2.5f / %2.3f %s" %
                  (learning_rate, settings.global_step, batch_loss, nats, reg))
             info("Dataset global step %d, epoch index %d, batch sizes %s, batch index train %d" %
@@ -342,7 +345,8 @@ def main(init_file, seed=0, device=None):
                              nesterov=settings.train.nesterov if settings.train else False,
                              weight_decay=settings.train.weight_decay if settings.train else 0.0,
                              accumulate=settings.train.accumulate if settings.train else 1,
-                             fc_dropout_keep_prob=settings.get_fc_dropout())
+                             fc_dropout_keep_prob=settings.get_fc_dropout(),
+                             tensor_stats_interval=settings.get_tensor_stats_interval())
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

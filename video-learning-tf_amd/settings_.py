@@ -33,6 +33,7 @@ class ValSettings:
 class Settings:
     def __init__(self):
         self.run_id, self.resume_file, self.run_folder = "", None, None
+        self.tensor_stats_interval = 0
         self.global_step = 0
         self.feeder = None
         self.pipelines, self.pipeline_names = {}, []
@@ -47,6 +48,10 @@ class Settings:
     def get_fc_dropout(self):
         """train.fc_dropout_keep_prob (dropout on relu(fc6) / relu(fc7) of the dcnn towers); 0 = off, and outside the train phase."""
         return self.train.fc_dropout_keep_prob if self.phase == defs.phase.train else 0.0
+
+    def get_tensor_stats_interval(self):
+        """logging.tensor_stats_interval (per-variable gradient / weight statistics every N updates); 0 = off, and outside the train phase."""
+        return self.tensor_stats_interval if self.phase == defs.phase.train else 0
 
     # ---- pipelines (settings_.py:134-208) ---------------------------------------------------------------
     def read_field(self, config, fieldname, validate=None, required=False, listify=False):
@@ -116,6 +121,23 @@ class Settings:
             error(str(ex))
         return str(layer)
 
+    @staticmethod
+    def read_tensor_stats_interval(lg):
+        """`logging: tensor_stats_interval: N` (this project's extension of the logging block, next to the reference's print_tensors /
+        tensorboard_folder): per-variable statistics every N updates (engine.stat_segments).  Absent / None / 0 = off; a quoted number
+        is read as the number."""
+        from .engine import VltfError, check_tensor_stats_interval
+        n = lg.get("tensor_stats_interval")
+        if isinstance(n, str) and n != "None":
+            try:
+                n = int(n)
+            except ValueError:
+                pass
+        try:
+            return check_tensor_stats_interval(None if n == "None" else n)
+        except VltfError as ex:
+            error("logging.tensor_stats_interval: %s" % ex)
+
     # ---- run block (settings_.py:210-366) -------------------------------------------------------------------
     def read_config(self, config, init_file):
         self.resume_file = config.get("resume_file")
@@ -135,6 +157,7 @@ class Settings:
         self.tensorboard_folder = lg.get("tensorboard_folder", "tensorboard")
         self.print_tensors = lg.get("print_tensors", False)
         self.configure_logging()
+        self.tensor_stats_interval = self.read_tensor_stats_interval(lg)
 
         for pipeline in config["network"]["pipelines"]:
             pname, content = list(pipeline.items())[0]

@@ -1,4 +1,5 @@
 """Train: learning-rate table and the per-step call with the reference's surface (train.py:50-149, 199-222)."""
+import json
 import math
 import os
 
@@ -6,7 +7,7 @@ import numpy as np
 import torch
 
 from .defs_ import defs
-from .utils_ import error, info
+from .utils_ import error, info, warning
 
 
 def precompute_learning_rates(settings, num_batches):
@@ -58,6 +59,54 @@ def accumulate_groups(num_batches, k, start_batch=0):
     return [(first, min(first + k, num_batches) - 1) for first in range(start_batch, num_batches, k)]
 
 
+def json_safe(v):
+    """v with every non-finite float replaced by the string "nan" / "inf" / "-inf", so that json.dumps(.., allow_nan=False) takes it."""
+    if isinstance(v, dict):
+        return {k: json_safe(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [json_safe(x) for x in v]
+    if isinstance(v, (float, np.floating)):
+        v = float(v)
+        return v if math.isfinite(v) else ("nan" if v != v else "inf" if v > 0 else "-inf")
+    if isinstance(v, np.integer):
+        return int(v)
+    return v
+
+
+def tensor_stats_lines(stats):
+    """(info line, warning line or None) for one stats step: the variables with the largest and the smallest sgd_update_ratio, and
+    the variables that hold NaN / Inf in their gradient or their weights."""
+    rated = [(d["sgd_update_ratio"], n) for n, d in stats.items() if d["sgd_update_ratio"] is not None and math.isfinite(d["sgd_update_ratio"])]
+    line = "Tensor statistics over %d variables: no update-to-weight ratio is defined" % len(stats)
+    if rated:
+        hi, lo = max(rated), min(rated)
+        line = "Tensor statistics over %d variables: update / weight norm largest %.3e [%s], smallest %.3e [%s]" % (
+            len(stats), hi[0], hi[1], lo[0], lo[1])
+    bad = ["%s (gradient %d, weights %d)" % (n, d["grad_nonfinite"], d["weight_nonfinite"]) for n, d in stats.items()
+           if d["grad_nonfinite"] > 0 or d["weight_nonfinite"] > 0]
+    return line, ("Non-finite elements in: " + ", ".join(bad)) if bad else None
+
+
+class TensorStatsLog:
+    """<run_folder>/<run_id>_tensor_stats.jsonl: one strict-JSON line per stats step, appended (a resumed run goes on in the file it
+    finds).  Rank 0 owns the file like the run's log; the other ranks write nothing."""
+
+    def __init__(self, run_folder, run_id, rank=0):
+        self.path = os.path.join(run_folder, run_id + "_tensor_stats.jsonl") if rank == 0 else None
+
+    def write(self, global_step, update, lr, clip_norm, out):
+        """out: the result of a stats step (it holds tensor_stats).  Returns the record, or None on a rank that does not write."""
+        if self.path is None:
+            return None
+        from .engine import clip_scale_of
+        rec = {"global_step": int(global_step), "update": int(update), "lr": float(lr),
+               "clip_scale": clip_scale_of(out["grad_norm"] ** 2, clip_norm), "grad_norm": out["grad_norm"],
+               "grads_norm_mean": out["grads_norm_mean"], "vars": out["tensor_stats"]}
+        with open(self.path, "a") as f:
+            f.write(json.dumps(json_safe(rec), allow_nan=False) + "\n")
+        return rec
+
+
 class Train:
     """train.py:112-149: owns the LR table and global_step; run_step is the train sess.run.
     train.accumulate k > 1: the batches of an epoch go to the engine in groups (accumulate_groups) as the micro-steps of one update.
@@ -71,6 +120,21 @@ class Train:
         self.accumulate = int(getattr(settings.train, "accumulate", 1) or 1)
         self._group, self._group_clips = None, 0
         self.group_done = True                  # the last run_step closed an update: a checkpoint may be written
+        # per-variable statistics (logging.tensor_stats_interval): intervals count UPDATES (the engine's step_count), the line carries the
+        # workflow's global_step, which counts batches
+        self.stats_log = None
+        if getattr(engine, "tensor_stats_interval", 0) > 0:
+            self.stats_log = TensorStatsLog(settings.run_folder, settings.run_id, int(os.environ.get("RANK", "0")))
+
+    def _stats_step(self, out, lr):
+        """After a step: a stats step's result goes to the JSONL file and to the log."""
+        if self.stats_log is None or "tensor_stats" not in out:
+            return
+        self.stats_log.write(self.global_step, self.engine.step_count - 1, lr, self.clip_norm, out)
+        line, bad = tensor_stats_lines(out["tensor_stats"])
+        info(line)
+        if bad:
+            warning(bad)
 
     def _micro(self, fdict):
         """-> (micro, clips of the whole group over all ranks) of the batch in fdict; (None, None) without accumulation.  The group's
@@ -131,6 +195,7 @@ class Train:
             out = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
         self.global_step += 1
         self.last = out
+        self._stats_step(out, lr)
         return out["loss"], lr, self.global_step
 
     def run_step_graph(self, fdict, others):
@@ -166,4 +231,5 @@ class Train:
             out = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
         self.global_step += 1
         self.last = out
+        self._stats_step(out, lr)
         return out["loss"], lr, self.global_step
