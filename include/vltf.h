@@ -41,7 +41,8 @@ typedef struct vl_step_state {
     float lr;              /* learning rate */
     uint32_t tag_origin;   /* origin of the LSTM exchange tags of vl_lstm_seq_*_st */
     float adam_lr;         /* Adam's bias-corrected step size for count step + 1 (written by vl_step_state_set, see there) */
-    uint32_t reserved[3];
+    float ema_rate;        /* 1 - decay of this update's weight average (written by vl_step_state_set_ema alone, see vl_ema_update) */
+    uint32_t reserved[2];
 } vl_step_state;
 
 const char* vl_last_error(void);
@@ -434,6 +435,9 @@ int vl_step_state_set(vl_step_state* state, int64_t step, float lr, uint32_t tag
  * adam_lr comes from update_step by the code above.  vl_step_state_set(s, step, ...) is vl_step_state_set_micro(s, step, step, ...). */
 int vl_step_state_set_micro(vl_step_state* state, int64_t update_step, int64_t draw_step, float lr, uint32_t tag_origin,
                             vl_stream_t stream);
+/* One single-lane launch that writes state->ema_rate and nothing else (vl_step_state_set and _set_micro never touch that field).
+ * 0 < rate <= 1, finite. */
+int vl_step_state_set_ema(vl_step_state* state, float rate, vl_stream_t stream);
 /* vl_sgd_apply with lr = state->lr; vl_adam_apply with the step size state->adam_lr (= count state->step + 1). */
 int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
                     float gscale, const uint32_t* skip, vl_stream_t stream);
@@ -528,6 +532,26 @@ int vl_l2_regularize(const float* w, float* g, int64_t count, const vl_decay_ran
  * This is the accumulating caller vl_l2_regularize warns about: the engines regularise only the FINAL sum (mode 2 first, then
  * vl_l2_regularize on g, once per update), so the decay enters once however many micro-steps there were. */
 int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode, const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream);
+
+/* ---- exponential moving average of the weights: tf.train.ExponentialMovingAverage's shadow variables, one ranged launch ------------------
+ * shadow -= (1 - decay) * (shadow - w), restated with rate = 1 - decay so that nothing cancels near decay = 1.  Per element inside a range,
+ * two fp32 roundings in this order (no contraction is left to the compiler, and the scalar head / tail and the 16-byte interior share the
+ * element function, so an element's bits do not depend on which loop reached it):
+ *     d  = w - s
+ *     s' = fma(rate, d, s)
+ * The range table obeys the rules of vl_lr_tier (sorted, disjoint, inside [0, count), 1 .. VL_MAX_LR_TIERS entries; lr_mult must be valid
+ * and is ignored, as in vl_grad_accumulate); ranges == NULL && n_ranges == 0 is the full range.  It travels BY VALUE in the launch
+ * arguments.  Elements outside every range are neither loaded nor stored, in shadow and in w alike (they may hold NaN).  shadow and w that
+ * disagree in 16-byte phase take the scalar loops.  skip: as vl_sgd_apply -- when *skip != 0 at execution time the launch changes nothing.
+ * One launch, the grid of vl_sgd_apply; per element in range it moves 3 floats (reads w, shadow; writes shadow): vl_sgd_apply's traffic.
+ * Refused on the host: a null shadow or w, count <= 0, a rate outside (0, 1] or not finite, a bad table.
+ * vl_ema_update_st: rate = state->ema_rate, written by vl_step_state_set_ema.  The rate is NOT derived from state->step on the device:
+ * under accumulation that field holds the draw step, not the update count, and the warm-up rate max(1 - decay, 9 / (10 + n)) is computed
+ * on the host by one function for the eager and the replayed form, which therefore agree bit for bit (as adam_lr does). */
+int vl_ema_update(float* shadow, const float* w, int64_t count, float rate, const uint32_t* skip, const vl_lr_tier* ranges,
+                  int n_ranges, vl_stream_t stream);
+int vl_ema_update_st(float* shadow, const float* w, int64_t count, const vl_step_state* state, const uint32_t* skip,
+                     const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream);
 
 /* ---- per-variable gradient and weight statistics: one segmented, fixed-order reduction over the flat buffers -------------------------------
  * One launch returns a row of statistics per segment (= per variable), whether the segment is fc6W or a 96-float bias.  READ-ONLY on w

@@ -93,6 +93,7 @@ SIGNATURES = {
     "vl_step_state_bytes": (sz, []),
     "vl_step_state_set": (i32, [p, i64, f32, u32, p]),
     "vl_step_state_set_micro": (i32, [p, i64, i64, f32, u32, p]),
+    "vl_step_state_set_ema": (i32, [p, f32, p]),
     "vl_sgd_apply_st": (i32, [p, p, i64, p, f32, p, f32, p, p]),
     "vl_adam_apply_st": (i32, [p, p, p, p, i64, p, f32, p, f32, p, p]),
     "vl_sgd_apply_tiers": (i32, [p, p, i64, f32, f32, p, f32, p, p, i32, p]),
@@ -104,6 +105,8 @@ SIGNATURES = {
     "vl_momentum_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p]),
     "vl_l2_regularize": (i32, [p, p, i64, p, i32, p, p, p]),
     "vl_grad_accumulate": (i32, [p, p, i64, i32, p, i32, p]),
+    "vl_ema_update": (i32, [p, p, i64, f32, p, p, i32, p]),
+    "vl_ema_update_st": (i32, [p, p, i64, p, p, p, i32, p]),
     "vl_tensor_stats_ws_bytes": (sz, [p, i32]),
     "vl_tensor_stats": (i32, [p, p, i64, p, i32, p, p, sz, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
@@ -126,6 +129,11 @@ class LrTier(C.Structure):
 
 
 MAX_LR_TIERS = 16         # VL_MAX_LR_TIERS
+
+
+class StepState(C.Structure):
+    """vl_step_state (include/vltf.h): 32 bytes; the host never reads the device block, this is the layout's record."""
+    _fields_ = [("step", i64), ("lr", f32), ("tag_origin", u32), ("adam_lr", f32), ("ema_rate", f32), ("reserved", u32 * 2)]
 
 
 class DecayRange(C.Structure):

@@ -2362,6 +2362,19 @@ extern "C" int vl_step_state_set_micro(vl_step_state* state, int64_t update_step
     return step_state_write("vl_step_state_set_micro", state, update_step, draw_step, lr, tag_origin, stream);
 }
 
+// the weight average's rate: a field of its own, written by a launch of its own (vl_step_state_set / _set_micro stay as they are)
+static_assert(offsetof(vl_step_state, ema_rate) == 20, "vl_step_state layout");
+
+__global__ void step_state_set_ema_kernel(vl_step_state* __restrict__ st, float rate) { st->ema_rate = rate; }
+
+extern "C" int vl_step_state_set_ema(vl_step_state* state, float rate, vl_stream_t stream) {
+    VL_CHECK(state, "vl_step_state_set_ema: bad argument");
+    VL_CHECK(rate > 0.f && rate <= 1.f, "vl_step_state_set_ema: rate must lie in (0, 1], got %g", (double)rate);   // (NaN fails)
+    hipLaunchKernelGGL(step_state_set_ema_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, rate);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // the update kernels above with lr / Adam's step size read from the step state
 __global__ void sgd_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, const vl_step_state* __restrict__ st,
                                     float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
@@ -2525,6 +2538,80 @@ extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode,
     if (mode == 0) hipLaunchKernelGGL(grad_accumulate_kernel<0>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
     else if (mode == 1) hipLaunchKernelGGL(grad_accumulate_kernel<1>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
     else hipLaunchKernelGGL(grad_accumulate_kernel<2>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- exponential moving average of the weights (vltf.h: vl_ema_update) ------------------------------------------------------------------
+// s' = fma(rate, w - s, s): two roundings, spelled out, shared by the scalar head / tail and the 16-byte interior; the ranges are walked
+// as in sgd_apply_body, so an element outside every range is never addressed.
+__device__ __forceinline__ float ema_elem(float s, float w, float rate) {
+#pragma clang fp contract(off)
+    const float d = w - s;
+    return __builtin_fmaf(rate, d, s);
+}
+
+__device__ __forceinline__ void ema_update_body(float* __restrict__ s, const float* __restrict__ w, const tier_table& tt, float rate, int64_t i0,
+                                                int64_t step) {
+    const int phase = align_phase(s, w, nullptr, nullptr);
+    for (int k = 0; k < tt.n; ++k) {
+        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) s[i] = ema_elem(s[i], w[i], rate);
+        float4* __restrict__ s4 = reinterpret_cast<float4*>(s + v0);
+        const float4* __restrict__ w4 = reinterpret_cast<const float4*>(w + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            float4 sv = s4[i];
+            const float4 wv = w4[i];
+            sv.x = ema_elem(sv.x, wv.x, rate);
+            sv.y = ema_elem(sv.y, wv.y, rate);
+            sv.z = ema_elem(sv.z, wv.z, rate);
+            sv.w = ema_elem(sv.w, wv.w, rate);
+            s4[i] = sv;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) s[i] = ema_elem(s[i], w[i], rate);
+    }
+}
+
+__global__ void ema_update_kernel(float* __restrict__ s, const float* __restrict__ w, tier_table tt, float rate,
+                                  const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    ema_update_body(s, w, tt, rate, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void ema_update_st_kernel(float* __restrict__ s, const float* __restrict__ w, tier_table tt, const vl_step_state* __restrict__ st,
+                                     const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    ema_update_body(s, w, tt, st->ema_rate, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+static int ema_args(const char* who, const float* shadow, const float* w, int64_t count, const vl_lr_tier* ranges, int n_ranges,
+                    tier_table* tt) {
+    VL_CHECK(shadow && w && count > 0, "%s: bad argument", who);
+    if (!ranges && n_ranges == 0) {
+        *tt = tier_table_full(count);
+        return 0;
+    }
+    return tier_table_make(who, ranges, n_ranges, count, tt);
+}
+
+extern "C" int vl_ema_update(float* shadow, const float* w, int64_t count, float rate, const uint32_t* skip, const vl_lr_tier* ranges,
+                             int n_ranges, vl_stream_t stream) {
+    tier_table tt;
+    if (int rc = ema_args("vl_ema_update", shadow, w, count, ranges, n_ranges, &tt)) return rc;
+    VL_CHECK(rate > 0.f && rate <= 1.f, "vl_ema_update: rate must lie in (0, 1], got %g", (double)rate);   // (NaN fails)
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, shadow, w, tt, rate, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_ema_update_st(float* shadow, const float* w, int64_t count, const vl_step_state* state, const uint32_t* skip,
+                                const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream) {
+    VL_CHECK(state, "vl_ema_update_st: bad argument");
+    tier_table tt;
+    if (int rc = ema_args("vl_ema_update_st", shadow, w, count, ranges, n_ranges, &tt)) return rc;
+    hipLaunchKernelGGL(ema_update_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, shadow, w, tt, state, skip);
     VL_LAUNCH_CHECK();
     return 0;
 }

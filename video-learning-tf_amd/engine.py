@@ -66,6 +66,8 @@ class NetConfig:
     fc_dropout_keep_prob: float = 0.0           # train.fc_dropout_keep_prob: dropout on relu(fc6) / relu(fc7) (Caffe's drop6 / drop7); 0 = off
     fc_dropout_salt: int = 0                    # which mask stream this tower draws from (fc_dropout_salt): a GraphEngine numbers its towers
     tensor_stats_interval: int = 0              # logging.tensor_stats_interval: per-variable statistics every N updates (stat_segments); 0 = off
+    ema_decay: float = 0.0                      # train.ema_decay: tf.train.ExponentialMovingAverage's decay, in (0, 1); 0 = no shadow weights
+    ema_warmup: bool = False                    # train.ema_warmup: its num_updates form, decay min(decay, (1 + n) / (10 + n)) (ema_rate)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -180,6 +182,38 @@ def check_momentum(optimizer, momentum, nesterov):
     if optimizer == "adam" and (m > 0.0 or nesterov):
         raise VltfError("momentum / nesterov belong to optimizer sgd; adam has its own first moment")
     return m, nesterov
+
+
+def check_ema(decay, warmup):
+    """(decay, warmup) of the weight average, None read as 0 / False; 0 = off.  Refused: a decay that is not a number, not finite or
+    outside (0, 1), and warm-up without a decay."""
+    if isinstance(decay, (bool, np.bool_, str, bytes)) or (decay is not None and not isinstance(decay, (int, float, np.integer, np.floating))):
+        raise VltfError("ema_decay must be a number in (0, 1) (or 0 / None for none), got %r" % (decay,))
+    if warmup is not None and not isinstance(warmup, (bool, np.bool_)):
+        raise VltfError("ema_warmup must be True or False, got %r" % (warmup,))
+    d = 0.0 if decay is None else float(decay)
+    warmup = bool(warmup)
+    if not (d == 0.0 or 0.0 < d < 1.0):           # (NaN fails both)
+        raise VltfError("ema_decay must lie in (0, 1) (or be 0 / None for none), got %r" % (decay,))
+    if warmup and d == 0.0:
+        raise VltfError("ema_warmup needs ema_decay > 0")
+    return d, warmup
+
+
+def ema_rate(decay, warmup, n):
+    """The rate 1 - decay_n of the update applied after n earlier ones (n = step_count before its increment: updates, not
+    micro-batches), as the float32 the launch gets.  Without warm-up float32(1 - decay); with it TF's min(decay, (1 + n) / (10 + n))
+    written for 1 - decay, max(1 - decay, 9 / (10 + n)), in double and rounded once, so nothing is lost to cancellation near 1.  The
+    ONE place the rate is computed: the eager launch takes it as an argument, a replayed step reads it from the step state."""
+    r = 1.0 - float(decay)
+    if warmup:
+        r = max(r, 9.0 / (10.0 + int(n)))
+    return float(np.float32(r))
+
+
+def ema_extra_bytes(count):
+    """Device memory the shadow weights cost: one float per parameter (178 MB at the 44.6 M of the full LRCN)."""
+    return 4 * int(count)
 
 
 def check_weight_decay(weight_decay):
@@ -490,7 +524,9 @@ class LRCNEngine:
     replay.  The host step_count stays the only count (checkpoints, load_opt_state).  Not with data parallelism, not with a probe.
     With NetConfig.accumulate > 1 the key also holds the micro-step's role (first / middle / last / single) and k: three launch sequences,
     three graphs; the state's count is then the dropout draw index and Adam's step size follows step_count (ops.step_state_set_micro).
-    With NetConfig.tensor_stats_interval > 0 the key also holds whether the update is a stats step (_stats_due): two launch sequences."""
+    With NetConfig.tensor_stats_interval > 0 the key also holds whether the update is a stats step (_stats_due): two launch sequences.
+    With NetConfig.ema_decay > 0 the captured update is followed by the weight average's launch, which reads its rate from the block:
+    ops.step_state_set_ema writes it (engine.ema_rate of the host's step_count) before every replay that applies an update."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -505,6 +541,9 @@ class LRCNEngine:
         self.momentum, self.nesterov = check_momentum(cfg.optimizer, cfg.momentum, cfg.nesterov)
         self.weight_decay = check_weight_decay(cfg.weight_decay)
         self.accumulate = check_accumulate(cfg.accumulate)
+        self.ema_decay, self.ema_warmup = check_ema(cfg.ema_decay, cfg.ema_warmup)
+        if self.ema_decay > 0.0 and cfg.classifier == "none":
+            raise VltfError("a feature pipeline (classifier none) has no step of its own: give ema_decay to the GraphEngine it trains in")
         self.fc_keep = check_fc_dropout(cfg.fc_dropout_keep_prob)      # 0: off; 1: on paper only, nothing is launched
         self.cfg, self.B, self.T = cfg, max_clips, cfg.fpc
         self.N = max_clips * cfg.fpc
@@ -554,6 +593,9 @@ class LRCNEngine:
         # gradient accumulation (train_step_*(micro=(i, k))): the running sum of an update's micro-step gradients.  Written by the first
         # micro-step's store over plan.tiers, so it needs no fill; frozen ranges are never touched.  Allocated here, never in a capture.
         self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None
+        # the weight average's shadow (ema_decay): a copy of the whole flat w from the moment the weights are set (load_params) until the
+        # first update; each update then averages the trained ranges only, so a frozen range stays equal to its weights.
+        self.ema = torch.zeros(total, device=dev) if self.ema_decay > 0.0 and training else None
         self.micro = MicroSequence(self.accumulate)
         self._mi = None                       # the (i, k) of the train step being issued; None: a plain step
 
@@ -788,10 +830,62 @@ class LRCNEngine:
             if tuple(a.shape) != tuple(shp):
                 raise VltfError("parameter %s has shape %s, expected %s" % (name, a.shape, shp))
             self.P[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        self._ema_follow()
 
     def get_params(self):
         torch.cuda.synchronize(self.dev)
         return {n: self.P[n].detach().cpu().numpy().copy() for n, _ in self.specs}
+
+    # ---- exponential moving average of the weights (ema_decay; shared with GraphEngine) ---------------------------------------------------
+    def _ema_follow(self):
+        """The weights were just set: before the first update the shadow starts as their copy (TF: a shadow variable is initialised with
+        its variable's initial value)."""
+        if getattr(self, "ema", None) is not None and self.step_count == 0:
+            self.ema.copy_(self.w)
+
+    def _ema_launch(self, skip):
+        """_finish_step, right behind the optimizer launch (step_count already counts this update): one ranged launch over the trained
+        ranges, under the update's skip word.  Captured: the rate comes from the step state (_graph_step writes it before the replay)."""
+        if self.ema is None:
+            return
+        if getattr(self, "_tag_off", None) is not None:
+            ops.ema_update_st(self.ema, self.w, self.state, skip=skip, ranges=self._acc_tiers())
+        else:
+            ops.ema_update(self.ema, self.w, ema_rate(self.ema_decay, self.ema_warmup, self.step_count - 1), skip=skip,
+                           ranges=self._acc_tiers())
+
+    def _ema_required(self):
+        if getattr(self, "ema", None) is None:
+            raise VltfError("this engine keeps no averaged weights (ema_decay is 0, or it was built with training=False)")
+        return self.ema
+
+    def _flat_f32(self, flat, what):
+        a = np.asarray(flat, np.float32)
+        if a.shape != (self.w.numel(),):
+            raise VltfError("%s has shape %s, expected (%d,)" % (what, a.shape, self.w.numel()))
+        return torch.from_numpy(np.ascontiguousarray(a))
+
+    def get_ema_params(self):
+        """{name: array} of the averaged weights, by the engine's specs (frozen variables: their weights)."""
+        ema = self._ema_required()
+        torch.cuda.synchronize(self.dev)
+        flat = ema.detach().cpu().numpy()
+        out, off = {}, 0
+        for name, shp in self.specs:
+            n = int(np.prod(shp))
+            out[name] = flat[off:off + n].reshape(shp).copy()
+            off += n
+        return out
+
+    def load_ema(self, flat):
+        """Sets the shadow from a flat array of `count` floats (get_opt_state's __optimizer__/ema)."""
+        self._ema_required().copy_(self._flat_f32(flat, "the averaged weights"))
+
+    def use_ema_weights(self, flat):
+        """Validation: a stored shadow (get_opt_state's __optimizer__/ema) becomes the weights of an engine built with training=False."""
+        if self.training:
+            raise VltfError("use_ema_weights is for an engine built with training=False: a training engine keeps its own shadow (load_ema)")
+        self.w.copy_(self._flat_f32(flat, "the averaged weights"))
 
     def get_grads(self):
         torch.cuda.synchronize(self.dev)
@@ -865,6 +959,8 @@ class LRCNEngine:
             st[self.OPT_PREFIX + "adam_v"] = self.adam_v.detach().cpu().numpy().copy()
         if self.mom is not None:
             st[self.OPT_PREFIX + "momentum"] = self.mom.detach().cpu().numpy().copy()
+        if getattr(self, "ema", None) is not None:
+            st[self.OPT_PREFIX + "ema"] = self.ema.detach().cpu().numpy().copy()
         return st
 
     def load_opt_state(self, state, global_step=None):
@@ -891,6 +987,13 @@ class LRCNEngine:
             if a.shape != (t.numel(),):
                 raise VltfError("optimizer state %s has shape %s, expected (%d,)" % (name, a.shape, t.numel()))
             t.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        if getattr(self, "ema", None) is not None:
+            a = state.get(self.OPT_PREFIX + "ema")
+            if a is None:                         # a checkpoint from a run without the average: it starts at the loaded weights
+                missing.append(self.OPT_PREFIX + "ema")
+                self.ema.copy_(self.w)
+            else:
+                self.load_ema(a)
         return missing
 
     def check_status(self):
@@ -1551,6 +1654,7 @@ class LRCNEngine:
             ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
+        self._ema_launch(skip)
         return self._fetch(rows, fetch)
 
     def _fetch(self, rows, fetch, partial=False):
@@ -1638,6 +1742,8 @@ class LRCNEngine:
             ops.step_state_set(self.state, self.step_count, lr, self._graph_tag_origin(g["span"]))
         else:                                     # accumulation: the dropout seed follows the draw index, Adam's step size the update count
             ops.step_state_set_micro(self.state, self.step_count, draw, lr, self._graph_tag_origin(g["span"]))
+        if train and final and self.ema is not None:      # the update this replay applies follows step_count earlier ones
+            ops.step_state_set_ema(self.state, ema_rate(self.ema_decay, self.ema_warmup, self.step_count))
         g["graph"].replay()
         self._rows = g["rows"]
         if not train:

@@ -239,6 +239,8 @@ class Feeder:
         """feeder.py:198-257: restore variables; a variable-set mismatch fails instead of prompting."""
         self.compute_save_interval()
         if not self.resume:
+            if self.phase == defs.phase.val and getattr(self.val, "use_ema", False):
+                error("val.use_ema needs a resume_file: the averaged weights are read from a checkpoint")
             return
         base = self._resolve(resume_file)
         wfile = base + ".weights.npz"
@@ -255,6 +257,13 @@ class Feeder:
         if missing or extra:
             error("Failed to load checkpoint: variables missing from it %s, unknown to the network %s" % (missing, extra))
         engine.load_params({k: v for k, v in stored.items() if k in want})
+        # val.use_ema: the shadow a run with train.ema_decay stored (engine.get_opt_state) takes the weights' place
+        if self.phase == defs.phase.val and getattr(self.val, "use_ema", False):
+            key = engine.OPT_PREFIX + "ema"
+            if key not in opt_state:
+                error("val.use_ema: checkpoint [%s] holds no averaged weights [%s] (it was not trained with train.ema_decay)" % (wfile, key))
+            info("Evaluating the averaged weights [%s] of the checkpoint" % key)
+            engine.use_ema_weights(opt_state[key])
         # tf.train.Saver() saves every global variable (feeder.py:201), i.e. also the Adam slots and beta powers: without them a
         # resumed adam run restarts its moments and bias correction.  Their absence (a weights-only file) means a fresh optimizer.
         if engine.training:

@@ -40,7 +40,7 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_fc_dropout, check_momentum,
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_momentum,
                      check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
 
 
@@ -752,7 +752,7 @@ def model_specs(pipelines, datasets, num_classes):
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
-                 accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0):
+                 accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -761,12 +761,15 @@ class GraphEngine:
         dcnn tower in a training forward (engine.check_fc_dropout), each tower under a salt of its own (1 + its node index: two towers
         draw different masks at one step; data-parallel ranks are not salted, as with the heads' dropout); 0 = off.
         tensor_stats_interval: per-variable gradient / weight statistics every N updates (engine.stat_segments over this engine's
-        variable list, `<pipeline>/<tf name>` in a scoped model; LRCNEngine._stats_launch); None / 0 = off."""
+        variable list, `<pipeline>/<tf name>` in a scoped model; LRCNEngine._stats_launch); None / 0 = off.  ema_decay, ema_warmup:
+        tf.train.ExponentialMovingAverage's shadow of every variable of the model, averaged over the trained ranges after each update
+        (engine.check_ema, engine.ema_rate, LRCNEngine._ema_launch); 0 = off."""
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
         self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)
         self.weight_decay = check_weight_decay(weight_decay)
+        self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
@@ -877,6 +880,7 @@ class GraphEngine:
             self.adam_m, self.adam_v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
         self.mom = torch.zeros(total, device=dev) if self.momentum > 0.0 and training else None    # the momentum accumulator
         self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None   # LRCNEngine.__init__: the running sum
+        self.ema = torch.zeros(total, device=dev) if self.ema_decay > 0.0 and training else None   # LRCNEngine.__init__: the shadow weights
         rows = self.last.max_rows
         self.stats = torch.zeros(2, device=dev)
         self.loss_rows = torch.zeros(2 * rows, device=dev)
@@ -909,6 +913,7 @@ class GraphEngine:
             if tuple(a.shape) != tuple(shp):
                 raise VltfError("parameter %s has shape %s, expected %s" % (name, a.shape, shp))
             self.P[name].copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        self._ema_follow()
 
     def init_params(self, seed=0, stddev=0.05, well_scaled=False):
         """Reference initialisers for every variable (alexnet.py:40-46, tf_util.py:44-45; BasicLSTMCell: glorot-uniform / zeros)."""
@@ -941,6 +946,9 @@ class GraphEngine:
 
     _draw_index = LRCNEngine._draw_index
     _acc_tiers = LRCNEngine._acc_tiers
+    _ema_follow, _ema_launch, _ema_required, _flat_f32 = (LRCNEngine._ema_follow, LRCNEngine._ema_launch, LRCNEngine._ema_required,
+                                                          LRCNEngine._flat_f32)
+    get_ema_params, load_ema, use_ema_weights = LRCNEngine.get_ema_params, LRCNEngine.load_ema, LRCNEngine.use_ema_weights
     _stats_setup, _stats_due, _stats_launch, _stats_note = (LRCNEngine._stats_setup, LRCNEngine._stats_due, LRCNEngine._stats_launch,
                                                             LRCNEngine._stats_note)
     _stats_collect, _stats_result, tensor_stats = LRCNEngine._stats_collect, LRCNEngine._stats_result, LRCNEngine.tensor_stats
@@ -1133,6 +1141,7 @@ class GraphEngine:
             ops.sgd_apply_tiers(self.w, self.g, tiers, lr, clip_norm, self.ss, 1.0, skip=skip)
         else:
             ops.sgd_apply(self.w, self.g, lr, clip_norm, self.ss, 1.0, skip=skip)
+        self._ema_launch(skip)
         return self._fetch(rows, fetch)
 
     def _fetch(self, rows, fetch, partial=False):

@@ -685,6 +685,11 @@ def step_state_set_micro(state, update_step, draw_step, lr, tag_origin):
     _ffi.call("vl_step_state_set_micro", _state(state), int(update_step), int(draw_step), lr, int(tag_origin), stream())
 
 
+def step_state_set_ema(state, rate):
+    """state.ema_rate = rate, and nothing else of the block, written on the stream (vl_step_state_set_ema)."""
+    _ffi.call("vl_step_state_set_ema", _state(state), rate, stream())
+
+
 def sgd_apply_st(w, g, state, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
     """sgd_apply with lr read from the step state."""
     _f32(w, g, sumsq_t)
@@ -879,6 +884,29 @@ def momentum_apply_st(w, g, accum, state, momentum, nesterov=False, clip_norm=0.
     arr, n = (None, 0) if tiers is None else _tiers(tiers)
     _ffi.call("vl_momentum_apply_st", _p(w), _p(g), _p(accum), w.numel(), _state(state), momentum, int(bool(nesterov)), clip_norm,
               _p(sumsq_t), gscale, _skip_word(skip), arr, n, stream())
+
+
+def _ema_sizes(shadow, w):
+    if shadow.numel() != w.numel():
+        raise _ffi.VltfError("ema_update: shadow and w must have one element count")
+
+
+def ema_update(shadow, w, rate, skip=None, ranges=None):
+    """Exponential moving average of the weights (tf.train.ExponentialMovingAverage; vltf.h: vl_ema_update): shadow += rate * (w - shadow)
+    with rate = 1 - decay.  ranges = [(begin, end, lr_mult)] (plan.tiers; the factor is ignored) or None for everything; elements outside
+    every range are not touched in either buffer.  skip: as sgd_apply.  One launch."""
+    _f32(shadow, w)
+    _ema_sizes(shadow, w)
+    arr, n = (None, 0) if ranges is None else _tiers(ranges)
+    _ffi.call("vl_ema_update", _p(shadow), _p(w), w.numel(), rate, _skip_word(skip), arr, n, stream())
+
+
+def ema_update_st(shadow, w, state, skip=None, ranges=None):
+    """ema_update with the rate read from the step state (step_state_set_ema)."""
+    _f32(shadow, w)
+    _ema_sizes(shadow, w)
+    arr, n = (None, 0) if ranges is None else _tiers(ranges)
+    _ffi.call("vl_ema_update_st", _p(shadow), _p(w), w.numel(), _state(state), _skip_word(skip), arr, n, stream())
 
 
 def step_guard(skip, *lstm_workspaces):

@@ -57,7 +57,8 @@ def pipeline_net_config(settings, p, dataset):
               momentum=settings.train.momentum if settings.train else 0.0, nesterov=settings.train.nesterov if settings.train else False,
               weight_decay=settings.train.weight_decay if settings.train else 0.0,
               accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout(),
-              tensor_stats_interval=settings.get_tensor_stats_interval())
+              tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
+              ema_warmup=settings.get_ema()[1])
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -346,7 +347,8 @@ def main(init_file, seed=0, device=None):
                              weight_decay=settings.train.weight_decay if settings.train else 0.0,
                              accumulate=settings.train.accumulate if settings.train else 1,
                              fc_dropout_keep_prob=settings.get_fc_dropout(),
-                             tensor_stats_interval=settings.get_tensor_stats_interval())
+                             tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
+                             ema_warmup=settings.get_ema()[1])
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

@@ -23,11 +23,13 @@ class TrainSettings:
     weight_decay = 0.0
     accumulate = 1
     fc_dropout_keep_prob = 0.0
+    ema_decay, ema_warmup = 0.0, False
 
 
 class ValSettings:
     batch_size, logits_save_interval = 88, -1
     clip_fusion_type, clip_fusion_method = defs.fusion_type.late, defs.fusion_method.avg
+    use_ema = False
 
 
 class Settings:
@@ -48,6 +50,11 @@ class Settings:
     def get_fc_dropout(self):
         """train.fc_dropout_keep_prob (dropout on relu(fc6) / relu(fc7) of the dcnn towers); 0 = off, and outside the train phase."""
         return self.train.fc_dropout_keep_prob if self.phase == defs.phase.train else 0.0
+
+    def get_ema(self):
+        """(train.ema_decay, train.ema_warmup): the shadow weights of tf.train.ExponentialMovingAverage; (0, False) = off, and outside
+        the train phase (validation reads a stored shadow through val.use_ema, it keeps none of its own)."""
+        return (self.train.ema_decay, self.train.ema_warmup) if self.phase == defs.phase.train else (0.0, False)
 
     def get_tensor_stats_interval(self):
         """logging.tensor_stats_interval (per-variable gradient / weight statistics every N updates); 0 = off, and outside the train phase."""
@@ -221,6 +228,19 @@ class Settings:
                     t.fc_dropout_keep_prob = check_fc_dropout(None if fk == "None" else fk)
                 except VltfError as ex:
                     error("train.fc_dropout_keep_prob: %s" % ex)
+                # exponential moving average of the weights (tf.train.ExponentialMovingAverage; engine.check_ema): absent / None = off
+                from .engine import check_ema
+                ed = obj.get("ema_decay")
+                if isinstance(ed, str) and ed != "None":         # a quoted number; nan / inf come as strings too
+                    try:
+                        ed = float(ed)
+                    except ValueError:
+                        pass
+                try:
+                    t.ema_decay, t.ema_warmup = check_ema(None if ed == "None" else ed,
+                                                          None if obj.get("ema_warmup") == "None" else obj.get("ema_warmup"))
+                except VltfError as ex:
+                    error("train.ema_decay / train.ema_warmup: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
@@ -235,6 +255,11 @@ class Settings:
                 v.logits_save_interval = int(obj["logits_save_interval"])
                 cf = parse_seq(obj["clip_fusion"])
                 v.clip_fusion_type, v.clip_fusion_method = defs.check(cf[0], defs.fusion_type), defs.check(cf[1], defs.fusion_method)
+                # evaluate the averaged weights a training run with train.ema_decay stored beside its weights: absent / None = the weights
+                ue = obj.get("use_ema") if obj.get("use_ema") not in (None, "None") else False
+                if not isinstance(ue, bool):
+                    error("val.use_ema must be a boolean, got [%s]" % (ue,))
+                v.use_ema = ue
 
         self.feeder = Feeder(defs.input_mode.video, self.phases, (self.train, self.val), self.save_freq_per_epoch, self.run_folder,
                              self.should_resume())

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from .defs_ import defs
+from .engine import ema_extra_bytes
 from .utils_ import error, info, warning
 
 
@@ -125,6 +126,10 @@ class Train:
         self.stats_log = None
         if getattr(engine, "tensor_stats_interval", 0) > 0:
             self.stats_log = TensorStatsLog(settings.run_folder, settings.run_id, int(os.environ.get("RANK", "0")))
+        if getattr(engine, "ema", None) is not None:
+            info("Averaging the trained weights: decay %s, warm-up %s (rate max(1 - decay, 9 / (10 + updates)) if on), +%.1f MB of device memory "
+                 "for the shadow; validate it with val.use_ema" %
+                 (engine.ema_decay, "on" if engine.ema_warmup else "off", ema_extra_bytes(engine.ema.numel()) / 1e6))
 
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
