@@ -43,6 +43,44 @@ def test_conv_fwd_bwd(h, w, k, s, g, ci, co):
     np.testing.assert_allclose(db, bt.grad.numpy(), rtol=1e-9, atol=1e-9)
 
 
+@pytest.mark.parametrize("n,h,w,ci,co,kh,kw,s,g", [
+    (2, 9, 8, 8, 12, 2, 2, 1, 1),      # even kernel at stride 1: pad before < pad after
+    (2, 9, 8, 8, 12, 4, 4, 1, 2),
+    (2, 10, 7, 6, 8, 3, 5, 1, 1),      # kh != kw
+    (2, 10, 7, 6, 8, 5, 3, 1, 2),
+    (2, 11, 13, 6, 9, 3, 3, 2, 3),     # stride 2, three groups
+    (2, 12, 10, 4, 8, 7, 7, 2, 1),
+    (2, 11, 10, 3, 8, 5, 5, 3, 1),     # stride 3
+    (3, 3, 3, 16, 32, 5, 5, 1, 2),     # plane smaller than the kernel
+    (3, 2, 2, 16, 16, 3, 3, 1, 1),
+    (3, 1, 1, 32, 48, 3, 3, 1, 1),
+    (2, 4, 3, 8, 8, 5, 5, 1, 1),
+    (2, 6, 6, 8, 8, 1, 1, 2, 1),       # strided 1x1: no padding at all
+    (2, 9, 9, 12, 12, 3, 3, 1, 12),    # depthwise
+    (2, 5, 9, 8, 8, 1, 7, 1, 1),       # one row / one column of taps
+    (2, 9, 5, 8, 8, 7, 1, 1, 1),
+    (2, 13, 12, 3, 8, 6, 6, 2, 1),     # even kernel, strided
+])
+def test_conv_fwd_bwd_any_geometry(n, h, w, ci, co, kh, kw, s, g):
+    """The geometries the C ABI accepts beyond AlexNet's (tests/test_conv_geometry_gpu.py holds the kernels to this oracle there):
+    kh and kw apart, asymmetric SAME padding at stride 1, strides 2 and 3, more than two groups, planes smaller than the kernel."""
+    rng = np.random.default_rng(0)
+    x = rng.standard_normal((n, h, w, ci)).astype(np.float32)
+    wt = rng.standard_normal((kh, kw, ci // g, co)).astype(np.float32)
+    b = rng.standard_normal(co).astype(np.float32)
+    y = O.grouped_conv(x, wt, b, s, g)
+    assert y.shape == (n, -(-h // s), -(-w // s), co)
+    xt, wtt, bt = t(x).requires_grad_(), t(wt).requires_grad_(), t(b).requires_grad_()
+    yt = torch_conv_same(xt, wtt, s, g) + bt
+    np.testing.assert_allclose(y, yt.detach().numpy(), rtol=1e-10, atol=1e-10)
+    dy = rng.standard_normal(y.shape)
+    yt.backward(t(dy))
+    dx, dw, db = O.grouped_conv_grad(x, wt, dy, s, g)
+    np.testing.assert_allclose(dx, xt.grad.numpy(), rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(dw, wtt.grad.numpy(), rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(db, bt.grad.numpy(), rtol=1e-9, atol=1e-9)
+
+
 def test_same_pad_rule():
     assert O.same_pad(227, 11, 4) == (57, 4, 4)       # conv1: 57x57, not Caffe's 55x55
     assert O.same_pad(224, 11, 4) == (56, 3, 4)       # asymmetric
