@@ -587,6 +587,43 @@ size_t vl_tensor_stats_ws_bytes(const vl_stat_segment* segs, int n_segs);
 int vl_tensor_stats(const float* w, const float* g, int64_t count, const vl_stat_segment* segs, int n_segs, vl_tensor_stat* out,
                     void* ws, size_t ws_bytes, vl_stream_t stream);
 
+/* ---- LARS: layer-wise adaptive learning rates for the momentum update (tf.contrib.opt.LARSOptimizer; You, Gitman, Ginsburg 2017) ---------
+ * Two calls behind a vl_tensor_stats launch over the RAW gradient (after accumulation and exchange, before vl_l2_regularize): the rows
+ * stay on the device, so does the trust table, and a captured step replays all of it.
+ *
+ * vl_lars_trust: trust[k] for the n_segs rows of a vl_tensor_stats launch, one workgroup, lane k = row k.  In double, rounded to float once:
+ *     sc      = the clip scale of vl_sgd_apply, from clip_norm, *sumsq and gscale as the update launches take them
+ *     wn      = sqrt(rows[k].w_sumsq)              gn = sc * sqrt(rows[k].g_sumsq)
+ *     trust   = eeta * wn / (gn + decay[k] * wn + eps)     if wn > 0 and gn > 0 and the row counts no non-finite element of w or g
+ *             = 1                                          otherwise (TF's where(w_norm > 0, where(g_norm > 0, .., 1), 1); a NaN travels
+ *                                                          through the update exactly as it does without LARS)
+ * decay: HOST array of n_segs coefficients (the one vl_l2_regularize gives the variable, 0 without weight decay); it travels by value in
+ * the launch arguments like eeta and eps.  Read-only on rows; every one of the n_segs entries of trust is overwritten.  Refused on the
+ * host: a null pointer, n_segs outside 1 .. VL_MAX_STAT_SEGMENTS, eeta not finite or <= 0, eps or a decay negative or not finite.
+ *
+ * vl_lars_apply: vl_momentum_apply over a range table whose entries carry a trust index.  Inside an entry the element rule is
+ * vl_momentum_apply's (the same element function) with
+ *     lr_k = (float)((float)(lr * lr_mult) * t),   t = 1 for trust_index == -1 (not read), else trust[trust_index] read when the kernel runs
+ * so an entry's elements get, bit for bit, what vl_momentum_apply gives on that sub-range with that lr.  The accumulator never sees lr_k.
+ * The table obeys the rules of vl_lr_tier (sorted, disjoint, inside [0, count), lr_mult finite and > 0) with 1 .. VL_MAX_STAT_SEGMENTS
+ * entries, travels BY VALUE, and every trust_index is -1 or in [0, n_trust); anything else is refused on the host.  trust may be NULL when
+ * n_trust == 0.  Elements outside every range are neither loaded nor stored (w, g and accum alike).  skip, gscale, clip_norm, sumsq,
+ * nesterov, the scalar head / tail and the 16-byte interior: as vl_momentum_apply.  One launch, the grid of vl_sgd_apply, 5 floats per
+ * element; the trust value is one uniform load per range.  vl_lars_apply_st: lr = state->lr. */
+typedef struct vl_lars_range {
+    int64_t begin, end;
+    float lr_mult;
+    int32_t trust_index;
+} vl_lars_range;
+int vl_lars_trust(const vl_tensor_stat* rows, int n_segs, double eeta, double eps, const float* decay, float clip_norm,
+                  const float* sumsq, float gscale, float* trust, vl_stream_t stream);
+int vl_lars_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov, float clip_norm,
+                  const float* sumsq, float gscale, const uint32_t* skip, const vl_lars_range* ranges, int n_ranges,
+                  const float* trust, int n_trust, vl_stream_t stream);
+int vl_lars_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
+                     int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                     const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream);
+
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);
 /* ReluGrad in place: d[i] = y[i] > 0 ? d[i] : 0 (y = the ReLU's forward output, alexnet.py:228,248). */

@@ -109,6 +109,9 @@ SIGNATURES = {
     "vl_ema_update_st": (i32, [p, p, i64, p, p, p, i32, p]),
     "vl_tensor_stats_ws_bytes": (sz, [p, i32]),
     "vl_tensor_stats": (i32, [p, p, i64, p, i32, p, p, sz, p]),
+    "vl_lars_trust": (i32, [p, i32, C.c_double, C.c_double, p, f32, p, f32, p, p]),
+    "vl_lars_apply": (i32, [p, p, p, i64, f32, f32, i32, f32, p, f32, p, p, i32, p, i32, p]),
+    "vl_lars_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p, i32, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),
@@ -158,6 +161,11 @@ class TensorStat(C.Structure):
 
 MAX_STAT_SEGMENTS = 64    # VL_MAX_STAT_SEGMENTS
 STAT_CHUNK = 16384        # VL_STAT_CHUNK
+
+
+class LarsRange(C.Structure):
+    """vl_lars_range (include/vltf.h)."""
+    _fields_ = [("begin", i64), ("end", i64), ("lr_mult", f32), ("trust_index", C.c_int32)]
 
 
 class VltfError(RuntimeError):

@@ -2217,32 +2217,37 @@ __device__ __forceinline__ void momentum_elem(float& w, float g, float& a, float
     w = __builtin_fmaf(-lr_k, nesterov ? __builtin_fmaf(momentum, ai, gi) : ai, w);
 }
 
+// one range [begin, end) of the momentum update with its own lr_k: scalar head, 16-byte interior, scalar tail (tier_split).  Shared by the
+// tier walk below and by the LARS walk (lars_apply_body), so a range's bits do not depend on which table named it.
+__device__ __forceinline__ void momentum_range(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, int64_t begin,
+                                               int64_t end, int phase, float sc, float lr_k, float momentum, bool nesterov, int64_t i0,
+                                               int64_t step) {
+    int64_t v0, v1;
+    tier_split(begin, end, phase, v0, v1);
+    for (int64_t i = begin + i0; i < v0; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
+    float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
+    float4* __restrict__ a4 = reinterpret_cast<float4*>(a + v0);
+    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+        float4 wv = w4[i], av = a4[i];
+        const float4 gv = g4[i];
+        momentum_elem(wv.x, gv.x, av.x, sc, lr_k, momentum, nesterov);
+        momentum_elem(wv.y, gv.y, av.y, sc, lr_k, momentum, nesterov);
+        momentum_elem(wv.z, gv.z, av.z, sc, lr_k, momentum, nesterov);
+        momentum_elem(wv.w, gv.w, av.w, sc, lr_k, momentum, nesterov);
+        a4[i] = av;
+        w4[i] = wv;
+    }
+    for (int64_t i = v1 + i0; i < end; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
+}
+
 __device__ __forceinline__ void momentum_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a,
                                                     const tier_table& tt, float lr, float momentum, bool nesterov, float clip_norm,
                                                     const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
     const float sc = clip_scale(clip_norm, sumsq, gscale);
     const int phase = align_phase(w, g, a, nullptr);
-    for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
-        const float lr_k = lr * tt.t[k].lr_mult;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
-        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-        float4* __restrict__ a4 = reinterpret_cast<float4*>(a + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            float4 wv = w4[i], av = a4[i];
-            const float4 gv = g4[i];
-            momentum_elem(wv.x, gv.x, av.x, sc, lr_k, momentum, nesterov);
-            momentum_elem(wv.y, gv.y, av.y, sc, lr_k, momentum, nesterov);
-            momentum_elem(wv.z, gv.z, av.z, sc, lr_k, momentum, nesterov);
-            momentum_elem(wv.w, gv.w, av.w, sc, lr_k, momentum, nesterov);
-            a4[i] = av;
-            w4[i] = wv;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
-    }
+    for (int k = 0; k < tt.n; ++k)
+        momentum_range(w, g, a, tt.t[k].begin, tt.t[k].end, phase, sc, lr * tt.t[k].lr_mult, momentum, nesterov, i0, step);
 }
 
 __global__ void momentum_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, tier_table tt, float lr,
@@ -2858,6 +2863,131 @@ extern "C" int vl_tensor_stats(const float* w, const float* g, int64_t count, co
                        reinterpret_cast<vl_tensor_stat*>(ws));
     VL_LAUNCH_CHECK();
     hipLaunchKernelGGL(tensor_stats_stage2, dim3(st.n), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const vl_tensor_stat*>(ws), st, out);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- LARS (vltf.h: vl_lars_trust, vl_lars_apply): a per-variable trust ratio on the device, then the momentum update through it ----------
+struct lars_decay {
+    float d[VL_MAX_STAT_SEGMENTS];
+};
+
+// one workgroup, lane k = segment k: the row's two fp64 sums -> trust[k], in double, rounded to float once
+__global__ __launch_bounds__(VL_MAX_STAT_SEGMENTS) void lars_trust_kernel(const vl_tensor_stat* __restrict__ rows, int n, double eeta,
+                                                                          double eps, lars_decay dec, float clip_norm,
+                                                                          const float* __restrict__ sumsq, float gscale,
+                                                                          float* __restrict__ trust) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x;
+    if (k >= n) return;
+    const double sc = (double)clip_scale(clip_norm, sumsq, gscale);
+    const double wn = sqrt(rows[k].w_sumsq), gn = sc * sqrt(rows[k].g_sumsq);
+    const bool finite = rows[k].g_nonfinite == 0u && rows[k].w_nonfinite == 0u;
+    float t = 1.f;
+    if (finite && wn > 0.0 && gn > 0.0) t = (float)(eeta * wn / (gn + (double)dec.d[k] * wn + eps));      // (a NaN norm fails > 0)
+    trust[k] = t;
+}
+
+extern "C" int vl_lars_trust(const vl_tensor_stat* rows, int n_segs, double eeta, double eps, const float* decay, float clip_norm,
+                             const float* sumsq, float gscale, float* trust, vl_stream_t stream) {
+    VL_CHECK(rows && decay && trust, "vl_lars_trust: bad argument");
+    VL_CHECK(n_segs >= 1 && n_segs <= VL_MAX_STAT_SEGMENTS, "vl_lars_trust: 1 .. %d segments, got %d", VL_MAX_STAT_SEGMENTS, n_segs);
+    VL_CHECK(((uintptr_t)rows & 7) == 0 && ((uintptr_t)trust & 3) == 0, "vl_lars_trust: misaligned pointer");
+    VL_CHECK(eeta > 0.0 && eeta <= 1.7976931348623157e308, "vl_lars_trust: eeta must be finite and > 0, got %g", eeta);       // (NaN fails)
+    VL_CHECK(eps >= 0.0 && eps <= 1.7976931348623157e308, "vl_lars_trust: eps must be finite and >= 0, got %g", eps);
+    lars_decay dec;
+    for (int k = 0; k < n_segs; ++k) {
+        VL_CHECK(decay[k] >= 0.f && decay[k] <= 3.402823466e38f, "vl_lars_trust: segment %d: decay must be finite and >= 0", k);
+        dec.d[k] = decay[k];
+    }
+    for (int k = n_segs; k < VL_MAX_STAT_SEGMENTS; ++k) dec.d[k] = 0.f;
+    hipLaunchKernelGGL(lars_trust_kernel, dim3(1), dim3(VL_MAX_STAT_SEGMENTS), 0, (hipStream_t)stream, rows, n_segs, eeta, eps, dec, clip_norm,
+                       sumsq, gscale, trust);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+struct lars_table {
+    vl_lars_range r[VL_MAX_STAT_SEGMENTS];
+    int n;
+};
+
+// the rules of tier_table_make, and every trust_index is -1 or inside the trust array (the kernel reads trust[index] unchecked)
+static int lars_table_make(const char* who, const vl_lars_range* ranges, int n_ranges, int64_t count, const float* trust, int n_trust,
+                           lars_table* out) {
+    VL_CHECK(ranges && n_ranges >= 1 && n_ranges <= VL_MAX_STAT_SEGMENTS, "%s: 1 .. %d ranges, got %d", who, VL_MAX_STAT_SEGMENTS, n_ranges);
+    VL_CHECK(n_trust >= 0 && (trust || n_trust == 0), "%s: a trust array of %d entries at a null pointer", who, n_trust);
+    int64_t prev = 0;
+    for (int k = 0; k < n_ranges; ++k) {
+        const vl_lars_range& r = ranges[k];
+        VL_CHECK(r.begin >= prev && r.end > r.begin && r.end <= count,
+                 "%s: range %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
+                 (long long)r.end, (long long)count);
+        VL_CHECK(r.lr_mult > 0.f && r.lr_mult <= 3.402823466e38f, "%s: range %d: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
+        VL_CHECK(r.trust_index >= -1 && r.trust_index < n_trust, "%s: range %d: trust_index %d is neither -1 nor inside the %d trust entries",
+                 who, k, r.trust_index, n_trust);
+        out->r[k] = r;
+        prev = r.end;
+    }
+    out->n = n_ranges;
+    return 0;
+}
+
+// momentum_apply_body with lr_k = (lr * lr_mult) * trust: the trust value is one uniform load per range, the elements are momentum_range's
+__device__ __forceinline__ void lars_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, const lars_table& lt,
+                                                const float* __restrict__ trust, float lr, float momentum, bool nesterov, float clip_norm,
+                                                const float* __restrict__ sumsq, float gscale, int64_t i0, int64_t step) {
+    const float sc = clip_scale(clip_norm, sumsq, gscale);
+    const int phase = align_phase(w, g, a, nullptr);
+    for (int k = 0; k < lt.n; ++k) {
+        const int ti = lt.r[k].trust_index;
+        const float lr_k = (lr * lt.r[k].lr_mult) * (ti < 0 ? 1.f : trust[ti]);
+        momentum_range(w, g, a, lt.r[k].begin, lt.r[k].end, phase, sc, lr_k, momentum, nesterov, i0, step);
+    }
+}
+
+__global__ void lars_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, lars_table lt,
+                                  const float* __restrict__ trust, float lr, float momentum, int nesterov, float clip_norm,
+                                  const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    lars_apply_body(w, g, a, lt, trust, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                    (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void lars_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, lars_table lt,
+                                     const float* __restrict__ trust, const vl_step_state* __restrict__ st, float momentum, int nesterov,
+                                     float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (skip && *skip) return;
+    lars_apply_body(w, g, a, lt, trust, st->lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
+                    (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+static int lars_args(const char* who, const float* w, const float* g, const float* accum, int64_t count, float momentum,
+                     const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, lars_table* lt) {
+    VL_CHECK(w && g && accum && count > 0, "%s: bad argument", who);
+    VL_CHECK(momentum > 0.f && momentum < 1.f, "%s: momentum must lie in (0, 1), got %g", who, (double)momentum);   // (NaN fails)
+    return lars_table_make(who, ranges, n_ranges, count, trust, n_trust, lt);
+}
+
+extern "C" int vl_lars_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov, float clip_norm,
+                             const float* sumsq, float gscale, const uint32_t* skip, const vl_lars_range* ranges, int n_ranges,
+                             const float* trust, int n_trust, vl_stream_t stream) {
+    lars_table lt;
+    if (int rc = lars_args("vl_lars_apply", w, g, accum, count, momentum, ranges, n_ranges, trust, n_trust, &lt)) return rc;
+    hipLaunchKernelGGL(lars_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, lt, trust, lr,
+                       momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_lars_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
+                                int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                                const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream) {
+    VL_CHECK(state, "vl_lars_apply_st: bad argument");
+    lars_table lt;
+    if (int rc = lars_args("vl_lars_apply_st", w, g, accum, count, momentum, ranges, n_ranges, trust, n_trust, &lt)) return rc;
+    hipLaunchKernelGGL(lars_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, lt, trust,
+                       state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
 }

@@ -68,6 +68,8 @@ class NetConfig:
     tensor_stats_interval: int = 0              # logging.tensor_stats_interval: per-variable statistics every N updates (stat_segments); 0 = off
     ema_decay: float = 0.0                      # train.ema_decay: tf.train.ExponentialMovingAverage's decay, in (0, 1); 0 = no shadow weights
     ema_warmup: bool = False                    # train.ema_warmup: its num_updates form, decay min(decay, (1 + n) / (10 + n)) (ema_rate)
+    lars_eeta: float = 0.0                      # train.lars_eeta: tf.contrib.opt.LARSOptimizer's eeta, > 0 (needs momentum > 0); 0 = no LARS
+    lars_epsilon: float = 0.0                   # train.lars_epsilon: its epsilon, >= 0, added to the trust ratio's denominator (lars_ranges)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -182,6 +184,30 @@ def check_momentum(optimizer, momentum, nesterov):
     if optimizer == "adam" and (m > 0.0 or nesterov):
         raise VltfError("momentum / nesterov belong to optimizer sgd; adam has its own first moment")
     return m, nesterov
+
+
+def check_lars(optimizer, momentum, eeta, epsilon):
+    """(eeta, epsilon) of tf.contrib.opt.LARSOptimizer, None read as 0; eeta 0 = off.  Refused: either value not a number, negative or
+    not finite; an epsilon without an eeta; LARS with Adam; LARS without momentum > 0 (TF's optimizer is a momentum optimizer, and
+    vl_momentum_apply's rule is not defined at momentum 0)."""
+    vals = []
+    for key, v in (("lars_eeta", eeta), ("lars_epsilon", epsilon)):
+        if v is not None and (isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating))):
+            raise VltfError("%s must be a finite number >= 0 (0 / None = off), got %r" % (key, v))
+        f = 0.0 if v is None else float(v)
+        if not (f >= 0.0 and math.isfinite(f)):       # (NaN fails)
+            raise VltfError("%s must be a finite number >= 0 (0 / None = off), got %r" % (key, v))
+        vals.append(f)
+    e, eps = vals
+    if e == 0.0:
+        if eps > 0.0:
+            raise VltfError("lars_epsilon needs lars_eeta > 0")
+        return 0.0, 0.0
+    if optimizer == "adam":
+        raise VltfError("lars_eeta belongs to optimizer sgd with momentum; adam scales its own step per element")
+    if not (momentum is not None and float(momentum) > 0.0):
+        raise VltfError("lars_eeta needs momentum > 0: LARS is a momentum optimizer")
+    return e, eps
 
 
 def check_ema(decay, warmup):
@@ -369,6 +395,32 @@ def stat_segments(specs, plan):
     return out
 
 
+def lars_ranges(specs, plan, weight_decay):
+    """The tables of a LARS update, host only: (ranges, segments, decays).
+    ranges   [(begin, end, lr_mult, trust_index)] for ops.lars_apply: every variable of specs inside plan.tiers, in flat order, with its
+             tier's factor.  A variable of rank >= 2 is an entry of its own whose trust_index counts those variables from 0; variables of
+             rank 1 (every bias: TF's skip_list, the exemption decay_ranges makes) get -1, adjacent ones with one factor merged.
+    segments [(name, begin, end)] for ops.tensor_stats: the entries with a trust index, in that order -- biases need no norms.
+    decays   the coefficient decay_ranges gives each of them (weight_decay, or 0 when it is off).
+    Frozen variables lie outside plan.tiers and are absent from all three."""
+    d = check_weight_decay(weight_decay)
+    ranges, segs, decays, off = [], [], [], 0
+    for name, shp in specs:
+        n = int(np.prod(shp))
+        mult = next((float(m) for lo, hi, m in plan.tiers if lo <= off and off + n <= hi), None)
+        if n > 0 and mult is not None:
+            if len(shp) >= 2:
+                ranges.append((off, off + n, mult, len(segs)))
+                segs.append((name, off, off + n))
+                decays.append(d)
+            elif ranges and ranges[-1][3] == -1 and ranges[-1][1] == off and ranges[-1][2] == mult:
+                ranges[-1] = (ranges[-1][0], off + n, mult, -1)
+            else:
+                ranges.append((off, off + n, mult, -1))
+        off += n
+    return ranges, segs, decays
+
+
 def clip_scale_of(sumsq, clip_norm):
     """The factor the update applies to the gradient: clip_norm / max(sqrt(sumsq), clip_norm), or 1 without a clip."""
     if not clip_norm or clip_norm <= 0.0:
@@ -542,6 +594,9 @@ class LRCNEngine:
         self.weight_decay = check_weight_decay(cfg.weight_decay)
         self.accumulate = check_accumulate(cfg.accumulate)
         self.ema_decay, self.ema_warmup = check_ema(cfg.ema_decay, cfg.ema_warmup)
+        self.lars_eeta, self.lars_epsilon = check_lars(cfg.optimizer, self.momentum, cfg.lars_eeta, cfg.lars_epsilon)
+        if self.lars_eeta > 0.0 and cfg.classifier == "none":
+            raise VltfError("a feature pipeline (classifier none) has no step of its own: give lars_eeta to the GraphEngine it trains in")
         if self.ema_decay > 0.0 and cfg.classifier == "none":
             raise VltfError("a feature pipeline (classifier none) has no step of its own: give ema_decay to the GraphEngine it trains in")
         self.fc_keep = check_fc_dropout(cfg.fc_dropout_keep_prob)      # 0: off; 1: on paper only, nothing is launched
@@ -777,6 +832,7 @@ class LRCNEngine:
             raise VltfError("a feature pipeline (classifier none) has no step of its own: give tensor_stats_interval to the GraphEngine "
                             "it trains in")
         self._stats_setup(cfg.tensor_stats_interval)
+        self._lars_setup()
         self._skip = torch.zeros(1, dtype=torch.int32, device=dev)      # ops.step_guard: the optimizer launch's skip word
         self.probe, self.probe_events = None, []
         self._resizers = {}
@@ -926,6 +982,9 @@ class LRCNEngine:
         rows = ops.stat_rows(self.stat_out, len(self.stat_segs))
         ss = float(self.stat_ss.item())
         stats, mean = tensor_stats_report(self.stat_segs, rows, self.plan.tiers, meta["lr"], meta["clip_norm"], ss)
+        if getattr(self, "lars", None) is not None:          # the trust ratios of that update (kept by _lars_trust_launch)
+            for name, t in self._lars_named(self.lars["stat_trust"]).items():
+                stats[name]["lars_trust"] = t
         self._stats_last = dict(update=meta["update"], tensor_stats=stats, grads_norm_mean=mean)
         return self._stats_last
 
@@ -943,6 +1002,52 @@ class LRCNEngine:
             torch.cuda.synchronize(self.dev)
             self._stats_collect()
         return None if self._stats_last is None else self._stats_last["tensor_stats"]
+
+    # ---- LARS (lars_eeta; shared with GraphEngine) ----------------------------------------------------------------------------------------
+    def _lars_setup(self):
+        """Off (lars_eeta 0, or an engine that does not train): nothing is allocated and no launch changes.  On: the tables of lars_ranges,
+        rows and a chunk workspace of its own for the tensor_stats launch over the raw gradient (not the logging option's: that one runs
+        on the regularised gradient, and only when due) and the trust table -- allocated here, never inside a capture.  No optimizer
+        state: the momentum accumulator is all a checkpoint needs."""
+        self.lars = None
+        if not (self.lars_eeta > 0.0 and self.training):
+            return
+        ranges, segs, decays = lars_ranges(self.specs, self.plan, self.weight_decay)
+        n = len(segs)
+        L = dict(ranges=ranges, segs=segs, decays=decays, names=[name for name, _, _ in stat_segments(self.specs, self.plan)],
+                 trust=torch.ones(max(n, 1), device=self.dev), stat_trust=None)
+        if n:
+            L["rows"] = torch.empty(n * ops.STAT_ROW_BYTES, dtype=torch.uint8, device=self.dev)
+            L["ws"] = torch.empty(ops.tensor_stats_ws_bytes(segs), dtype=torch.uint8, device=self.dev)
+        if self.stat_segs is not None:            # a stats step keeps its update's table for _stats_collect, as stat_ss keeps the norm
+            L["stat_trust"] = torch.ones(max(n, 1), device=self.dev)
+        self.lars = L
+
+    def _lars_stats_launch(self):
+        """_finish_step, before the regulariser: Σw² and Σg² of every weight tensor while g is still the raw gradient."""
+        if self.lars is not None and self.lars["segs"]:
+            ops.tensor_stats(self.w, self.g, self.lars["segs"], self.lars["rows"], self.lars["ws"])
+
+    def _lars_trust_launch(self, clip_norm, stats_step):
+        """_finish_step, behind the norm: the rows and the clip scale (of the regularised gradient) -> the trust table."""
+        L = self.lars
+        if L["segs"]:
+            ops.lars_trust(L["rows"], L["decays"], L["trust"], self.lars_eeta, self.lars_epsilon, clip_norm, self.ss, 1.0)
+        if stats_step and L["stat_trust"] is not None:
+            L["stat_trust"].copy_(L["trust"])
+
+    def _lars_named(self, table):
+        t = table.detach().cpu().numpy()
+        idx = {name: k for k, (name, _, _) in enumerate(self.lars["segs"])}
+        return collections.OrderedDict((name, float(t[idx[name]]) if name in idx else 1.0) for name in self.lars["names"])
+
+    def lars_trust(self):
+        """{variable name: trust ratio} of the most recent update, every trained variable in flat order: what the device computed for
+        the weight tensors, 1.0 for the biases (and for everything before the first update).  Frozen variables are absent.  Synchronises."""
+        if getattr(self, "lars", None) is None:
+            raise VltfError("this engine computes no trust ratios (lars_eeta is 0, or it was built with training=False)")
+        torch.cuda.synchronize(self.dev)
+        return self._lars_named(self.lars["trust"])
 
     # ---- optimizer state (what tf.train.Saver() keeps besides the weights, feeder.py:201: Adam slots + beta powers) -------
     OPT_PREFIX = "__optimizer__/"
@@ -1620,23 +1725,30 @@ class LRCNEngine:
         if self.dp is not None:
             self.dp.wait()
         tiers = None if self.plan.full_range() else self.plan.tiers      # None: the plain calls (one full-range tier, same bits)
+        self._lars_stats_launch()                 # LARS: the norms of the raw gradient, before the regulariser writes over it
         if self.decay is not None:                # g <- g + decay w in place; self.ss = self.ss2[:1] is the regularised gradient's norm
             ops.l2_regularize(self.w, self.g, self.decay, self.ss2, self.small_ws)
         elif tiers is None:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
-        if self._stats_due():
+        stats_step = self._stats_due()
+        if stats_step:
             self._stats_launch(lr, clip_norm)
         self.step_count += 1
         # a step whose LSTM cluster launch timed out must not reach the weights -- also with fetch=False, where the host reads the
         # status only later: the optimizer launch drops the update on the device (ops.step_guard), check_status raises at the next fetch
         skip = ops.step_guard(self._skip, getattr(self, "lstm_ws", None), self.lstm_ws_graph)
+        if self.lars is not None:
+            self._lars_trust_launch(clip_norm, stats_step)
         if self._tag_off is not None:             # captured: lr and Adam's step size from the step state (written before each replay)
             if self.cfg.optimizer == "adam" and tiers is not None:
                 ops.adam_apply_tiers_st(self.w, self.g, self.adam_m, self.adam_v, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
             elif self.cfg.optimizer == "adam":
                 ops.adam_apply_st(self.w, self.g, self.adam_m, self.adam_v, self.state, clip_norm, self.ss, 1.0, skip=skip)
+            elif self.lars is not None:
+                ops.lars_apply_st(self.w, self.g, self.mom, self.lars["ranges"], self.lars["trust"], self.state, self.momentum,
+                                  self.nesterov, clip_norm, self.ss, 1.0, skip=skip)
             elif self.mom is not None:
                 ops.momentum_apply_st(self.w, self.g, self.mom, self.state, self.momentum, self.nesterov, clip_norm, self.ss, 1.0,
                                       skip=skip, tiers=tiers)
@@ -1648,6 +1760,9 @@ class LRCNEngine:
             ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         elif self.cfg.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.lars is not None:
+            ops.lars_apply(self.w, self.g, self.mom, self.lars["ranges"], self.lars["trust"], lr, self.momentum, self.nesterov, clip_norm,
+                           self.ss, 1.0, skip=skip)
         elif self.mom is not None:
             ops.momentum_apply(self.w, self.g, self.mom, lr, self.momentum, self.nesterov, clip_norm, self.ss, 1.0, skip=skip, tiers=tiers)
         elif tiers is not None:

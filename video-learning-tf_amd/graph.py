@@ -40,7 +40,7 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_momentum,
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_lars, check_momentum,
                      check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
 
 
@@ -752,7 +752,8 @@ def model_specs(pipelines, datasets, num_classes):
 class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
-                 accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False):
+                 accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
+                 lars_eeta=0.0, lars_epsilon=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -763,13 +764,16 @@ class GraphEngine:
         tensor_stats_interval: per-variable gradient / weight statistics every N updates (engine.stat_segments over this engine's
         variable list, `<pipeline>/<tf name>` in a scoped model; LRCNEngine._stats_launch); None / 0 = off.  ema_decay, ema_warmup:
         tf.train.ExponentialMovingAverage's shadow of every variable of the model, averaged over the trained ranges after each update
-        (engine.check_ema, engine.ema_rate, LRCNEngine._ema_launch); 0 = off."""
+        (engine.check_ema, engine.ema_rate, LRCNEngine._ema_launch); 0 = off.  lars_eeta, lars_epsilon: tf.contrib.opt.LARSOptimizer's
+        trust ratio on the learning rate of every trained weight tensor of rank >= 2 of every pipeline (engine.check_lars,
+        engine.lars_ranges, LRCNEngine._lars_setup); needs momentum > 0; 0 = off."""
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
         self.momentum, self.nesterov = check_momentum(optimizer, momentum, nesterov)
         self.weight_decay = check_weight_decay(weight_decay)
         self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
+        self.lars_eeta, self.lars_epsilon = check_lars(optimizer, self.momentum, lars_eeta, lars_epsilon)
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
@@ -777,6 +781,7 @@ class GraphEngine:
         self.decay = decay_ranges(self.specs, self.plan, self.weight_decay) if self.weight_decay > 0.0 and training else None
         self._allocate()
         self._stats_setup(tensor_stats_interval)
+        self._lars_setup()
 
     def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
         """The graph, its variable list and its training plan (self.nodes, self.specs, self.plan): host logic only, no device
@@ -952,6 +957,8 @@ class GraphEngine:
     _stats_setup, _stats_due, _stats_launch, _stats_note = (LRCNEngine._stats_setup, LRCNEngine._stats_due, LRCNEngine._stats_launch,
                                                             LRCNEngine._stats_note)
     _stats_collect, _stats_result, tensor_stats = LRCNEngine._stats_collect, LRCNEngine._stats_result, LRCNEngine.tensor_stats
+    _lars_setup, _lars_stats_launch, _lars_trust_launch = LRCNEngine._lars_setup, LRCNEngine._lars_stats_launch, LRCNEngine._lars_trust_launch
+    _lars_named, lars_trust = LRCNEngine._lars_named, LRCNEngine.lars_trust
 
     def logits_host(self):
         self._sync()
@@ -1121,20 +1128,27 @@ class GraphEngine:
         if self.dp is not None:
             self.dp.wait()
         tiers = None if self.plan.full_range() else self.plan.tiers      # LRCNEngine._finish_step
+        self._lars_stats_launch()
         if self.decay is not None:
             ops.l2_regularize(self.w, self.g, self.decay, self.ss2, self.small_ws)
         elif tiers is None:
             ops.sumsq(self.g, self.ss, self.small_ws)
         else:
             ops.sumsq_tiers(self.g, tiers, self.ss, self.small_ws)
-        if self._stats_due():
+        stats_step = self._stats_due()
+        if stats_step:
             self._stats_launch(lr, clip_norm)
         self.step_count += 1
         skip = ops.step_guard(self._skip, *[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])   # LRCNEngine._finish_step
+        if self.lars is not None:
+            self._lars_trust_launch(clip_norm, stats_step)
         if tiers is not None and self.optimizer == "adam":
             ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         elif self.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
+        elif self.lars is not None:
+            ops.lars_apply(self.w, self.g, self.mom, self.lars["ranges"], self.lars["trust"], lr, self.momentum, self.nesterov, clip_norm,
+                           self.ss, 1.0, skip=skip)
         elif self.mom is not None:
             ops.momentum_apply(self.w, self.g, self.mom, lr, self.momentum, self.nesterov, clip_norm, self.ss, 1.0, skip=skip, tiers=tiers)
         elif tiers is not None:

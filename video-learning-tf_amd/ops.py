@@ -886,6 +886,70 @@ def momentum_apply_st(w, g, accum, state, momentum, nesterov=False, clip_norm=0.
               _p(sumsq_t), gscale, _skip_word(skip), arr, n, stream())
 
 
+# ---- LARS (vltf.h: vl_lars_trust, vl_lars_apply): per-variable trust ratios on the device, the momentum update through them ---------------
+def lars_trust(rows, decay, trust, eeta, eps=0.0, clip_norm=0.0, sumsq_t=None, gscale=1.0):
+    """trust[k] = eeta * |w_k| / (sc * |g_k| + decay[k] * |w_k| + eps) from row k of a tensor_stats `out` (rows: its uint8 tensor), or 1
+    where a norm is 0 or the row counts a non-finite element; sc is the clip scale the update forms from clip_norm, sumsq_t and gscale.
+    decay: one coefficient per row, on the host, any number of rows: ceil(n / MAX_STAT_SEGMENTS) launches over consecutive slices, as
+    tensor_stats.  trust: float32 device tensor of at least len(decay) entries, overwritten."""
+    _f32(trust, sumsq_t)
+    decay = [float(d) for d in decay]
+    n = len(decay)
+    if n == 0:
+        raise _ffi.VltfError("lars_trust: no segments")
+    if rows is None or not (rows.is_cuda and rows.dtype == torch.uint8 and rows.is_contiguous()) or rows.numel() < n * STAT_ROW_BYTES:
+        raise _ffi.VltfError("lars_trust: rows must be a contiguous CUDA/HIP uint8 tensor of %d bytes per segment" % STAT_ROW_BYTES)
+    if trust.numel() < n:
+        raise _ffi.VltfError("lars_trust: trust needs %d floats, has %d" % (n, trust.numel()))
+    for lo in range(0, n, MAX_STAT_SEGMENTS):
+        part = decay[lo:lo + MAX_STAT_SEGMENTS]
+        arr = (_ffi.f32 * len(part))(*part)
+        _ffi.call("vl_lars_trust", rows.data_ptr() + lo * STAT_ROW_BYTES, len(part), float(eeta), float(eps), arr, clip_norm, _p(sumsq_t),
+                  gscale, trust.data_ptr() + 4 * lo, stream())
+
+
+def _lars_slices(ranges):
+    """[(begin, end, lr_mult, trust_index)] -> [(vl_lars_range array, count)] over consecutive slices of MAX_STAT_SEGMENTS entries; the
+    library validates each."""
+    ranges = list(ranges)
+    out = []
+    for lo in range(0, max(len(ranges), 1), MAX_STAT_SEGMENTS):
+        part = ranges[lo:lo + MAX_STAT_SEGMENTS]
+        arr = (_ffi.LarsRange * max(len(part), 1))()
+        for k, (a, b, mult, ti) in enumerate(part):
+            arr[k].begin, arr[k].end, arr[k].lr_mult, arr[k].trust_index = int(a), int(b), float(mult), int(ti)
+        out.append((arr, len(part)))
+    return out
+
+
+def _lars_trust_arg(trust):
+    if trust is None:
+        return None, 0
+    _f32(trust)
+    return _p(trust), trust.numel()
+
+
+def lars_apply(w, g, accum, ranges, trust, lr, momentum, nesterov=False, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """momentum_apply over ranges = [(begin, end, lr_mult, trust_index)], each with lr * lr_mult * trust[trust_index] (index -1: trust 1,
+    nothing read); trust is read on the device when the launch runs (lars_trust).  One launch per MAX_STAT_SEGMENTS ranges."""
+    _f32(w, g, accum, sumsq_t)
+    _momentum_sizes(w, g, accum)
+    tp, nt = _lars_trust_arg(trust)
+    for arr, n in _lars_slices(ranges):
+        _ffi.call("vl_lars_apply", _p(w), _p(g), _p(accum), w.numel(), lr, momentum, int(bool(nesterov)), clip_norm, _p(sumsq_t), gscale,
+                  _skip_word(skip), arr, n, tp, nt, stream())
+
+
+def lars_apply_st(w, g, accum, ranges, trust, state, momentum, nesterov=False, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """lars_apply with lr read from the step state."""
+    _f32(w, g, accum, sumsq_t)
+    _momentum_sizes(w, g, accum)
+    tp, nt = _lars_trust_arg(trust)
+    for arr, n in _lars_slices(ranges):
+        _ffi.call("vl_lars_apply_st", _p(w), _p(g), _p(accum), w.numel(), _state(state), momentum, int(bool(nesterov)), clip_norm,
+                  _p(sumsq_t), gscale, _skip_word(skip), arr, n, tp, nt, stream())
+
+
 def _ema_sizes(shadow, w):
     if shadow.numel() != w.numel():
         raise _ffi.VltfError("ema_update: shadow and w must have one element count")

@@ -58,7 +58,7 @@ def pipeline_net_config(settings, p, dataset):
               weight_decay=settings.train.weight_decay if settings.train else 0.0,
               accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout(),
               tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
-              ema_warmup=settings.get_ema()[1])
+              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1])
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -348,7 +348,7 @@ def main(init_file, seed=0, device=None):
                              accumulate=settings.train.accumulate if settings.train else 1,
                              fc_dropout_keep_prob=settings.get_fc_dropout(),
                              tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
-                             ema_warmup=settings.get_ema()[1])
+                             ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1])
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

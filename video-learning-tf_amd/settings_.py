@@ -24,6 +24,7 @@ class TrainSettings:
     accumulate = 1
     fc_dropout_keep_prob = 0.0
     ema_decay, ema_warmup = 0.0, False
+    lars_eeta, lars_epsilon = 0.0, 0.0
 
 
 class ValSettings:
@@ -55,6 +56,11 @@ class Settings:
         """(train.ema_decay, train.ema_warmup): the shadow weights of tf.train.ExponentialMovingAverage; (0, False) = off, and outside
         the train phase (validation reads a stored shadow through val.use_ema, it keeps none of its own)."""
         return (self.train.ema_decay, self.train.ema_warmup) if self.phase == defs.phase.train else (0.0, False)
+
+    def get_lars(self):
+        """(train.lars_eeta, train.lars_epsilon): tf.contrib.opt.LARSOptimizer's trust ratio on the momentum update; (0, 0) = off, and
+        outside the train phase."""
+        return (self.train.lars_eeta, self.train.lars_epsilon) if self.phase == defs.phase.train else (0.0, 0.0)
 
     def get_tensor_stats_interval(self):
         """logging.tensor_stats_interval (per-variable gradient / weight statistics every N updates); 0 = off, and outside the train phase."""
@@ -241,6 +247,22 @@ class Settings:
                                                           None if obj.get("ema_warmup") == "None" else obj.get("ema_warmup"))
                 except VltfError as ex:
                     error("train.ema_decay / train.ema_warmup: %s" % ex)
+                # LARS, layer-wise adaptive learning rates on the momentum update (tf.contrib.opt.LARSOptimizer; engine.check_lars):
+                # absent / None = off
+                from .engine import check_lars
+                lv = []
+                for key in ("lars_eeta", "lars_epsilon"):
+                    v = obj.get(key)
+                    if isinstance(v, str) and v != "None":       # YAML reads 1e-3 (no dot) and nan / inf as strings
+                        try:
+                            v = float(v)
+                        except ValueError:
+                            pass
+                    lv.append(None if v == "None" else v)
+                try:
+                    t.lars_eeta, t.lars_epsilon = check_lars(t.optimizer, t.momentum, lv[0], lv[1])
+                except VltfError as ex:
+                    error("train.lars_eeta / train.lars_epsilon: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:

@@ -130,6 +130,9 @@ class Train:
             info("Averaging the trained weights: decay %s, warm-up %s (rate max(1 - decay, 9 / (10 + updates)) if on), +%.1f MB of device memory "
                  "for the shadow; validate it with val.use_ema" %
                  (engine.ema_decay, "on" if engine.ema_warmup else "off", ema_extra_bytes(engine.ema.numel()) / 1e6))
+        if getattr(engine, "lars", None) is not None:
+            info("LARS on the momentum update: eeta %s, epsilon %s; %d weight tensors get a trust ratio, the biases learn with the plain rate" %
+                 (engine.lars_eeta, engine.lars_epsilon, len(engine.lars["segs"])))
 
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
