@@ -405,6 +405,16 @@ int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, 
  * and gets dlogits = 0.  The caller divides by the live-row count: grad_scale = 1 / sum(seq_len).  seq_len NULL = vl_softmax_xent. */
 int vl_softmax_xent_len(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows,
                         int batch, int classes, float grad_scale, const int32_t* seq_len, int T, vl_stream_t stream);
+/* vl_softmax_xent_len with label smoothing and top-k hits, one launch (tf.losses.softmax_cross_entropy(label_smoothing=smoothing)):
+ * y'_c = labels_c (1 - smoothing) + smoothing / classes takes the labels' place, per element, in the row loss sum_c y'_c (lse - z_c)
+ * and in dlogits = (softmax - y') * grad_scale; smoothing == 0 gives vl_softmax_xent_len's bits.  0 <= smoothing < 1.
+ * stats is float[3]: [0] += row losses, [1] += top-1 hits, [2] += top-k hits (top_k == 0: untouched).  With t the first arg-max of a
+ * label row, rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}; the row is a top-k hit iff rank < top_k (top_k == 1: the top-1 hit;
+ * top_k >= classes: every live row).  rows: float[3*batch] (losses | top-1 hits | top-k hits) or NULL, as above.  seq_len NULL:
+ * every row is live.  No atomics: the sums are bitwise reproducible. */
+int vl_softmax_xent_ls(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows,
+                       int batch, int classes, float grad_scale, const int32_t* seq_len, int T, float smoothing, int top_k,
+                       vl_stream_t stream);
 
 /* ---- optimizer: clip_by_global_norm + GradientDescentOptimizer (train.py:199-222) ---------------
  * vl_sumsq: out[0] (+)= sum g^2 over count elements (ws: float[1024]); accumulate != 0 adds to out. */

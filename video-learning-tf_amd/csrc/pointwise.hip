@@ -1876,6 +1876,168 @@ extern "C" int vl_softmax_xent_len(const float* logits, const int32_t* labels, f
     return softmax_xent(logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, seq_len ? T : 1, (hipStream_t)stream);
 }
 
+// ---- label smoothing + top-k hits (vl_softmax_xent_ls) ----------------------------------------------------------------------------
+// The row of softmax_xent_row with y' = y (1 - eps) + eps / C in place of y, per element (not the algebraic form: at eps == 0 y' is y
+// exactly and every sum is the one above, bit for bit), and one more lane-strided pass for the label's rank among the logits:
+// rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}, t the first arg-max of the label row; a top-k hit iff rank < k (k == 0: no pass).
+// A function of its own, so that the three kernels above keep their code.
+__device__ __forceinline__ void softmax_xent_ls_row(const float* __restrict__ z, const int32_t* __restrict__ y, float* __restrict__ dz,
+                                                    int C, float gscale, float eps, int top_k, int lane, float& loss, float& hit,
+                                                    float& hitk) {
+    float mx = -INFINITY;
+    int am = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const float v = z[c];
+        if (v > mx) {
+            mx = v;
+            am = c;
+        }
+    }
+    const float gmx = wave_max(mx);
+    int cand = (mx == gmx) ? am : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
+    se = wave_sum(se);
+    const float lse = logf(se) + gmx;
+    const float on = 1.0f - eps, off = eps / (float)C;
+    float l = 0.f;
+    int ymax = -2147483647 - 1, yarg = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const int yv = y[c];
+        const float ys = (float)yv * on + off;
+        l += ys * (lse - z[c]);
+        if (yv > ymax) {
+            ymax = yv;
+            yarg = c;
+        }
+        if (dz) dz[c] = (expf(z[c] - lse) - ys) * gscale;
+    }
+    l = wave_sum(l);
+    int gy = ymax;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gy = max(gy, __shfl_xor(gy, o, 64));
+    int ycand = (ymax == gy) ? yarg : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ycand = min(ycand, __shfl_xor(ycand, o, 64));
+    loss = l;
+    hit = (cand == ycand) ? 1.f : 0.f;
+    hitk = 0.f;
+    if (top_k > 0) {                              // (uniform over the wave: every lane takes part in the shuffles)
+        const int t = min(ycand, C - 1);          // (ycand < C unless every label is INT_MIN: never index past the row)
+        const float zt = z[t];
+        int rank = 0;
+        for (int c = lane; c < C; c += 64) {
+            const float v = z[c];
+            rank += (v > zt || (v == zt && c < t)) ? 1 : 0;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+        hitk = rank < top_k ? 1.f : 0.f;
+    }
+}
+
+__global__ void softmax_xent_ls_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                       float* __restrict__ dlogits, float* __restrict__ stats, int batch, int C, float gscale,
+                                       const int32_t* __restrict__ seq_len, int T, float eps, int top_k) {
+    __shared__ float sl[4], sc[4], sk[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float loss_acc = 0.f, corr_acc = 0.f, topk_acc = 0.f;
+    for (int b = wv; b < batch; b += 4) {
+        float l, h, hk;
+        if (xent_row_dead(seq_len, T, b)) {
+            xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+            continue;
+        }
+        softmax_xent_ls_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
+                            eps, top_k, lane, l, h, hk);
+        loss_acc += l;
+        corr_acc += h;
+        topk_acc += hk;
+    }
+    if (lane == 0) {
+        sl[wv] = loss_acc;
+        sc[wv] = corr_acc;
+        sk[wv] = topk_acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
+        stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
+        if (top_k > 0) stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
+    }
+}
+
+__global__ void softmax_xent_ls_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                            float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale,
+                                            const int32_t* __restrict__ seq_len, int T, float eps, int top_k) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= batch) return;
+    float l = 0.f, h = 0.f, hk = 0.f;
+    if (xent_row_dead(seq_len, T, b))
+        xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+    else
+        softmax_xent_ls_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
+                            eps, top_k, lane, l, h, hk);
+    if (lane == 0) {
+        rows[b] = l;
+        rows[batch + b] = h;
+        rows[2 * (int64_t)batch + b] = hk;
+    }
+}
+
+// softmax_xent_sum_kernel with a third column: rows[2 batch .. 3 batch) top-k hits -> stats[2] (top_k == 0: stats[2] is not touched).
+// Columns 0 and 1 are added in the order of that kernel, so stats[0] and stats[1] are its bits.
+__global__ void softmax_xent_ls_sum_kernel(const float* __restrict__ rows, float* __restrict__ stats, int batch, int top_k) {
+    __shared__ float sl[256], sc[256], sk[256];
+    float l = 0.f, h = 0.f, hk = 0.f;
+    for (int b = threadIdx.x; b < batch; b += 256) {
+        l += rows[b];
+        h += rows[batch + b];
+        hk += rows[2 * (int64_t)batch + b];
+    }
+    sl[threadIdx.x] = l;
+    sc[threadIdx.x] = h;
+    sk[threadIdx.x] = hk;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sl[threadIdx.x] += sl[threadIdx.x + s];
+            sc[threadIdx.x] += sc[threadIdx.x + s];
+            sk[threadIdx.x] += sk[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        stats[0] += sl[0];
+        stats[1] += sc[0];
+        if (top_k > 0) stats[2] += sk[0];
+    }
+}
+
+extern "C" int vl_softmax_xent_ls(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                  int classes, float grad_scale, const int32_t* seq_len, int T, float smoothing, int top_k,
+                                  vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_ls: bad argument");
+    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_ls: batch (%d rows) is not whole sequences of T = %d", batch, T);
+    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_ls: smoothing must lie in [0, 1), got %g", (double)smoothing);
+    VL_CHECK(top_k >= 0, "vl_softmax_xent_ls: top_k must be >= 0, got %d", top_k);
+    const int Tl = seq_len ? T : 1;
+    if (!rows) {
+        hipLaunchKernelGGL(softmax_xent_ls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch,
+                           classes, grad_scale, seq_len, Tl, smoothing, top_k);
+        VL_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL(softmax_xent_ls_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits,
+                       rows, batch, classes, grad_scale, seq_len, Tl, smoothing, top_k);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_ls_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch, top_k);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- global norm + SGD / Adam (train.py:199-222) ----------------------------------------------
 // ---- tier table (vltf.h: vl_lr_tier): the ranges of the flat buffer an update / a norm touches, by value in the launch arguments --
 struct tier_table {

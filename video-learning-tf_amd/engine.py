@@ -70,6 +70,8 @@ class NetConfig:
     ema_warmup: bool = False                    # train.ema_warmup: its num_updates form, decay min(decay, (1 + n) / (10 + n)) (ema_rate)
     lars_eeta: float = 0.0                      # train.lars_eeta: tf.contrib.opt.LARSOptimizer's eeta, > 0 (needs momentum > 0); 0 = no LARS
     lars_epsilon: float = 0.0                   # train.lars_epsilon: its epsilon, >= 0, added to the trust ratio's denominator (lars_ranges)
+    label_smoothing: float = 0.0                # train.label_smoothing: tf.losses.softmax_cross_entropy's, in [0, 1); 0 = hard labels
+    top_k: int = 0                              # train.top_k: also count the rows whose label is among the k largest logits; 0 = off
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -264,6 +266,34 @@ def check_fc_dropout(keep_prob):
     k = float(keep_prob)
     if not (0.0 <= k <= 1.0):                     # (NaN fails both)
         raise VltfError("fc_dropout_keep_prob must be a number in [0, 1] (0 = off), got %r" % (keep_prob,))
+    return k
+
+
+def check_label_smoothing(label_smoothing):
+    """The label smoothing of the loss as a float, None read as 0 (off).  Accepted: [0, 1).  Refused: negative, 1 or above, NaN,
+    infinite, not a number (booleans included)."""
+    if label_smoothing is None:
+        return 0.0
+    if isinstance(label_smoothing, (bool, np.bool_, str, bytes)) or not isinstance(label_smoothing, (int, float, np.integer, np.floating)):
+        raise VltfError("label_smoothing must be a number in [0, 1) (0 / None = off), got %r" % (label_smoothing,))
+    s = float(label_smoothing)
+    if not (0.0 <= s < 1.0):                      # (NaN fails both, inf the second)
+        raise VltfError("label_smoothing must be a number in [0, 1) (0 / None = off), got %r" % (label_smoothing,))
+    return s
+
+
+def check_top_k(top_k):
+    """The k of the top-k accuracy as an int, None read as 0 (off).  A k above the row width is allowed (every live row is a hit).
+    Refused: bools, strings, floats that are not whole (NaN and inf among them), values < 0."""
+    if top_k is None:
+        return 0
+    if isinstance(top_k, (bool, np.bool_, str, bytes)) or not isinstance(top_k, (int, float, np.integer, np.floating)):
+        raise VltfError("top_k must be a whole number >= 0 (0 / None = off), got %r" % (top_k,))
+    if isinstance(top_k, (float, np.floating)) and not (math.isfinite(top_k) and float(top_k) == int(top_k)):
+        raise VltfError("top_k must be a whole number >= 0 (0 / None = off), got %r" % (top_k,))
+    k = int(top_k)
+    if not (0 <= k <= 0x7fffffff):
+        raise VltfError("top_k must be a whole number >= 0 (0 / None = off), got %r" % (top_k,))
     return k
 
 
@@ -816,8 +846,7 @@ class LRCNEngine:
         self.rows_out = self.logits.shape[0]
         if training:
             self.dlogits = buf(*self.logits.shape)
-        self.stats = torch.zeros(2, device=dev)
-        self.loss_rows = torch.zeros(2 * self.rows_out, device=dev)     # per-row losses | hits (vl_softmax_xent workspace)
+        self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out)
         self.ss = torch.zeros(1, device=dev)
         # L2 weight decay: ops.l2_regularize takes the norm's place in _finish_step and returns {sum g'^2, regulariser}; the update calls
         # and _fetch read the first word through self.ss.  Off: nothing is allocated, the norm calls are the ones of before.
@@ -1002,6 +1031,31 @@ class LRCNEngine:
             torch.cuda.synchronize(self.dev)
             self._stats_collect()
         return None if self._stats_last is None else self._stats_last["tensor_stats"]
+
+    # ---- label smoothing / top-k accuracy (label_smoothing, top_k; setup and fetch shared with GraphEngine) -------------------------------------
+    def _loss_setup(self, label_smoothing, top_k, rows):
+        """Both off (or an engine that does not train: validation computes no loss): the two sums and the 2 * rows workspace of
+        ops.softmax_xent, as ever.  Either on: three sums and 3 * rows, for ops.softmax_xent_ls."""
+        self.label_smoothing, self.top_k = check_label_smoothing(label_smoothing), check_top_k(top_k)
+        if not self.training:
+            self.label_smoothing, self.top_k = 0.0, 0
+        self.xent_ls = self.label_smoothing > 0.0 or self.top_k > 0
+        cols = 3 if self.xent_ls else 2
+        self.stats = torch.zeros(cols, device=self.dev)
+        self.loss_rows = torch.zeros(cols * rows, device=self.dev)      # per-row losses | hits (| top-k hits): the loss launch's workspace
+
+    def _xent_launch(self, logits, onehot, dlogits, grad_scale):
+        """The loss launch of a train step: stats += {loss sum, hits (, top-k hits)}, dlogits = (softmax - labels') * grad_scale."""
+        if self.xent_ls:
+            ops.softmax_xent_ls(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k)
+        else:
+            ops.softmax_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows)
+
+    def _fetch_topk(self, out, st, rows):
+        """_fetch: with top_k > 0 the result gains the top-k accuracy of the rows so far and the count behind it."""
+        if getattr(self, "top_k", 0) > 0:
+            out["topk_accuracy"], out["topk_correct"] = float(st[2]) / max(rows, 1), float(st[2])
+        return out
 
     # ---- LARS (lars_eeta; shared with GraphEngine) ----------------------------------------------------------------------------------------
     def _lars_setup(self):
@@ -1686,7 +1740,7 @@ class LRCNEngine:
             # mean over the GLOBAL batch (train.py:123): each rank scales its rows by 1/global_rows and the all-reduce sums.
             # global_rows defaults to rows*world*k (equal shards, equal micro-batches); a workflow with ragged shards or unequal
             # micro-batches passes the true count of the whole update on every call.
-            ops.softmax_xent(self.logits[:rows], onehot, self.dlogits, self.stats, 1.0 / (global_rows or rows * world * k), self.loss_rows)
+            self._xent_launch(self.logits[:rows], onehot, self.dlogits, 1.0 / (global_rows or rows * world * k))
             self._backward(n, b)
         finally:
             self._mi = None
@@ -1780,10 +1834,11 @@ class LRCNEngine:
         self.check_status()
         st = self.stats.cpu().numpy()
         if partial:
-            return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows, "loss_sum": float(st[0]),
-                    "correct": float(st[1])}
+            return self._fetch_topk({"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows,
+                                     "loss_sum": float(st[0]), "correct": float(st[1])}, st, rows)
         out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "grad_norm": math.sqrt(float(self.ss.item())),
                "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        self._fetch_topk(out, st, rows)
         if self.ss2 is not None:                  # the regulariser at the weights the forward pass used; `loss` stays the data loss
             out["reg_loss"] = float(self.ss2[1].item())
         return self._stats_result(out)

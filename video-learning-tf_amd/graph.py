@@ -40,8 +40,9 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_lars, check_momentum,
-                     check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers, param_specs, tier_plan)
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_label_smoothing,
+                     check_lars, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
+                     param_specs, tier_plan)
 
 
 @dataclass
@@ -753,7 +754,7 @@ class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
-                 lars_eeta=0.0, lars_epsilon=0.0):
+                 lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -766,7 +767,10 @@ class GraphEngine:
         tf.train.ExponentialMovingAverage's shadow of every variable of the model, averaged over the trained ranges after each update
         (engine.check_ema, engine.ema_rate, LRCNEngine._ema_launch); 0 = off.  lars_eeta, lars_epsilon: tf.contrib.opt.LARSOptimizer's
         trust ratio on the learning rate of every trained weight tensor of rank >= 2 of every pipeline (engine.check_lars,
-        engine.lars_ranges, LRCNEngine._lars_setup); needs momentum > 0; 0 = off."""
+        engine.lars_ranges, LRCNEngine._lars_setup); needs momentum > 0; 0 = off.  label_smoothing, top_k: the smoothed labels of
+        tf.losses.softmax_cross_entropy and the top-k hit count, both in the loss launch of the last pipeline (engine.check_label_smoothing,
+        engine.check_top_k, LRCNEngine._loss_setup); a forward-only engine ignores them; 0 = off."""
+        self._loss_opts = (check_label_smoothing(label_smoothing), check_top_k(top_k))
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
@@ -887,8 +891,7 @@ class GraphEngine:
         self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None   # LRCNEngine.__init__: the running sum
         self.ema = torch.zeros(total, device=dev) if self.ema_decay > 0.0 and training else None   # LRCNEngine.__init__: the shadow weights
         rows = self.last.max_rows
-        self.stats = torch.zeros(2, device=dev)
-        self.loss_rows = torch.zeros(2 * rows, device=dev)
+        self._loss_setup(*self._loss_opts, rows)
         self.ss = torch.zeros(1, device=dev)
         self.ss2 = None
         if self.decay is not None:                # L2 weight decay (LRCNEngine.__init__): {sum g'^2, regulariser}, self.ss its first word
@@ -959,6 +962,14 @@ class GraphEngine:
     _stats_collect, _stats_result, tensor_stats = LRCNEngine._stats_collect, LRCNEngine._stats_result, LRCNEngine.tensor_stats
     _lars_setup, _lars_stats_launch, _lars_trust_launch = LRCNEngine._lars_setup, LRCNEngine._lars_stats_launch, LRCNEngine._lars_trust_launch
     _lars_named, lars_trust = LRCNEngine._lars_named, LRCNEngine.lars_trust
+    _loss_setup, _fetch_topk = LRCNEngine._loss_setup, LRCNEngine._fetch_topk
+
+    def _xent_launch(self, logits, onehot, dlogits, grad_scale, **lengths):
+        """LRCNEngine._xent_launch through this module's ops (lengths: seq_len and T of a loss masked by seq_len, or nothing)."""
+        if self.xent_ls:
+            ops.softmax_xent_ls(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k, **lengths)
+        else:
+            ops.softmax_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, **lengths)
 
     def logits_host(self):
         self._sync()
@@ -1043,10 +1054,9 @@ class GraphEngine:
             ops.fill(self.stats, 0.0)
         last = self.last
         if n_valid is not None:       # padded steps are kept out of the loss (non_padding_index, dataset_.py:327-383)
-            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or n_valid * k), self.loss_rows,
-                             seq_len=last.seq_len, T=last.fpc)
+            self._xent_launch(last.out[:rows], onehot, last.dout, 1.0 / (global_rows or n_valid * k), seq_len=last.seq_len, T=last.fpc)
         else:
-            ops.softmax_xent(last.out[:rows], onehot, last.dout, self.stats, 1.0 / (global_rows or rows * world * k), self.loss_rows)
+            self._xent_launch(last.out[:rows], onehot, last.dout, 1.0 / (global_rows or rows * world * k))
         # backward, last pipeline first.  RCCL chunks are held back while an LSTM backward launch is still to come: the cluster
         # form of the recurrence needs every CU and must not spin under an all-reduce kernel that holds some (vl_lstm_seq_status)
         self._pending_lstm = sum(1 for nd in self.nodes if nd.cls == "lstm")
@@ -1166,10 +1176,11 @@ class GraphEngine:
         self.check_status()
         st = self.stats.cpu().numpy()
         if partial:
-            return {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows, "loss_sum": float(st[0]),
-                    "correct": float(st[1])}
+            return self._fetch_topk({"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1), "rows": rows,
+                                     "loss_sum": float(st[0]), "correct": float(st[1])}, st, rows)
         out = {"loss": float(st[0]) / max(rows, 1), "accuracy": float(st[1]) / max(rows, 1),
                "grad_norm": math.sqrt(float(self.ss.item())), "rows": rows, "loss_sum": float(st[0]), "correct": float(st[1])}
+        self._fetch_topk(out, st, rows)
         if self.ss2 is not None:
             out["reg_loss"] = float(self.ss2[1].item())
         return self._stats_result(out)

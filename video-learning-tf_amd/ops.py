@@ -637,6 +637,29 @@ def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None, seq_len=
     _ffi.call("vl_softmax_xent", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, stream())
 
 
+def softmax_xent_ls(logits, labels, dlogits, stats, grad_scale, rows, smoothing, top_k, seq_len=None, T=None):
+    """softmax_xent with label smoothing (y' = y (1 - smoothing) + smoothing / classes) and top-k hits in the same launch
+    (vl_softmax_xent_ls).  stats: 3 floats (loss sum, top-1 hits, top-k hits; top_k 0 leaves the third alone); rows: None or a float32
+    workspace of >= 3*batch elements.  seq_len / T as in softmax_xent."""
+    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
+    if labels.dtype != torch.int32:
+        raise _ffi.VltfError("softmax_xent_ls: labels must be int32 one-hot")
+    b, c = logits.shape
+    if stats.numel() < 3:
+        raise _ffi.VltfError("softmax_xent_ls: stats needs 3 floats")
+    if rows is not None:
+        _f32(rows)
+        if rows.numel() < 3 * b:
+            raise _ffi.VltfError("softmax_xent_ls: rows workspace needs 3*batch floats")
+    sl, t = None, 1
+    if seq_len is not None:
+        if not T or T < 1 or b % int(T):
+            raise _ffi.VltfError("softmax_xent_ls: seq_len needs T with rows = clips * T (rows %d, T %s)" % (b, T))
+        sl, t = _seq_len(seq_len, b // int(T), "softmax_xent_ls"), int(T)
+    _ffi.call("vl_softmax_xent_ls", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, _p(sl), t,
+              float(smoothing), int(top_k), stream())
+
+
 def sumsq(g, out, ws, accumulate=False):
     _f32(g, out, ws)
     if ws.numel() < 1024:

@@ -58,7 +58,8 @@ def pipeline_net_config(settings, p, dataset):
               weight_decay=settings.train.weight_decay if settings.train else 0.0,
               accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout(),
               tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
-              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1])
+              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
+              label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k())
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -218,6 +219,8 @@ def do_train(settings, train, feeder, engine):
             reg = "+ L2 regulariser : %2.6f" % train.last["reg_loss"] if "reg_loss" in train.last else ""
             if "grads_norm_mean" in train.last:      # a stats step (logging.tensor_stats_interval): the reference's `grads_norm` summary
                 reg += " gradient norm : %.8g, mean per variable : %.8g" % (train.last["grad_norm"], train.last["grads_norm_mean"])
+            if "topk_accuracy" in train.last:        # train.top_k: of the batch (the update so far), global under data parallelism
+                reg += " top-%d accuracy : %2.5f" % (engine.top_k, train.last["topk_accuracy"])
             info("Learning rate %2.8f, global step: %d, batch loss/nats : %2.5f / %2.3f %s" %
                  (learning_rate, settings.global_step, batch_loss, nats, reg))
             info("Dataset global step %d, epoch index %d, batch sizes %s, batch index train %d" %
@@ -297,6 +300,13 @@ def do_test(settings, val, feeder, engine, rank=0, world=1):
     if val.save_interval is not None:
         with open(os.path.join(settings.run_folder, "accuracy_" + settings.run_id), "w") as f:
             f.write(str(accuracy))
+    top_k = getattr(settings.val, "top_k", 0)
+    if top_k > 0:                                        # val.top_k: the label among the k largest fused logits (val.topk_hits)
+        topk = val.get_topk_accuracy(top_k)
+        info("Validation top-%d accuracy: %2.5f" % (top_k, topk))
+        if val.save_interval is not None:
+            with open(os.path.join(settings.run_folder, "accuracy_top%d_%s" % (top_k, settings.run_id)), "w") as f:
+                f.write(str(topk))
     return accuracy
 
 
@@ -348,7 +358,8 @@ def main(init_file, seed=0, device=None):
                              accumulate=settings.train.accumulate if settings.train else 1,
                              fc_dropout_keep_prob=settings.get_fc_dropout(),
                              tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
-                             ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1])
+                             ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
+                             label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k())
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

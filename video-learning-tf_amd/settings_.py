@@ -25,12 +25,14 @@ class TrainSettings:
     fc_dropout_keep_prob = 0.0
     ema_decay, ema_warmup = 0.0, False
     lars_eeta, lars_epsilon = 0.0, 0.0
+    label_smoothing, top_k = 0.0, 0
 
 
 class ValSettings:
     batch_size, logits_save_interval = 88, -1
     clip_fusion_type, clip_fusion_method = defs.fusion_type.late, defs.fusion_method.avg
     use_ema = False
+    top_k = 0
 
 
 class Settings:
@@ -61,6 +63,15 @@ class Settings:
         """(train.lars_eeta, train.lars_epsilon): tf.contrib.opt.LARSOptimizer's trust ratio on the momentum update; (0, 0) = off, and
         outside the train phase."""
         return (self.train.lars_eeta, self.train.lars_epsilon) if self.phase == defs.phase.train else (0.0, 0.0)
+
+    def get_label_smoothing(self):
+        """train.label_smoothing (tf.losses.softmax_cross_entropy's label_smoothing); 0 = off, and outside the train phase."""
+        return self.train.label_smoothing if self.phase == defs.phase.train else 0.0
+
+    def get_top_k(self):
+        """train.top_k: the k of the top-k accuracy a training step also counts; 0 = off, and outside the train phase (validation ranks
+        its fused logits on the host under val.top_k, Validation.get_topk_accuracy)."""
+        return self.train.top_k if self.phase == defs.phase.train else 0
 
     def get_tensor_stats_interval(self):
         """logging.tensor_stats_interval (per-variable gradient / weight statistics every N updates); 0 = off, and outside the train phase."""
@@ -150,6 +161,21 @@ class Settings:
             return check_tensor_stats_interval(None if n == "None" else n)
         except VltfError as ex:
             error("logging.tensor_stats_interval: %s" % ex)
+
+    @staticmethod
+    def read_top_k(obj, where):
+        """`train: top_k: K` / `val: top_k: K` (this project's extension): absent / None / 0 = off; a quoted number is read as the number."""
+        from .engine import VltfError, check_top_k
+        k = obj.get("top_k")
+        if isinstance(k, str) and k != "None":
+            try:
+                k = int(k)
+            except ValueError:
+                pass
+        try:
+            return check_top_k(None if k == "None" else k)
+        except VltfError as ex:
+            error("%s.top_k: %s" % (where, ex))
 
     # ---- run block (settings_.py:210-366) -------------------------------------------------------------------
     def read_config(self, config, init_file):
@@ -263,6 +289,20 @@ class Settings:
                     t.lars_eeta, t.lars_epsilon = check_lars(t.optimizer, t.momentum, lv[0], lv[1])
                 except VltfError as ex:
                     error("train.lars_eeta / train.lars_epsilon: %s" % ex)
+                # label smoothing of the loss (tf.losses.softmax_cross_entropy(label_smoothing=); engine.check_label_smoothing) and the top-k
+                # accuracy counted in the same launch (engine.check_top_k): absent / None = off
+                from .engine import check_label_smoothing
+                ls = obj.get("label_smoothing")
+                if isinstance(ls, str) and ls != "None":         # a quoted number; nan / inf come as strings too
+                    try:
+                        ls = float(ls)
+                    except ValueError:
+                        pass
+                try:
+                    t.label_smoothing = check_label_smoothing(None if ls == "None" else ls)
+                except VltfError as ex:
+                    error("train.label_smoothing: %s" % ex)
+                t.top_k = self.read_top_k(obj, "train")
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
@@ -282,6 +322,8 @@ class Settings:
                 if not isinstance(ue, bool):
                     error("val.use_ema must be a boolean, got [%s]" % (ue,))
                 v.use_ema = ue
+                # top-k accuracy of the fused per-video logits beside the top-1 one (Validation.get_topk_accuracy): absent / None = off
+                v.top_k = self.read_top_k(obj, "val")
 
         self.feeder = Feeder(defs.input_mode.video, self.phases, (self.train, self.val), self.save_freq_per_epoch, self.run_folder,
                              self.should_resume())

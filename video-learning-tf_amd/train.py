@@ -108,6 +108,23 @@ class TensorStatsLog:
         return rec
 
 
+def dp_scalars(out):
+    """The per-rank sums a data-parallel step adds over the ranks (dp.sum_scalars): loss sum, hits, rows -- and the top-k hits as a
+    fourth only when the engine counts them (train.top_k), so that a run without them exchanges the vector it always did."""
+    v = [out["loss_sum"], out["correct"], float(out["rows"])]
+    if "topk_correct" in out:
+        v.append(out["topk_correct"])
+    return v
+
+
+def dp_global(out, tot):
+    """out with loss / accuracy (/ topk_accuracy) of the GLOBAL batch, from the summed dp_scalars vector."""
+    g = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
+    if "topk_correct" in out:
+        g["topk_accuracy"] = float(tot[3] / max(tot[2], 1))
+    return g
+
+
 class Train:
     """train.py:112-149: owns the LR table and global_step; run_step is the train sess.run.
     train.accumulate k > 1: the batches of an epoch go to the engine in groups (accumulate_groups) as the micro-steps of one update.
@@ -133,6 +150,10 @@ class Train:
         if getattr(engine, "lars", None) is not None:
             info("LARS on the momentum update: eeta %s, epsilon %s; %d weight tensors get a trust ratio, the biases learn with the plain rate" %
                  (engine.lars_eeta, engine.lars_epsilon, len(engine.lars["segs"])))
+
+        if getattr(engine, "xent_ls", False):
+            info("Loss: label smoothing %s (labels y (1 - eps) + eps / %d; the logged loss is the smoothed one), top-k accuracy %s" %
+                 (engine.label_smoothing, settings.num_classes, ("k = %d" % engine.top_k) if engine.top_k > 0 else "off"))
 
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
@@ -198,9 +219,8 @@ class Train:
                                     torch.from_numpy(fdict["crop_y"]).to(dev), torch.from_numpy(fdict["crop_x"]).to(dev),
                                     torch.from_numpy(fdict["mirror"]).to(dev), global_rows=grows, resize=fdict.get("resize"), **kw)
         if dpg is not None:              # log the global-batch loss, not the shard's
-            tot = dpg.sum_scalars(torch.tensor([out["loss_sum"], out["correct"], float(out["rows"])], device=dev, dtype=torch.float64))
-            tot = tot.cpu().numpy()
-            out = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
+            tot = dpg.sum_scalars(torch.tensor(dp_scalars(out), device=dev, dtype=torch.float64))
+            out = dp_global(out, tot.cpu().numpy())
         self.global_step += 1
         self.last = out
         self._stats_step(out, lr)
@@ -234,9 +254,8 @@ class Train:
             out = eng.train_step(graph_feeds(fdicts, sorted(fdicts), dev), torch.from_numpy(np.ascontiguousarray(labels)).to(dev), lr,
                                  self.clip_norm, global_rows=grows, **kw)
         if eng.dp is not None:
-            tot = eng.dp.sum_scalars(torch.tensor([out["loss_sum"], out["correct"], float(out["rows"])], device=dev, dtype=torch.float64))
-            tot = tot.cpu().numpy()
-            out = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
+            tot = eng.dp.sum_scalars(torch.tensor(dp_scalars(out), device=dev, dtype=torch.float64))
+            out = dp_global(out, tot.cpu().numpy())
         self.global_step += 1
         self.last = out
         self._stats_step(out, lr)

@@ -9,6 +9,18 @@ from .defs_ import defs
 from .utils_ import debug, error, info
 
 
+def topk_hits(logits, labels, k):
+    """Per row: the label t (first arg-max of the label row) is among the k largest logits, ties going to the lower index:
+    #{c : z_c > z_t} + #{c < t : z_c == z_t} < k -- the rule of the training loss launch (vl_softmax_xent_ls), the same set as
+    t in np.argsort(-z, kind="stable")[:k].  k = 1 is the arg-max comparison of get_chunk_accuracy."""
+    logits = np.asarray(logits)
+    t = np.argmax(labels, axis=1)
+    zt = logits[np.arange(len(logits)), t][:, None]
+    before = np.arange(logits.shape[1])[None, :] < t[:, None]
+    rank = np.sum(logits > zt, axis=1) + np.sum((logits == zt) & before, axis=1)
+    return rank < int(k)
+
+
 class Validation:
     def __init__(self, settings):
         self.item_logits = np.zeros([0, settings.num_classes], np.float32)
@@ -83,6 +95,18 @@ class Validation:
         if len(self.item_logits) > 0:
             n = len(self.item_logits)
             accuracies.append(self.get_chunk_accuracy(self.item_logits, self.item_labels[cur:cur + n, :]))
+        return float(np.mean(accuracies))
+
+    def get_topk_accuracy(self, k):
+        """get_accuracy with topk_hits(.., k) in place of the arg-max comparison: the same chunks, the same mean of per-chunk means."""
+        accuracies, cur = [], 0
+        for c in range(self.save_counter):
+            logits = self.load_validation_logits_chunk(c)
+            accuracies.append(np.mean(topk_hits(logits, self.item_labels[cur:cur + len(logits), :], k)))
+            cur += len(logits)
+        if len(self.item_logits) > 0:
+            n = len(self.item_logits)
+            accuracies.append(np.mean(topk_hits(self.item_logits, self.item_labels[cur:cur + n, :], k)))
         return float(np.mean(accuracies))
 
     def get_chunk_accuracy(self, logits, labels):
