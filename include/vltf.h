@@ -42,8 +42,11 @@ typedef struct vl_step_state {
     uint32_t tag_origin;   /* origin of the LSTM exchange tags of vl_lstm_seq_*_st */
     float adam_lr;         /* Adam's bias-corrected step size for count step + 1 (written by vl_step_state_set, see there) */
     float ema_rate;        /* 1 - decay of this update's weight average (written by vl_step_state_set_ema alone, see vl_ema_update) */
-    uint32_t reserved[2];
+    uint32_t reserved[2];  /* LAMB's bias corrections as fp32 bit patterns: word VL_STEP_STATE_LAMB_C1 = c1, word VL_STEP_STATE_LAMB_C2 =
+                              c2 (bytes 24 and 28; written by vl_step_state_set_lamb alone, see vl_lamb_moments); 0 until then */
 } vl_step_state;
+#define VL_STEP_STATE_LAMB_C1 0
+#define VL_STEP_STATE_LAMB_C2 1
 
 const char* vl_last_error(void);
 int vl_version(void);
@@ -508,7 +511,8 @@ int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, 
 
 /* ---- L2 weight decay: the regulariser's gradient and both sums in the launch that was the global norm ---------------------------------
  * loss_total = loss + sum_k (decay_k / 2) |w_k|^2 (tf.nn.l2_loss, Caffe weight_decay, torch.optim.SGD(weight_decay=)): the gradient
- * every later stage sees -- the global-norm clip, SGD, momentum, Adam (so Adam gets coupled L2, not AdamW) -- is g + decay w.  This call
+ * every later stage sees -- the global-norm clip, SGD, momentum, Adam (so Adam gets coupled L2, not AdamW; LAMB's decoupled decay,
+ * vl_lamb_moments below, does not use this call) -- is g + decay w.  This call
  * REPLACES vl_sumsq / vl_sumsq_tiers in a step: it writes the regularised gradient over g IN PLACE and returns the two sums; the update
  * entry points above then run unchanged on g, with out as their sumsq.
  * The range table obeys the rules of vl_lr_tier: sorted, disjoint, inside [0, count), 1 .. VL_MAX_DECAY_RANGES entries; decay finite and
@@ -633,6 +637,64 @@ int vl_lars_apply(float* w, const float* g, float* accum, int64_t count, float l
 int vl_lars_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
                      int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
                      const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream);
+
+/* ---- LAMB: layer-wise trust ratios and decoupled decay for the Adam update (You et al. 2019, "Large Batch Optimization for Deep
+ * Learning"; tfa.optimizers.LAMB) ------------------------------------------------------------------------------------------------------
+ * Two calls in the place of vl_adam_apply.  Element rule, fp32, contraction off, one element function for the scalar head / tail and
+ * the 16-byte interior; sc = the clip scale of vl_sgd_apply (clip_norm, *sumsq, gscale), decay = the range's coefficient:
+ *     gi = g * sc
+ *     m' = fma(0.9f, m, 0.1f * gi)                 v' = fma(0.999f, v, gi * (0.001f * gi))       (vl_adam_apply's two lines: the same bits)
+ *     mh = m' * c1        vh = v' * c2             r = mh / (sqrtf(vh) + eps)
+ *     u  = decay > 0 ? fma(decay, w, r) : r        (decoupled decay, AdamW-style: it never enters g, m or v)
+ * c1 = fl32(1 / (1 - 0.9^t)), c2 = fl32(1 / (1 - 0.999^t)) for update t >= 1 come from the caller (ONE host function computes them for
+ * the eager and the replayed form; they are not derived from state->step, which holds the draw step under accumulation).
+ * Per range with trust_index k >= 0 (a weight tensor), in double and rounded to float once:
+ *     wn = sqrt(sum w^2)   un = sqrt(sum u^2)
+ *     trust[k] = wn / un   if wn > 0 and un > 0 and no element of w or u in the range is non-finite,   else 1       (no clamp)
+ * (TF's where(w_norm > 0, where(g_norm > 0, .., 1), 1); a NaN then travels through the update as it does under Adam.)
+ *
+ * vl_lamb_moments: inside every range m <- m', v <- v'; w and g are never written, w is read only inside ranges with trust_index >= 0
+ * (a range with index -1 needs neither norms nor u).  For each range with an index it overwrites rows[index] and trust[index].  The
+ * reduction order is vl_tensor_stats's: chunks of VL_STAT_CHUNK that never span ranges, element j of a chunk into accumulator j mod 1024,
+ * the fixed tree, one workgroup per range for stage 2 (which also forms the trust value), squares formed in double, a non-finite element
+ * adds +0 and counts.  So the bits depend on the table alone and rows[k].w_sumsq equals, bit for bit, the w_sumsq vl_tensor_stats
+ * returns for the same segment.  No atomics.  *skip != 0 when the launch runs: m, v, rows and trust stay untouched.  Elements outside
+ * every range are neither loaded nor stored.  Traffic: 6 floats per element (w, g, m, v read, m, v written).
+ * ws: vl_lamb_moments_ws_bytes(ranges, n_ranges) bytes, 8-byte aligned (one vl_lamb_row per chunk; 0 = the table was refused).
+ *
+ * vl_lamb_apply: w' = fma(-a, u, w), a = (float)((float)(lr * lr_mult) * t), t = 1 for trust_index -1 (nothing read) else
+ * trust[trust_index], one uniform load per range; u is recomputed from the stored m', v' and the unchanged w by the element function
+ * above.  m and v are read-only.  The grid of vl_sgd_apply; 4 floats per element.  *skip != 0: nothing is touched.
+ *
+ * The table obeys the rules of vl_lr_tier (sorted, disjoint, inside [0, count), lr_mult finite and > 0) with 1 .. VL_MAX_STAT_SEGMENTS
+ * entries, travels BY VALUE; decay finite and >= 0; trust_index -1 or in [0, n_trust); `reserved` is ignored.  rows and trust may be NULL
+ * when n_trust == 0.  Refused on the host, each with a message that names the argument: null pointers, count <= 0, a bad table, an index
+ * outside the trust array, eps not finite or <= 0 (it keeps 0 / 0 out where v' = 0), c1 or c2 not finite or < 1, a workspace too small.
+ * The _st forms read c1, c2 (vl_lamb_moments_st) and lr, c1, c2 (vl_lamb_apply_st) from the step state when they run.
+ * vl_step_state_set_lamb: one single-lane launch that writes the two words and nothing else; no other setter touches them. */
+typedef struct vl_lamb_range {
+    int64_t begin, end;
+    float lr_mult;
+    float decay;
+    int32_t trust_index;
+    int32_t reserved;
+} vl_lamb_range;
+typedef struct vl_lamb_row {
+    double w_sumsq, u_sumsq;
+    uint32_t nonfinite, reserved;
+} vl_lamb_row;
+size_t vl_lamb_moments_ws_bytes(const vl_lamb_range* ranges, int n_ranges);
+int vl_lamb_moments(const float* w, const float* g, float* m, float* v, int64_t count, float c1, float c2, float eps, float clip_norm,
+                    const float* sumsq, float gscale, const uint32_t* skip, const vl_lamb_range* ranges, int n_ranges, vl_lamb_row* rows,
+                    float* trust, int n_trust, void* ws, size_t ws_bytes, vl_stream_t stream);
+int vl_lamb_moments_st(const float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float eps,
+                       float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, const vl_lamb_range* ranges, int n_ranges,
+                       vl_lamb_row* rows, float* trust, int n_trust, void* ws, size_t ws_bytes, vl_stream_t stream);
+int vl_lamb_apply(float* w, const float* m, const float* v, int64_t count, float lr, float c1, float c2, float eps, const uint32_t* skip,
+                  const vl_lamb_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream);
+int vl_lamb_apply_st(float* w, const float* m, const float* v, int64_t count, const vl_step_state* state, float eps, const uint32_t* skip,
+                     const vl_lamb_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream);
+int vl_step_state_set_lamb(vl_step_state* state, float c1, float c2, vl_stream_t stream);
 
 /* ---- utilities ------------------------------------------------------------------------------- */
 int vl_fill(float* p, int64_t count, float value, vl_stream_t stream);

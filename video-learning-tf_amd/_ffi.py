@@ -113,6 +113,12 @@ SIGNATURES = {
     "vl_lars_trust": (i32, [p, i32, C.c_double, C.c_double, p, f32, p, f32, p, p]),
     "vl_lars_apply": (i32, [p, p, p, i64, f32, f32, i32, f32, p, f32, p, p, i32, p, i32, p]),
     "vl_lars_apply_st": (i32, [p, p, p, i64, p, f32, i32, f32, p, f32, p, p, i32, p, i32, p]),
+    "vl_lamb_moments_ws_bytes": (sz, [p, i32]),
+    "vl_lamb_moments": (i32, [p, p, p, p, i64, f32, f32, f32, f32, p, f32, p, p, i32, p, p, i32, p, sz, p]),
+    "vl_lamb_moments_st": (i32, [p, p, p, p, i64, p, f32, f32, p, f32, p, p, i32, p, p, i32, p, sz, p]),
+    "vl_lamb_apply": (i32, [p, p, p, i64, f32, f32, f32, f32, p, p, i32, p, i32, p]),
+    "vl_lamb_apply_st": (i32, [p, p, p, i64, p, f32, p, p, i32, p, i32, p]),
+    "vl_step_state_set_lamb": (i32, [p, f32, f32, p]),
     "vl_fill": (i32, [p, i64, f32, p]),
     "vl_resize_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32]),
     "vl_resize_destroy": (None, [p]),
@@ -167,6 +173,21 @@ STAT_CHUNK = 16384        # VL_STAT_CHUNK
 class LarsRange(C.Structure):
     """vl_lars_range (include/vltf.h)."""
     _fields_ = [("begin", i64), ("end", i64), ("lr_mult", f32), ("trust_index", C.c_int32)]
+
+
+class LambRange(C.Structure):
+    """vl_lamb_range (include/vltf.h): 32 bytes."""
+    _fields_ = [("begin", i64), ("end", i64), ("lr_mult", f32), ("decay", f32), ("trust_index", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LambRow(C.Structure):
+    """vl_lamb_row (include/vltf.h): 24 bytes, one per trust index."""
+    _fields_ = [("w_sumsq", C.c_double), ("u_sumsq", C.c_double), ("nonfinite", u32), ("reserved", u32)]
+
+
+# LAMB's bias corrections in vl_step_state: the words reserved[VL_STEP_STATE_LAMB_C1 / _C2], as byte offsets of the block
+STEP_STATE_LAMB_C1_OFFSET = 24
+STEP_STATE_LAMB_C2_OFFSET = 28
 
 
 class VltfError(RuntimeError):

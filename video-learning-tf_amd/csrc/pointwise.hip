@@ -3154,6 +3154,394 @@ extern "C" int vl_lars_apply_st(float* w, const float* g, float* accum, int64_t 
     return 0;
 }
 
+// ---- LAMB (vltf.h: vl_lamb_moments, vl_lamb_apply): Adam's moments, a per-tensor trust ratio |w| / |u| on the device, decoupled decay -----
+static_assert(sizeof(vl_lamb_range) == 32 && sizeof(vl_lamb_row) == 24, "vl_lamb_range / vl_lamb_row layout");
+static_assert(offsetof(vl_step_state, reserved) == 24, "vl_step_state layout");
+
+struct lamb_table {
+    vl_lamb_range r[VL_MAX_STAT_SEGMENTS];
+    int first[VL_MAX_STAT_SEGMENTS + 1];      // a range's first chunk index (stat_table's plan over ALL ranges); first[n] = the chunks of the table
+    int n;
+};
+
+// the rules of lars_table_make plus a decay per range; count < 0: the bound of the buffers is not known (vl_lamb_moments_ws_bytes)
+static int lamb_table_make(const char* who, const vl_lamb_range* ranges, int n_ranges, int64_t count, int n_trust, lamb_table* out) {
+    VL_CHECK(ranges && n_ranges >= 1 && n_ranges <= VL_MAX_STAT_SEGMENTS, "%s: ranges: 1 .. %d entries, got %d", who, VL_MAX_STAT_SEGMENTS,
+             n_ranges);
+    int64_t prev = 0, chunks = 0;
+    for (int k = 0; k < n_ranges; ++k) {
+        const vl_lamb_range& r = ranges[k];
+        VL_CHECK(r.begin >= prev && r.end > r.begin && (count < 0 || r.end <= count),
+                 "%s: ranges[%d] = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
+                 (long long)r.end, (long long)count);
+        VL_CHECK(r.end - r.begin <= 0x7FFFFFFFll, "%s: ranges[%d] has %lld elements, more than 2^31 - 1", who, k, (long long)(r.end - r.begin));
+        VL_CHECK(r.lr_mult > 0.f && r.lr_mult <= 3.402823466e38f, "%s: ranges[%d]: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
+        VL_CHECK(r.decay >= 0.f && r.decay <= 3.402823466e38f, "%s: ranges[%d]: decay must be finite and >= 0", who, k);
+        VL_CHECK(r.trust_index >= -1 && (count < 0 || r.trust_index < n_trust),
+                 "%s: ranges[%d]: trust_index %d is neither -1 nor inside the %d entries of trust", who, k, r.trust_index, n_trust);
+        out->r[k] = r;
+        out->first[k] = (int)chunks;
+        chunks += (r.end - r.begin + VL_STAT_CHUNK - 1) / VL_STAT_CHUNK;
+        VL_CHECK(chunks <= 0x7FFFFFFFll, "%s: ranges: more than 2^31 - 1 chunks", who);
+        prev = r.end;
+    }
+    out->first[n_ranges] = (int)chunks;
+    out->n = n_ranges;
+    return 0;
+}
+
+// u of one element from the moments of THIS update: the one function vl_lamb_moments sums and vl_lamb_apply subtracts
+__device__ __forceinline__ float lamb_dir(float w, float mi, float vi, float c1, float c2, float eps, float decay) {
+#pragma clang fp contract(off)
+    const float mh = mi * c1;
+    const float vh = vi * c2;
+    const float r = mh / (sqrtf(vh) + eps);
+    return decay > 0.f ? __builtin_fmaf(decay, w, r) : r;
+}
+
+// adam_elem's two moment lines, unchanged
+__device__ __forceinline__ void lamb_moment_elem(float g, float& m, float& v, float sc) {
+#pragma clang fp contract(off)
+    const float gi = g * sc;
+    const float mi = __builtin_fmaf(0.9f, m, 0.1f * gi);
+    const float vi = __builtin_fmaf(0.999f, v, gi * (0.001f * gi));
+    m = mi;
+    v = vi;
+}
+
+// stat_elem's w_sumsq lines for w and for u
+__device__ __forceinline__ void lamb_stat_elem(float w, float u, double& wq, double& uq, uint32_t& bad) {
+    const bool wf = (__float_as_int(w) & 0x7f800000) != 0x7f800000, uf = (__float_as_int(u) & 0x7f800000) != 0x7f800000;
+    const double wd = wf ? (double)w : 0.0, ud = uf ? (double)u : 0.0;
+    wq = __builtin_fma(wd, wd, wq);
+    uq = __builtin_fma(ud, ud, uq);
+    bad += (wf ? 0u : 1u) + (uf ? 0u : 1u);
+}
+
+struct lamb_consts {
+    float sc, c1, c2, eps, decay;
+};
+
+template <bool NORMS>
+__device__ __forceinline__ void lamb_moments_elem(float w, float g, float& m, float& v, const lamb_consts& k, double& wq, double& uq,
+                                                  uint32_t& bad) {
+    lamb_moment_elem(g, m, v, k.sc);
+    if (NORMS) lamb_stat_elem(w, lamb_dir(w, m, v, k.c1, k.c2, k.eps, k.decay), wq, uq, bad);
+}
+
+// stat_block_reduce for two sums and one count: the same butterfly, the same wave order
+__device__ __forceinline__ void lamb_block_reduce(double& wq, double& uq, uint32_t& bad, double* smd /* [8] */, uint32_t* smi /* [4] */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        wq += __shfl_xor(wq, o, 64);
+        uq += __shfl_xor(uq, o, 64);
+        bad += (uint32_t)__shfl_xor((int)bad, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+        smd[wv * 2] = wq;
+        smd[wv * 2 + 1] = uq;
+        smi[wv] = bad;
+    }
+    __syncthreads();
+    wq = ((smd[0] + smd[2]) + smd[4]) + smd[6];
+    uq = ((smd[1] + smd[3]) + smd[5]) + smd[7];
+    bad = smi[0] + smi[1] + smi[2] + smi[3];
+    __syncthreads();
+}
+
+// one chunk [cb, cb + len) of a range: tensor_stats_stage1's walk (vector v of thread t = t, t + 256, ..., component c of vector v is chunk
+// element 4 v + c - r) with the moments written back.  NORMS false (trust_index -1): w is not read, nothing is summed.
+template <bool NORMS>
+__device__ __forceinline__ void lamb_chunk(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, int64_t cb, int len, int phase, const lamb_consts& k, double (&wq)[4],
+                                           double (&uq)[4], uint32_t& bad) {
+    const int t = threadIdx.x;
+    const int r = phase < 0 ? 0 : (int)((cb + phase) & 3);
+    const int64_t base = cb - r;              // the element of vector 0, component 0: 16-byte aligned in all four arrays when phase >= 0
+    const int nv = (len + r + 3) >> 2;
+    constexpr int U = 2;
+    for (int v0 = t; v0 < nv; v0 += 256 * U) {
+        if (phase >= 0 && 4 * v0 >= r && 4 * (v0 + 256 * (U - 1)) + 4 - r <= len) {      // U whole vectors: every load issued first
+            float4 wv[U], gv[U], mv[U], qv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t e = base + 4 * (int64_t)(v0 + 256 * u);
+                if (NORMS) wv[u] = *reinterpret_cast<const float4*>(w + e);
+                else wv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                gv[u] = *reinterpret_cast<const float4*>(g + e);
+                mv[u] = *reinterpret_cast<const float4*>(m + e);
+                qv[u] = *reinterpret_cast<const float4*>(v + e);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                lamb_moments_elem<NORMS>(wv[u].x, gv[u].x, mv[u].x, qv[u].x, k, wq[0], uq[0], bad);
+                lamb_moments_elem<NORMS>(wv[u].y, gv[u].y, mv[u].y, qv[u].y, k, wq[1], uq[1], bad);
+                lamb_moments_elem<NORMS>(wv[u].z, gv[u].z, mv[u].z, qv[u].z, k, wq[2], uq[2], bad);
+                lamb_moments_elem<NORMS>(wv[u].w, gv[u].w, mv[u].w, qv[u].w, k, wq[3], uq[3], bad);
+                const int64_t e = base + 4 * (int64_t)(v0 + 256 * u);
+                *reinterpret_cast<float4*>(m + e) = mv[u];
+                *reinterpret_cast<float4*>(v + e) = qv[u];
+            }
+            continue;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int vi = v0 + 256 * u;
+            if (vi >= nv) break;
+            const int j0 = 4 * vi - r;        // the chunk index of component 0
+            const int64_t e = base + 4 * (int64_t)vi;
+            if (phase >= 0 && j0 >= 0 && j0 + 4 <= len) {
+                const float4 wv = NORMS ? *reinterpret_cast<const float4*>(w + e) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 gv = *reinterpret_cast<const float4*>(g + e);
+                float4 mv = *reinterpret_cast<const float4*>(m + e), qv = *reinterpret_cast<const float4*>(v + e);
+                lamb_moments_elem<NORMS>(wv.x, gv.x, mv.x, qv.x, k, wq[0], uq[0], bad);
+                lamb_moments_elem<NORMS>(wv.y, gv.y, mv.y, qv.y, k, wq[1], uq[1], bad);
+                lamb_moments_elem<NORMS>(wv.z, gv.z, mv.z, qv.z, k, wq[2], uq[2], bad);
+                lamb_moments_elem<NORMS>(wv.w, gv.w, mv.w, qv.w, k, wq[3], uq[3], bad);
+                *reinterpret_cast<float4*>(m + e) = mv;
+                *reinterpret_cast<float4*>(v + e) = qv;
+            } else {                          // the chunk's head or tail, or the arrays disagree in phase: only elements of the chunk are addressed
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (j0 + c >= 0 && j0 + c < len) {
+                        float mi = m[e + c], qi = v[e + c];
+                        lamb_moments_elem<NORMS>(NORMS ? w[e + c] : 0.f, g[e + c], mi, qi, k, wq[c], uq[c], bad);
+                        m[e + c] = mi;
+                        v[e + c] = qi;
+                    }
+            }
+        }
+    }
+}
+
+// one workgroup per chunk -> the moments of the chunk, and ws[chunk] where the range has a trust index.  st != nullptr: c1, c2 from the state.
+__global__ __launch_bounds__(256) void lamb_moments_stage1(const float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, lamb_table lt, float c1, float c2,
+                                                           const vl_step_state* __restrict__ st, float eps, float clip_norm,
+                                                           const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip,
+                                                           vl_lamb_row* __restrict__ ws) {
+    __shared__ double sl[2][STAT_SLOTS];
+    __shared__ uint32_t smi[4];
+    if (skip && *skip) return;
+    const int b = blockIdx.x, t = threadIdx.x;
+    int s = 0;
+    for (int k = 1; k < lt.n; ++k)
+        if (lt.first[k] <= b) s = k;
+    const int64_t cb = lt.r[s].begin + (int64_t)(b - lt.first[s]) * VL_STAT_CHUNK;
+    const int64_t rest = lt.r[s].end - cb;
+    const int len = rest < VL_STAT_CHUNK ? (int)rest : VL_STAT_CHUNK;
+    const bool norms = lt.r[s].trust_index >= 0;
+    const int phase = norms ? align_phase(w, g, m, v) : align_phase(g, m, v, nullptr);
+    lamb_consts k;
+    k.sc = clip_scale(clip_norm, sumsq, gscale);
+    k.c1 = st ? __uint_as_float(st->reserved[VL_STEP_STATE_LAMB_C1]) : c1;
+    k.c2 = st ? __uint_as_float(st->reserved[VL_STEP_STATE_LAMB_C2]) : c2;
+    k.eps = eps;
+    k.decay = lt.r[s].decay;
+    double wq[4] = {0.0, 0.0, 0.0, 0.0}, uq[4] = {0.0, 0.0, 0.0, 0.0};
+    uint32_t bad = 0u;
+    if (!norms) {
+        lamb_chunk<false>(w, g, m, v, cb, len, phase, k, wq, uq, bad);
+        return;
+    }
+    lamb_chunk<true>(w, g, m, v, cb, len, phase, k, wq, uq, bad);
+    const int r = phase < 0 ? 0 : (int)((cb + phase) & 3);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int slot = (4 * t + c - r) & (STAT_SLOTS - 1);
+        sl[0][slot] = wq[c];
+        sl[1][slot] = uq[c];
+    }
+    __syncthreads();
+    double wt = ((sl[0][4 * t] + sl[0][4 * t + 1]) + sl[0][4 * t + 2]) + sl[0][4 * t + 3];
+    double ut = ((sl[1][4 * t] + sl[1][4 * t + 1]) + sl[1][4 * t + 2]) + sl[1][4 * t + 3];
+    __syncthreads();
+    lamb_block_reduce(wt, ut, bad, &sl[0][0], smi);
+    if (t == 0) {
+        vl_lamb_row row;
+        row.w_sumsq = wt;
+        row.u_sumsq = ut;
+        row.nonfinite = bad;
+        row.reserved = 0u;
+        ws[b] = row;
+    }
+}
+
+// one workgroup per range: its chunk rows in the order row t, t + 256, ... per thread, then the block's tree -> rows[index], trust[index]
+__global__ __launch_bounds__(256) void lamb_moments_stage2(const vl_lamb_row* __restrict__ ws, lamb_table lt, const uint32_t* __restrict__ skip,
+                                                           vl_lamb_row* __restrict__ rows, float* __restrict__ trust) {
+#pragma clang fp contract(off)
+    __shared__ double smd[8];
+    __shared__ uint32_t smi[4];
+    if (skip && *skip) return;
+    const int s = blockIdx.x, idx = lt.r[s].trust_index;
+    if (idx < 0) return;
+    double wt = 0.0, ut = 0.0;
+    uint32_t bad = 0u;
+    for (int i = lt.first[s] + (int)threadIdx.x; i < lt.first[s + 1]; i += 256) {
+        const vl_lamb_row r = ws[i];
+        wt += r.w_sumsq;
+        ut += r.u_sumsq;
+        bad += r.nonfinite;
+    }
+    lamb_block_reduce(wt, ut, bad, smd, smi);
+    if (threadIdx.x == 0) {
+        vl_lamb_row row;
+        row.w_sumsq = wt;
+        row.u_sumsq = ut;
+        row.nonfinite = bad;
+        row.reserved = 0u;
+        rows[idx] = row;
+        const double wn = sqrt(wt), un = sqrt(ut);
+        trust[idx] = (bad == 0u && wn > 0.0 && un > 0.0) ? (float)(wn / un) : 1.f;      // (a NaN norm fails > 0)
+    }
+}
+
+static int lamb_scalars(const char* who, float c1, float c2, float eps, bool with_c) {
+    VL_CHECK(eps > 0.f && eps <= 3.402823466e38f, "%s: eps must be finite and > 0, got %g", who, (double)eps);       // (NaN fails)
+    if (with_c) {
+        VL_CHECK(c1 >= 1.f && c1 <= 3.402823466e38f, "%s: c1 must be finite and >= 1, got %g", who, (double)c1);
+        VL_CHECK(c2 >= 1.f && c2 <= 3.402823466e38f, "%s: c2 must be finite and >= 1, got %g", who, (double)c2);
+    }
+    return 0;
+}
+
+static int lamb_moments_launch(const char* who, const float* w, const float* g, float* m, float* v, int64_t count, float c1, float c2,
+                               const vl_step_state* state, float eps, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                               const vl_lamb_range* ranges, int n_ranges, vl_lamb_row* rows, float* trust, int n_trust, void* ws,
+                               size_t ws_bytes, vl_stream_t stream) {
+    VL_CHECK(w, "%s: w is null", who);
+    VL_CHECK(g, "%s: g is null", who);
+    VL_CHECK(m, "%s: m is null", who);
+    VL_CHECK(v, "%s: v is null", who);
+    VL_CHECK(count > 0, "%s: count must be > 0, got %lld", who, (long long)count);
+    VL_CHECK(n_trust >= 0 && ((rows && trust) || n_trust == 0), "%s: rows / trust: %d entries at a null pointer", who, n_trust);
+    VL_CHECK(ws, "%s: ws is null", who);
+    VL_CHECK((((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)trust) & 3) == 0 &&
+                 (((uintptr_t)rows | (uintptr_t)ws) & 7) == 0, "%s: misaligned pointer", who);
+    if (int rc = lamb_scalars(who, c1, c2, eps, state == nullptr)) return rc;
+    lamb_table lt;
+    if (int rc = lamb_table_make(who, ranges, n_ranges, count, n_trust, &lt)) return rc;
+    const size_t need = (size_t)lt.first[lt.n] * sizeof(vl_lamb_row);
+    VL_CHECK(ws_bytes >= need, "%s: ws has %zu bytes, this table needs %zu (vl_lamb_moments_ws_bytes)", who, ws_bytes, need);
+    hipLaunchKernelGGL(lamb_moments_stage1, dim3(lt.first[lt.n]), dim3(256), 0, (hipStream_t)stream, w, g, m, v, lt, c1, c2, state, eps,
+                       clip_norm, sumsq, gscale, skip, reinterpret_cast<vl_lamb_row*>(ws));
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lamb_moments_stage2, dim3(lt.n), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const vl_lamb_row*>(ws), lt, skip,
+                       rows, trust);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t vl_lamb_moments_ws_bytes(const vl_lamb_range* ranges, int n_ranges) {
+    lamb_table lt;
+    if (lamb_table_make("vl_lamb_moments_ws_bytes", ranges, n_ranges, -1, 0, &lt)) return 0;
+    return (size_t)lt.first[lt.n] * sizeof(vl_lamb_row);
+}
+
+extern "C" int vl_lamb_moments(const float* w, const float* g, float* m, float* v, int64_t count, float c1, float c2, float eps,
+                               float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, const vl_lamb_range* ranges,
+                               int n_ranges, vl_lamb_row* rows, float* trust, int n_trust, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    return lamb_moments_launch("vl_lamb_moments", w, g, m, v, count, c1, c2, nullptr, eps, clip_norm, sumsq, gscale, skip, ranges, n_ranges,
+                               rows, trust, n_trust, ws, ws_bytes, stream);
+}
+
+extern "C" int vl_lamb_moments_st(const float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float eps,
+                                  float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, const vl_lamb_range* ranges,
+                                  int n_ranges, vl_lamb_row* rows, float* trust, int n_trust, void* ws, size_t ws_bytes,
+                                  vl_stream_t stream) {
+    VL_CHECK(state, "vl_lamb_moments_st: state is null");
+    return lamb_moments_launch("vl_lamb_moments_st", w, g, m, v, count, 1.f, 1.f, state, eps, clip_norm, sumsq, gscale, skip, ranges,
+                               n_ranges, rows, trust, n_trust, ws, ws_bytes, stream);
+}
+
+__device__ __forceinline__ void lamb_apply_elem(float& w, float m, float v, float a, float c1, float c2, float eps, float decay) {
+#pragma clang fp contract(off)
+    w = __builtin_fmaf(-a, lamb_dir(w, m, v, c1, c2, eps, decay), w);
+}
+
+// st != nullptr: lr, c1, c2 from the state.  The trust value is one uniform load per range.
+__global__ void lamb_apply_kernel(float* __restrict__ w, const float* __restrict__ m, const float* __restrict__ v, lamb_table lt,
+                                  const float* __restrict__ trust, float lr, float c1, float c2, const vl_step_state* __restrict__ st,
+                                  float eps, const uint32_t* __restrict__ skip) {
+#pragma clang fp contract(off)
+    if (skip && *skip) return;
+    if (st) {
+        lr = st->lr;
+        c1 = __uint_as_float(st->reserved[VL_STEP_STATE_LAMB_C1]);
+        c2 = __uint_as_float(st->reserved[VL_STEP_STATE_LAMB_C2]);
+    }
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    const int phase = align_phase(w, m, v, nullptr);
+    for (int k = 0; k < lt.n; ++k) {
+        const int64_t begin = lt.r[k].begin, end = lt.r[k].end;
+        const int ti = lt.r[k].trust_index;
+        const float a = (lr * lt.r[k].lr_mult) * (ti < 0 ? 1.f : trust[ti]);
+        const float decay = lt.r[k].decay;
+        int64_t v0, v1;
+        tier_split(begin, end, phase, v0, v1);
+        for (int64_t i = begin + i0; i < v0; i += step) lamb_apply_elem(w[i], m[i], v[i], a, c1, c2, eps, decay);
+        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
+        const float4* __restrict__ m4 = reinterpret_cast<const float4*>(m + v0);
+        const float4* __restrict__ q4 = reinterpret_cast<const float4*>(v + v0);
+        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
+            float4 wv = w4[i];
+            const float4 mv = m4[i], qv = q4[i];
+            lamb_apply_elem(wv.x, mv.x, qv.x, a, c1, c2, eps, decay);
+            lamb_apply_elem(wv.y, mv.y, qv.y, a, c1, c2, eps, decay);
+            lamb_apply_elem(wv.z, mv.z, qv.z, a, c1, c2, eps, decay);
+            lamb_apply_elem(wv.w, mv.w, qv.w, a, c1, c2, eps, decay);
+            w4[i] = wv;
+        }
+        for (int64_t i = v1 + i0; i < end; i += step) lamb_apply_elem(w[i], m[i], v[i], a, c1, c2, eps, decay);
+    }
+}
+
+static int lamb_apply_launch(const char* who, float* w, const float* m, const float* v, int64_t count, float lr, float c1, float c2,
+                             const vl_step_state* state, float eps, const uint32_t* skip, const vl_lamb_range* ranges, int n_ranges,
+                             const float* trust, int n_trust, vl_stream_t stream) {
+    VL_CHECK(w, "%s: w is null", who);
+    VL_CHECK(m, "%s: m is null", who);
+    VL_CHECK(v, "%s: v is null", who);
+    VL_CHECK(count > 0, "%s: count must be > 0, got %lld", who, (long long)count);
+    VL_CHECK(n_trust >= 0 && (trust || n_trust == 0), "%s: trust: %d entries at a null pointer", who, n_trust);
+    if (int rc = lamb_scalars(who, c1, c2, eps, state == nullptr)) return rc;
+    lamb_table lt;
+    if (int rc = lamb_table_make(who, ranges, n_ranges, count, n_trust, &lt)) return rc;
+    hipLaunchKernelGGL(lamb_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, m, v, lt, trust, lr, c1, c2,
+                       state, eps, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_lamb_apply(float* w, const float* m, const float* v, int64_t count, float lr, float c1, float c2, float eps,
+                             const uint32_t* skip, const vl_lamb_range* ranges, int n_ranges, const float* trust, int n_trust,
+                             vl_stream_t stream) {
+    return lamb_apply_launch("vl_lamb_apply", w, m, v, count, lr, c1, c2, nullptr, eps, skip, ranges, n_ranges, trust, n_trust, stream);
+}
+
+extern "C" int vl_lamb_apply_st(float* w, const float* m, const float* v, int64_t count, const vl_step_state* state, float eps,
+                                const uint32_t* skip, const vl_lamb_range* ranges, int n_ranges, const float* trust, int n_trust,
+                                vl_stream_t stream) {
+    VL_CHECK(state, "vl_lamb_apply_st: state is null");
+    return lamb_apply_launch("vl_lamb_apply_st", w, m, v, count, 0.f, 1.f, 1.f, state, eps, skip, ranges, n_ranges, trust, n_trust, stream);
+}
+
+// LAMB's two bias corrections: words of their own, written by a launch of their own (every other setter leaves them alone)
+__global__ void step_state_set_lamb_kernel(vl_step_state* __restrict__ st, float c1, float c2) {
+    st->reserved[VL_STEP_STATE_LAMB_C1] = __float_as_uint(c1);
+    st->reserved[VL_STEP_STATE_LAMB_C2] = __float_as_uint(c2);
+}
+
+extern "C" int vl_step_state_set_lamb(vl_step_state* state, float c1, float c2, vl_stream_t stream) {
+    VL_CHECK(state, "vl_step_state_set_lamb: state is null");
+    if (int rc = lamb_scalars("vl_step_state_set_lamb", c1, c2, 1.f, true)) return rc;
+    hipLaunchKernelGGL(step_state_set_lamb_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, c1, c2);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void fill_kernel(float* __restrict__ p, int64_t count, float value) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) p[i] = value;
 }

@@ -70,6 +70,8 @@ class NetConfig:
     ema_warmup: bool = False                    # train.ema_warmup: its num_updates form, decay min(decay, (1 + n) / (10 + n)) (ema_rate)
     lars_eeta: float = 0.0                      # train.lars_eeta: tf.contrib.opt.LARSOptimizer's eeta, > 0 (needs momentum > 0); 0 = no LARS
     lars_epsilon: float = 0.0                   # train.lars_epsilon: its epsilon, >= 0, added to the trust ratio's denominator (lars_ranges)
+    lamb: bool = False                          # train.lamb: LAMB (tfa.optimizers.LAMB) in the place of the Adam update; optimizer adam only
+    lamb_epsilon: Optional[float] = None        # train.lamb_epsilon: its epsilon, > 0; None = 1e-6 when lamb is on (check_lamb)
     label_smoothing: float = 0.0                # train.label_smoothing: tf.losses.softmax_cross_entropy's, in [0, 1); 0 = hard labels
     top_k: int = 0                              # train.top_k: also count the rows whose label is among the k largest logits; 0 = off
 
@@ -210,6 +212,44 @@ def check_lars(optimizer, momentum, eeta, epsilon):
     if not (momentum is not None and float(momentum) > 0.0):
         raise VltfError("lars_eeta needs momentum > 0: LARS is a momentum optimizer")
     return e, eps
+
+
+LAMB_EPSILON = 1e-6       # tfa.optimizers.LAMB's default epsilon
+
+
+def check_lamb(optimizer, lamb, lamb_epsilon):
+    """(lamb, epsilon) of a run, None read as off / the default.  lamb is True or False; on, the epsilon defaults to LAMB_EPSILON (TFA's).
+    Refused: lamb that is not a bool; lamb with any optimizer but adam (it is Adam's moments with a trust ratio); an epsilon that is not
+    a number, not finite or <= 0; an epsilon given without lamb (it names a rule that is off, a likely slip)."""
+    if lamb is not None and not isinstance(lamb, (bool, np.bool_)):
+        raise VltfError("lamb must be True or False, got %r" % (lamb,))
+    on = bool(lamb)
+    eps = None
+    if lamb_epsilon is not None:
+        if isinstance(lamb_epsilon, (bool, np.bool_, str, bytes)) or not isinstance(lamb_epsilon, (int, float, np.integer, np.floating)):
+            raise VltfError("lamb_epsilon must be a finite number > 0, got %r" % (lamb_epsilon,))
+        eps = float(lamb_epsilon)
+        if not (eps > 0.0 and math.isfinite(eps)):        # (NaN fails)
+            raise VltfError("lamb_epsilon must be a finite number > 0, got %r" % (lamb_epsilon,))
+        if not (float(np.float32(eps)) > 0.0 and math.isfinite(float(np.float32(eps)))):
+            raise VltfError("lamb_epsilon must be a positive finite float32, got %r" % (lamb_epsilon,))
+    if not on:
+        if eps is not None:
+            raise VltfError("lamb_epsilon needs lamb: True")
+        return False, 0.0
+    if optimizer != "adam":
+        raise VltfError("lamb belongs to optimizer adam (it keeps Adam's moments); got optimizer %r" % (optimizer,))
+    return True, LAMB_EPSILON if eps is None else eps
+
+
+def lamb_corrections(n):
+    """(c1, c2) = (1 / (1 - 0.9^t), 1 / (1 - 0.999^t)) of the update applied after n earlier ones, t = n + 1 (n = step_count before its
+    increment: updates, not micro-batches), in double and rounded to float32 once.  The ONE place they are computed: the eager launches
+    take them as arguments, a replayed step reads them from the step state (ops.step_state_set_lamb)."""
+    t = int(n) + 1
+    if t < 1:
+        raise VltfError("lamb_corrections: n must be >= 0, got %r" % (n,))
+    return float(np.float32(1.0 / (1.0 - 0.9 ** t))), float(np.float32(1.0 / (1.0 - 0.999 ** t)))
 
 
 def check_ema(decay, warmup):
@@ -451,6 +491,31 @@ def lars_ranges(specs, plan, weight_decay):
     return ranges, segs, decays
 
 
+def lamb_ranges(specs, plan, weight_decay):
+    """The tables of a LAMB update, host only: (ranges, segments).
+    ranges   [(begin, end, lr_mult, decay, trust_index)] for ops.lamb_moments / ops.lamb_apply: every variable of specs inside
+             plan.tiers, in flat order, with its tier's factor.  A variable of rank >= 2 is an entry of its own with the coefficient
+             decay_ranges gives it (weight_decay, or 0 when it is off) and a trust_index that counts those variables from 0; variables of
+             rank 1 (every bias) get decay 0 and index -1, adjacent ones with one factor merged -- lars_ranges' rules.
+    segments [(name, begin, end)]: the entries with a trust index, in that order.
+    Frozen variables lie outside plan.tiers and are absent from both."""
+    d = check_weight_decay(weight_decay)
+    ranges, segs, off = [], [], 0
+    for name, shp in specs:
+        n = int(np.prod(shp))
+        mult = next((float(m) for lo, hi, m in plan.tiers if lo <= off and off + n <= hi), None)
+        if n > 0 and mult is not None:
+            if len(shp) >= 2:
+                ranges.append((off, off + n, mult, d, len(segs)))
+                segs.append((name, off, off + n))
+            elif ranges and ranges[-1][4] == -1 and ranges[-1][1] == off and ranges[-1][2] == mult:
+                ranges[-1] = (ranges[-1][0], off + n, mult, 0.0, -1)
+            else:
+                ranges.append((off, off + n, mult, 0.0, -1))
+        off += n
+    return ranges, segs
+
+
 def clip_scale_of(sumsq, clip_norm):
     """The factor the update applies to the gradient: clip_norm / max(sqrt(sumsq), clip_norm), or 1 without a clip."""
     if not clip_norm or clip_norm <= 0.0:
@@ -625,6 +690,9 @@ class LRCNEngine:
         self.accumulate = check_accumulate(cfg.accumulate)
         self.ema_decay, self.ema_warmup = check_ema(cfg.ema_decay, cfg.ema_warmup)
         self.lars_eeta, self.lars_epsilon = check_lars(cfg.optimizer, self.momentum, cfg.lars_eeta, cfg.lars_epsilon)
+        self.lamb_on, self.lamb_epsilon = check_lamb(cfg.optimizer, cfg.lamb, cfg.lamb_epsilon)
+        if self.lamb_on and cfg.classifier == "none":
+            raise VltfError("a feature pipeline (classifier none) has no step of its own: give lamb to the GraphEngine it trains in")
         if self.lars_eeta > 0.0 and cfg.classifier == "none":
             raise VltfError("a feature pipeline (classifier none) has no step of its own: give lars_eeta to the GraphEngine it trains in")
         if self.ema_decay > 0.0 and cfg.classifier == "none":
@@ -853,7 +921,7 @@ class LRCNEngine:
         self.decay, self.ss2 = None, None
         if self.weight_decay > 0.0 and cfg.classifier == "none":
             raise VltfError("a feature pipeline (classifier none) has no step of its own: give weight_decay to the GraphEngine it trains in")
-        if self.weight_decay > 0.0 and training:
+        if self.weight_decay > 0.0 and training and not self.lamb_on:      # under LAMB the decay is decoupled: it enters through u alone
             self.decay = decay_ranges(self.specs, self.plan, self.weight_decay)
             self.ss2 = torch.zeros(2, device=dev)
             self.ss = self.ss2[:1]
@@ -862,6 +930,7 @@ class LRCNEngine:
                             "it trains in")
         self._stats_setup(cfg.tensor_stats_interval)
         self._lars_setup()
+        self._lamb_setup()
         self._skip = torch.zeros(1, dtype=torch.int32, device=dev)      # ops.step_guard: the optimizer launch's skip word
         self.probe, self.probe_events = None, []
         self._resizers = {}
@@ -1014,6 +1083,9 @@ class LRCNEngine:
         if getattr(self, "lars", None) is not None:          # the trust ratios of that update (kept by _lars_trust_launch)
             for name, t in self._lars_named(self.lars["stat_trust"]).items():
                 stats[name]["lars_trust"] = t
+        if getattr(self, "lamb", None) is not None:          # LAMB's, kept by _lamb_launch
+            for name, t in self._lamb_named(self.lamb["stat_trust"]).items():
+                stats[name]["lamb_trust"] = t
         self._stats_last = dict(update=meta["update"], tensor_stats=stats, grads_norm_mean=mean)
         return self._stats_last
 
@@ -1102,6 +1174,57 @@ class LRCNEngine:
             raise VltfError("this engine computes no trust ratios (lars_eeta is 0, or it was built with training=False)")
         torch.cuda.synchronize(self.dev)
         return self._lars_named(self.lars["trust"])
+
+    # ---- LAMB (lamb, lamb_epsilon; shared with GraphEngine) ---------------------------------------------------------------------------------
+    def _lamb_setup(self):
+        """Off (lamb False, or an engine that does not train): nothing is allocated and no launch changes.  On: the table of lamb_ranges,
+        the rows, the trust table and the chunk workspace of ops.lamb_moments -- allocated here, never inside a capture.  The optimizer
+        state is Adam's: adam_m, adam_v and step_count are all a checkpoint needs."""
+        self.lamb = None
+        if not (self.lamb_on and self.training):
+            return
+        ranges, segs = lamb_ranges(self.specs, self.plan, self.weight_decay)
+        if not ranges:
+            raise VltfError("lamb: the plan trains no variable")
+        n = len(segs)
+        L = dict(ranges=ranges, segs=segs, names=[name for name, _, _ in stat_segments(self.specs, self.plan)],
+                 trust=torch.ones(max(n, 1), device=self.dev), stat_trust=None,
+                 rows=torch.zeros(max(n, 1) * ops.LAMB_ROW_BYTES, dtype=torch.uint8, device=self.dev),
+                 ws=torch.empty(ops.lamb_moments_ws_bytes(ranges), dtype=torch.uint8, device=self.dev))
+        if self.stat_segs is not None:            # a stats step keeps its update's table for _stats_collect, as stat_ss keeps the norm
+            L["stat_trust"] = torch.ones(max(n, 1), device=self.dev)
+        self.lamb = L
+
+    def _lamb_launch(self, lr, clip_norm, skip, stats_step, captured):
+        """_finish_step, in the place of the Adam launch (step_count already counts this update): the moments and the trust table, then
+        the weights.  Captured: lr, c1 and c2 come from the step state (_graph_step writes them before the replay)."""
+        L = self.lamb
+        if captured:
+            ops.lamb_moments_st(self.w, self.g, self.adam_m, self.adam_v, L["ranges"], L["rows"], L["trust"], L["ws"], self.state,
+                                self.lamb_epsilon, clip_norm, self.ss, 1.0, skip=skip)
+        else:
+            c1, c2 = lamb_corrections(self.step_count - 1)
+            ops.lamb_moments(self.w, self.g, self.adam_m, self.adam_v, L["ranges"], L["rows"], L["trust"], L["ws"], c1, c2,
+                             self.lamb_epsilon, clip_norm, self.ss, 1.0, skip=skip)
+        if stats_step and L["stat_trust"] is not None:
+            L["stat_trust"].copy_(L["trust"])
+        if captured:
+            ops.lamb_apply_st(self.w, self.adam_m, self.adam_v, L["ranges"], L["trust"], self.state, self.lamb_epsilon, skip=skip)
+        else:
+            ops.lamb_apply(self.w, self.adam_m, self.adam_v, L["ranges"], L["trust"], lr, c1, c2, self.lamb_epsilon, skip=skip)
+
+    def _lamb_named(self, table):
+        t = table.detach().cpu().numpy()
+        idx = {name: k for k, (name, _, _) in enumerate(self.lamb["segs"])}
+        return collections.OrderedDict((name, float(t[idx[name]]) if name in idx else 1.0) for name in self.lamb["names"])
+
+    def lamb_trust(self):
+        """{variable name: trust ratio} of the most recent update, every trained variable in flat order: what the device computed for
+        the weight tensors, 1.0 for the biases (and for everything before the first update).  Frozen variables are absent.  Synchronises."""
+        if getattr(self, "lamb", None) is None:
+            raise VltfError("this engine computes no trust ratios (lamb is off, or it was built with training=False)")
+        torch.cuda.synchronize(self.dev)
+        return self._lamb_named(self.lamb["trust"])
 
     # ---- optimizer state (what tf.train.Saver() keeps besides the weights, feeder.py:201: Adam slots + beta powers) -------
     OPT_PREFIX = "__optimizer__/"
@@ -1795,7 +1918,9 @@ class LRCNEngine:
         skip = ops.step_guard(self._skip, getattr(self, "lstm_ws", None), self.lstm_ws_graph)
         if self.lars is not None:
             self._lars_trust_launch(clip_norm, stats_step)
-        if self._tag_off is not None:             # captured: lr and Adam's step size from the step state (written before each replay)
+        if self.lamb is not None:                 # LAMB: two launches in the place of Adam's; g stays the raw gradient
+            self._lamb_launch(lr, clip_norm, skip, stats_step, self._tag_off is not None)
+        elif self._tag_off is not None:           # captured: lr and Adam's step size from the step state (written before each replay)
             if self.cfg.optimizer == "adam" and tiers is not None:
                 ops.adam_apply_tiers_st(self.w, self.g, self.adam_m, self.adam_v, tiers, self.state, clip_norm, self.ss, 1.0, skip=skip)
             elif self.cfg.optimizer == "adam":
@@ -1914,6 +2039,8 @@ class LRCNEngine:
             ops.step_state_set_micro(self.state, self.step_count, draw, lr, self._graph_tag_origin(g["span"]))
         if train and final and self.ema is not None:      # the update this replay applies follows step_count earlier ones
             ops.step_state_set_ema(self.state, ema_rate(self.ema_decay, self.ema_warmup, self.step_count))
+        if train and final and self.lamb is not None:     # likewise LAMB's bias corrections
+            ops.step_state_set_lamb(self.state, *lamb_corrections(self.step_count))
         g["graph"].replay()
         self._rows = g["rows"]
         if not train:

@@ -41,7 +41,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_label_smoothing,
-                     check_lars, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
+                     check_lamb, check_lars, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
 
 
@@ -754,7 +754,8 @@ class GraphEngine:
     def __init__(self, pipelines: List[PipelineSpec], datasets: dict, num_classes: int, device="cuda:0", training=True, dp=None,
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
-                 lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0):
+                 lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0,
+                 lamb=False, lamb_epsilon=None):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -769,7 +770,10 @@ class GraphEngine:
         trust ratio on the learning rate of every trained weight tensor of rank >= 2 of every pipeline (engine.check_lars,
         engine.lars_ranges, LRCNEngine._lars_setup); needs momentum > 0; 0 = off.  label_smoothing, top_k: the smoothed labels of
         tf.losses.softmax_cross_entropy and the top-k hit count, both in the loss launch of the last pipeline (engine.check_label_smoothing,
-        engine.check_top_k, LRCNEngine._loss_setup); a forward-only engine ignores them; 0 = off."""
+        engine.check_top_k, LRCNEngine._loss_setup); a forward-only engine ignores them; 0 = off.  lamb, lamb_epsilon: LAMB
+        (tfa.optimizers.LAMB) in the place of the Adam update -- Adam's moments, a trust ratio |w| / |u| per trained weight tensor of rank
+        >= 2 of every pipeline, weight_decay decoupled (engine.check_lamb, engine.lamb_ranges, LRCNEngine._lamb_setup); optimizer adam
+        only; False = off."""
         self._loss_opts = (check_label_smoothing(label_smoothing), check_top_k(top_k))
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
@@ -778,14 +782,17 @@ class GraphEngine:
         self.weight_decay = check_weight_decay(weight_decay)
         self.ema_decay, self.ema_warmup = check_ema(ema_decay, ema_warmup)
         self.lars_eeta, self.lars_epsilon = check_lars(optimizer, self.momentum, lars_eeta, lars_epsilon)
+        self.lamb_on, self.lamb_epsilon = check_lamb(optimizer, lamb, lamb_epsilon)
         self.dev = torch.device(device)
         self._require_device()
         self.training, self.dp = training, dp
         self._plan(pipelines, datasets, num_classes, optimizer, dropout_keep_prob, conv_math, lr_mult)
-        self.decay = decay_ranges(self.specs, self.plan, self.weight_decay) if self.weight_decay > 0.0 and training else None
+        # (under LAMB the decay is decoupled: no regulariser launch, it enters through u alone)
+        self.decay = decay_ranges(self.specs, self.plan, self.weight_decay) if self.weight_decay > 0.0 and training and not self.lamb_on else None
         self._allocate()
         self._stats_setup(tensor_stats_interval)
         self._lars_setup()
+        self._lamb_setup()
 
     def _plan(self, pipelines, datasets, num_classes, optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None):
         """The graph, its variable list and its training plan (self.nodes, self.specs, self.plan): host logic only, no device
@@ -962,6 +969,8 @@ class GraphEngine:
     _stats_collect, _stats_result, tensor_stats = LRCNEngine._stats_collect, LRCNEngine._stats_result, LRCNEngine.tensor_stats
     _lars_setup, _lars_stats_launch, _lars_trust_launch = LRCNEngine._lars_setup, LRCNEngine._lars_stats_launch, LRCNEngine._lars_trust_launch
     _lars_named, lars_trust = LRCNEngine._lars_named, LRCNEngine.lars_trust
+    _lamb_setup, _lamb_launch, _lamb_named, lamb_trust = (LRCNEngine._lamb_setup, LRCNEngine._lamb_launch, LRCNEngine._lamb_named,
+                                                          LRCNEngine.lamb_trust)
     _loss_setup, _fetch_topk = LRCNEngine._loss_setup, LRCNEngine._fetch_topk
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale, **lengths):
@@ -1152,7 +1161,9 @@ class GraphEngine:
         skip = ops.step_guard(self._skip, *[nd.lstm_ws for nd in self.nodes if nd.cls == "lstm"])   # LRCNEngine._finish_step
         if self.lars is not None:
             self._lars_trust_launch(clip_norm, stats_step)
-        if tiers is not None and self.optimizer == "adam":
+        if self.lamb is not None:                 # LRCNEngine._finish_step
+            self._lamb_launch(lr, clip_norm, skip, stats_step, False)
+        elif tiers is not None and self.optimizer == "adam":
             ops.adam_apply_tiers(self.w, self.g, self.adam_m, self.adam_v, tiers, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)
         elif self.optimizer == "adam":
             ops.adam_apply(self.w, self.g, self.adam_m, self.adam_v, lr, self.step_count, clip_norm, self.ss, 1.0, skip=skip)

@@ -973,6 +973,113 @@ def lars_apply_st(w, g, accum, ranges, trust, state, momentum, nesterov=False, c
                   _p(sumsq_t), gscale, _skip_word(skip), arr, n, tp, nt, stream())
 
 
+# ---- LAMB (vltf.h: vl_lamb_moments, vl_lamb_apply): Adam's moments, per-tensor trust ratios on the device, decoupled decay ---------------
+LAMB_ROW_BYTES = 24
+# a vl_lamb_row as numpy reads it from the bytes of `rows`
+LAMB_ROW_DTYPE = np.dtype([("w_sumsq", "<f8"), ("u_sumsq", "<f8"), ("nonfinite", "<u4"), ("reserved", "<u4")])
+
+
+def _lamb_slices(ranges, who):
+    """[(begin, end, lr_mult, decay, trust_index)] -> [(vl_lamb_range array, count)] over consecutive slices of MAX_STAT_SEGMENTS entries;
+    the library validates each."""
+    ranges = list(ranges)
+    if not ranges:
+        raise _ffi.VltfError("%s: the range table is empty" % who)
+    out = []
+    for lo in range(0, len(ranges), MAX_STAT_SEGMENTS):
+        part = ranges[lo:lo + MAX_STAT_SEGMENTS]
+        arr = (_ffi.LambRange * len(part))()
+        for k, (a, b, mult, decay, ti) in enumerate(part):
+            arr[k].begin, arr[k].end, arr[k].lr_mult, arr[k].decay, arr[k].trust_index = int(a), int(b), float(mult), float(decay), int(ti)
+        out.append((arr, len(part)))
+    return out
+
+
+def lamb_moments_ws_bytes(ranges):
+    """Bytes of workspace lamb_moments needs for this table: the largest requirement over its slices.  Host only.  A table the library
+    refuses raises."""
+    need = 0
+    for arr, n in _lamb_slices(ranges, "lamb_moments_ws_bytes"):
+        b = int(_ffi.lib().vl_lamb_moments_ws_bytes(arr, n))
+        if b == 0:
+            raise _ffi.VltfError("lamb_moments_ws_bytes: %s" % (_ffi.lib().vl_last_error() or b"bad range table").decode())
+        need = max(need, b)
+    return need
+
+
+def _lamb_moments_args(w, g, m, v, rows, trust, ws, sumsq_t, who):
+    if any(t is None for t in (w, g, m, v)):
+        raise _ffi.VltfError("%s: w, g, m and v must be tensors" % who)
+    _f32(w, g, m, v, sumsq_t)
+    if not (g.numel() == w.numel() == m.numel() == v.numel()):
+        raise _ffi.VltfError("%s: w, g, m and v must have one element count" % who)
+    if ws is None or not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()):
+        raise _ffi.VltfError("%s: ws must be a contiguous CUDA/HIP uint8 tensor" % who)
+    if trust is None:
+        return None, None, 0
+    _f32(trust)
+    nt = trust.numel()
+    if rows is None or not (rows.is_cuda and rows.dtype == torch.uint8 and rows.is_contiguous()) or rows.numel() < nt * LAMB_ROW_BYTES:
+        raise _ffi.VltfError("%s: rows must be a contiguous CUDA/HIP uint8 tensor of %d bytes per entry of trust" % (who, LAMB_ROW_BYTES))
+    return _p(rows), _p(trust), nt
+
+
+def lamb_moments(w, g, m, v, ranges, rows, trust, ws, c1, c2, eps, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """The first launch of a LAMB update (vltf.h: vl_lamb_moments).  ranges = [(begin, end, lr_mult, decay, trust_index)], any number: one
+    launch per MAX_STAT_SEGMENTS entries, all indexing the one rows / trust pair.  Inside every range m and v become this update's
+    moments (adam_apply's bits); for each range with an index, rows[index] = (sum w^2, sum u^2, non-finite count) in fp64 and
+    trust[index] = |w| / |u| (1 where a norm is 0 or an element is not finite).  w and g are read only.  rows: uint8 device tensor of
+    LAMB_ROW_BYTES per entry of trust (lamb_rows reads it), trust: float32, ws: uint8 of lamb_moments_ws_bytes(ranges); rows and trust
+    may be None for a table without an index.  c1, c2: engine.lamb_corrections."""
+    rp, tp, nt = _lamb_moments_args(w, g, m, v, rows, trust, ws, sumsq_t, "lamb_moments")
+    for arr, n in _lamb_slices(ranges, "lamb_moments"):
+        _ffi.call("vl_lamb_moments", _p(w), _p(g), _p(m), _p(v), w.numel(), c1, c2, eps, clip_norm, _p(sumsq_t), gscale, _skip_word(skip),
+                  arr, n, rp, tp, nt, _p(ws), ws.numel(), stream())
+
+
+def lamb_moments_st(w, g, m, v, ranges, rows, trust, ws, state, eps, clip_norm=0.0, sumsq_t=None, gscale=1.0, skip=None):
+    """lamb_moments with c1 and c2 read from the step state (step_state_set_lamb)."""
+    rp, tp, nt = _lamb_moments_args(w, g, m, v, rows, trust, ws, sumsq_t, "lamb_moments_st")
+    for arr, n in _lamb_slices(ranges, "lamb_moments_st"):
+        _ffi.call("vl_lamb_moments_st", _p(w), _p(g), _p(m), _p(v), w.numel(), _state(state), eps, clip_norm, _p(sumsq_t), gscale,
+                  _skip_word(skip), arr, n, rp, tp, nt, _p(ws), ws.numel(), stream())
+
+
+def lamb_rows(rows, n):
+    """The first n rows of a lamb_moments `rows` on the host, as a numpy array of LAMB_ROW_DTYPE (synchronises through the copy)."""
+    return rows[:n * LAMB_ROW_BYTES].cpu().numpy().view(LAMB_ROW_DTYPE).copy()
+
+
+def _lamb_apply_args(w, m, v, trust, who):
+    if any(t is None for t in (w, m, v)):
+        raise _ffi.VltfError("%s: w, m and v must be tensors" % who)
+    _f32(w, m, v)
+    if not (w.numel() == m.numel() == v.numel()):
+        raise _ffi.VltfError("%s: w, m and v must have one element count" % who)
+    return _lars_trust_arg(trust)
+
+
+def lamb_apply(w, m, v, ranges, trust, lr, c1, c2, eps, skip=None):
+    """The second launch of a LAMB update (vltf.h: vl_lamb_apply): w <- w - (lr * lr_mult * trust[trust_index]) * u over the ranges of
+    lamb_moments, u recomputed from the stored moments and the unchanged w; index -1: trust 1, nothing read.  trust is read on the device
+    when the launch runs.  One launch per MAX_STAT_SEGMENTS ranges."""
+    tp, nt = _lamb_apply_args(w, m, v, trust, "lamb_apply")
+    for arr, n in _lamb_slices(ranges, "lamb_apply"):
+        _ffi.call("vl_lamb_apply", _p(w), _p(m), _p(v), w.numel(), lr, c1, c2, eps, _skip_word(skip), arr, n, tp, nt, stream())
+
+
+def lamb_apply_st(w, m, v, ranges, trust, state, eps, skip=None):
+    """lamb_apply with lr, c1 and c2 read from the step state."""
+    tp, nt = _lamb_apply_args(w, m, v, trust, "lamb_apply_st")
+    for arr, n in _lamb_slices(ranges, "lamb_apply_st"):
+        _ffi.call("vl_lamb_apply_st", _p(w), _p(m), _p(v), w.numel(), _state(state), eps, _skip_word(skip), arr, n, tp, nt, stream())
+
+
+def step_state_set_lamb(state, c1, c2):
+    """The state's two LAMB words = (c1, c2), and nothing else of the block, written on the stream (vl_step_state_set_lamb)."""
+    _ffi.call("vl_step_state_set_lamb", _state(state), c1, c2, stream())
+
+
 def _ema_sizes(shadow, w):
     if shadow.numel() != w.numel():
         raise _ffi.VltfError("ema_update: shadow and w must have one element count")

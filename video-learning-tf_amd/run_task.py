@@ -59,7 +59,8 @@ def pipeline_net_config(settings, p, dataset):
               accumulate=settings.train.accumulate if settings.train else 1, fc_dropout_keep_prob=settings.get_fc_dropout(),
               tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
               ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
-              label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k())
+              label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
+              lamb_epsilon=settings.get_lamb()[1])
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -359,7 +360,8 @@ def main(init_file, seed=0, device=None):
                              fc_dropout_keep_prob=settings.get_fc_dropout(),
                              tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
                              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
-                             label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k())
+                             label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
+                             lamb_epsilon=settings.get_lamb()[1])
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

@@ -25,6 +25,7 @@ class TrainSettings:
     fc_dropout_keep_prob = 0.0
     ema_decay, ema_warmup = 0.0, False
     lars_eeta, lars_epsilon = 0.0, 0.0
+    lamb, lamb_epsilon = False, None
     label_smoothing, top_k = 0.0, 0
 
 
@@ -72,6 +73,12 @@ class Settings:
         """train.top_k: the k of the top-k accuracy a training step also counts; 0 = off, and outside the train phase (validation ranks
         its fused logits on the host under val.top_k, Validation.get_topk_accuracy)."""
         return self.train.top_k if self.phase == defs.phase.train else 0
+
+    def get_lamb(self):
+        """(train.lamb, train.lamb_epsilon): LAMB in the place of the Adam update (engine.check_lamb; the epsilon is the checked one,
+        TFA's 1e-6 when the key is absent); (False, None) = off, and outside the train phase."""
+        on = self.phase == defs.phase.train and self.train.lamb
+        return (True, self.train.lamb_epsilon) if on else (False, None)
 
     def get_tensor_stats_interval(self):
         """logging.tensor_stats_interval (per-variable gradient / weight statistics every N updates); 0 = off, and outside the train phase."""
@@ -289,6 +296,20 @@ class Settings:
                     t.lars_eeta, t.lars_epsilon = check_lars(t.optimizer, t.momentum, lv[0], lv[1])
                 except VltfError as ex:
                     error("train.lars_eeta / train.lars_epsilon: %s" % ex)
+                # LAMB, layer-wise trust ratios and decoupled decay on the Adam update (tfa.optimizers.LAMB; engine.check_lamb):
+                # absent / None = off
+                from .engine import check_lamb
+                le = obj.get("lamb_epsilon")
+                if isinstance(le, str) and le != "None":         # YAML reads 1e-6 (no dot) and nan / inf as strings
+                    try:
+                        le = float(le)
+                    except ValueError:
+                        pass
+                try:
+                    t.lamb, eps = check_lamb(t.optimizer, None if obj.get("lamb") == "None" else obj.get("lamb"), None if le == "None" else le)
+                    t.lamb_epsilon = eps if t.lamb else None
+                except VltfError as ex:
+                    error("train.lamb / train.lamb_epsilon: %s" % ex)
                 # label smoothing of the loss (tf.losses.softmax_cross_entropy(label_smoothing=); engine.check_label_smoothing) and the top-k
                 # accuracy counted in the same launch (engine.check_top_k): absent / None = off
                 from .engine import check_label_smoothing

@@ -150,7 +150,9 @@ class Train:
         if getattr(engine, "lars", None) is not None:
             info("LARS on the momentum update: eeta %s, epsilon %s; %d weight tensors get a trust ratio, the biases learn with the plain rate" %
                  (engine.lars_eeta, engine.lars_epsilon, len(engine.lars["segs"])))
-
+        if getattr(engine, "lamb", None) is not None:
+            info("LAMB on the Adam update: epsilon %s, decoupled weight decay %s; %d weight tensors get a trust ratio |w| / |u|, the biases "
+                 "learn with the plain rate and no decay" % (engine.lamb_epsilon, engine.weight_decay, len(engine.lamb["segs"])))
         if getattr(engine, "xent_ls", False):
             info("Loss: label smoothing %s (labels y (1 - eps) + eps / %d; the logged loss is the smoothed one), top-k accuracy %s" %
                  (engine.label_smoothing, settings.num_classes, ("k = %d" % engine.top_k) if engine.top_k > 0 else "off"))
