@@ -419,6 +419,21 @@ int vl_softmax_xent_ls(const float* logits, const int32_t* labels, float* dlogit
                        int batch, int classes, float grad_scale, const int32_t* seq_len, int T, float smoothing, int top_k,
                        vl_stream_t stream);
 
+/* ---- mixup (Zhang et al. 2018): clip i is paired with clip clips - 1 - i --------------
+ * vl_mixup_pairs: x is [clips][clip_elems], blended in place per pair: x_i' = lam x_i + (1 - lam) x_p, x_p' = lam x_p + (1 - lam) x_i,
+ * whatever the layout inside a clip (halo and padding zeros blend to zero).  dtype 0: fp32; 1: packed bf16, blended in fp32 and
+ * rounded to nearest even (clip_elems a multiple of 8).  lam_dev != NULL: *lam_dev is read when the kernel runs (capturable) and lam
+ * is ignored; else 0 <= lam <= 1.  lam == 1 leaves every bit.  The middle clip of an odd count is not touched; clips <= 1 launches
+ * nothing. */
+int vl_mixup_pairs(void* x, int dtype, int clips, int64_t clip_elems, float lam, const float* lam_dev, vl_stream_t stream);
+/* vl_softmax_xent_ls (without lengths) on the labels of the blended clips: y' = lam y_r + (1 - lam) y_p, then the smoothing.  Rows are
+ * batch / rows_per_clip clips of rows_per_clip rows; the partner of row r is row r % rows_per_clip of clip
+ * batch / rows_per_clip - 1 - r / rows_per_clip (a row that is its own partner reads one label row).  Hits are counted against the
+ * row's OWN labels.  lam / lam_dev as above; lam == 1 gives vl_softmax_xent_ls's bits.  stats, rows, both launch forms: as there. */
+int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
+                        float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam, const float* lam_dev,
+                        vl_stream_t stream);
+
 /* ---- optimizer: clip_by_global_norm + GradientDescentOptimizer (train.py:199-222) ---------------
  * vl_sumsq: out[0] (+)= sum g^2 over count elements (ws: float[1024]); accumulate != 0 adds to out. */
 int vl_sumsq(const float* g, int64_t count, float* out, float* ws, int accumulate, vl_stream_t stream);

@@ -2038,6 +2038,260 @@ extern "C" int vl_softmax_xent_ls(const float* logits, const int32_t* labels, fl
     return 0;
 }
 
+// ---- mixup (Zhang et al. 2018): the paired in-place blend of the clips and the loss on the mixed labels ---------------
+// Clip i is paired with clip clips - 1 - i.  lam comes from the launch arguments or, when lam_dev is given, from the device when the
+// kernel runs (a captured step replays with the lambda the host wrote before the replay).
+// One element function, used by every loop of both dtypes: the rounding steps are spelled out (1 - lam, two products, one sum), so an
+// element's bits do not depend on which loop reached it.
+__device__ __forceinline__ float mix_elem(float a, float b, float lam, float oml) {
+#pragma clang fp contract(off)
+    return lam * a + oml * b;
+}
+
+__device__ __forceinline__ float bf16_bits_to_f32(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
+__device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {      // round to nearest even (v_cvt_pk_bf16_f32)
+    const __bf16 h = (__bf16)f;
+    return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+// one 32-bit word = two bf16: both halves of a and b blended in fp32, a' into wa and b' into wb
+__device__ __forceinline__ void mix_word_bf16(uint32_t& wa, uint32_t& wb, float lam, float oml) {
+    const float a0 = bf16_bits_to_f32(wa & 0xffffu), a1 = __builtin_bit_cast(float, wa & 0xffff0000u);
+    const float b0 = bf16_bits_to_f32(wb & 0xffffu), b1 = __builtin_bit_cast(float, wb & 0xffff0000u);
+    wa = f32_to_bf16_bits(mix_elem(a0, b0, lam, oml)) | (f32_to_bf16_bits(mix_elem(a1, b1, lam, oml)) << 16);
+    wb = f32_to_bf16_bits(mix_elem(b0, a0, lam, oml)) | (f32_to_bf16_bits(mix_elem(b1, a1, lam, oml)) << 16);
+}
+
+// grid (x: the threads that walk one pair's elements, y: pairs).  A thread loads the same offset of both partners and writes both:
+// the pairing is an involution, so nothing is read after it was written and no second buffer is needed.  The middle clip of an odd
+// count belongs to no pair.  lam == 1 returns before any access: the identity holds for every bit pattern (-0, inf and NaN too).
+// 16-byte accesses where both clip bases are 16-byte aligned (an odd elems misaligns every second clip: those pairs go element by
+// element); the last elems % 4 floats of an aligned pair go element by element too.
+__global__ void mixup_pairs_f32_kernel(float* __restrict__ x, int clips, int64_t elems, float lam_arg, const float* __restrict__ lam_dev) {
+    const float lam = lam_dev ? *lam_dev : lam_arg;
+    if (lam == 1.0f) return;
+    const float oml = 1.0f - lam;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    for (int j = blockIdx.y; j < clips / 2; j += gridDim.y) {
+        float* __restrict__ a = x + (int64_t)j * elems;
+        float* __restrict__ b = x + (int64_t)(clips - 1 - j) * elems;
+        int64_t vec = 0;                                              // floats of the pair that go as 16-byte words
+        if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) {              // (uniform over the workgroup)
+            vec = elems & ~(int64_t)3;
+            float4* __restrict__ a4 = reinterpret_cast<float4*>(a);
+            float4* __restrict__ b4 = reinterpret_cast<float4*>(b);
+            for (int64_t i = i0; i < vec / 4; i += step) {
+                const float4 av = a4[i], bv = b4[i];
+                a4[i] = make_float4(mix_elem(av.x, bv.x, lam, oml), mix_elem(av.y, bv.y, lam, oml), mix_elem(av.z, bv.z, lam, oml),
+                                    mix_elem(av.w, bv.w, lam, oml));
+                b4[i] = make_float4(mix_elem(bv.x, av.x, lam, oml), mix_elem(bv.y, av.y, lam, oml), mix_elem(bv.z, av.z, lam, oml),
+                                    mix_elem(bv.w, av.w, lam, oml));
+            }
+        }
+        for (int64_t i = vec + i0; i < elems; i += step) {
+            const float av = a[i], bv = b[i];
+            a[i] = mix_elem(av, bv, lam, oml);
+            b[i] = mix_elem(bv, av, lam, oml);
+        }
+    }
+}
+
+// packed bf16: elems is a multiple of 8 (checked on the host), so every clip base is 16-byte aligned iff x is; else word by word
+// (4-byte alignment is checked on the host)
+__global__ void mixup_pairs_bf16_kernel(uint32_t* __restrict__ x, int clips, int64_t words, float lam_arg,
+                                        const float* __restrict__ lam_dev) {
+    const float lam = lam_dev ? *lam_dev : lam_arg;
+    if (lam == 1.0f) return;
+    const float oml = 1.0f - lam;
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    for (int j = blockIdx.y; j < clips / 2; j += gridDim.y) {
+        uint32_t* __restrict__ a = x + (int64_t)j * words;
+        uint32_t* __restrict__ b = x + (int64_t)(clips - 1 - j) * words;
+        if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+            uint4* __restrict__ a4 = reinterpret_cast<uint4*>(a);
+            uint4* __restrict__ b4 = reinterpret_cast<uint4*>(b);
+            for (int64_t i = i0; i < words / 4; i += step) {
+                uint4 av = a4[i], bv = b4[i];
+                mix_word_bf16(av.x, bv.x, lam, oml);
+                mix_word_bf16(av.y, bv.y, lam, oml);
+                mix_word_bf16(av.z, bv.z, lam, oml);
+                mix_word_bf16(av.w, bv.w, lam, oml);
+                a4[i] = av;
+                b4[i] = bv;
+            }
+        } else {
+            for (int64_t i = i0; i < words; i += step) {
+                uint32_t av = a[i], bv = b[i];
+                mix_word_bf16(av, bv, lam, oml);
+                a[i] = av;
+                b[i] = bv;
+            }
+        }
+    }
+}
+
+extern "C" int vl_mixup_pairs(void* x, int dtype, int clips, int64_t clip_elems, float lam, const float* lam_dev, vl_stream_t stream) {
+    VL_CHECK(x, "vl_mixup_pairs: x is null");
+    VL_CHECK(clips >= 0, "vl_mixup_pairs: clips must be >= 0, got %d", clips);
+    VL_CHECK(clip_elems > 0, "vl_mixup_pairs: clip_elems must be > 0, got %lld", (long long)clip_elems);
+    VL_CHECK(dtype == 0 || dtype == 1, "vl_mixup_pairs: dtype must be 0 (fp32) or 1 (packed bf16), got %d", dtype);
+    VL_CHECK(dtype == 0 || clip_elems % 8 == 0, "vl_mixup_pairs: a packed-bf16 clip is whole 16-byte blocks: clip_elems %lld is no multiple of 8",
+             (long long)clip_elems);
+    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_mixup_pairs: lam must lie in [0, 1], got %g", (double)lam);   // (NaN fails both)
+    VL_CHECK(((uintptr_t)x & 3) == 0, "vl_mixup_pairs: x is not 4-byte aligned");
+    if (clips <= 1) return 0;
+    // pairs on grid y; per pair one thread per 4 16-byte words, so that a large clip is a few passes of a grid of at most 4096 workgroups
+    const int pairs = clips / 2, gy = pairs < 4096 ? pairs : 4096;
+    const int64_t words16 = (dtype == 0 ? clip_elems / 4 : clip_elems / 8) + 1;
+    const dim3 grid(grid_for((words16 + 3) / 4, 256, 4096 / gy), gy);
+    if (dtype == 0)
+        hipLaunchKernelGGL(mixup_pairs_f32_kernel, grid, dim3(256), 0, (hipStream_t)stream, (float*)x, clips, clip_elems, lam, lam_dev);
+    else
+        hipLaunchKernelGGL(mixup_pairs_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (uint32_t*)x, clips, clip_elems / 2, lam,
+                           lam_dev);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// The row of softmax_xent_ls_row with the labels y' = lam y + (1 - lam) yp in y's place ahead of the smoothing, yp the partner's
+// label row (nullptr: the row is its own partner and reads no other label row than its own).  The hits are counted against the row's OWN labels.  At
+// lam == 1 y' is y exactly (labels are small non-negative integers) and every sum is the one of softmax_xent_ls_row, bit for bit.
+// A function of its own, so that the kernels above keep their code.
+__device__ __forceinline__ void softmax_xent_mix_row(const float* __restrict__ z, const int32_t* __restrict__ y,
+                                                     const int32_t* __restrict__ yp, float* __restrict__ dz, int C, float gscale,
+                                                     float eps, int top_k, float lam, int lane, float& loss, float& hit, float& hitk) {
+    float mx = -INFINITY;
+    int am = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const float v = z[c];
+        if (v > mx) {
+            mx = v;
+            am = c;
+        }
+    }
+    const float gmx = wave_max(mx);
+    int cand = (mx == gmx) ? am : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
+    se = wave_sum(se);
+    const float lse = logf(se) + gmx;
+    const float on = 1.0f - eps, off = eps / (float)C;
+    float l = 0.f;
+    int ymax = -2147483647 - 1, yarg = 0x7fffffff;
+    // No branch inside the loop: with one, the partner's load was issued only after the row's own had come back and the logit's only
+    // after both -- three memory latencies per iteration in the place of one.  A row that is its own partner loads its own row twice
+    // (the same addresses) under the weights 1 and 0, which give y exactly.
+    const int32_t* yq = yp ? yp : y;
+    const float lam_r = yp ? lam : 1.0f, oml = 1.0f - lam_r;
+    for (int c = lane; c < C; c += 64) {
+        const int yv = y[c];
+        const float ym = mix_elem((float)yv, (float)yq[c], lam_r, oml);
+        const float ys = ym * on + off;
+        l += ys * (lse - z[c]);
+        if (yv > ymax) {
+            ymax = yv;
+            yarg = c;
+        }
+        if (dz) dz[c] = (expf(z[c] - lse) - ys) * gscale;
+    }
+    l = wave_sum(l);
+    int gy = ymax;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gy = max(gy, __shfl_xor(gy, o, 64));
+    int ycand = (ymax == gy) ? yarg : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ycand = min(ycand, __shfl_xor(ycand, o, 64));
+    loss = l;
+    hit = (cand == ycand) ? 1.f : 0.f;
+    hitk = 0.f;
+    if (top_k > 0) {                              // (uniform over the wave: every lane takes part in the shuffles)
+        const int t = min(ycand, C - 1);
+        const float zt = z[t];
+        int rank = 0;
+        for (int c = lane; c < C; c += 64) {
+            const float v = z[c];
+            rank += (v > zt || (v == zt && c < t)) ? 1 : 0;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+        hitk = rank < top_k ? 1.f : 0.f;
+    }
+}
+
+// the label row of row b's partner: row b % rpc of clip clips - 1 - b / rpc (nullptr: b is its own partner)
+__device__ __forceinline__ const int32_t* mix_partner_labels(const int32_t* __restrict__ labels, int b, int batch, int rpc, int C) {
+    const int pr = (batch / rpc - 1 - b / rpc) * rpc + b % rpc;
+    return pr == b ? nullptr : labels + (int64_t)pr * C;
+}
+
+__global__ void softmax_xent_mix_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                                        float* __restrict__ stats, int batch, int C, float gscale, int rpc, float eps, int top_k,
+                                        float lam_arg, const float* __restrict__ lam_dev) {
+    __shared__ float sl[4], sc[4], sk[4];
+    const float lam = lam_dev ? *lam_dev : lam_arg;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float loss_acc = 0.f, corr_acc = 0.f, topk_acc = 0.f;
+    for (int b = wv; b < batch; b += 4) {
+        float l, h, hk;
+        softmax_xent_mix_row(logits + (int64_t)b * C, labels + (int64_t)b * C, mix_partner_labels(labels, b, batch, rpc, C),
+                             dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, eps, top_k, lam, lane, l, h, hk);
+        loss_acc += l;
+        corr_acc += h;
+        topk_acc += hk;
+    }
+    if (lane == 0) {
+        sl[wv] = loss_acc;
+        sc[wv] = corr_acc;
+        sk[wv] = topk_acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
+        stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
+        if (top_k > 0) stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
+    }
+}
+
+__global__ void softmax_xent_mix_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                             float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale, int rpc,
+                                             float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= batch) return;
+    const float lam = lam_dev ? *lam_dev : lam_arg;
+    float l, h, hk;
+    softmax_xent_mix_row(logits + (int64_t)b * C, labels + (int64_t)b * C, mix_partner_labels(labels, b, batch, rpc, C),
+                         dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, eps, top_k, lam, lane, l, h, hk);
+    if (lane == 0) {
+        rows[b] = l;
+        rows[batch + b] = h;
+        rows[2 * (int64_t)batch + b] = hk;
+    }
+}
+
+extern "C" int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                   int classes, float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam,
+                                   const float* lam_dev, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_mix: bad argument");
+    VL_CHECK(rows_per_clip > 0 && batch % rows_per_clip == 0, "vl_softmax_xent_mix: batch (%d rows) is not whole clips of %d rows", batch,
+             rows_per_clip);
+    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_mix: smoothing must lie in [0, 1), got %g", (double)smoothing);
+    VL_CHECK(top_k >= 0, "vl_softmax_xent_mix: top_k must be >= 0, got %d", top_k);
+    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_softmax_xent_mix: lam must lie in [0, 1], got %g", (double)lam);
+    if (!rows) {
+        hipLaunchKernelGGL(softmax_xent_mix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch,
+                           classes, grad_scale, rows_per_clip, smoothing, top_k, lam, lam_dev);
+        VL_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL(softmax_xent_mix_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits,
+                       rows, batch, classes, grad_scale, rows_per_clip, smoothing, top_k, lam, lam_dev);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(softmax_xent_ls_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch, top_k);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- global norm + SGD / Adam (train.py:199-222) ----------------------------------------------
 // ---- tier table (vltf.h: vl_lr_tier): the ranges of the flat buffer an update / a norm touches, by value in the launch arguments --
 struct tier_table {

@@ -74,6 +74,8 @@ class NetConfig:
     lamb_epsilon: Optional[float] = None        # train.lamb_epsilon: its epsilon, > 0; None = 1e-6 when lamb is on (check_lamb)
     label_smoothing: float = 0.0                # train.label_smoothing: tf.losses.softmax_cross_entropy's, in [0, 1); 0 = hard labels
     top_k: int = 0                              # train.top_k: also count the rows whose label is among the k largest logits; 0 = off
+    mixup_alpha: float = 0.0                    # train.mixup_alpha: mixup's Beta(alpha, alpha) (clips and labels blended in pairs); 0 = off
+    mixup_seed: int = 0                         # train.mixup_seed: the key of the blend-weight draws (mixup_lambda)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -335,6 +337,55 @@ def check_top_k(top_k):
     if not (0 <= k <= 0x7fffffff):
         raise VltfError("top_k must be a whole number >= 0 (0 / None = off), got %r" % (top_k,))
     return k
+
+
+def check_mixup(alpha, seed=None):
+    """(alpha, seed) of mixup as (float, int), None read as 0 (off).  alpha: a finite number >= 0, the Beta(alpha, alpha) the blend
+    weight is drawn from.  seed: a whole number in [0, 2^64), the key of the draws (mixup_lambda).  Refused: bools and strings for
+    either, a negative, NaN or infinite alpha, a seed that is not whole or negative, and a seed other than 0 without an alpha."""
+    if alpha is None:
+        a = 0.0
+    else:
+        if isinstance(alpha, (bool, np.bool_, str, bytes)) or not isinstance(alpha, (int, float, np.integer, np.floating)):
+            raise VltfError("mixup_alpha must be a finite number >= 0 (0 / None = off), got %r" % (alpha,))
+        a = float(alpha)
+        if not (math.isfinite(a) and a >= 0.0):
+            raise VltfError("mixup_alpha must be a finite number >= 0 (0 / None = off), got %r" % (alpha,))
+    if seed is None:
+        s = 0
+    else:
+        if isinstance(seed, (bool, np.bool_, str, bytes)) or not isinstance(seed, (int, float, np.integer, np.floating)):
+            raise VltfError("mixup_seed must be a whole number >= 0, got %r" % (seed,))
+        if isinstance(seed, (float, np.floating)) and not (math.isfinite(seed) and float(seed) == int(seed)):
+            raise VltfError("mixup_seed must be a whole number >= 0, got %r" % (seed,))
+        s = int(seed)
+        if not (0 <= s < 2 ** 64):
+            raise VltfError("mixup_seed must be a whole number >= 0 (below 2^64), got %r" % (seed,))
+    if s != 0 and a == 0.0:
+        raise VltfError("mixup_seed %d is given without mixup_alpha: mixup is off and nothing would be drawn" % s)
+    return a, s
+
+
+def fold_lambda(lam):
+    """max(lam, 1 - lam) of a blend weight in [0, 1]: under the pairing i <-> B - 1 - i swapping lam and 1 - lam only swaps the
+    partners, so the fold loses nothing, and a row's own label is always the dominant one.  Refused: outside [0, 1], NaN, not a number."""
+    if isinstance(lam, (bool, np.bool_, str, bytes)) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise VltfError("mix_lambda must be a number in [0, 1], got %r" % (lam,))
+    lam = float(lam)
+    if not (0.0 <= lam <= 1.0):                   # (NaN fails both)
+        raise VltfError("mix_lambda must be a number in [0, 1], got %r" % (lam,))
+    return max(lam, 1.0 - lam)
+
+
+def mixup_lambda(alpha, seed, draw_index):
+    """The folded blend weight of the step with this draw index (LRCNEngine._draw_index): one Beta(alpha, alpha) draw from a Philox
+    generator keyed by (seed, draw_index), then fold_lambda.  A pure function of its arguments: every rank draws the same value, every
+    micro-step of an accumulated update its own, and a resumed run continues the sequence."""
+    alpha, seed = check_mixup(alpha, seed)
+    if alpha == 0.0:
+        return 1.0
+    rng = np.random.Generator(np.random.Philox(key=np.array([seed, int(draw_index)], np.uint64)))
+    return fold_lambda(float(rng.beta(alpha, alpha)))
 
 
 def dropout_seed(draw_index):
@@ -673,7 +724,9 @@ class LRCNEngine:
     three graphs; the state's count is then the dropout draw index and Adam's step size follows step_count (ops.step_state_set_micro).
     With NetConfig.tensor_stats_interval > 0 the key also holds whether the update is a stats step (_stats_due): two launch sequences.
     With NetConfig.ema_decay > 0 the captured update is followed by the weight average's launch, which reads its rate from the block:
-    ops.step_state_set_ema writes it (engine.ema_rate of the host's step_count) before every replay that applies an update."""
+    ops.step_state_set_ema writes it (engine.ema_rate of the host's step_count) before every replay that applies an update.
+    With NetConfig.mixup_alpha > 0 the captured step holds the blend and the mixed-label loss launch; both read the blend weight from
+    a one-float device word (mix_lam) the host fills before every step, eager or replayed (_mix_write): the block stays as it is."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -915,6 +968,7 @@ class LRCNEngine:
         if training:
             self.dlogits = buf(*self.logits.shape)
         self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out)
+        self._mix_setup(cfg.mixup_alpha, cfg.mixup_seed, self.rows_out)
         self.ss = torch.zeros(1, device=dev)
         # L2 weight decay: ops.l2_regularize takes the norm's place in _finish_step and returns {sum g'^2, regulariser}; the update calls
         # and _fetch read the first word through self.ss.  Off: nothing is allocated, the norm calls are the ones of before.
@@ -1118,7 +1172,10 @@ class LRCNEngine:
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale):
         """The loss launch of a train step: stats += {loss sum, hits (, top-k hits)}, dlogits = (softmax - labels') * grad_scale."""
-        if self.xent_ls:
+        if self.mix_lam is not None:              # mixup: the labels of the blended clips, the weight read from the device
+            ops.softmax_xent_mix(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.rows_out // self.B,
+                                 self.label_smoothing, self.top_k, self.mix_lam)
+        elif self.xent_ls:
             ops.softmax_xent_ls(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k)
         else:
             ops.softmax_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows)
@@ -1128,6 +1185,38 @@ class LRCNEngine:
         if getattr(self, "top_k", 0) > 0:
             out["topk_accuracy"], out["topk_correct"] = float(st[2]) / max(rows, 1), float(st[2])
         return out
+
+    # ---- mixup (mixup_alpha, mixup_seed) ---------------------------------------------------------------------------------
+    def _mix_setup(self, alpha, seed, rows):
+        """Off (alpha 0, or an engine that does not train): nothing is allocated and no launch changes.  On: the one-float device word
+        both launches read (written before every step, outside any capture), and the three sums and 3 * rows workspace of
+        ops.softmax_xent_mix when label smoothing / top-k have not asked for them already."""
+        self.mixup_alpha, self.mixup_seed = check_mixup(alpha, seed)
+        self.mix_lam = None
+        if not self.training or self.mixup_alpha == 0.0:
+            self.mixup_alpha, self.mixup_seed = 0.0, 0
+            return
+        self.mix_lam = torch.ones(1, device=self.dev)
+        if not self.xent_ls:
+            self.stats = torch.zeros(3, device=self.dev)
+            self.loss_rows = torch.zeros(3 * rows, device=self.dev)
+
+    def _mix_write(self, mix_lambda, mi):
+        """Before a train step, eager or replayed: the step's blend weight goes to the device word on the stream (the caller's
+        mix_lambda folded, or the draw of the step's draw index), and is kept as self.mix_lambda_last."""
+        if self.mix_lam is None:
+            if mix_lambda is not None:
+                raise VltfError("mix_lambda is given, but mixup is off on this engine (NetConfig.mixup_alpha is 0)")
+            return
+        lam = fold_lambda(mix_lambda) if mix_lambda is not None else mixup_lambda(self.mixup_alpha, self.mixup_seed, self._draw_index(mi))
+        ops.fill(self.mix_lam, lam)
+        self.mix_lambda_last = lam
+
+    def _mix_launch(self, n, b):
+        """The blend of the clips just fed, in place, in the layout conv1 reads: the packed space-to-depth input when feed_u8 wrote it
+        directly (bf16 path), else x0.  Clip i with clip b - 1 - i; the halo and padding zeros blend to zero."""
+        if self.mix_lam is not None:
+            ops.mixup_pairs(self.layers[0]["xb"][:n] if (self.c8 and self._xb_fed) else self.x0[:n], b, self.mix_lam)
 
     # ---- LARS (lars_eeta; shared with GraphEngine) ----------------------------------------------------------------------------------------
     def _lars_setup(self):
@@ -1855,6 +1944,7 @@ class LRCNEngine:
             raise VltfError("labels must be int32 one-hot of shape (%d, %d)" % (self._rows_for(b, n), self.cfg.num_classes))
         self._mi = mi
         try:
+            self._mix_launch(n, b)                # mixup: the clips just fed are blended in pairs before conv1 reads them
             rows = self._forward(n, b, train=True)
             world = self.dp.world if self.dp is not None else 1
             i, k = mi if mi is not None else (0, 1)
@@ -1974,13 +2064,16 @@ class LRCNEngine:
         return b if (self.early or self.late) else n
 
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                      fetch=True, global_rows=None, resize=None, micro=None):
+                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None):
         """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44).
         micro = (i, k): micro-step i of an update that sums k of them (k <= cfg.accumulate), called in order i = 0 .. k - 1.  Only the
         last one exchanges, regularises, clips and updates, with its lr; the others return the running loss of the update and no
-        grad_norm.  The loss is scaled by 1 / (rows * world * k) unless global_rows gives the rows of the whole update."""
+        grad_norm.  The loss is scaled by 1 / (rows * world * k) unless global_rows gives the rows of the whole update.
+        mix_lambda: with mixup on (cfg.mixup_alpha > 0), this step's blend weight in [0, 1] in the place of the draw (folded to
+        max(lam, 1 - lam)); refused with mixup off."""
         mi = self.micro.enter(micro)
         try:
+            self._mix_write(mix_lambda, mi)
             if self.step_graph:
                 done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
                                              global_rows, mi)
@@ -1992,9 +2085,10 @@ class LRCNEngine:
             self.micro.reset()
             raise
 
-    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None):
+    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None, mix_lambda=None):
         mi = self.micro.enter(micro)
         try:
+            self._mix_write(mix_lambda, mi)
             n, b = self.feed_f32_nhwc(frames_nhwc)
             return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
         except VltfError:

@@ -660,6 +660,52 @@ def softmax_xent_ls(logits, labels, dlogits, stats, grad_scale, rows, smoothing,
               float(smoothing), int(top_k), stream())
 
 
+def _lam(lam, what):
+    """(host lam, device pointer) of a mixup launch: a one-float device tensor is read when the kernel runs, a number is an argument."""
+    if torch.is_tensor(lam):
+        _f32(lam)
+        if lam.numel() != 1:
+            raise _ffi.VltfError("%s: a device lam is one float32, got %d elements" % (what, lam.numel()))
+        return 0.0, _p(lam)
+    return float(lam), None
+
+
+def mixup_pairs(x, clips, lam):
+    """mixup's blend in place (vl_mixup_pairs): x holds `clips` equal clips back to back (any layout inside a clip), float32 or
+    bfloat16; clip i and clip clips - 1 - i become lam x_i + (1 - lam) x_p and lam x_p + (1 - lam) x_i.  lam: a number in [0, 1] or
+    a one-float device tensor (read when the kernel runs)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (F32, torch.bfloat16)):
+        raise _ffi.VltfError("mixup_pairs: expected a CUDA/HIP float32 or bfloat16 tensor")
+    _dense(x)
+    clips = int(clips)
+    if clips > 0 and x.numel() % clips:
+        raise _ffi.VltfError("mixup_pairs: %d elements are not %d equal clips" % (x.numel(), clips))
+    lam_host, lam_dev = _lam(lam, "mixup_pairs")
+    _ffi.call("vl_mixup_pairs", _p(x), 0 if x.dtype == F32 else 1, clips, x.numel() // max(clips, 1), lam_host, lam_dev,
+              stream())
+
+
+def softmax_xent_mix(logits, labels, dlogits, stats, grad_scale, rows, rows_per_clip, smoothing, top_k, lam):
+    """softmax_xent_ls on the labels of clips blended by mixup_pairs (vl_softmax_xent_mix): y' = lam y + (1 - lam) y_partner ahead of
+    the smoothing, the partner being the same row of the clip mirrored in the batch; hits against the row's own label.  logits are
+    clips of rows_per_clip rows.  stats: 3 floats; rows: None or >= 3*batch floats; lam as in mixup_pairs."""
+    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
+    if labels.dtype != torch.int32:
+        raise _ffi.VltfError("softmax_xent_mix: labels must be int32 one-hot")
+    b, c = logits.shape
+    if tuple(labels.shape) != (b, c):
+        raise _ffi.VltfError("softmax_xent_mix: labels must have the logits' shape (the partner's row is found by index)")
+    if stats.numel() < 3:
+        raise _ffi.VltfError("softmax_xent_mix: stats needs 3 floats")
+    if rows is not None:
+        _f32(rows)
+        if rows.numel() < 3 * b:
+            raise _ffi.VltfError("softmax_xent_mix: rows workspace needs 3*batch floats")
+    lam_host, lam_dev = _lam(lam, "softmax_xent_mix")
+    _ffi.call("vl_softmax_xent_mix", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, int(rows_per_clip),
+              float(smoothing), int(top_k), lam_host, lam_dev, stream())
+
+
 def sumsq(g, out, ws, accumulate=False):
     _f32(g, out, ws)
     if ws.numel() < 1024:

@@ -27,6 +27,7 @@ class TrainSettings:
     lars_eeta, lars_epsilon = 0.0, 0.0
     lamb, lamb_epsilon = False, None
     label_smoothing, top_k = 0.0, 0
+    mixup_alpha, mixup_seed = 0.0, 0
 
 
 class ValSettings:
@@ -73,6 +74,11 @@ class Settings:
         """train.top_k: the k of the top-k accuracy a training step also counts; 0 = off, and outside the train phase (validation ranks
         its fused logits on the host under val.top_k, Validation.get_topk_accuracy)."""
         return self.train.top_k if self.phase == defs.phase.train else 0
+
+    def get_mixup(self):
+        """(train.mixup_alpha, train.mixup_seed): mixup's Beta(alpha, alpha) and the key of its draws (engine.check_mixup,
+        engine.mixup_lambda); (0, 0) = off, and outside the train phase (validation never blends)."""
+        return (self.train.mixup_alpha, self.train.mixup_seed) if self.phase == defs.phase.train else (0.0, 0)
 
     def get_lamb(self):
         """(train.lamb, train.lamb_epsilon): LAMB in the place of the Adam update (engine.check_lamb; the epsilon is the checked one,
@@ -324,6 +330,20 @@ class Settings:
                 except VltfError as ex:
                     error("train.label_smoothing: %s" % ex)
                 t.top_k = self.read_top_k(obj, "train")
+                # mixup (Zhang et al. 2018): clips and labels blended in pairs inside a rank's batch, the weight drawn from
+                # Beta(mixup_alpha, mixup_alpha) under the key mixup_seed (engine.check_mixup, engine.mixup_lambda): absent / None = off
+                from .engine import check_mixup
+                mx = [obj.get("mixup_alpha"), obj.get("mixup_seed")]
+                for i, conv in enumerate((float, int)):
+                    if isinstance(mx[i], str) and mx[i] != "None":     # a quoted number; nan / inf come as strings too
+                        try:
+                            mx[i] = conv(mx[i])
+                        except ValueError:
+                            pass
+                try:
+                    t.mixup_alpha, t.mixup_seed = check_mixup(*(None if v == "None" else v for v in mx))
+                except VltfError as ex:
+                    error("train.mixup_alpha / train.mixup_seed: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:

@@ -157,6 +157,11 @@ class Train:
             info("Loss: label smoothing %s (labels y (1 - eps) + eps / %d; the logged loss is the smoothed one), top-k accuracy %s" %
                  (engine.label_smoothing, settings.num_classes, ("k = %d" % engine.top_k) if engine.top_k > 0 else "off"))
 
+        if getattr(engine, "mix_lam", None) is not None:
+            info("Mixup: alpha %s, seed %d (one Beta(alpha, alpha) weight per batch, folded to max(lam, 1 - lam)); clip i is blended with "
+                 "clip B - 1 - i inside a rank's batch, and the logged loss is the one on the mixed labels" %
+                 (engine.mixup_alpha, engine.mixup_seed))
+
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
         if self.stats_log is None or "tensor_stats" not in out:
