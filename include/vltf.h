@@ -434,6 +434,22 @@ int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogi
                         float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam, const float* lam_dev,
                         vl_stream_t stream);
 
+/* ---- CutMix / VideoMix (Yun et al. 2019, 2020): one box swapped between clip i and clip clips - 1 - i ---------------
+ * The box is {t0, t1, y0, y1, x0, x1}, half-open, in frames of the clip and pixels of the out_h x out_w frame conv1 sees; all channels
+ * are swapped, frame t of clip i with frame t of its partner, bit for bit, in place; no byte outside the box changes (halo, phase
+ * padding, unused channel slots).  box_dev != NULL: six device words read when the kernel runs (capturable, the grid does not depend
+ * on them; box_host is ignored); every bound is clamped to its axis and a reversed or empty range swaps nothing.  Else box_host: six
+ * host ints inside [0, fpc] x [0, out_h] x [0, out_w], no reversed range.  The middle clip of an odd count is not touched; clips <= 1
+ * or an empty host box launches nothing.
+ * vl_cutmix_pairs: x0 is vl_input_prep_u8's destination for clips * fpc frames (dst_halo = halo, dst_phase = phase): pixel (y, x) of
+ * channel c is in plane c * phase + (x + halo) % phase, row y + halo, column (x + halo) / phase. */
+int vl_cutmix_pairs(float* x0, int clips, int fpc, int out_h, int out_w, int halo, int phase, const int32_t* box_host,
+                    const int32_t* box_dev, vl_stream_t stream);
+/* The same on vl_input_prep_u8_s2d's destination for the descriptor d (the frame is d's h x w): element j of chunk (cb, R, S) is
+ * channel cp = 8 cb + j with px = cp % s, py = (cp / s) % s, c = cp / s^2, at pixel (s R + py - pt, s S + px - pl). */
+int vl_cutmix_pairs_s2d(const vl_conv_desc* d, void* xb, int clips, int fpc, const int32_t* box_host, const int32_t* box_dev,
+                        vl_stream_t stream);
+
 /* ---- optimizer: clip_by_global_norm + GradientDescentOptimizer (train.py:199-222) ---------------
  * vl_sumsq: out[0] (+)= sum g^2 over count elements (ws: float[1024]); accumulate != 0 adds to out. */
 int vl_sumsq(const float* g, int64_t count, float* out, float* ws, int accumulate, vl_stream_t stream);

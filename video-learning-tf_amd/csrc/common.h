@@ -86,6 +86,38 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- CutMix box (vl_cutmix_pairs in pointwise.hip, vl_cutmix_pairs_s2d in conv_c8.hip) ---------------------------------
+// {t0, t1, y0, y1, x0, x1}, half-open.  A launch takes it by value (a checked host box) or reads six device words when it runs.
+struct vl_cut_box {
+    int v[6];
+};
+
+// The box a kernel works on: every bound clamped to its axis [0, n], so that no content of the device words reaches an address;
+// false when an axis is then empty (reversed ranges included).  Wave-uniform: the words are the same for every thread.
+__device__ __forceinline__ bool cut_box_get(const vl_cut_box& arg, const int32_t* __restrict__ dev, int fpc, int H, int W, int (&b)[6]) {
+    const int lim[3] = {fpc, H, W};
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int v = dev ? dev[i] : arg.v[i];
+        b[i] = v < 0 ? 0 : (v > lim[i >> 1] ? lim[i >> 1] : v);
+    }
+    return b[0] < b[1] && b[2] < b[3] && b[4] < b[5];
+}
+
+// host side of both launches: six host ints inside [0, fpc] x [0, H] x [0, W], no reversed range
+static inline int cut_box_host_check(const int32_t* box, int fpc, int H, int W, const char* who, vl_cut_box* out) {
+    const int lim[3] = {fpc, H, W};
+    static const char* const axis[3] = {"t", "y", "x"};
+    for (int a = 0; a < 3; ++a) {
+        const int lo = box[2 * a], hi = box[2 * a + 1];
+        VL_CHECK(lo >= 0 && hi <= lim[a], "%s: the box's %s range [%d, %d) leaves [0, %d]", who, axis[a], lo, hi, lim[a]);
+        VL_CHECK(lo <= hi, "%s: the box's %s range [%d, %d) is reversed", who, axis[a], lo, hi);
+        out->v[2 * a] = lo;
+        out->v[2 * a + 1] = hi;
+    }
+    return 0;
+}
+
 // ---- LSTM recurrence: per-clip form (pointwise.hip), the fallback / A-B reference of the cluster form (lstm_cluster.hip) ------
 int vl_lstm_perclip_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
                         float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, hipStream_t stream);

@@ -1293,6 +1293,103 @@ extern "C" int vl_input_prep_u8_s2d(const vl_conv_desc* d, const uint8_t* src, v
     return 0;
 }
 
+// CutMix / VideoMix in that packed input (vl_cutmix_pairs in pointwise.hip is the fp32 form): the (t, y, x) box of the
+// frames is swapped between clip i and clip clips - 1 - i.  Element j of chunk (cb, R, S) is channel cp = 8 cb + j of the
+// space-to-depth input -- px = cp % s, py = (cp / s) % s, c = cp / s^2 -- at pixel (s R + py - pt, s S + px - pl); AlexNet's
+// 3-channel stride-4 feed kernel writes this same map.  A box edge that is no multiple of s cuts through a chunk: the kernel picks per
+// element (a 16-bit mask per half word) and stores the chunk whole; a chunk with no element in the box is neither loaded nor stored,
+// and the unused channel slots of the last chunk (c >= C) are never picked.
+// grid (x: tiles of CUT_S2D_ROWS chunk rows, y: the frame of the clip, z: pairs), the same for every box; blockDim (64, 4): a wave
+// takes one (chunk plane, row) at a time, lanes along the row's chunks (16 bytes each).  Workgroups whose frame or rows hold nothing
+// of the box return after a uniform branch.
+#define CUT_S2D_ROWS 4
+__global__ __launch_bounds__(256) void cutmix_pairs_s2d_kernel(uint4* __restrict__ xb, int clips, int fpc, int C, int s, int H, int W, int pt,
+                                                               int pl, int OHp, int OWp, int CB, vl_cut_box arg,
+                                                               const int32_t* __restrict__ box_dev) {
+    int b[6];
+    if (!cut_box_get(arg, box_dev, fpc, H, W, b)) return;
+    const int t = blockIdx.y;
+    if (t < b[0] || t >= b[1]) return;
+    // the chunk rows / columns that hold a pixel of the box (never past the buffer, whatever pt / pl are)
+    const int Rlo = max((b[2] + pt) / s, (int)blockIdx.x * CUT_S2D_ROWS);
+    const int Rhi = min(min((b[3] - 1 + pt) / s + 1, OHp), ((int)blockIdx.x + 1) * CUT_S2D_ROWS);
+    if (Rlo >= Rhi) return;
+    const int Slo = (b[4] + pl) / s, Shi = min((b[5] - 1 + pl) / s + 1, OWp);
+    const int64_t plane = (int64_t)OHp * OWp, frame = CB * plane;
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    for (int pj = blockIdx.z; pj < clips / 2; pj += gridDim.z) {
+        uint4* __restrict__ pa = xb + ((int64_t)pj * fpc + t) * frame;
+        uint4* __restrict__ pb = xb + ((int64_t)(clips - 1 - pj) * fpc + t) * frame;
+        for (int i = wv; i < CB * CUT_S2D_ROWS; i += 4) {
+            const int cb = i / CUT_S2D_ROWS, R = Rlo + i % CUT_S2D_ROWS;
+            if (R >= Rhi) continue;
+            // the chunk's eight (c, py, px), counted up from those of its first element; rows: the elements whose pixel row is in the box
+            int px = (8 * cb) % s, py = ((8 * cb) / s) % s, c = (8 * cb) / (s * s);
+            int pxs[8];
+            uint32_t rows = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int y = s * R + py - pt;
+                if (c < C && y >= b[2] && y < b[3]) rows |= 1u << j;
+                pxs[j] = px;
+                if (++px == s) {
+                    px = 0;
+                    if (++py == s) {
+                        py = 0;
+                        ++c;
+                    }
+                }
+            }
+            if (!rows) continue;                                      // (uniform over the wave)
+            const int64_t row = cb * plane + (int64_t)R * OWp;
+            for (int S = Slo + lane; S < Shi; S += 64) {
+                uint32_t m = 0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int x = s * S + pxs[j] - pl;
+                    if (x >= b[4] && x < b[5]) m |= 1u << j;
+                }
+                m &= rows;
+                if (!m) continue;
+                const uint4 av = pa[row + S], bv = pb[row + S];
+                const uint32_t aw[4] = {av.x, av.y, av.z, av.w}, bw[4] = {bv.x, bv.y, bv.z, bv.w};
+                uint32_t na[4], nb[4];
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const uint32_t sel = ((m >> (2 * w)) & 1u ? 0xffffu : 0u) | ((m >> (2 * w + 1)) & 1u ? 0xffff0000u : 0u);
+                    na[w] = (aw[w] & ~sel) | (bw[w] & sel);
+                    nb[w] = (bw[w] & ~sel) | (aw[w] & sel);
+                }
+                pa[row + S] = make_uint4(na[0], na[1], na[2], na[3]);
+                pb[row + S] = make_uint4(nb[0], nb[1], nb[2], nb[3]);
+            }
+        }
+    }
+}
+
+extern "C" int vl_cutmix_pairs_s2d(const vl_conv_desc* d, void* xb, int clips, int fpc, const int32_t* box_host, const int32_t* box_dev,
+                                   vl_stream_t stream) {
+    VL_CHECK(xb, "vl_cutmix_pairs_s2d: xb is null");
+    VL_CHECK(box_host || box_dev, "vl_cutmix_pairs_s2d: both box pointers are null");
+    VL_CHECK(clips >= 0, "vl_cutmix_pairs_s2d: clips must be >= 0, got %d", clips);
+    VL_CHECK(fpc > 0 && fpc <= 65535, "vl_cutmix_pairs_s2d: fpc must lie in [1, 65535], got %d", fpc);
+    if (int rc = s2d_check(d, "vl_cutmix_pairs_s2d")) return rc;
+    VL_CHECK(((uintptr_t)xb & 15) == 0, "vl_cutmix_pairs_s2d: xb is not 16-byte aligned");
+    vl_cut_box box = {{0, 0, 0, 0, 0, 0}};
+    if (!box_dev) {
+        if (int rc = cut_box_host_check(box_host, fpc, d->h, d->w, "vl_cutmix_pairs_s2d", &box)) return rc;
+        if (box.v[0] == box.v[1] || box.v[2] == box.v[3] || box.v[4] == box.v[5]) return 0;
+    }
+    if (clips <= 1) return 0;
+    const int s = d->stride, ka = (d->kh - 1) / s + 1, OHp = d->oh + ka - 1, OWp = d->ow + ka - 1, CB = (d->cin * s * s + 7) / 8;
+    const int pairs = clips / 2;
+    const dim3 grid((OHp + CUT_S2D_ROWS - 1) / CUT_S2D_ROWS, fpc, pairs < 65535 ? pairs : 65535);
+    hipLaunchKernelGGL(cutmix_pairs_s2d_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, (uint4*)xb, clips, fpc, d->cin, s, d->h, d->w,
+                       d->pt, d->pl, OHp, OWp, CB, box, box_dev);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- dense products on the wgrad kernel --------------------------------------------------------------------------------------------
 // C[m][n] = sum_k A[k][m] B[k][n] is what wgrad_c8_kernel computes when "positions" are k and both operands are stored position-major
 // in 8-channel blocks: "kc8" = [channel block][k][8] bf16 (one image, no halo, one tap per block of A).  fc6's three products are

@@ -2292,6 +2292,66 @@ extern "C" int vl_softmax_xent_mix(const float* logits, const int32_t* labels, f
     return 0;
 }
 
+// ---- CutMix / VideoMix (Yun et al. 2019, 2020): one (t, y, x) box swapped between the paired clips, in place, in x0 -----
+// x0 is what input_prep_u8_kernel writes: [clips * fpc][3][phase][oh + 2 halo][wq] with logical pixel (y, x) of channel c in plane
+// c * phase + (x + halo) % phase, row y + halo, column (x + halo) / phase.  In the plane of phase ph the box's columns are the
+// contiguous run q in [ceil((x0 + halo - ph) / phase), ceil((x1 + halo - ph) / phase)).
+// grid (x: tiles of CUT_ROWS rows, y: the frame of the clip, z: pairs), the same for every box; blockDim (64, 4).  A workgroup whose
+// frame or rows lie outside the box returns after a uniform branch.  A wave takes one (plane, row) piece at a time, its lanes along the
+// row; a thread loads the same offset of both partners and stores both (the pairing is an involution: nothing is read after it was
+// written).  The words move as integers, so every bit pattern (-0, NaN payloads) arrives as it left.
+#define CUT_ROWS 8
+__global__ __launch_bounds__(256) void cutmix_pairs_f32_kernel(uint32_t* __restrict__ x, int clips, int fpc, int oh, int ow, int halo,
+                                                               int phase, int wq, vl_cut_box arg, const int32_t* __restrict__ box_dev) {
+    int b[6];
+    if (!cut_box_get(arg, box_dev, fpc, oh, ow, b)) return;
+    const int t = blockIdx.y;
+    if (t < b[0] || t >= b[1]) return;
+    const int ylo = max(b[2], (int)blockIdx.x * CUT_ROWS), yhi = min(b[3], ((int)blockIdx.x + 1) * CUT_ROWS);
+    if (ylo >= yhi) return;
+    const int64_t plane = (int64_t)(oh + 2 * halo) * wq, frame = 3 * phase * plane;
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    for (int j = blockIdx.z; j < clips / 2; j += gridDim.z) {
+        uint32_t* __restrict__ pa = x + ((int64_t)j * fpc + t) * frame;
+        uint32_t* __restrict__ pb = x + ((int64_t)(clips - 1 - j) * fpc + t) * frame;
+        for (int i = wv; i < 3 * phase * CUT_ROWS; i += 4) {
+            const int pl = i / CUT_ROWS, y = ylo + i % CUT_ROWS, ph = pl % phase;
+            if (y >= yhi) continue;
+            const int qlo = (b[4] + halo - ph + phase - 1) / phase, qhi = (b[5] + halo - ph + phase - 1) / phase;
+            const int64_t row = pl * plane + (int64_t)(y + halo) * wq;
+            for (int q = qlo + lane; q < qhi; q += 64) {
+                const uint32_t av = pa[row + q], bv = pb[row + q];
+                pa[row + q] = bv;
+                pb[row + q] = av;
+            }
+        }
+    }
+}
+
+extern "C" int vl_cutmix_pairs(float* x0, int clips, int fpc, int out_h, int out_w, int halo, int phase, const int32_t* box_host,
+                               const int32_t* box_dev, vl_stream_t stream) {
+    VL_CHECK(x0, "vl_cutmix_pairs: x0 is null");
+    VL_CHECK(box_host || box_dev, "vl_cutmix_pairs: both box pointers are null");
+    VL_CHECK(clips >= 0, "vl_cutmix_pairs: clips must be >= 0, got %d", clips);
+    VL_CHECK(fpc > 0 && fpc <= 65535, "vl_cutmix_pairs: fpc must lie in [1, 65535], got %d", fpc);
+    VL_CHECK(out_h > 0 && out_w > 0, "vl_cutmix_pairs: bad frame size %d x %d", out_h, out_w);
+    VL_CHECK(halo >= 0, "vl_cutmix_pairs: halo must be >= 0, got %d", halo);
+    VL_CHECK(phase >= 1, "vl_cutmix_pairs: phase must be >= 1, got %d", phase);
+    VL_CHECK(((uintptr_t)x0 & 3) == 0, "vl_cutmix_pairs: x0 is not 4-byte aligned");
+    vl_cut_box box = {{0, 0, 0, 0, 0, 0}};
+    if (!box_dev) {
+        if (int rc = cut_box_host_check(box_host, fpc, out_h, out_w, "vl_cutmix_pairs", &box)) return rc;
+        if (box.v[0] == box.v[1] || box.v[2] == box.v[3] || box.v[4] == box.v[5]) return 0;
+    }
+    if (clips <= 1) return 0;
+    const int wq = (out_w + 2 * halo + phase - 1) / phase, pairs = clips / 2;
+    const dim3 grid((out_h + CUT_ROWS - 1) / CUT_ROWS, fpc, pairs < 65535 ? pairs : 65535);
+    hipLaunchKernelGGL(cutmix_pairs_f32_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, (uint32_t*)x0, clips, fpc, out_h, out_w, halo,
+                       phase, wq, box, box_dev);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- global norm + SGD / Adam (train.py:199-222) ----------------------------------------------
 // ---- tier table (vltf.h: vl_lr_tier): the ranges of the flat buffer an update / a norm touches, by value in the launch arguments --
 struct tier_table {

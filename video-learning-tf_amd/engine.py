@@ -76,6 +76,10 @@ class NetConfig:
     top_k: int = 0                              # train.top_k: also count the rows whose label is among the k largest logits; 0 = off
     mixup_alpha: float = 0.0                    # train.mixup_alpha: mixup's Beta(alpha, alpha) (clips and labels blended in pairs); 0 = off
     mixup_seed: int = 0                         # train.mixup_seed: the key of the blend-weight draws (mixup_lambda)
+    cutmix_alpha: float = 0.0                   # train.cutmix_alpha: CutMix / VideoMix's Beta(alpha, alpha) (a box swapped in pairs); 0 = off
+    cutmix_seed: int = 0                        # train.cutmix_seed: the key of the box draws (cutmix_box)
+    cutmix_mode: Optional[str] = None           # train.cutmix_mode: spatial | temporal | cuboid; None = spatial when cutmix is on
+    cutmix_prob: Optional[float] = None         # train.cutmix_prob: with mixup on too, the chance that a batch is cut; None = 0.5
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -386,6 +390,112 @@ def mixup_lambda(alpha, seed, draw_index):
         return 1.0
     rng = np.random.Generator(np.random.Philox(key=np.array([seed, int(draw_index)], np.uint64)))
     return fold_lambda(float(rng.beta(alpha, alpha)))
+
+
+CUTMIX_MODES = ("spatial", "temporal", "cuboid")
+
+
+def check_cutmix(alpha, seed=None, mode=None, prob=None):
+    """(alpha, seed, mode, prob) of CutMix / VideoMix as (float, int, str, float), None read as off / the default.  alpha: a finite
+    number >= 0, the Beta(alpha, alpha) the cut fraction is drawn from (0 = off).  seed: a whole number in [0, 2^64), the key of the
+    draws (cutmix_box).  mode: which axes the box spans -- 'spatial' (every frame, a y-x rectangle; the default), 'temporal' (whole
+    frames, a run of t) or 'cuboid' (all three).  prob: with mixup on as well, the chance in [0, 1] that a batch is cut and not blended
+    (default 0.5).  Refused: bools and strings for a number, a negative, NaN or infinite alpha, a seed that is not whole or negative,
+    an unknown mode, a prob outside [0, 1], and a seed, mode or prob without an alpha."""
+    def number(v, name, what):
+        if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise VltfError("%s must be %s, got %r" % (name, what, v))
+        return v
+
+    a = 0.0
+    if alpha is not None:
+        a = float(number(alpha, "cutmix_alpha", "a finite number >= 0 (0 / None = off)"))
+        if not (math.isfinite(a) and a >= 0.0):
+            raise VltfError("cutmix_alpha must be a finite number >= 0 (0 / None = off), got %r" % (alpha,))
+    s = 0
+    if seed is not None:
+        number(seed, "cutmix_seed", "a whole number >= 0")
+        if isinstance(seed, (float, np.floating)) and not (math.isfinite(seed) and float(seed) == int(seed)):
+            raise VltfError("cutmix_seed must be a whole number >= 0, got %r" % (seed,))
+        s = int(seed)
+        if not (0 <= s < 2 ** 64):
+            raise VltfError("cutmix_seed must be a whole number >= 0 (below 2^64), got %r" % (seed,))
+    if mode is not None and (not isinstance(mode, str) or mode not in CUTMIX_MODES):
+        raise VltfError("cutmix_mode must be one of %s, got %r" % (" | ".join(CUTMIX_MODES), mode))
+    pr = 0.5
+    if prob is not None:
+        pr = float(number(prob, "cutmix_prob", "a number in [0, 1]"))
+        if not (0.0 <= pr <= 1.0):                # (NaN fails both)
+            raise VltfError("cutmix_prob must be a number in [0, 1], got %r" % (prob,))
+    if a == 0.0:
+        for name, given in (("cutmix_seed", s != 0), ("cutmix_mode", mode is not None), ("cutmix_prob", prob is not None)):
+            if given:
+                raise VltfError("%s is given without cutmix_alpha: CutMix is off and nothing would be drawn" % name)
+    return a, s, mode if mode is not None else "spatial", pr
+
+
+def cutmix_lambda(box, fpc, h, w):
+    """The label weight of a cut: 1 - volume(box) / (fpc * h * w), from the integers in fp64, then rounded to the fp32 the device word
+    holds.  1.0 exactly when the box is empty."""
+    t0, t1, y0, y1, x0, x1 = (int(v) for v in box)
+    vol = max(t1 - t0, 0) * max(y1 - y0, 0) * max(x1 - x0, 0)
+    return float(np.float32(1.0 - vol / float(fpc * h * w)))
+
+
+def check_cut_box(box, fpc, h, w):
+    """A caller's box (t0, t1, y0, y1, x0, x1) as six ints.  Refused: anything but six whole numbers, a range that leaves
+    [0, fpc] x [0, h] x [0, w] or is reversed, and a volume above half the clip (the own label has to stay the dominant one)."""
+    try:
+        vals = tuple(int(v) for v in box)
+        ok = len(vals) == 6 and all(not isinstance(v, (bool, np.bool_, str, bytes)) and float(v) == int(v) for v in box)
+    except (TypeError, ValueError):
+        vals, ok = (), False
+    if not ok:
+        raise VltfError("cut_box must be six whole numbers (t0, t1, y0, y1, x0, x1), got %r" % (box,))
+    for a, (name, n) in enumerate((("t", fpc), ("y", h), ("x", w))):
+        lo, hi = vals[2 * a], vals[2 * a + 1]
+        if lo < 0 or hi > n or lo > n or hi < 0:
+            raise VltfError("cut_box: the %s range [%d, %d) leaves the frame's [0, %d]" % (name, lo, hi, n))
+        if lo > hi:
+            raise VltfError("cut_box: the %s range [%d, %d) is reversed" % (name, lo, hi))
+    vol = (vals[1] - vals[0]) * (vals[3] - vals[2]) * (vals[5] - vals[4])
+    if 2 * vol > fpc * h * w:
+        raise VltfError("cut_box: the volume %d is above half the clip (%d x %d x %d): the partner's label would dominate"
+                        % (vol, fpc, h, w))
+    return vals
+
+
+def cutmix_box(alpha, seed, mode, draw_index, fpc, h, w):
+    """((t0, t1, y0, y1, x0, x1), u) of the step with this draw index (LRCNEngine._draw_index): the half-open box that clip i and clip
+    B - 1 - i exchange, and the uniform number that decides between CutMix and mixup when both are on (u < cutmix_prob: cut).  One
+    Philox generator keyed by (seed, draw_index), drawn from in a fixed order whatever the mode: lam0 = Beta(alpha, alpha) folded to
+    max(lam0, 1 - lam0) (the cut is at most half the clip); the centres ct, cy, cx, uniform over fpc, h, w; last u.  The extents are
+    (fpc, int(h r), int(w r)) with r = sqrt(1 - lam0) for 'spatial', (int(fpc (1 - lam0)), h, w) for 'temporal' and
+    (int(fpc r), int(h r), int(w r)) with r = cbrt(1 - lam0) for 'cuboid'; an axis runs over [c - b // 2, c - b // 2 + b) clipped
+    to it (timm's rule), a full-extent axis over all of it.  A pure function of its arguments: every rank draws the same box, every
+    micro-step its own, and a resumed run continues the sequence."""
+    alpha, seed, mode, _ = check_cutmix(alpha, seed, mode)
+    fpc, h, w = int(fpc), int(h), int(w)
+    if alpha == 0.0:
+        return (0, 0, 0, 0, 0, 0), 1.0
+    rng = np.random.Generator(np.random.Philox(key=np.array([seed, int(draw_index)], np.uint64)))
+    lam0 = fold_lambda(float(rng.beta(alpha, alpha)))
+    cut = 1.0 - lam0
+    if mode == "spatial":
+        r = math.sqrt(cut)
+        ext = (fpc, int(h * r), int(w * r))
+    elif mode == "temporal":
+        ext = (int(fpc * cut), h, w)
+    else:
+        r = float(np.cbrt(cut))
+        ext = (int(fpc * r), int(h * r), int(w * r))
+    centres = [int(rng.integers(n)) for n in (fpc, h, w)]
+    box = []
+    for c, b, n in zip(centres, ext, (fpc, h, w)):
+        lo = c - b // 2
+        box += [0, n] if b >= n else [min(max(lo, 0), n), min(max(lo + b, 0), n)]
+    u = float(rng.random())
+    return tuple(box), u
 
 
 def dropout_seed(draw_index):
@@ -726,7 +836,8 @@ class LRCNEngine:
     With NetConfig.ema_decay > 0 the captured update is followed by the weight average's launch, which reads its rate from the block:
     ops.step_state_set_ema writes it (engine.ema_rate of the host's step_count) before every replay that applies an update.
     With NetConfig.mixup_alpha > 0 the captured step holds the blend and the mixed-label loss launch; both read the blend weight from
-    a one-float device word (mix_lam) the host fills before every step, eager or replayed (_mix_write): the block stays as it is."""
+    a one-float device word (mix_lam) the host fills before every step, eager or replayed (_mix_write): the block stays as it is.
+    With NetConfig.cutmix_alpha > 0 the captured step holds the box swap too, which reads its six-int32 box (cut_box) the same way."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -1186,37 +1297,90 @@ class LRCNEngine:
             out["topk_accuracy"], out["topk_correct"] = float(st[2]) / max(rows, 1), float(st[2])
         return out
 
-    # ---- mixup (mixup_alpha, mixup_seed) ---------------------------------------------------------------------------------
+    # ---- mixup (mixup_alpha, mixup_seed) and CutMix / VideoMix (cutmix_*) -----------------------------------
     def _mix_setup(self, alpha, seed, rows):
-        """Off (alpha 0, or an engine that does not train): nothing is allocated and no launch changes.  On: the one-float device word
-        both launches read (written before every step, outside any capture), and the three sums and 3 * rows workspace of
-        ops.softmax_xent_mix when label smoothing / top-k have not asked for them already."""
+        """Off (both alphas 0, or an engine that does not train): nothing is allocated and no launch changes.  On: the one-float device
+        word the loss launch reads (mix_lam; written before every step, outside any capture), and the three sums and 3 * rows workspace
+        of ops.softmax_xent_mix when label smoothing / top-k have not asked for them already.  Mixup's blend reads the same word.
+        CutMix adds the six-int32 box its launch reads (cut_box); with both on the blend reads a word of its own (blend_lam), which
+        holds 1 for a batch that is cut, while mix_lam holds the weight of the method the batch uses."""
+        cfg = self.cfg
         self.mixup_alpha, self.mixup_seed = check_mixup(alpha, seed)
-        self.mix_lam = None
+        self.cutmix_alpha, self.cutmix_seed, self.cutmix_mode, self.cutmix_prob = check_cutmix(cfg.cutmix_alpha, cfg.cutmix_seed,
+                                                                                               cfg.cutmix_mode, cfg.cutmix_prob)
+        self.mix_lam = self.blend_lam = self.cut_box = None
         if not self.training or self.mixup_alpha == 0.0:
             self.mixup_alpha, self.mixup_seed = 0.0, 0
+        if not self.training or self.cutmix_alpha == 0.0:
+            self.cutmix_alpha, self.cutmix_seed = 0.0, 0
+        if self.mixup_alpha == 0.0 and self.cutmix_alpha == 0.0:
             return
         self.mix_lam = torch.ones(1, device=self.dev)
+        if self.mixup_alpha > 0.0:
+            self.blend_lam = self.mix_lam
+        if self.cutmix_alpha > 0.0:
+            self.cut_box = torch.zeros(6, dtype=torch.int32, device=self.dev)
+            self.cut_box_last = (0, 0, 0, 0, 0, 0)
+            if self.mixup_alpha > 0.0:
+                self.blend_lam = torch.ones(1, device=self.dev)
         if not self.xent_ls:
             self.stats = torch.zeros(3, device=self.dev)
             self.loss_rows = torch.zeros(3 * rows, device=self.dev)
 
-    def _mix_write(self, mix_lambda, mi):
-        """Before a train step, eager or replayed: the step's blend weight goes to the device word on the stream (the caller's
-        mix_lambda folded, or the draw of the step's draw index), and is kept as self.mix_lambda_last."""
-        if self.mix_lam is None:
+    def _mix_write(self, mix_lambda, mi, cut_box=None):
+        """Before a train step, eager or replayed: the step's label weight (and, with CutMix on, its box) go to the device words on the
+        stream, and are kept as self.mix_lambda_last / self.cut_box_last.  Mixup alone: the caller's mix_lambda folded, or the draw of
+        the step's draw index.  CutMix alone: the caller's cut_box, or cutmix_box's draw; the weight is cutmix_lambda of the box.  Both
+        on: the batch is cut when cutmix_box's u < cutmix_prob, else blended with mixup_lambda's weight (a caller's cut_box or
+        mix_lambda decides instead); the method not chosen gets its identity, an empty box or a blend weight of 1."""
+        if cut_box is not None:
+            if self.cut_box is None:
+                raise VltfError("cut_box is given, but CutMix is off on this engine (NetConfig.cutmix_alpha is 0)")
             if mix_lambda is not None:
-                raise VltfError("mix_lambda is given, but mixup is off on this engine (NetConfig.mixup_alpha is 0)")
+                raise VltfError("cut_box and mix_lambda are given together: a batch is either cut or blended")
+        if mix_lambda is not None and self.blend_lam is None:
+            raise VltfError("mix_lambda is given, but mixup is off on this engine (NetConfig.mixup_alpha is 0)")
+        if self.mix_lam is None:
             return
-        lam = fold_lambda(mix_lambda) if mix_lambda is not None else mixup_lambda(self.mixup_alpha, self.mixup_seed, self._draw_index(mi))
+        draw = self._draw_index(mi)
+        if self.cut_box is None:                  # mixup alone: as before
+            lam = fold_lambda(mix_lambda) if mix_lambda is not None else mixup_lambda(self.mixup_alpha, self.mixup_seed, draw)
+            ops.fill(self.mix_lam, lam)
+            self.mix_lambda_last = lam
+            return
+        fpc, (h, w) = self.T, self.cfg.image_shape[:2]
+        if cut_box is not None:
+            box, cut = check_cut_box(cut_box, fpc, h, w), True
+        elif mix_lambda is not None:
+            box, cut = None, False
+        else:
+            box, u = cutmix_box(self.cutmix_alpha, self.cutmix_seed, self.cutmix_mode, draw, fpc, h, w)
+            cut = self.blend_lam is None or u < self.cutmix_prob
+        if cut:
+            lam = cutmix_lambda(box, fpc, h, w)
+        else:
+            box = (0, 0, 0, 0, 0, 0)
+            lam = fold_lambda(mix_lambda) if mix_lambda is not None else mixup_lambda(self.mixup_alpha, self.mixup_seed, draw)
+        self.cut_box.copy_(torch.tensor(box, dtype=torch.int32))
         ops.fill(self.mix_lam, lam)
-        self.mix_lambda_last = lam
+        if self.blend_lam is not None:
+            ops.fill(self.blend_lam, 1.0 if cut else lam)
+        self.mix_lambda_last, self.cut_box_last = lam, tuple(box)
 
     def _mix_launch(self, n, b):
-        """The blend of the clips just fed, in place, in the layout conv1 reads: the packed space-to-depth input when feed_u8 wrote it
-        directly (bf16 path), else x0.  Clip i with clip b - 1 - i; the halo and padding zeros blend to zero."""
-        if self.mix_lam is not None:
-            ops.mixup_pairs(self.layers[0]["xb"][:n] if (self.c8 and self._xb_fed) else self.x0[:n], b, self.mix_lam)
+        """The blend and / or the cut of the clips just fed, in place, in the layout conv1 reads: the packed space-to-depth input when
+        feed_u8 wrote it directly (bf16 path), else x0 (frames fed as fp32 on the bf16 path are mixed there, ahead of the pack).  Clip i
+        with clip b - 1 - i; the halo and padding zeros blend to zero, and the cut leaves them alone."""
+        if self.mix_lam is None:
+            return
+        packed = self.c8 and self._xb_fed
+        if self.blend_lam is not None:
+            ops.mixup_pairs(self.layers[0]["xb"][:n] if packed else self.x0[:n], b, self.blend_lam)
+        if self.cut_box is not None:
+            if packed:
+                self.layers[0]["conv"].cutmix_pairs_s2d(self.layers[0]["xb"][:n], b, self.T, self.cut_box)
+            else:
+                ops.cutmix_pairs(self.x0[:n], b, self.T, self.cfg.image_shape[:2], self.x0_halo, self.x0_phase, self.cut_box)
 
     # ---- LARS (lars_eeta; shared with GraphEngine) ----------------------------------------------------------------------------------------
     def _lars_setup(self):
@@ -2064,16 +2228,18 @@ class LRCNEngine:
         return b if (self.early or self.late) else n
 
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None):
+                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None, cut_box=None):
         """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44).
         micro = (i, k): micro-step i of an update that sums k of them (k <= cfg.accumulate), called in order i = 0 .. k - 1.  Only the
         last one exchanges, regularises, clips and updates, with its lr; the others return the running loss of the update and no
         grad_norm.  The loss is scaled by 1 / (rows * world * k) unless global_rows gives the rows of the whole update.
         mix_lambda: with mixup on (cfg.mixup_alpha > 0), this step's blend weight in [0, 1] in the place of the draw (folded to
-        max(lam, 1 - lam)); refused with mixup off."""
+        max(lam, 1 - lam)); refused with mixup off.
+        cut_box: with CutMix on (cfg.cutmix_alpha > 0), this step's box (t0, t1, y0, y1, x0, x1) in the place of the draw; refused with
+        CutMix off, outside the frame, reversed, above half the clip's volume, or together with mix_lambda (check_cut_box)."""
         mi = self.micro.enter(micro)
         try:
-            self._mix_write(mix_lambda, mi)
+            self._mix_write(mix_lambda, mi, cut_box)
             if self.step_graph:
                 done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
                                              global_rows, mi)
@@ -2085,10 +2251,11 @@ class LRCNEngine:
             self.micro.reset()
             raise
 
-    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None, mix_lambda=None):
+    def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None, mix_lambda=None,
+                       cut_box=None):
         mi = self.micro.enter(micro)
         try:
-            self._mix_write(mix_lambda, mi)
+            self._mix_write(mix_lambda, mi, cut_box)
             n, b = self.feed_f32_nhwc(frames_nhwc)
             return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
         except VltfError:

@@ -41,7 +41,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_label_smoothing,
-                     check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
+                     check_cutmix, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
 
 
@@ -755,7 +755,7 @@ class GraphEngine:
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
                  lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0,
-                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0):
+                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -773,7 +773,12 @@ class GraphEngine:
         engine.check_top_k, LRCNEngine._loss_setup); a forward-only engine ignores them; 0 = off.  lamb, lamb_epsilon: LAMB
         (tfa.optimizers.LAMB) in the place of the Adam update -- Adam's moments, a trust ratio |w| / |u| per trained weight tensor of rank
         >= 2 of every pipeline, weight_decay decoupled (engine.check_lamb, engine.lamb_ranges, LRCNEngine._lamb_setup); optimizer adam
-        only; False = off.  mixup_alpha: refused when > 0 -- mixup pairs the clips of ONE dcnn pipeline (LRCNEngine)."""
+        only; False = off.  mixup_alpha: refused when > 0 -- mixup pairs the clips of ONE dcnn pipeline (LRCNEngine).
+        cutmix_alpha: refused when > 0 for the same reason."""
+        if check_cutmix(cutmix_alpha)[0] > 0.0:
+            raise VltfError("cutmix_alpha = %s is refused by GraphEngine: frame towers, vector inputs, clips-per-video ratios and word-level "
+                            "losses have no one clip to pair; CutMix runs on single-pipeline models (LRCNEngine, NetConfig.cutmix_alpha)"
+                            % (cutmix_alpha,))
         if check_mixup(mixup_alpha)[0] > 0.0:
             raise VltfError("mixup_alpha = %s is refused by GraphEngine: frame towers, vector inputs, clips-per-video ratios and word-level "
                             "losses have no one clip to pair; mixup runs on single-pipeline models (LRCNEngine, NetConfig.mixup_alpha)"

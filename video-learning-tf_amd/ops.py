@@ -227,6 +227,20 @@ class Conv:
         _ffi.call("vl_input_prep_u8_s2d", self._d, _p(src), _p(xb), n, src.shape[1], src.shape[2], _p(crop_y), _p(crop_x), _p(mirror),
                   _p(mean_bgr), stream())
 
+    def cutmix_pairs_s2d(self, xb, clips, fpc, box):
+        """CutMix / VideoMix in place in the packed space-to-depth input (vl_cutmix_pairs_s2d): xb is what input_prep_u8_s2d writes
+        for clips * fpc frames; the box (t0, t1, y0, y1, x0, x1) of the h x w frames is exchanged between clip i and clip
+        clips - 1 - i bit for bit.  box: a 6-tuple or a six-int32 device tensor, as in ops.cutmix_pairs."""
+        clips, fpc = int(clips), int(fpc)
+        s, ka = self.stride, (self.kh - 1) // self.stride + 1
+        if not torch.is_tensor(xb) or not xb.is_cuda or xb.dtype != torch.bfloat16 or not xb.is_contiguous() or \
+                (clips >= 0 and fpc > 0 and tuple(xb.shape) != c8_shape(clips * fpc, self.cin * s * s, self.oh, self.ow, (ka - 1) // 2)):
+            raise _ffi.VltfError("conv.cutmix_pairs_s2d: xb must be the contiguous bf16 packed input of %d clips of %d frames, got %s"
+                                 % (clips, fpc, tuple(xb.shape) if torch.is_tensor(xb) else type(xb)))
+        host, dev, keep = _cut_box(box, "conv.cutmix_pairs_s2d")
+        _ffi.call("vl_cutmix_pairs_s2d", self._d, _p(xb), clips, fpc, host, dev, stream())
+        del keep
+
     def s2d_weights(self, src, dst, grad=False):
         """grad=False: w [k][k][cin][cout] -> [ka][ka][cin s^2][cout]; grad=True: the stride-1 layer's dw -> dw."""
         _f32(src, dst); _dense(src, dst)
@@ -683,6 +697,38 @@ def mixup_pairs(x, clips, lam):
     lam_host, lam_dev = _lam(lam, "mixup_pairs")
     _ffi.call("vl_mixup_pairs", _p(x), 0 if x.dtype == F32 else 1, clips, x.numel() // max(clips, 1), lam_host, lam_dev,
               stream())
+
+
+def _cut_box(box, what):
+    """(host pointer, device pointer, keep-alive) of a CutMix launch's box: a six-int32 device tensor is read when the kernel runs,
+    a 6-tuple (t0, t1, y0, y1, x0, x1) is six host ints."""
+    if torch.is_tensor(box):
+        if not (box.is_cuda and box.dtype == torch.int32 and box.numel() == 6 and box.is_contiguous()):
+            raise _ffi.VltfError("%s: a device box is six contiguous int32 words (t0, t1, y0, y1, x0, x1)" % what)
+        return None, _p(box), None
+    try:
+        vals = [int(v) for v in box]
+        whole = not isinstance(box, (str, bytes)) and all(not isinstance(v, (str, bytes)) and float(v) == int(v) for v in box)
+    except (TypeError, ValueError):
+        vals, whole = [], False
+    if len(vals) != 6 or not whole or any(not -2 ** 31 <= v < 2 ** 31 for v in vals):
+        raise _ffi.VltfError("%s: the box is six whole numbers (t0, t1, y0, y1, x0, x1), got %r" % (what, box))
+    host = (C.c_int32 * 6)(*vals)
+    return C.cast(host, C.c_void_p), None, host
+
+
+def cutmix_pairs(x0, clips, fpc, out_hw, halo, phase, box):
+    """CutMix / VideoMix in place in x0 (vl_cutmix_pairs): x0 is phase_split_shape(clips * fpc, 3, *out_hw, halo, phase), what
+    input_prep_u8 writes; the half-open box (t0, t1, y0, y1, x0, x1) of clip i and clip clips - 1 - i is exchanged bit for bit.
+    box: a 6-tuple, or a six-int32 device tensor (read when the kernel runs, clamped to the frame)."""
+    _f32(x0); _dense(x0)
+    clips, fpc = int(clips), int(fpc)
+    if clips >= 0 and fpc > 0 and tuple(x0.shape) != phase_split_shape(clips * fpc, 3, out_hw[0], out_hw[1], halo, phase):
+        raise _ffi.VltfError("cutmix_pairs: x0 %s is not %d clips of %d frames %s (halo %d, phase %d)"
+                             % (tuple(x0.shape), clips, fpc, tuple(out_hw), halo, phase))
+    host, dev, keep = _cut_box(box, "cutmix_pairs")
+    _ffi.call("vl_cutmix_pairs", _p(x0), clips, fpc, int(out_hw[0]), int(out_hw[1]), int(halo), int(phase), host, dev, stream())
+    del keep
 
 
 def softmax_xent_mix(logits, labels, dlogits, stats, grad_scale, rows, rows_per_clip, smoothing, top_k, lam):

@@ -60,7 +60,8 @@ def pipeline_net_config(settings, p, dataset):
               tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
               ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
               label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
-              lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0], mixup_seed=settings.get_mixup()[1])
+              lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0], mixup_seed=settings.get_mixup()[1],
+              **dict(zip(("cutmix_alpha", "cutmix_seed", "cutmix_mode", "cutmix_prob"), settings.get_cutmix())))
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -328,6 +329,9 @@ def main(init_file, seed=0, device=None):
         error("VLTF_STEP_GRAPH=1 is refused for this model: it runs on the multi-pipeline GraphEngine, which has no captured step")
     if settings.get_mixup()[0] > 0 and not single:
         error("train.mixup_alpha is refused for this model: it runs on the multi-pipeline GraphEngine, which has no mixup (frame towers, "
+              "vector inputs and word-level losses have no one clip to pair); use it with a single-pipeline model")
+    if settings.get_cutmix()[0] > 0 and not single:
+        error("train.cutmix_alpha is refused for this model: it runs on the multi-pipeline GraphEngine, which has no CutMix (frame towers, "
               "vector inputs and word-level losses have no one clip to pair); use it with a single-pipeline model")
     if world > 1:
         batch = -(-batch // world)           # data parallel: `batch_size` stays the GLOBAL batch of the config

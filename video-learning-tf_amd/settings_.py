@@ -28,6 +28,7 @@ class TrainSettings:
     lamb, lamb_epsilon = False, None
     label_smoothing, top_k = 0.0, 0
     mixup_alpha, mixup_seed = 0.0, 0
+    cutmix_alpha, cutmix_seed, cutmix_mode, cutmix_prob = 0.0, 0, None, None
 
 
 class ValSettings:
@@ -79,6 +80,13 @@ class Settings:
         """(train.mixup_alpha, train.mixup_seed): mixup's Beta(alpha, alpha) and the key of its draws (engine.check_mixup,
         engine.mixup_lambda); (0, 0) = off, and outside the train phase (validation never blends)."""
         return (self.train.mixup_alpha, self.train.mixup_seed) if self.phase == defs.phase.train else (0.0, 0)
+
+    def get_cutmix(self):
+        """(train.cutmix_alpha, train.cutmix_seed, train.cutmix_mode, train.cutmix_prob): CutMix / VideoMix's Beta(alpha, alpha), the key
+        of its box draws, the axes the box spans and, with mixup on too, the chance that a batch is cut (engine.check_cutmix,
+        engine.cutmix_box); (0, 0, None, None) = off, and outside the train phase (validation never cuts)."""
+        t = self.train
+        return (t.cutmix_alpha, t.cutmix_seed, t.cutmix_mode, t.cutmix_prob) if self.phase == defs.phase.train else (0.0, 0, None, None)
 
     def get_lamb(self):
         """(train.lamb, train.lamb_epsilon): LAMB in the place of the Adam update (engine.check_lamb; the epsilon is the checked one,
@@ -344,6 +352,22 @@ class Settings:
                     t.mixup_alpha, t.mixup_seed = check_mixup(*(None if v == "None" else v for v in mx))
                 except VltfError as ex:
                     error("train.mixup_alpha / train.mixup_seed: %s" % ex)
+                # CutMix / VideoMix (Yun et al. 2019, 2020): one box swapped in pairs inside a rank's batch, the cut fraction drawn from
+                # Beta(cutmix_alpha, cutmix_alpha) under the key cutmix_seed (engine.check_cutmix, engine.cutmix_box): absent / None = off
+                from .engine import check_cutmix
+                cm = [obj.get("cutmix_alpha"), obj.get("cutmix_seed"), obj.get("cutmix_mode"), obj.get("cutmix_prob")]
+                for i, conv in enumerate((float, int, None, float)):
+                    if conv is not None and isinstance(cm[i], str) and cm[i] != "None":      # a quoted number
+                        try:
+                            cm[i] = conv(cm[i])
+                        except ValueError:
+                            pass
+                try:
+                    a, sd, md, pr = check_cutmix(*(None if v == "None" else v for v in cm))
+                    t.cutmix_alpha, t.cutmix_seed = a, sd
+                    t.cutmix_mode, t.cutmix_prob = (md, pr) if a > 0.0 else (None, None)
+                except VltfError as ex:
+                    error("train.cutmix_alpha / train.cutmix_seed / train.cutmix_mode / train.cutmix_prob: %s" % ex)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:

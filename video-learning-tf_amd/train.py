@@ -162,6 +162,13 @@ class Train:
                  "clip B - 1 - i inside a rank's batch, and the logged loss is the one on the mixed labels" %
                  (engine.mixup_alpha, engine.mixup_seed))
 
+        if getattr(engine, "cut_box", None) is not None:
+            info("CutMix: alpha %s, seed %d, mode %s (one box per batch, at most half the clip); inside a rank's batch clip i and clip "
+                 "B - 1 - i exchange the box, the label weight is 1 - volume / clip volume%s" %
+                 (engine.cutmix_alpha, engine.cutmix_seed, engine.cutmix_mode,
+                  ("; with mixup on a batch is cut with probability %s, else blended" % engine.cutmix_prob)
+                  if engine.blend_lam is not None else ""))
+
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
         if self.stats_log is None or "tensor_stats" not in out:
