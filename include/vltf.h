@@ -65,6 +65,17 @@ int vl_device_count(void);
 int vl_input_prep_u8(const uint8_t* src, float* dst, int n, int raw_h, int raw_w, int out_h, int out_w,
                      const int32_t* crop_y, const int32_t* crop_x, const uint8_t* mirror,
                      const float* mean_bgr, int dst_halo, int dst_phase, vl_stream_t stream);
+/* Random resized crop: the same destination contract (interior rows whole, halo / padding columns 0.0, halo rows untouched,
+ * n <= 65535), the source a box per frame.  box: DEVICE int32 [n][4] = {y0, x0, bh, bw} in pixels of the raw_h x raw_w frame; the
+ * kernel clamps bh, bw into [1, raw] and then y0, x0 into [0, raw - b] before use, so no box value reads outside the frame.  Output
+ * pixel (oy, ox) is the bilinear sample of the box (half-pixel centres, clamped to the box's edge, no antialiasing), taps and weights
+ * from integers:  num = max((2 oy + 1) bh - out_h, 0); i0 = min(num / (2 out_h), bh - 1); i1 = min(num / (2 out_h) + 1, bh - 1);
+ * fy = (num % (2 out_h)) / (2 out_h) (taken as 0 where i0 == i1); columns alike; value = lerp(lerp(p[i0][j0], p[i0][j1], fx),
+ * lerp(p[i1][j0], p[i1][j1], fx), fy) - mean[c], lerp(a, b, f) = a (1 - f) + b f.  mirror flips the output W axis after sampling.
+ * out_h / out_w may exceed raw_h / raw_w (a box may be upsampled); bh == out_h and bw == out_w give vl_input_prep_u8's crop at
+ * (y0, x0) bit for bit.  mirror, mean_bgr may be NULL; src, dst, box may not. */
+int vl_input_prep_u8_box(const uint8_t* src, float* dst, int n, int raw_h, int raw_w, int out_h, int out_w, const int32_t* box,
+                         const uint8_t* mirror, const float* mean_bgr, int dst_halo, int dst_phase, vl_stream_t stream);
 /* The reference's own feed format: fp32 NHWC placeholder (models/model.py:54) -> NCHW (+halo, dst_phase as above). */
 int vl_nhwc_to_nchw(const float* src, float* dst, int n, int h, int w, int c, int dst_halo, int dst_phase, vl_stream_t stream);
 int vl_nchw_to_nhwc(const float* src, float* dst, int n, int c, int h, int w, vl_stream_t stream);
@@ -183,10 +194,14 @@ int vl_gemm_kc8(const void* a_kc8, const void* b_kc8, float* c, int m, int n, in
  *   vl_s2d_c8_from_x0   x0 (fp32, as the strided layer d's vl_conv_fwd takes it) -> packed input [n][cin s^2 / 8][oh + ka - 1][ow + ka - 1][8]
  *   vl_s2d_weights      grad = 0: w [k][k][cin][cout] -> [ka][ka][cin s^2][cout];  grad = 1: the stride-1 layer's dw -> dw
  *   vl_input_prep_u8_s2d  the uint8 frames straight into that packed input (arguments as vl_input_prep_u8; the crop is d's h x w):
- *                       the same values as vl_input_prep_u8 followed by vl_s2d_c8_from_x0 */
+ *                       the same values as vl_input_prep_u8 followed by vl_s2d_c8_from_x0
+ *   vl_input_prep_u8_box_s2d  likewise for vl_input_prep_u8_box (box: device int32 [n][4], clamped by the kernel; out size d's h x w;
+ *                       n <= 65535): bit for bit vl_input_prep_u8_box followed by vl_s2d_c8_from_x0 */
 int vl_s2d_c8_from_x0(const vl_conv_desc* d, const float* x0, void* xb, int n, vl_stream_t stream);
 int vl_input_prep_u8_s2d(const vl_conv_desc* d, const uint8_t* src, void* xb, int n, int raw_h, int raw_w, const int32_t* crop_y,
                          const int32_t* crop_x, const uint8_t* mirror, const float* mean_bgr, vl_stream_t stream);
+int vl_input_prep_u8_box_s2d(const vl_conv_desc* d, const uint8_t* src, void* xb, int n, int raw_h, int raw_w, const int32_t* box,
+                             const uint8_t* mirror, const float* mean_bgr, vl_stream_t stream);
 int vl_s2d_weights(const vl_conv_desc* d, const float* src, float* dst, int grad, vl_stream_t stream);
 /* db[c] = sum_{n,h,w} dy[n][c][h][w]  (gradient of tf.nn.bias_add, alexnet.py:31).
  * ws: float[64*c] scratch. */

@@ -15,6 +15,7 @@ SIGNATURES = {
     "vl_version": (i32, []),
     "vl_device_count": (i32, []),
     "vl_input_prep_u8": (i32, [p, p, i32, i32, i32, i32, i32, p, p, p, p, i32, i32, p]),
+    "vl_input_prep_u8_box": (i32, [p, p, i32, i32, i32, i32, i32, p, p, p, i32, i32, p]),
     "vl_nhwc_to_nchw": (i32, [p, p, i32, i32, i32, i32, i32, i32, p]),
     "vl_nchw_to_nhwc": (i32, [p, p, i32, i32, i32, i32, p]),
     "vl_conv_create": (i32, [C.POINTER(p), i32, i32, i32, i32, i32, i32, i32, i32]),
@@ -44,6 +45,7 @@ SIGNATURES = {
     "vl_gemm_kc8": (i32, [p, p, p, i32, i32, i32, p, i32, p, sz, p]),
     "vl_s2d_c8_from_x0": (i32, [p, p, p, i32, p]),
     "vl_input_prep_u8_s2d": (i32, [p, p, p, i32, i32, i32, p, p, p, p, p]),
+    "vl_input_prep_u8_box_s2d": (i32, [p, p, p, i32, i32, i32, p, p, p, p]),
     "vl_s2d_weights": (i32, [p, p, p, i32, p]),
     "vl_bias_grad_c8": (i32, [p, p, p, i32, i32, i32, i32, i32, p]),
     "vl_conv_c8_wgrad_ws_bytes": (sz, [p, i32]),

@@ -83,20 +83,23 @@ class ComposedEngine(GraphEngine):
         self.Ts = self.last.fpc                  # steps the second LSTM runs (one more under ibias)
 
     @staticmethod
-    def _feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize):
-        return {"main": dict(frames_u8=frames_u8, mean_bgr=mean_bgr, crop_y=crop_y, crop_x=crop_x, mirror=mirror, resize=resize),
+    def _feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize, crop_box=None):
+        return {"main": dict(frames_u8=frames_u8, mean_bgr=mean_bgr, crop_y=crop_y, crop_x=crop_x, mirror=mirror, resize=resize,
+                             crop_box=crop_box),
                 "aux": words}
 
-    def forward(self, frames_u8, words, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None, seq_len=None):
+    def forward(self, frames_u8, words, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None, seq_len=None, crop_box=None):
         """sess.run(model.logits, fdict) for the two-pipeline model.  words: device float32 [clips * fpc, in_dim].
-        seq_len: {scope ("enc" / "dec" by default): host int32 lengths per clip} (GraphEngine.forward)."""
-        return GraphEngine.forward(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize), seq_len=seq_len)
+        seq_len: {scope ("enc" / "dec" by default): host int32 lengths per clip} (GraphEngine.forward).
+        crop_box: a box per frame in the place of crop_y / crop_x (LRCNEngine.feed_u8)."""
+        return GraphEngine.forward(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize, crop_box),
+                                   seq_len=seq_len)
 
     def train_step(self, frames_u8, words, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                   fetch=True, global_rows=None, resize=None, seq_len=None, micro=None):
+                   fetch=True, global_rows=None, resize=None, seq_len=None, micro=None, crop_box=None):
         """sess.run([.., loss, .., optimizer], fdict): labels int32 one-hot [rows, classes], rows = clips (fusion avg | last |
         state) or clips * steps (fusion reshape: one row per time step, clip-major).  seq_len: e.g. {"dec": caption lengths}: the
         padded word steps stay out of the loss (GraphEngine.train_step).  micro = (i, k): micro-step i of an accumulated update
         (enc_cfg.accumulate >= k)."""
-        return GraphEngine.train_step(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize), onehot, lr,
+        return GraphEngine.train_step(self, self._feeds(frames_u8, words, mean_bgr, crop_y, crop_x, mirror, resize, crop_box), onehot, lr,
                                       clip_norm, fetch, global_rows, seq_len=seq_len, micro=micro)

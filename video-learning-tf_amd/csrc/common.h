@@ -118,6 +118,51 @@ static inline int cut_box_host_check(const int32_t* box, int fpc, int H, int W, 
     return 0;
 }
 
+// ---- random resized crop (vl_input_prep_u8_box in pointwise.hip, vl_input_prep_u8_box_s2d in conv_c8.hip) --------------
+// A frame's box {y0, x0, bh, bw} as a kernel uses it: sizes clamped into [1, raw] first, then the corner into [0, raw - size], so
+// that no content of the device words reaches an address outside the frame.
+struct BoxRect {
+    int y0, x0, bh, bw;
+};
+__device__ __forceinline__ BoxRect box_get(const int32_t* __restrict__ box, int img, int rh, int rw) {
+    const int32_t* b = box + 4 * (int64_t)img;
+    BoxRect r;
+    r.bh = min(max(b[2], 1), rh);
+    r.bw = min(max(b[3], 1), rw);
+    r.y0 = min(max(b[0], 0), rh - r.bh);
+    r.x0 = min(max(b[1], 0), rw - r.bw);
+    return r;
+}
+
+// One axis of the bilinear rule (half-pixel centres, clamped to the box's edge): output index o of `out` over a box side of b pixels.
+// num = max((2 o + 1) b - out, 0) is 2 out times the source coordinate; taps i0 <= i1 and the weight of i1, all from integers.
+// Where both taps are the same pixel (a clamped edge) the weight is immaterial and taken as 0: the sample is then that pixel exactly.
+struct BoxTap {
+    int i0, i1;
+    float f;
+};
+__device__ __forceinline__ BoxTap box_tap(int o, int b, int out, const FastDiv& d2out) {
+    const uint32_t num = (uint32_t)max((2 * o + 1) * b - out, 0);
+    const uint32_t q = fd_div(num, d2out), r = num - q * (2u * (uint32_t)out);
+    BoxTap t;
+    t.i0 = min((int)q, b - 1);
+    t.i1 = min((int)q + 1, b - 1);
+    t.f = t.i0 == t.i1 ? 0.f : __fdiv_rn((float)r, (float)(2 * out));
+    return t;
+}
+
+// lerp(a, b, f) = a (1 - f) + b f in this one order of roundings, for both kernels
+__device__ __forceinline__ float box_lerp(float a, float b, float f) { return __fmaf_rn(b, f, __fmul_rn(a, __fsub_rn(1.f, f))); }
+
+// The sample: r0 / r1 point at the channel's byte of column 0 of the two tap rows, o0 / o1 are the byte offsets of the two tap
+// columns.  Horizontal lerps first, then the vertical one, then the mean.
+__device__ __forceinline__ float box_sample(const uint8_t* __restrict__ r0, const uint8_t* __restrict__ r1, int o0, int o1, float fx,
+                                            float fy, float mean) {
+    const float top = box_lerp((float)r0[o0], (float)r0[o1], fx);
+    const float bot = box_lerp((float)r1[o0], (float)r1[o1], fx);
+    return __fsub_rn(box_lerp(top, bot, fy), mean);
+}
+
 // ---- LSTM recurrence: per-clip form (pointwise.hip), the fallback / A-B reference of the cluster form (lstm_cluster.hip) ------
 int vl_lstm_perclip_fwd(const float* gx, const float* kh, const float* h0, const float* c0, float* act, float* cseq, float* hseq,
                         float* hprev, int batch, int T, int H, float forget_bias, const int32_t* seq_len, hipStream_t stream);

@@ -76,6 +76,65 @@ extern "C" int vl_input_prep_u8(const uint8_t* src, float* dst, int n, int raw_h
     return 0;
 }
 
+// ---- input prep with a box per frame: random resized crop ------------------------------------------------------------
+// input_prep_u8_kernel's destination walk (thread -> (phase plane, row, plane column), whole store runs, an image per blockIdx.y); the
+// source is the frame's own box {y0, x0, bh, bw}, resampled bilinearly to oh x ow by the rule of common.h (box_tap / box_sample): four
+// byte taps per channel where the crop reads one.  The taps' quotients are FastDiv by the launch-uniform 2 oh and 2 ow; the box is
+// clamped into the frame before any address is formed (box_get).
+__global__ __launch_bounds__(256) void input_prep_u8_box_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int rh, int rw,
+                                                                int oh, int ow, const int32_t* __restrict__ box,
+                                                                const uint8_t* __restrict__ mir, const float* __restrict__ mean, int halo,
+                                                                int phase, int wp, FastDiv d_plane, FastDiv d_wp, FastDiv d_2oh,
+                                                                FastDiv d_2ow) {
+    const int img = blockIdx.y;
+    const uint32_t plane_in = (uint32_t)oh * wp, per_img = plane_in * phase;
+    const int64_t pp = (int64_t)(oh + 2 * halo) * wp;
+    const float m0 = mean ? mean[0] : 0.f, m1 = mean ? mean[1] : 0.f, m2 = mean ? mean[2] : 0.f;
+    const BoxRect b = box_get(box, img, rh, rw);
+    const bool flip = mir && mir[img];
+    const int pitch = rw * 3;
+    const uint8_t* sbox = src + (int64_t)img * rh * pitch + (int64_t)b.y0 * pitch + b.x0 * 3;       // the box's first pixel
+    float* dimg = dst + (int64_t)img * 3 * phase * pp + (int64_t)halo * wp;
+    for (uint32_t e = blockIdx.x * 256u + threadIdx.x; e < per_img; e += gridDim.x * 256u) {
+        const uint32_t ph = fd_div(e, d_plane), r = e - ph * plane_in;
+        const uint32_t y = fd_div(r, d_wp), q = r - y * wp;
+        const int x = (int)(q * phase + ph) - halo;
+        float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+        if (x >= 0 && x < ow) {
+            const BoxTap ty = box_tap((int)y, b.bh, oh, d_2oh), tx = box_tap(flip ? ow - 1 - x : x, b.bw, ow, d_2ow);
+            const uint8_t *r0 = sbox + ty.i0 * pitch, *r1 = sbox + ty.i1 * pitch;
+            const int o0 = tx.i0 * 3, o1 = tx.i1 * 3;
+            v0 = box_sample(r0, r1, o0, o1, tx.f, ty.f, m0);
+            v1 = box_sample(r0 + 1, r1 + 1, o0, o1, tx.f, ty.f, m1);
+            v2 = box_sample(r0 + 2, r1 + 2, o0, o1, tx.f, ty.f, m2);
+        }
+        float* d = dimg + (int64_t)ph * pp + r;
+        d[0] = v0;
+        d[(int64_t)phase * pp] = v1;
+        d[2 * (int64_t)phase * pp] = v2;
+    }
+}
+
+extern "C" int vl_input_prep_u8_box(const uint8_t* src, float* dst, int n, int raw_h, int raw_w, int out_h, int out_w, const int32_t* box,
+                                    const uint8_t* mirror, const float* mean_bgr, int dst_halo, int dst_phase, vl_stream_t stream) {
+    VL_CHECK(src && dst && box && dst_halo >= 0 && dst_phase >= 1, "vl_input_prep_u8_box: bad argument");
+    VL_CHECK(n > 0 && out_h > 0 && out_w > 0 && raw_h > 0 && raw_w > 0, "vl_input_prep_u8_box: bad shape");
+    VL_CHECK(n <= 65535, "vl_input_prep_u8_box: batch %d exceeds the grid limit", n);
+    // the taps' numerators (2 o + 1) b and a frame's byte offsets stay inside 31 bits
+    VL_CHECK((2ll * out_h + 1) * raw_h < (1ll << 31) && (2ll * out_w + 1) * raw_w < (1ll << 31) && 3ll * raw_h * raw_w < (1ll << 31),
+             "vl_input_prep_u8_box: image too large");
+    const int wp = (out_w + 2 * dst_halo + dst_phase - 1) / dst_phase;
+    const int64_t per_img = (int64_t)out_h * dst_phase * wp;
+    VL_CHECK(per_img < (1ll << 31), "vl_input_prep_u8_box: image too large");
+    int bx = (int)((per_img + 1023) / 1024);
+    if ((int64_t)bx * n < 8ll * vl_device_cus()) bx = (int)((per_img + 255) / 256);
+    hipLaunchKernelGGL(input_prep_u8_box_kernel, dim3(bx, n), dim3(256), 0, (hipStream_t)stream, src, dst, raw_h, raw_w, out_h, out_w, box,
+                       mirror, mean_bgr, dst_halo, dst_phase, wp, make_fastdiv((uint32_t)out_h * wp), make_fastdiv((uint32_t)wp),
+                       make_fastdiv(2u * (uint32_t)out_h), make_fastdiv(2u * (uint32_t)out_w));
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // generic 3-level strided copy: dst[(a*nb + b)*nc + c] = src[a*sa + b*sb + c*sc]
 __global__ void permute3_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t na, int nb, int nc, int64_t sa,
                                 int64_t sb, int64_t sc) {

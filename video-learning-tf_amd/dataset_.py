@@ -14,10 +14,71 @@ from .defs_ import defs
 from .utils_ import debug, error, info, labels_to_one_hot, warning
 
 
+CROP_SCALE, CROP_RATIO, CROP_SEED = (0.08, 1.0), (3.0 / 4.0, 4.0 / 3.0), 0      # torchvision RandomResizedCrop's defaults
+CROP_ATTEMPTS = 10
+
+
+def check_crop_jitter(scale=None, ratio=None, seed=None):
+    """(crop_scale, crop_ratio, crop_seed) of a dataset with imgproc rand_resized_crop -> ((lo, hi), (lo, hi), seed), None = the
+    default.  scale: the box's area as a share of the frame, 0 < lo <= hi <= 1; ratio: bw / bh, 0 < lo <= hi; both two finite
+    numbers.  seed: a whole number in [0, 2^64), one word of the Philox key.  ValueError with the reason otherwise."""
+    out = []
+    for name, v, top in (("crop_scale", scale, 1.0), ("crop_ratio", ratio, None)):
+        if v is None:
+            out.append(CROP_SCALE if top else CROP_RATIO)
+            continue
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in v):
+            raise ValueError("%s must be two numbers [lo, hi], got [%s]" % (name, v))
+        lo, hi = float(v[0]), float(v[1])
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi) or (top is not None and hi > top):
+            raise ValueError("%s must be two finite numbers 0 < lo <= hi%s, got [%s]" % (name, " <= 1" if top else "", v))
+        out.append((lo, hi))
+    if seed is None:
+        seed = CROP_SEED
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError("crop_seed must be a whole number in [0, 2^64), got [%s]" % (seed,))
+    return out[0], out[1], seed
+
+
+def resized_crop_boxes(seed, counter, clips, raw_h, raw_w, scale, ratio, mirror_on):
+    """The draws of imgproc rand_resized_crop for one GLOBAL batch -> (int32 [clips, 4] boxes (y0, x0, bh, bw), uint8 [clips] mirror
+    flags).  A pure function: one Philox generator keyed by (seed, counter), walked clip by clip.  Per clip torchvision's
+    RandomResizedCrop.get_params: up to 10 attempts of area = raw_h raw_w U(scale), ar = exp(U(log ratio)), bw = round(sqrt(area ar)),
+    bh = round(sqrt(area / ar)), accepted when the box fits the frame, its corner then uniform over the positions that fit; after 10
+    misses the centred box of the frame's own ratio clamped into `ratio`.  Then one mirror draw, made whether or not mirroring is on
+    (the flag is zeroed when it is off), so that the boxes do not depend on it."""
+    g = np.random.Generator(np.random.Philox(key=[int(seed), int(counter)]))
+    raw_h, raw_w = int(raw_h), int(raw_w)
+    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
+    boxes, mirror = np.zeros((clips, 4), np.int32), np.zeros(clips, np.uint8)
+    for i in range(clips):
+        for _ in range(CROP_ATTEMPTS):
+            area = raw_h * raw_w * g.uniform(scale[0], scale[1])
+            ar = math.exp(g.uniform(lr0, lr1))
+            bw, bh = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+            if 0 < bw <= raw_w and 0 < bh <= raw_h:
+                y0 = int(g.integers(0, raw_h - bh + 1))
+                x0 = int(g.integers(0, raw_w - bw + 1))
+                break
+        else:
+            bh, bw = raw_h, raw_w
+            if raw_w / raw_h < ratio[0]:
+                bh = min(raw_h, max(1, int(round(raw_w / ratio[0]))))
+            elif raw_w / raw_h > ratio[1]:
+                bw = min(raw_w, max(1, int(round(raw_h * ratio[1]))))
+            y0, x0 = (raw_h - bh) // 2, (raw_w - bw) // 2
+        boxes[i] = (y0, x0, bh, bw)
+        flip = int(g.integers(2))
+        mirror[i] = flip if mirror_on else 0
+    return boxes, mirror
+
+
 class Dataset:
     def initialize(self, id, path, mean_image, prepend_folder, desired_image_shape, imgproc, raw_image_shape, data_format,
-                   frame_format, batch_item, num_classes, tag, read_tries):
-        """dataset_.py:503-519."""
+                   frame_format, batch_item, num_classes, tag, read_tries, crop_jitter=None):
+        """dataset_.py:503-519.  crop_jitter: check_crop_jitter's (scale, ratio, seed) of imgproc rand_resized_crop (None: defaults)."""
+        self.crop_scale, self.crop_ratio, self.crop_seed = crop_jitter if crop_jitter is not None else check_crop_jitter()
+        self.crop_counter, self.crop_box = 0, None
         info("Initializing dataset [%s]" % id)
         self.id, self.path, self.tag = id, path, tag
         self.data_format, self.frame_format, self.prepend_folder = data_format, frame_format, prepend_folder
@@ -88,6 +149,9 @@ class Dataset:
     def initialize_imgproc(self):
         """dataset_.py:540-560 (+ build_mean_image 521-530: mean_image[0] is blue)."""
         if self.input_mode == defs.input_mode.vectors:
+            if defs.imgproc.rand_resized_crop in self.imgproc:
+                error("imgproc [%s] on dataset [%s] of input mode [%s]: there are no frames to crop" %
+                      (defs.imgproc.rand_resized_crop, self.id, self.input_mode))
             if self.imgproc:
                 info("Ignoring imgproc due to input mode: [%s]" % self.input_mode)
             self.imgproc, self.mean_bgr, self.crop_mode, self.resize_chain = [], None, None, []
@@ -98,6 +162,10 @@ class Dataset:
             self.crop_mode = defs.imgproc.rand_crop
         elif defs.imgproc.center_crop in self.imgproc:
             self.crop_mode = defs.imgproc.center_crop
+        elif defs.imgproc.rand_resized_crop in self.imgproc:      # a box per clip, resampled to the input size on the device
+            self.crop_mode = defs.imgproc.rand_resized_crop
+            info("Random resized crop: scale %s, ratio %s, seed %d: one box and one mirror flag per clip, resampled to %s on the device" %
+                 (self.crop_scale, self.crop_ratio, self.crop_seed, tuple(self.desired_image_shape[:2])))
         if self.raw_image_shape is None:
             self.raw_image_shape = self.desired_image_shape
         # imresize steps of process_image (dataset_.py:481-495), run on the device (vl_resize_u8, PIL bilinear bit for bit):
@@ -116,7 +184,7 @@ class Dataset:
             self.resize_chain.append((tuple(self.raw_image_shape[:2]), tuple(self.desired_image_shape[:2])))
         elif self.crop_mode is None and tuple(self.raw_image_shape) != tuple(self.desired_image_shape):
             error("Encountered image shape %s but desired shape is %s" % (self.raw_image_shape, self.desired_image_shape))
-        if self.crop_mode:
+        if self.crop_mode in (defs.imgproc.rand_crop, defs.imgproc.center_crop):
             self.crop_h, self.crop_w = self.compute_crop(self.raw_image_shape, self.desired_image_shape, self.crop_mode)
 
     def calculate_batches(self, batch_size, input_mode):
@@ -229,7 +297,8 @@ class Dataset:
         frame records; one label per clip (its first frame's).  Returns (frames uint8 [n,H,W,C] raw, crop_y, crop_x,
         mirror, onehot int32 [clips, classes]).  With a shard set, only this rank's videos of the batch are read (the records
         of the other ranks are skipped by their length headers) and `self.global_clips` holds the clip count of the WHOLE batch
-        (the loss is its mean, train.py:123)."""
+        (the loss is its mean, train.py:123).  Under imgproc rand_resized_crop the tuple keeps its shape: crop_y and crop_x are None,
+        mirror is the per-frame repeat of the clips' flags and `self.crop_box` holds the boxes, int32 [n, 4] per frame (None otherwise)."""
         v0 = self.batch_index * self.batch_size
         cpv_all = self.clips_per_video[v0:v0 + self.batch_size]
         fpc = self.num_frames_per_clip
@@ -272,6 +341,18 @@ class Dataset:
         for c in cpv:
             labels.extend([labels_per_frame[first]] * c)
             first += c * fpc
+        ground_truth = labels_to_one_hot(labels, self.num_classes) if labels else np.zeros((0, self.num_classes), np.int32)
+        if self.crop_mode == defs.imgproc.rand_resized_crop:
+            # one box and one mirror flag per CLIP, for every clip of the global batch (N ranks apply what one process would), repeated
+            # over the clip's frames; the generator is keyed by the batches served so far, and self.rng is not consumed
+            boxes, flips = resized_crop_boxes(self.crop_seed, self.crop_counter, sum(cpv_all), self.raw_image_shape[0],
+                                              self.raw_image_shape[1], self.crop_scale, self.crop_ratio,
+                                              defs.imgproc.rand_mirror in self.imgproc)
+            self.crop_box = np.repeat(boxes, fpc, axis=0)[before:before + n].copy()
+            mirror = np.repeat(flips, fpc)[before:before + n].copy()
+            self.crop_counter += 1
+            self.batch_index += 1
+            return frames, None, None, mirror, ground_truth
         # per-frame draws, like process_image per frame (dataset_.py:481-501), for EVERY frame of the global batch in order, so
         # that N ranks with one seed apply exactly the augmentation one process would
         cy = np.zeros(n_all, np.int32)
@@ -285,7 +366,6 @@ class Dataset:
             if defs.imgproc.rand_mirror in self.imgproc:
                 mirror[i] = 0 if self.rng.randrange(2) else 1          # `if not randrange(2)` mirrors
         cy, cx, mirror = cy[before:before + n].copy(), cx[before:before + n].copy(), mirror[before:before + n].copy()
-        ground_truth = labels_to_one_hot(labels, self.num_classes) if labels else np.zeros((0, self.num_classes), np.int32)
         self.batch_index += 1
         return frames, cy, cx, mirror, ground_truth
 
@@ -293,6 +373,8 @@ class Dataset:
     def restore(self, batch_index, epoch_index):
         """dataset_.py:534-538."""
         self.batch_index, self.epoch_index = batch_index, epoch_index
+        # the draws of rand_resized_crop are keyed by the batches served since the start of the run
+        self.crop_counter = epoch_index * len(self.batches or ()) + batch_index
         self.fast_forward_iter()
 
     def fast_forward_iter(self):

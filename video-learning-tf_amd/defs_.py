@@ -81,9 +81,10 @@ class defs:
     class imgproc:
         rand_mirror, rand_crop, center_crop, resize, raw_resize, sub_mean = \
             "rand_mirror", "rand_crop", "center_crop", "resize", "raw_resize", "sub_mean"
+        rand_resized_crop = "rand_resized_crop"      # not in the reference: scale / aspect jitter per clip
 
         @staticmethod
         def to_str(vec):
             m = (("rand_mirror", "rm"), ("rand_crop", "rc"), ("center_crop", "cc"), ("resize", "rs"), ("raw_resize", "rr"),
-                 ("sub_mean", "sm"))
+                 ("sub_mean", "sm"), ("rand_resized_crop", "rrc"))
             return "-".join(s for k, s in m if k in vec)

@@ -1552,11 +1552,14 @@ class LRCNEngine:
             raise VltfError("got %d frames: need a positive multiple of fpc=%d, at most %d" % (n, self.T, self.N))
         return n // self.T
 
-    def feed_u8(self, frames_u8, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None):
+    def feed_u8(self, frames_u8, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None, crop_box=None):
         """frames uint8 [n, raw_h, raw_w, 3] on device (TFRecord image_raw bytes) -> x0 (dataset_.py:481-501).
-        resize: [((h, w), (oh, ow)), ...] imresize steps applied first (imgproc raw_resize / resize: PIL bilinear on uint8)."""
+        resize: [((h, w), (oh, ow)), ...] imresize steps applied first (imgproc raw_resize / resize: PIL bilinear on uint8).
+        crop_box: device int32 [n, 4] = (y0, x0, bh, bw) per frame of the frame the feed receives (after `resize`): random resized
+        crop, the box resampled bilinearly to the network input (ops.input_prep_u8_box); not with crop_y / crop_x."""
         n = frames_u8.shape[0]
         b = self._check_frames(n)
+        self._check_crop_box(crop_box, crop_y, crop_x)
         for src_hw, dst_hw in (resize or ()):
             key = (tuple(src_hw), tuple(dst_hw))
             if key not in self._resizers:
@@ -1566,13 +1569,27 @@ class LRCNEngine:
         if mean_bgr is not None:
             self.mean_dev.copy_(torch.as_tensor(np.asarray(mean_bgr, np.float32)), non_blocking=True)
             mean = self.mean_dev
-        return self._feed_dev(frames_u8, n, b, mean, crop_y, crop_x, mirror)
+        return self._feed_dev(frames_u8, n, b, mean, crop_y, crop_x, mirror, crop_box)
 
-    def _feed_dev(self, frames_u8, n, b, mean, crop_y, crop_x, mirror):
+    @staticmethod
+    def _check_crop_box(crop_box, crop_y, crop_x):
+        """Before anything is launched: a box per frame takes the place of the crop offsets, never both."""
+        if crop_box is not None and (crop_y is not None or crop_x is not None):
+            raise VltfError("crop_box (random resized crop) is refused together with crop_y / crop_x: a frame is either cropped at an "
+                            "offset or resampled from its box")
+
+    def _feed_dev(self, frames_u8, n, b, mean, crop_y, crop_x, mirror, crop_box=None):
         """feed_u8 from here on, every input on the device (what a captured step runs)."""
         if self.c8:     # bf16 path: the frames go straight into conv1's packed (space-to-depth) input; x0 is not written
-            self.layers[0]["conv"].input_prep_u8_s2d(frames_u8, self.layers[0]["xb"][:n], crop_y, crop_x, mirror, mean)
+            if crop_box is not None:
+                self.layers[0]["conv"].input_prep_u8_box_s2d(frames_u8, self.layers[0]["xb"][:n], crop_box, mirror, mean)
+            else:
+                self.layers[0]["conv"].input_prep_u8_s2d(frames_u8, self.layers[0]["xb"][:n], crop_y, crop_x, mirror, mean)
             self._xb_fed = True
+            return n, b
+        if crop_box is not None:
+            ops.input_prep_u8_box(frames_u8, self.x0[:n], crop_box, mirror, mean, halo=self.x0_halo, phase=self.x0_phase,
+                                  out_hw=self.cfg.image_shape[:2])
             return n, b
         ops.input_prep_u8(frames_u8, self.x0[:n], crop_y, crop_x, mirror, mean, halo=self.x0_halo, phase=self.x0_phase,
                           out_hw=self.cfg.image_shape[:2])
@@ -1715,13 +1732,14 @@ class LRCNEngine:
             self._rows = rows
         return self._rows
 
-    def forward_u8(self, frames_u8, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None):
+    def forward_u8(self, frames_u8, mean_bgr=None, crop_y=None, crop_x=None, mirror=None, resize=None, crop_box=None):
         """sess.run(model.logits, fdict) (run_task.py:95).  Returns a device view [rows, classes]."""
+        self._check_crop_box(crop_box, crop_y, crop_x)
         if self.step_graph:
-            done, out = self._graph_step(False, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
+            done, out = self._graph_step(False, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, crop_box=crop_box)
             if done:
                 return out
-        n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
+        n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, crop_box)
         rows = self._forward(n, b, train=False)
         return self.logits[:rows]
 
@@ -2228,8 +2246,9 @@ class LRCNEngine:
         return b if (self.early or self.late) else n
 
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None, cut_box=None):
+                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None, cut_box=None, crop_box=None):
         """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44).
+        crop_box: a box per frame in the place of crop_y / crop_x (feed_u8); refused together with them.
         micro = (i, k): micro-step i of an update that sums k of them (k <= cfg.accumulate), called in order i = 0 .. k - 1.  Only the
         last one exchanges, regularises, clips and updates, with its lr; the others return the running loss of the update and no
         grad_norm.  The loss is scaled by 1 / (rows * world * k) unless global_rows gives the rows of the whole update.
@@ -2237,15 +2256,16 @@ class LRCNEngine:
         max(lam, 1 - lam)); refused with mixup off.
         cut_box: with CutMix on (cfg.cutmix_alpha > 0), this step's box (t0, t1, y0, y1, x0, x1) in the place of the draw; refused with
         CutMix off, outside the frame, reversed, above half the clip's volume, or together with mix_lambda (check_cut_box)."""
+        self._check_crop_box(crop_box, crop_y, crop_x)
         mi = self.micro.enter(micro)
         try:
             self._mix_write(mix_lambda, mi, cut_box)
             if self.step_graph:
                 done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
-                                             global_rows, mi)
+                                             global_rows, mi, crop_box=crop_box)
                 if done:
                     return out
-            n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize)
+            n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, crop_box)
             return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
         except VltfError:
             self.micro.reset()
@@ -2264,12 +2284,12 @@ class LRCNEngine:
 
     # ---- captured steps (NetConfig.step_graph, class docstring) ---------------------------------------------------------------
     def _graph_step(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot=None, lr=0.0, clip_norm=0.0, fetch=True,
-                    global_rows=None, mi=None):
+                    global_rows=None, mi=None, crop_box=None):
         """(True, the call's result) when the call was replayed; (False, None) when it runs eagerly (the first call of its key)."""
         rz = tuple((tuple(int(v) for v in s_), tuple(int(v) for v in d_)) for s_, d_ in (resize or ()))
         key = ("train" if train else "forward", int(frames_u8.shape[0]), tuple(frames_u8.shape[1:]), rz, crop_y is not None,
                crop_x is not None, mirror is not None, mean_bgr is not None, float(clip_norm) if train else None,
-               global_rows if train else None, self.cfg.dropout_keep_prob if train else None)
+               global_rows if train else None, self.cfg.dropout_keep_prob if train else None, crop_box is not None)
         if train and self.accumulate > 1:     # first / middle / last micro-steps are different launch sequences: a graph each
             key += MicroSequence.role(mi)
         final = mi is None or mi[0] == mi[1] - 1
@@ -2282,8 +2302,9 @@ class LRCNEngine:
                 self._graph_warm.add(key)
                 return False, None
             g = self._graphs[key] = self._capture(train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm,
-                                                  global_rows, mi)
-        for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x), ("mirror", mirror), ("onehot", onehot)):
+                                                  global_rows, mi, crop_box)
+        for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x), ("mirror", mirror), ("onehot", onehot),
+                        ("crop_box", crop_box)):
             dst = g["inputs"].get(name)
             if dst is None:
                 continue
@@ -2324,11 +2345,13 @@ class LRCNEngine:
         self.graph_tag_next += span
         return origin
 
-    def _capture(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm, global_rows, mi=None):
+    def _capture(self, train, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, clip_norm, global_rows, mi=None,
+                 crop_box=None):
         """Captures one call over static input buffers.  Nothing runs and no host state moves: the replay that follows is the step."""
         t0 = time.perf_counter()
         inputs = {name: torch.empty_like(t) for name, t in (("frames", frames_u8), ("crop_y", crop_y), ("crop_x", crop_x),
-                                                              ("mirror", mirror), ("onehot", onehot)) if t is not None}
+                                                              ("mirror", mirror), ("onehot", onehot), ("crop_box", crop_box))
+                  if t is not None}
         n = frames_u8.shape[0]
         b = self._check_frames(n)
         # every buffer the capture bakes in lives as long as the graph: the resize chain's outputs and intermediates are the graph's
@@ -2355,7 +2378,7 @@ class LRCNEngine:
                 for rs, dst, tmp in chain:
                     frames = rs(frames, dst=dst, tmp=tmp)
                 self._feed_dev(frames, n, b, self.mean_dev if mean_bgr is not None else None, inputs.get("crop_y"), inputs.get("crop_x"),
-                               inputs.get("mirror"))
+                               inputs.get("mirror"), inputs.get("crop_box"))
                 if train:
                     self._train(n, b, inputs["onehot"], 0.0, clip_norm, False, global_rows, mi)
                     rows = self._rows

@@ -50,10 +50,14 @@ class BatchPrefetcher:
                 with torch.cuda.stream(self.copy_stream):
                     slot["dev"][:n].copy_(slot["pin"][:n], non_blocking=True)
                     dev = {key: torch.from_numpy(v).to(self.device, non_blocking=True)
-                           for key, v in (("crop_y", cy), ("crop_x", cx), ("mirror", mirror), ("labels", onehot))}
+                           for key, v in (("crop_y", cy), ("crop_x", cx), ("mirror", mirror), ("labels", onehot),
+                                          ("crop_box", d.crop_box)) if v is not None}
+                    for key in ("crop_y", "crop_x", "crop_box"):      # rand_resized_crop: a box per frame and no crop offsets
+                        dev.setdefault(key, None)
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
-                item = {"frames_u8": frames, "crop_y": cy, "crop_x": cx, "mirror": mirror, "labels": onehot, "mean_bgr": d.mean_bgr,
+                item = {"frames_u8": frames, "crop_y": cy, "crop_x": cx, "mirror": mirror, "crop_box": d.crop_box, "labels": onehot,
+                        "mean_bgr": d.mean_bgr,
                         "resize": d.resize_chain, "dataset": d, "batch_index": d.batch_index, "global_clips": d.global_clips, "device": dict(dev, frames_u8=slot["dev"][:n]), "ready": ev}
                 k += 1
                 while not stop.is_set():
@@ -107,12 +111,12 @@ class Feeder:
         self.prefetchers = {}         # tag -> BatchPrefetcher: every frame dataset a multi-pipeline model reads
 
     def add_dataset(self, dataset_phase, id, path, mean_image, prepend_folder, image_shape, imgproc, raw_image_shape, data_format,
-                    frame_format, batch_item, num_classes, tag, read_tries, captioning_config=None):
+                    frame_format, batch_item, num_classes, tag, read_tries, captioning_config=None, crop_jitter=None):
         """feeder.py:31-38."""
         dset = dataset_.Dataset()
         self.datasets.setdefault(dataset_phase, []).append(dset)
         dset.initialize(id, path, mean_image, prepend_folder, image_shape, imgproc, raw_image_shape, data_format, frame_format,
-                        batch_item, num_classes, tag, read_tries)
+                        batch_item, num_classes, tag, read_tries, crop_jitter=crop_jitter)
 
     def set_phase(self, phase):
         self.phase = phase
@@ -188,7 +192,8 @@ class Feeder:
             fdict = {"vectors": frames, "labels": onehot, "record_labels": d.record_onehot, "dataset": d, "batch_index": d.batch_index,
                      "global_clips": d.global_clips}
             return fdict, [len(frames)], len(onehot), 0
-        fdict = {"frames_u8": frames, "crop_y": cy, "crop_x": cx, "mirror": mirror, "labels": onehot, "mean_bgr": d.mean_bgr,
+        fdict = {"frames_u8": frames, "crop_y": cy, "crop_x": cx, "mirror": mirror, "crop_box": d.crop_box, "labels": onehot,
+                 "mean_bgr": d.mean_bgr,
                  "resize": d.resize_chain, "dataset": d, "batch_index": d.batch_index, "global_clips": d.global_clips}
         return fdict, [len(frames)], len(onehot), 0
 

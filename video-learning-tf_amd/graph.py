@@ -434,7 +434,8 @@ class PipeNode:
             n = b = None
             for i, x in enumerate(seq):        # each dataset's frames through input prep into x0; all but the last are set aside
                 f = feeds[x.ref]
-                ni, bi = tw.feed_u8(f["frames_u8"], f.get("mean_bgr"), f.get("crop_y"), f.get("crop_x"), f.get("mirror"), f.get("resize"))
+                ni, bi = tw.feed_u8(f["frames_u8"], f.get("mean_bgr"), f.get("crop_y"), f.get("crop_x"), f.get("mirror"), f.get("resize"),
+                                     **({"crop_box": f["crop_box"]} if f.get("crop_box") is not None else {}))
                 if n is not None and ni != n:
                     raise VltfError("pipeline [%s]: fused frame datasets gave %d and %d frames" % (s.name, n, ni))
                 n, b = ni, bi

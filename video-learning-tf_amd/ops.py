@@ -58,6 +58,33 @@ def input_prep_u8(src, dst, crop_y=None, crop_x=None, mirror=None, mean_bgr=None
               _p(mean_bgr), halo, phase, stream())
 
 
+def _check_box(who, box, mirror, n):
+    """box int32 [n, 4] and mirror uint8 [n] (or None), contiguous on the device: what the box kernels read per frame."""
+    if not torch.is_tensor(box) or not box.is_cuda or box.dtype != torch.int32 or tuple(box.shape) != (n, 4) or not box.is_contiguous():
+        raise _ffi.VltfError("%s: box must be a contiguous device int32 [%d, 4] tensor (y0, x0, bh, bw per frame)" % (who, n))
+    if mirror is not None and (not mirror.is_cuda or mirror.dtype != torch.uint8 or mirror.numel() < n or not mirror.is_contiguous()):
+        raise _ffi.VltfError("%s: mirror must be a contiguous device uint8 tensor of %d entries" % (who, n))
+
+
+def input_prep_u8_box(src, dst, box, mirror=None, mean_bgr=None, halo=0, phase=1, out_hw=None):
+    """Random resized crop (vl_input_prep_u8_box): frame i's box[i] = (y0, x0, bh, bw) of src uint8 [n, raw_h, raw_w, 3] is resampled
+    bilinearly to out_hw, mirrored and mean-subtracted into dst, input_prep_u8's destination.  The kernel clamps every box into the frame."""
+    if src.dtype != torch.uint8 or not src.is_cuda or src.dim() != 4:
+        raise _ffi.VltfError("input_prep_u8_box: src must be a device uint8 [n, h, w, 3] tensor")
+    _f32(dst, mean_bgr)
+    _dense(src, dst, mean_bgr)
+    n, rh, rw, c = src.shape
+    _check_box("input_prep_u8_box", box, mirror, n)
+    if out_hw is None:
+        if phase > 1:
+            raise _ffi.VltfError("input_prep_u8_box: out_hw is required with a phase-split destination")
+        out_hw = (dst.shape[2] - 2 * halo, dst.shape[3] - 2 * halo)
+    if c != 3 or tuple(dst.shape) != phase_split_shape(n, 3, out_hw[0], out_hw[1], halo, phase):
+        raise _ffi.VltfError("input_prep_u8_box: shape mismatch %s -> %s" % (tuple(src.shape), tuple(dst.shape)))
+    _ffi.call("vl_input_prep_u8_box", _p(src), _p(dst), n, rh, rw, out_hw[0], out_hw[1], _p(box), _p(mirror), _p(mean_bgr), halo, phase,
+              stream())
+
+
 def nhwc_to_nchw(src, dst, halo=0, phase=1):
     _f32(src, dst); _dense(src, dst)
     n, h, w, c = src.shape
@@ -226,6 +253,19 @@ class Conv:
                 raise _ffi.VltfError("conv.input_prep_u8_s2d: crop / mirror must be contiguous int32 / uint8 tensors of n entries")
         _ffi.call("vl_input_prep_u8_s2d", self._d, _p(src), _p(xb), n, src.shape[1], src.shape[2], _p(crop_y), _p(crop_x), _p(mirror),
                   _p(mean_bgr), stream())
+
+    def input_prep_u8_box_s2d(self, src, xb, box, mirror=None, mean_bgr=None):
+        """Random resized crop into the packed space-to-depth input (= input_prep_u8_box + s2d_c8_from_x0, bit for bit)."""
+        if src.dtype != torch.uint8 or not src.is_cuda or src.dim() != 4 or src.shape[3] != self.cin:
+            raise _ffi.VltfError("conv.input_prep_u8_box_s2d: src must be a device uint8 [n, h, w, %d] tensor" % self.cin)
+        _f32(mean_bgr); _dense(src, xb, mean_bgr)
+        n = src.shape[0]
+        s, ka = self.stride, (self.kh - 1) // self.stride + 1
+        if xb.dtype != torch.bfloat16 or tuple(xb.shape) != c8_shape(n, self.cin * s * s, self.oh, self.ow, (ka - 1) // 2):
+            raise _ffi.VltfError("conv.input_prep_u8_box_s2d: xb shape %s" % (tuple(xb.shape),))
+        _check_box("conv.input_prep_u8_box_s2d", box, mirror, n)
+        _ffi.call("vl_input_prep_u8_box_s2d", self._d, _p(src), _p(xb), n, src.shape[1], src.shape[2], _p(box), _p(mirror), _p(mean_bgr),
+                  stream())
 
     def cutmix_pairs_s2d(self, xb, clips, fpc, box):
         """CutMix / VideoMix in place in the packed space-to-depth input (vl_cutmix_pairs_s2d): xb is what input_prep_u8_s2d writes

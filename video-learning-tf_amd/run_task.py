@@ -38,11 +38,12 @@ def graph_feeds(fdicts, tags, dev):
             torch.cuda.current_stream(dev).wait_event(fd["ready"])
             t = fd["device"]
             feeds[tag] = dict(frames_u8=t["frames_u8"], mean_bgr=fd["mean_bgr"], crop_y=t["crop_y"], crop_x=t["crop_x"], mirror=t["mirror"],
-                              resize=fd.get("resize"))
+                              resize=fd.get("resize"), crop_box=t.get("crop_box"))
         else:
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)      # rand_resized_crop: a box per frame, no offsets
             feeds[tag] = dict(frames_u8=torch.from_numpy(fd["frames_u8"]).to(dev, non_blocking=True), mean_bgr=fd["mean_bgr"],
-                              crop_y=torch.from_numpy(fd["crop_y"]).to(dev), crop_x=torch.from_numpy(fd["crop_x"]).to(dev),
-                              mirror=torch.from_numpy(fd["mirror"]).to(dev), resize=fd.get("resize"))
+                              crop_y=up(fd["crop_y"]), crop_x=up(fd["crop_x"]), mirror=up(fd["mirror"]), resize=fd.get("resize"),
+                              crop_box=up(fd.get("crop_box")))
     return feeds
 
 

@@ -411,10 +411,35 @@ class Settings:
                 imgproc.append(defs.imgproc.sub_mean)                      # settings_.py:341-342
             if self.val and (defs.imgproc.rand_crop in imgproc or defs.imgproc.rand_mirror in imgproc):
                 error("Random cropping / mirroring is enabled in validation mode (the reference prompts; we fail).")
+            crop_jitter = self.read_crop_jitter(dataid, dataobj, dataset_phase, imgproc)
             self.feeder.add_dataset(dataset_phase, dataid, dataobj["data_path"], mean_image, dataobj.get("prepend_folder"),
                                     image_shape, imgproc, raw_image_shape, defs.check(dataobj["data_format"], defs.data_format),
                                     dataobj.get("frame_format"), batch_item, self.num_classes,
-                                    defs.check(dataobj["tag"], defs.dataset_tag), int(dataobj.get("read_tries", 1)))
+                                    defs.check(dataobj["tag"], defs.dataset_tag), int(dataobj.get("read_tries", 1)),
+                                    crop_jitter=crop_jitter)
+
+    def read_crop_jitter(self, dataid, dataobj, dataset_phase, imgproc):
+        """imgproc rand_resized_crop with its keys crop_scale / crop_ratio / crop_seed of one dataset ->
+        dataset_.check_crop_jitter's (scale, ratio, seed), or None without the imgproc entry.  Every misuse is refused here."""
+        from .dataset_ import check_crop_jitter
+        name = defs.imgproc.rand_resized_crop
+        keys = [k for k in ("crop_scale", "crop_ratio", "crop_seed") if dataobj.get(k) not in (None, "None")]
+        if name not in imgproc:
+            if keys:
+                error("dataset [%s]: %s need imgproc [%s], which is not listed" % (dataid, keys, name))
+            return None
+        other = [o for o in (defs.imgproc.rand_crop, defs.imgproc.center_crop, defs.imgproc.resize) if o in imgproc]
+        if other:
+            error("dataset [%s]: imgproc [%s] resamples its own box to the network input and is refused together with %s" %
+                  (dataid, name, other))
+        if dataset_phase == defs.phase.val:
+            error("dataset [%s]: imgproc [%s] on a validation dataset: a random validation crop is a mistake" % (dataid, name))
+        # (a vectors dataset is known by its size file only: Dataset.initialize_imgproc refuses the entry there)
+        vals = [dataobj.get(k) if dataobj.get(k) != "None" else None for k in ("crop_scale", "crop_ratio", "crop_seed")]
+        try:
+            return check_crop_jitter(*(parse_seq(v) if isinstance(v, str) else v for v in vals))
+        except ValueError as ex:
+            error("dataset [%s]: %s" % (dataid, ex))
 
     def configure_logging(self):
         self.timestamp = get_datetime_str()

@@ -224,14 +224,18 @@ class Train:
         elif "device" in fdict:          # uploaded ahead of time by the feeder's BatchPrefetcher: wait for the copy on the stream
             torch.cuda.current_stream(dev).wait_event(fdict["ready"])
             t = fdict["device"]
+            if t.get("crop_box") is not None:    # imgproc rand_resized_crop: a box per frame in the place of the crop offsets
+                kw["crop_box"] = t["crop_box"]
             out = eng.train_step_u8(t["frames_u8"], t["labels"], lr, self.clip_norm, fdict["mean_bgr"], t["crop_y"], t["crop_x"],
                                     t["mirror"], global_rows=grows, resize=fdict.get("resize"), **kw)
         else:
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+            if fdict.get("crop_box") is not None:    # imgproc rand_resized_crop: a box per frame in the place of the crop offsets
+                kw["crop_box"] = up(fdict["crop_box"])
             out = eng.train_step_u8(torch.from_numpy(fdict["frames_u8"]).to(dev, non_blocking=True),
                                     torch.from_numpy(fdict["labels"]).to(dev),
-                                    lr, self.clip_norm, fdict["mean_bgr"],
-                                    torch.from_numpy(fdict["crop_y"]).to(dev), torch.from_numpy(fdict["crop_x"]).to(dev),
-                                    torch.from_numpy(fdict["mirror"]).to(dev), global_rows=grows, resize=fdict.get("resize"), **kw)
+                                    lr, self.clip_norm, fdict["mean_bgr"], up(fdict["crop_y"]), up(fdict["crop_x"]),
+                                    up(fdict["mirror"]), global_rows=grows, resize=fdict.get("resize"), **kw)
         if dpg is not None:              # log the global-batch loss, not the shard's
             tot = dpg.sum_scalars(torch.tensor(dp_scalars(out), device=dev, dtype=torch.float64))
             out = dp_global(out, tot.cpu().numpy())
