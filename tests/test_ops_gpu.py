@@ -466,6 +466,22 @@ def test_pool_lrn_bwd_channel_ranges(ops, request, ranges, n, h, w, c, ph, dh):
     close(nhwc(host(interior(dx, dh))), want, rtol=1e-5, atol_rel=1e-6)          # every interior element written (no NaN left)
 
 
+def near_tie_argmax(got_arg, arg, l, what=""):
+    """The fused forward's arg-max (NHWC) against the fp64 oracle's `arg` of the fp64 LRN output `l`: window-local index of the first
+    maximum; where the two differ, the two candidates must be a near-tie of the LRN output (the fused kernel rounds the LRN sums in a
+    slightly different order than any other kernel), and fewer than 1e-3 of the outputs may differ."""
+    got_arg = got_arg.astype(np.int64)
+    assert got_arg.min() >= 0 and got_arg.max() <= 8, what + ": arg-max outside 0..8"
+    n, oh, ow, c = got_arg.shape
+    oi, oj = np.meshgrid(np.arange(oh), np.arange(ow), indexing="ij")
+    def window_value(a):                                   # l at the window position a (NHWC)
+        ii, jj = 2 * oi[None, :, :, None] + a // 3, 2 * oj[None, :, :, None] + a % 3
+        return l[np.arange(n)[:, None, None, None], ii, jj, np.arange(c)[None, None, None, :]]
+    diff = np.abs(window_value(got_arg) - window_value(arg.astype(np.int64)))
+    share = float((got_arg != arg).mean())
+    assert share < 1e-3 and diff.max() <= 1e-5 * np.abs(l).max(), (what, share, float(diff.max()))
+
+
 @pytest.mark.parametrize("ranges", [0, 2, 3, 4])
 @pytest.mark.parametrize("n,h,w,c,ph", [(2, 9, 11, 7, 0), (3, 13, 13, 20, 1), (2, 57, 57, 96, 2), (2, 28, 28, 256, 1), (1, 31, 64, 5, 0), (2, 13, 13, 41, 1)])
 def test_lrn_pool_fwd_fused(ops, request, n, h, w, c, ph, ranges):
@@ -483,16 +499,7 @@ def test_lrn_pool_fwd_fused(ops, request, n, h, w, c, ph, ranges):
     ap = torch.full(p.shape, 77, dtype=torch.uint8, device=DEV)
     ops.lrn_pool_fwd(dev(nchw(x)), p, ap, p_halo=ph)
     close(nhwc(host(interior(p, ph))), y, rtol=1e-5, atol_rel=1e-6)
-    # arg-max: window-local index of the first maximum; where it differs from the fp64 oracle's, the two candidates must be a
-    # near-tie of the LRN output (the fused kernel rounds the LRN sums in a slightly different order than any other kernel)
-    got_arg = nhwc(host(interior(ap, ph))).astype(np.int64)
-    assert got_arg.min() >= 0 and got_arg.max() <= 8
-    oi, oj = np.meshgrid(np.arange(oh), np.arange(ow), indexing="ij")
-    def window_value(a):                                   # l at the window position a (NHWC)
-        ii, jj = 2 * oi[None, :, :, None] + a // 3, 2 * oj[None, :, :, None] + a % 3
-        return l[np.arange(n)[:, None, None, None], ii, jj, np.arange(c)[None, None, None, :]]
-    diff = np.abs(window_value(got_arg) - window_value(arg.astype(np.int64)))
-    assert (got_arg != arg).mean() < 1e-3 and diff.max() <= 1e-5 * np.abs(l).max()
+    near_tie_argmax(nhwc(host(interior(ap, ph))), arg, l)
     if ph:      # halo ROWS untouched; the halo columns of interior rows are stored with the row: 0.0 in p, unspecified in the arg-max map
         assert float((p[:, :, :ph] - 5.0).abs().max()) == 0 and float((p[:, :, -ph:] - 5.0).abs().max()) == 0
         assert int(ap[:, :, :ph].min()) == 77 and int(ap[:, :, -ph:].min()) == 77
