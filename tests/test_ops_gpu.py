@@ -612,7 +612,9 @@ def test_lstm_steps_match_layer(ops):
 @pytest.mark.parametrize("init", [False, True])
 def test_lstm_persistent_kernels(ops, b, T, d, H, init):
     """vl_lstm_seq_fwd / _bwd (one launch per direction for all steps) against the oracle layer: the weight-stationary cluster
-    form (H <= 512; groups of 1..8 clips, several launches beyond 128 clips) and the per-clip form (H = 600).
+    form (H <= 512; groups of 1, 3, 4 and 8 clips) and the per-clip form (H = 600).  Every case here is ONE launch per direction: the
+    130-clip case has H = 128, 8 workgroups per group, so a launch of a 256-CU device holds 256 clips.  The cases of several launches,
+    of every group size and of ragged groups are in tests/test_lstm_geometry_gpu.py (lists MULTI, FULL, RAGGED of tests/lstm_plan.py).
     init: a non-zero initial state c0 = h0 (lstm.py:34-42) and the gradients w.r.t. it."""
     if init and d >= 1024 and b > 8:
         pytest.skip("initial state is covered at the other sizes")
