@@ -1779,8 +1779,29 @@ extern "C" int vl_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, i
 // ---- softmax cross-entropy, mean over the batch (train.py:120-123) + accuracy (142-149) --------
 // One wave per row.  Row losses / hits go to a per-row workspace and are summed in a fixed order by a second one-workgroup
 // kernel -> bitwise reproducible at any batch; without a workspace one workgroup walks all rows (small batches only).
-__device__ __forceinline__ void softmax_xent_row(const float* __restrict__ z, const int32_t* __restrict__ y, float* __restrict__ dz,
-                                                 int C, float gscale, int lane, float& loss, float& hit) {
+// One row routine and one set of kernels serve every entry point, under two compile-time switches:
+//   LS   label smoothing + top-k hits (vl_softmax_xent_ls): y' = y (1 - eps) + eps / C in place of y, per element (not the
+//        algebraic form: at eps == 0 y' is y exactly and every sum is the plain one, bit for bit), one more lane-strided pass for the
+//        label's rank among the logits (top_k == 0: no pass), a third workspace column and stats[2].
+//   MIX  mixup / CutMix labels (vl_softmax_xent_mix; with LS): y' = lam y + (1 - lam) yp ahead of the smoothing, yp the
+//        partner's label row.  At lam == 1 y' is y exactly (labels are small non-negative integers): the bits of LS alone.
+// The switches are template parameters and not launch arguments: the plain launch holds neither the smoothing arithmetic nor a second
+// label load, and writes two workspace columns and stats[0..1] only (an ls launch costs 1.12 x a plain one at 1344 x 1000).
+
+// One element of a mixup blend, used by the label loop below and by every loop of both dtypes of vl_mixup_pairs: the rounding steps are
+// spelled out (1 - lam by the caller, two products, one sum), so an element's bits do not depend on which loop reached it.
+__device__ __forceinline__ float mix_elem(float a, float b, float lam, float oml) {
+#pragma clang fp contract(off)
+    return lam * a + oml * b;
+}
+
+// yp (MIX only): the partner's label row (nullptr: the row is its own partner and reads no other label row than its own).  The hits
+// are counted against the row's OWN labels.  hitk (LS only): rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}, t the first arg-max of
+// the label row; a top-k hit iff rank < k.
+template <bool LS, bool MIX>
+__device__ __forceinline__ void xent_row(const float* __restrict__ z, const int32_t* __restrict__ y, const int32_t* __restrict__ yp,
+                                         float* __restrict__ dz, int C, float gscale, float eps, int top_k, float lam, int lane,
+                                         float& loss, float& hit, float& hitk) {
     float mx = -INFINITY;
     int am = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
@@ -1799,173 +1820,19 @@ __device__ __forceinline__ void softmax_xent_row(const float* __restrict__ z, co
     for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
     se = wave_sum(se);
     const float lse = logf(se) + gmx;
-    float l = 0.f;
-    int ymax = -2147483647 - 1, yarg = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-        const int yv = y[c];
-        l += (float)yv * (lse - z[c]);
-        if (yv > ymax) {
-            ymax = yv;
-            yarg = c;
-        }
-        if (dz) dz[c] = (expf(z[c] - lse) - (float)yv) * gscale;
-    }
-    l = wave_sum(l);
-    int gy = ymax;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gy = max(gy, __shfl_xor(gy, o, 64));
-    int ycand = (ymax == gy) ? yarg : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ycand = min(ycand, __shfl_xor(ycand, o, 64));
-    loss = l;
-    hit = (cand == ycand) ? 1.f : 0.f;
-}
-
-// seq_len (nullable) with T: row r = b T + t is live iff t < seq_len[b].  A dead row is not read: it adds nothing to the sums and its
-// dlogits row is zeros (the reference's non_padding_index, dataset_.py:327-383).
-__device__ __forceinline__ bool xent_row_dead(const int32_t* __restrict__ seq_len, int T, int r) {
-    return seq_len && (r % T) >= seq_len[r / T];
-}
-
-__device__ __forceinline__ void xent_zero_row(float* __restrict__ dz, int C, int lane) {
-    if (dz)
-        for (int c = lane; c < C; c += 64) dz[c] = 0.f;
-}
-
-__global__ void softmax_xent_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                    float* __restrict__ dlogits, float* __restrict__ stats, int batch, int C, float gscale,
-                                    const int32_t* __restrict__ seq_len, int T) {
-    __shared__ float sl[4], sc[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float loss_acc = 0.f, corr_acc = 0.f;
-    for (int b = wv; b < batch; b += 4) {
-        float l, h;
-        if (xent_row_dead(seq_len, T, b)) {
-            xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
-            continue;
-        }
-        softmax_xent_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
-                         lane, l, h);
-        loss_acc += l;
-        corr_acc += h;
-    }
-    if (lane == 0) {
-        sl[wv] = loss_acc;
-        sc[wv] = corr_acc;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
-        stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
-    }
-}
-
-__global__ void softmax_xent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                         float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale,
-                                         const int32_t* __restrict__ seq_len, int T) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= batch) return;
-    float l, h;
-    if (xent_row_dead(seq_len, T, b)) {
-        xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
-        if (lane == 0) {
-            rows[b] = 0.f;
-            rows[batch + b] = 0.f;
-        }
-        return;
-    }
-    softmax_xent_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, lane,
-                     l, h);
-    if (lane == 0) {
-        rows[b] = l;
-        rows[batch + b] = h;
-    }
-}
-
-// rows[0..batch) losses, rows[batch..2 batch) hits -> stats += their sums; thread t adds rows t, t+256, ... then a fixed tree.
-__global__ void softmax_xent_sum_kernel(const float* __restrict__ rows, float* __restrict__ stats, int batch) {
-    __shared__ float sl[256], sc[256];
-    float l = 0.f, h = 0.f;
-    for (int b = threadIdx.x; b < batch; b += 256) {
-        l += rows[b];
-        h += rows[batch + b];
-    }
-    sl[threadIdx.x] = l;
-    sc[threadIdx.x] = h;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sl[threadIdx.x] += sl[threadIdx.x + s];
-            sc[threadIdx.x] += sc[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        stats[0] += sl[0];
-        stats[1] += sc[0];
-    }
-}
-
-static int softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
-                        float grad_scale, const int32_t* seq_len, int T, hipStream_t stream) {
-    if (!rows) {
-        hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(256), 0, stream, logits, labels, dlogits, stats, batch, classes, grad_scale,
-                           seq_len, T);
-        VL_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(softmax_xent_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, stream, logits, labels, dlogits, rows, batch,
-                       classes, grad_scale, seq_len, T);
-    VL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(softmax_xent_sum_kernel, dim3(1), dim3(256), 0, stream, rows, stats, batch);
-    VL_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
-                               int classes, float grad_scale, vl_stream_t stream) {
-    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent: bad argument");
-    return softmax_xent(logits, labels, dlogits, stats, rows, batch, classes, grad_scale, nullptr, 1, (hipStream_t)stream);
-}
-
-extern "C" int vl_softmax_xent_len(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
-                                   int classes, float grad_scale, const int32_t* seq_len, int T, vl_stream_t stream) {
-    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_len: bad argument");
-    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_len: batch (%d rows) is not whole sequences of T = %d", batch, T);
-    return softmax_xent(logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, seq_len ? T : 1, (hipStream_t)stream);
-}
-
-// ---- label smoothing + top-k hits (vl_softmax_xent_ls) ----------------------------------------------------------------------------
-// The row of softmax_xent_row with y' = y (1 - eps) + eps / C in place of y, per element (not the algebraic form: at eps == 0 y' is y
-// exactly and every sum is the one above, bit for bit), and one more lane-strided pass for the label's rank among the logits:
-// rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}, t the first arg-max of the label row; a top-k hit iff rank < k (k == 0: no pass).
-// A function of its own, so that the three kernels above keep their code.
-__device__ __forceinline__ void softmax_xent_ls_row(const float* __restrict__ z, const int32_t* __restrict__ y, float* __restrict__ dz,
-                                                    int C, float gscale, float eps, int top_k, int lane, float& loss, float& hit,
-                                                    float& hitk) {
-    float mx = -INFINITY;
-    int am = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-        const float v = z[c];
-        if (v > mx) {
-            mx = v;
-            am = c;
-        }
-    }
-    const float gmx = wave_max(mx);
-    int cand = (mx == gmx) ? am : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    float se = 0.f;
-    for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
-    se = wave_sum(se);
-    const float lse = logf(se) + gmx;
     const float on = 1.0f - eps, off = eps / (float)C;
     float l = 0.f;
     int ymax = -2147483647 - 1, yarg = 0x7fffffff;
+    // MIX: no branch inside the loop: with one, the partner's load was issued only after the row's own had come back and the logit's
+    // only after both -- three memory latencies per iteration in the place of one.  A row that is its own partner loads its own row
+    // twice (the same addresses) under the weights 1 and 0, which give y exactly.
+    const int32_t* yq = yp ? yp : y;
+    const float lam_r = yp ? lam : 1.0f, oml = 1.0f - lam_r;
     for (int c = lane; c < C; c += 64) {
         const int yv = y[c];
-        const float ys = (float)yv * on + off;
+        float ys = (float)yv;
+        if constexpr (MIX) ys = mix_elem(ys, (float)yq[c], lam_r, oml);
+        if constexpr (LS) ys = ys * on + off;
         l += ys * (lse - z[c]);
         if (yv > ymax) {
             ymax = yv;
@@ -1983,34 +1850,59 @@ __device__ __forceinline__ void softmax_xent_ls_row(const float* __restrict__ z,
     loss = l;
     hit = (cand == ycand) ? 1.f : 0.f;
     hitk = 0.f;
-    if (top_k > 0) {                              // (uniform over the wave: every lane takes part in the shuffles)
-        const int t = min(ycand, C - 1);          // (ycand < C unless every label is INT_MIN: never index past the row)
-        const float zt = z[t];
-        int rank = 0;
-        for (int c = lane; c < C; c += 64) {
-            const float v = z[c];
-            rank += (v > zt || (v == zt && c < t)) ? 1 : 0;
-        }
+    if constexpr (LS) {
+        if (top_k > 0) {                              // (uniform over the wave: every lane takes part in the shuffles)
+            const int t = min(ycand, C - 1);          // (ycand < C unless every label is INT_MIN: never index past the row)
+            const float zt = z[t];
+            int rank = 0;
+            for (int c = lane; c < C; c += 64) {
+                const float v = z[c];
+                rank += (v > zt || (v == zt && c < t)) ? 1 : 0;
+            }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
-        hitk = rank < top_k ? 1.f : 0.f;
+            for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+            hitk = rank < top_k ? 1.f : 0.f;
+        }
     }
 }
 
-__global__ void softmax_xent_ls_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                       float* __restrict__ dlogits, float* __restrict__ stats, int batch, int C, float gscale,
-                                       const int32_t* __restrict__ seq_len, int T, float eps, int top_k) {
+// seq_len (nullable) with T: row r = b T + t is live iff t < seq_len[b].  A dead row is not read: it adds nothing to the sums and its
+// dlogits row is zeros (the reference's non_padding_index, dataset_.py:327-383).  MIX takes no lengths and makes no such test.
+__device__ __forceinline__ bool xent_row_dead(const int32_t* __restrict__ seq_len, int T, int r) {
+    return seq_len && (r % T) >= seq_len[r / T];
+}
+
+__device__ __forceinline__ void xent_zero_row(float* __restrict__ dz, int C, int lane) {
+    if (dz)
+        for (int c = lane; c < C; c += 64) dz[c] = 0.f;
+}
+
+// the label row of row b's partner: row b % rpc of clip clips - 1 - b / rpc (nullptr: b is its own partner)
+__device__ __forceinline__ const int32_t* mix_partner_labels(const int32_t* __restrict__ labels, int b, int batch, int rpc, int C) {
+    const int pr = (batch / rpc - 1 - b / rpc) * rpc + b % rpc;
+    return pr == b ? nullptr : labels + (int64_t)pr * C;
+}
+
+// Both kernels take the same arguments but for stats / rows.  seq_len, T: !MIX only; rpc, lam_arg, lam_dev: MIX only (lam is read from
+// lam_dev, when given, as the kernel runs: a captured step replays with the lambda the host wrote before the replay); eps, top_k: LS.
+// Without a workspace: wave w walks rows w, w + 4, ...; stats += ((w0 + w1) + w2) + w3 per column.
+template <bool LS, bool MIX>
+__global__ void xent_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                            float* __restrict__ stats, int batch, int C, float gscale, const int32_t* __restrict__ seq_len, int T, int rpc,
+                            float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
     __shared__ float sl[4], sc[4], sk[4];
+    const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     float loss_acc = 0.f, corr_acc = 0.f, topk_acc = 0.f;
     for (int b = wv; b < batch; b += 4) {
+        float* dz = dlogits ? dlogits + (int64_t)b * C : nullptr;
         float l, h, hk;
-        if (xent_row_dead(seq_len, T, b)) {
-            xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+        if (!MIX && xent_row_dead(seq_len, T, b)) {
+            xent_zero_row(dz, C, lane);
             continue;
         }
-        softmax_xent_ls_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
-                            eps, top_k, lane, l, h, hk);
+        xent_row<LS, MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
+                          dz, C, gscale, eps, top_k, lam, lane, l, h, hk);
         loss_acc += l;
         corr_acc += h;
         topk_acc += hk;
@@ -2018,61 +1910,115 @@ __global__ void softmax_xent_ls_kernel(const float* __restrict__ logits, const i
     if (lane == 0) {
         sl[wv] = loss_acc;
         sc[wv] = corr_acc;
-        sk[wv] = topk_acc;
+        if constexpr (LS) sk[wv] = topk_acc;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
         stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
-        if (top_k > 0) stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
+        if constexpr (LS)
+            if (top_k > 0) stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
     }
 }
 
-__global__ void softmax_xent_ls_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                            float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale,
-                                            const int32_t* __restrict__ seq_len, int T, float eps, int top_k) {
+// With a workspace: row b's loss, hit and (LS) top-k hit to rows[b], rows[batch + b], rows[2 batch + b]; zeros for a dead row.
+template <bool LS, bool MIX>
+__global__ void xent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                                 float* __restrict__ rows, int batch, int C, float gscale, const int32_t* __restrict__ seq_len, int T,
+                                 int rpc, float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= batch) return;
+    const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
+    float* dz = dlogits ? dlogits + (int64_t)b * C : nullptr;
     float l = 0.f, h = 0.f, hk = 0.f;
-    if (xent_row_dead(seq_len, T, b))
-        xent_zero_row(dlogits ? dlogits + (int64_t)b * C : nullptr, C, lane);
+    if (!MIX && xent_row_dead(seq_len, T, b))
+        xent_zero_row(dz, C, lane);
     else
-        softmax_xent_ls_row(logits + (int64_t)b * C, labels + (int64_t)b * C, dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale,
-                            eps, top_k, lane, l, h, hk);
+        xent_row<LS, MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
+                          dz, C, gscale, eps, top_k, lam, lane, l, h, hk);
     if (lane == 0) {
         rows[b] = l;
         rows[batch + b] = h;
-        rows[2 * (int64_t)batch + b] = hk;
+        if constexpr (LS) rows[2 * (int64_t)batch + b] = hk;
     }
 }
 
-// softmax_xent_sum_kernel with a third column: rows[2 batch .. 3 batch) top-k hits -> stats[2] (top_k == 0: stats[2] is not touched).
-// Columns 0 and 1 are added in the order of that kernel, so stats[0] and stats[1] are its bits.
-__global__ void softmax_xent_ls_sum_kernel(const float* __restrict__ rows, float* __restrict__ stats, int batch, int top_k) {
+// rows[0..batch) losses, rows[batch..2 batch) hits, (LS) rows[2 batch..3 batch) top-k hits -> stats += their sums; thread t adds rows
+// t, t+256, ... then a fixed tree.  The columns do not mix, so stats[0..1] have the same bits under LS; top_k == 0: stats[2] is not
+// touched.
+template <bool LS>
+__global__ void xent_sum_kernel(const float* __restrict__ rows, float* __restrict__ stats, int batch, int top_k) {
     __shared__ float sl[256], sc[256], sk[256];
     float l = 0.f, h = 0.f, hk = 0.f;
     for (int b = threadIdx.x; b < batch; b += 256) {
         l += rows[b];
         h += rows[batch + b];
-        hk += rows[2 * (int64_t)batch + b];
+        if constexpr (LS) hk += rows[2 * (int64_t)batch + b];
     }
     sl[threadIdx.x] = l;
     sc[threadIdx.x] = h;
-    sk[threadIdx.x] = hk;
+    if constexpr (LS) sk[threadIdx.x] = hk;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
             sl[threadIdx.x] += sl[threadIdx.x + s];
             sc[threadIdx.x] += sc[threadIdx.x + s];
-            sk[threadIdx.x] += sk[threadIdx.x + s];
+            if constexpr (LS) sk[threadIdx.x] += sk[threadIdx.x + s];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         stats[0] += sl[0];
         stats[1] += sc[0];
-        if (top_k > 0) stats[2] += sk[0];
+        if constexpr (LS)
+            if (top_k > 0) stats[2] += sk[0];
     }
+}
+
+// what a loss launch takes; an entry point sets what it has and leaves the rest at the values under which it is the identity
+struct xent_args {
+    const float* logits;
+    const int32_t* labels;
+    float *dlogits, *stats, *rows;
+    int batch, classes;
+    float grad_scale;
+    const int32_t* seq_len = nullptr;
+    int T = 1, rows_per_clip = 1;
+    float smoothing = 0.f;
+    int top_k = 0;
+    float lam = 1.f;
+    const float* lam_dev = nullptr;
+};
+
+template <bool LS, bool MIX>
+static int xent_launch(xent_args a, vl_stream_t stream) {
+    if (!a.seq_len) a.T = 1;
+    if (!a.rows) {
+        hipLaunchKernelGGL((xent_kernel<LS, MIX>), dim3(1), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels, a.dlogits, a.stats,
+                           a.batch, a.classes, a.grad_scale, a.seq_len, a.T, a.rows_per_clip, a.smoothing, a.top_k, a.lam, a.lam_dev);
+        VL_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL((xent_rows_kernel<LS, MIX>), dim3((a.batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels,
+                       a.dlogits, a.rows, a.batch, a.classes, a.grad_scale, a.seq_len, a.T, a.rows_per_clip, a.smoothing, a.top_k, a.lam,
+                       a.lam_dev);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL((xent_sum_kernel<LS>), dim3(1), dim3(256), 0, (hipStream_t)stream, a.rows, a.stats, a.batch, a.top_k);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_softmax_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                               int classes, float grad_scale, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent: bad argument");
+    return xent_launch<false, false>({logits, labels, dlogits, stats, rows, batch, classes, grad_scale}, stream);
+}
+
+extern "C" int vl_softmax_xent_len(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                   int classes, float grad_scale, const int32_t* seq_len, int T, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_len: bad argument");
+    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_len: batch (%d rows) is not whole sequences of T = %d", batch, T);
+    return xent_launch<false, false>({logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, T}, stream);
 }
 
 extern "C" int vl_softmax_xent_ls(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
@@ -2082,31 +2028,27 @@ extern "C" int vl_softmax_xent_ls(const float* logits, const int32_t* labels, fl
     VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_ls: batch (%d rows) is not whole sequences of T = %d", batch, T);
     VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_ls: smoothing must lie in [0, 1), got %g", (double)smoothing);
     VL_CHECK(top_k >= 0, "vl_softmax_xent_ls: top_k must be >= 0, got %d", top_k);
-    const int Tl = seq_len ? T : 1;
-    if (!rows) {
-        hipLaunchKernelGGL(softmax_xent_ls_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch,
-                           classes, grad_scale, seq_len, Tl, smoothing, top_k);
-        VL_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(softmax_xent_ls_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits,
-                       rows, batch, classes, grad_scale, seq_len, Tl, smoothing, top_k);
-    VL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(softmax_xent_ls_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch, top_k);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return xent_launch<true, false>({logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, T, 1, smoothing, top_k},
+                                    stream);
 }
 
-// ---- mixup (Zhang et al. 2018): the paired in-place blend of the clips and the loss on the mixed labels ---------------
+extern "C" int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                   int classes, float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam,
+                                   const float* lam_dev, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_mix: bad argument");
+    VL_CHECK(rows_per_clip > 0 && batch % rows_per_clip == 0, "vl_softmax_xent_mix: batch (%d rows) is not whole clips of %d rows", batch,
+             rows_per_clip);
+    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_mix: smoothing must lie in [0, 1), got %g", (double)smoothing);
+    VL_CHECK(top_k >= 0, "vl_softmax_xent_mix: top_k must be >= 0, got %d", top_k);
+    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_softmax_xent_mix: lam must lie in [0, 1], got %g", (double)lam);
+    return xent_launch<true, true>(
+        {logits, labels, dlogits, stats, rows, batch, classes, grad_scale, nullptr, 1, rows_per_clip, smoothing, top_k, lam, lam_dev}, stream);
+}
+
+// ---- mixup (Zhang et al. 2018): the paired in-place blend of the clips (the loss on the mixed labels: xent_row<., MIX>) --
 // Clip i is paired with clip clips - 1 - i.  lam comes from the launch arguments or, when lam_dev is given, from the device when the
-// kernel runs (a captured step replays with the lambda the host wrote before the replay).
-// One element function, used by every loop of both dtypes: the rounding steps are spelled out (1 - lam, two products, one sum), so an
-// element's bits do not depend on which loop reached it.
-__device__ __forceinline__ float mix_elem(float a, float b, float lam, float oml) {
-#pragma clang fp contract(off)
-    return lam * a + oml * b;
-}
-
+// kernel runs (a captured step replays with the lambda the host wrote before the replay).  Every loop of both dtypes blends with
+// mix_elem (above), so an element's bits do not depend on which loop reached it.
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t h) { return __builtin_bit_cast(float, h << 16); }
 __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {      // round to nearest even (v_cvt_pk_bf16_f32)
     const __bf16 h = (__bf16)f;
@@ -2207,146 +2149,6 @@ extern "C" int vl_mixup_pairs(void* x, int dtype, int clips, int64_t clip_elems,
     else
         hipLaunchKernelGGL(mixup_pairs_bf16_kernel, grid, dim3(256), 0, (hipStream_t)stream, (uint32_t*)x, clips, clip_elems / 2, lam,
                            lam_dev);
-    VL_LAUNCH_CHECK();
-    return 0;
-}
-
-// The row of softmax_xent_ls_row with the labels y' = lam y + (1 - lam) yp in y's place ahead of the smoothing, yp the partner's
-// label row (nullptr: the row is its own partner and reads no other label row than its own).  The hits are counted against the row's OWN labels.  At
-// lam == 1 y' is y exactly (labels are small non-negative integers) and every sum is the one of softmax_xent_ls_row, bit for bit.
-// A function of its own, so that the kernels above keep their code.
-__device__ __forceinline__ void softmax_xent_mix_row(const float* __restrict__ z, const int32_t* __restrict__ y,
-                                                     const int32_t* __restrict__ yp, float* __restrict__ dz, int C, float gscale,
-                                                     float eps, int top_k, float lam, int lane, float& loss, float& hit, float& hitk) {
-    float mx = -INFINITY;
-    int am = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-        const float v = z[c];
-        if (v > mx) {
-            mx = v;
-            am = c;
-        }
-    }
-    const float gmx = wave_max(mx);
-    int cand = (mx == gmx) ? am : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    float se = 0.f;
-    for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
-    se = wave_sum(se);
-    const float lse = logf(se) + gmx;
-    const float on = 1.0f - eps, off = eps / (float)C;
-    float l = 0.f;
-    int ymax = -2147483647 - 1, yarg = 0x7fffffff;
-    // No branch inside the loop: with one, the partner's load was issued only after the row's own had come back and the logit's only
-    // after both -- three memory latencies per iteration in the place of one.  A row that is its own partner loads its own row twice
-    // (the same addresses) under the weights 1 and 0, which give y exactly.
-    const int32_t* yq = yp ? yp : y;
-    const float lam_r = yp ? lam : 1.0f, oml = 1.0f - lam_r;
-    for (int c = lane; c < C; c += 64) {
-        const int yv = y[c];
-        const float ym = mix_elem((float)yv, (float)yq[c], lam_r, oml);
-        const float ys = ym * on + off;
-        l += ys * (lse - z[c]);
-        if (yv > ymax) {
-            ymax = yv;
-            yarg = c;
-        }
-        if (dz) dz[c] = (expf(z[c] - lse) - ys) * gscale;
-    }
-    l = wave_sum(l);
-    int gy = ymax;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gy = max(gy, __shfl_xor(gy, o, 64));
-    int ycand = (ymax == gy) ? yarg : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ycand = min(ycand, __shfl_xor(ycand, o, 64));
-    loss = l;
-    hit = (cand == ycand) ? 1.f : 0.f;
-    hitk = 0.f;
-    if (top_k > 0) {                              // (uniform over the wave: every lane takes part in the shuffles)
-        const int t = min(ycand, C - 1);
-        const float zt = z[t];
-        int rank = 0;
-        for (int c = lane; c < C; c += 64) {
-            const float v = z[c];
-            rank += (v > zt || (v == zt && c < t)) ? 1 : 0;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
-        hitk = rank < top_k ? 1.f : 0.f;
-    }
-}
-
-// the label row of row b's partner: row b % rpc of clip clips - 1 - b / rpc (nullptr: b is its own partner)
-__device__ __forceinline__ const int32_t* mix_partner_labels(const int32_t* __restrict__ labels, int b, int batch, int rpc, int C) {
-    const int pr = (batch / rpc - 1 - b / rpc) * rpc + b % rpc;
-    return pr == b ? nullptr : labels + (int64_t)pr * C;
-}
-
-__global__ void softmax_xent_mix_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
-                                        float* __restrict__ stats, int batch, int C, float gscale, int rpc, float eps, int top_k,
-                                        float lam_arg, const float* __restrict__ lam_dev) {
-    __shared__ float sl[4], sc[4], sk[4];
-    const float lam = lam_dev ? *lam_dev : lam_arg;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float loss_acc = 0.f, corr_acc = 0.f, topk_acc = 0.f;
-    for (int b = wv; b < batch; b += 4) {
-        float l, h, hk;
-        softmax_xent_mix_row(logits + (int64_t)b * C, labels + (int64_t)b * C, mix_partner_labels(labels, b, batch, rpc, C),
-                             dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, eps, top_k, lam, lane, l, h, hk);
-        loss_acc += l;
-        corr_acc += h;
-        topk_acc += hk;
-    }
-    if (lane == 0) {
-        sl[wv] = loss_acc;
-        sc[wv] = corr_acc;
-        sk[wv] = topk_acc;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
-        stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
-        if (top_k > 0) stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
-    }
-}
-
-__global__ void softmax_xent_mix_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                             float* __restrict__ dlogits, float* __restrict__ rows, int batch, int C, float gscale, int rpc,
-                                             float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
-    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (b >= batch) return;
-    const float lam = lam_dev ? *lam_dev : lam_arg;
-    float l, h, hk;
-    softmax_xent_mix_row(logits + (int64_t)b * C, labels + (int64_t)b * C, mix_partner_labels(labels, b, batch, rpc, C),
-                         dlogits ? dlogits + (int64_t)b * C : nullptr, C, gscale, eps, top_k, lam, lane, l, h, hk);
-    if (lane == 0) {
-        rows[b] = l;
-        rows[batch + b] = h;
-        rows[2 * (int64_t)batch + b] = hk;
-    }
-}
-
-extern "C" int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
-                                   int classes, float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam,
-                                   const float* lam_dev, vl_stream_t stream) {
-    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_mix: bad argument");
-    VL_CHECK(rows_per_clip > 0 && batch % rows_per_clip == 0, "vl_softmax_xent_mix: batch (%d rows) is not whole clips of %d rows", batch,
-             rows_per_clip);
-    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_mix: smoothing must lie in [0, 1), got %g", (double)smoothing);
-    VL_CHECK(top_k >= 0, "vl_softmax_xent_mix: top_k must be >= 0, got %d", top_k);
-    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_softmax_xent_mix: lam must lie in [0, 1], got %g", (double)lam);
-    if (!rows) {
-        hipLaunchKernelGGL(softmax_xent_mix_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch,
-                           classes, grad_scale, rows_per_clip, smoothing, top_k, lam, lam_dev);
-        VL_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(softmax_xent_mix_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits,
-                       rows, batch, classes, grad_scale, rows_per_clip, smoothing, top_k, lam, lam_dev);
-    VL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(softmax_xent_ls_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch, top_k);
     VL_LAUNCH_CHECK();
     return 0;
 }

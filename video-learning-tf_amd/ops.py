@@ -670,23 +670,35 @@ def relu_dropout_grad(d, y, keep, count=None):
 
 
 # ---- loss / optimizer ----------------------------------------------------------------------------
+def _xent_args(who, cols, logits, labels, dlogits, stats, rows, seq_len=None, T=None, partner=False):
+    """The checks the loss wrappers share, for `who` with `cols` columns of stats / rows (partner: the labels are indexed by row, so
+    they need the logits' shape) -> (batch, classes, seq_len or None, T or 1)."""
+    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
+    if labels.dtype != torch.int32:
+        raise _ffi.VltfError("%s: labels must be int32 one-hot" % who)
+    b, c = logits.shape
+    if partner and tuple(labels.shape) != (b, c):
+        raise _ffi.VltfError("%s: labels must have the logits' shape (the partner's row is found by index)" % who)
+    if cols > 2 and stats.numel() < cols:
+        raise _ffi.VltfError("%s: stats needs %d floats" % (who, cols))
+    if rows is not None:
+        _f32(rows)
+        if rows.numel() < cols * b:
+            raise _ffi.VltfError("%s: rows workspace needs %d*batch floats" % (who, cols))
+    if seq_len is None:
+        return b, c, None, 1
+    if not T or T < 1 or b % int(T):
+        raise _ffi.VltfError("%s: seq_len needs T with rows = clips * T (rows %d, T %s)" % (who, b, T))
+    return b, c, _seq_len(seq_len, b // int(T), who), int(T)
+
+
 def softmax_xent(logits, labels, dlogits, stats, grad_scale, rows=None, seq_len=None, T=None):
     """rows: float32 workspace of >= 2*batch elements (per-row losses and hits); without it one workgroup walks the batch.
     seq_len with T: the rows are the steps of batch / T sequences; row b T + t with t >= seq_len[b] is padding -- not read, nothing
     added to `stats`, dlogits 0 (vl_softmax_xent_len; grad_scale is the caller's 1 / live rows)."""
-    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
-    if labels.dtype != torch.int32:
-        raise _ffi.VltfError("softmax_xent: labels must be int32 one-hot")
-    b, c = logits.shape
-    if rows is not None:
-        _f32(rows)
-        if rows.numel() < 2 * b:
-            raise _ffi.VltfError("softmax_xent: rows workspace needs 2*batch floats")
-    if seq_len is not None:
-        if not T or T < 1 or b % int(T):
-            raise _ffi.VltfError("softmax_xent: seq_len needs T with rows = clips * T (rows %d, T %s)" % (b, T))
-        _ffi.call("vl_softmax_xent_len", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale,
-                  _p(_seq_len(seq_len, b // int(T), "softmax_xent")), int(T), stream())
+    b, c, sl, t = _xent_args("softmax_xent", 2, logits, labels, dlogits, stats, rows, seq_len, T)
+    if sl is not None:
+        _ffi.call("vl_softmax_xent_len", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, _p(sl), t, stream())
         return
     _ffi.call("vl_softmax_xent", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, stream())
 
@@ -695,21 +707,7 @@ def softmax_xent_ls(logits, labels, dlogits, stats, grad_scale, rows, smoothing,
     """softmax_xent with label smoothing (y' = y (1 - smoothing) + smoothing / classes) and top-k hits in the same launch
     (vl_softmax_xent_ls).  stats: 3 floats (loss sum, top-1 hits, top-k hits; top_k 0 leaves the third alone); rows: None or a float32
     workspace of >= 3*batch elements.  seq_len / T as in softmax_xent."""
-    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
-    if labels.dtype != torch.int32:
-        raise _ffi.VltfError("softmax_xent_ls: labels must be int32 one-hot")
-    b, c = logits.shape
-    if stats.numel() < 3:
-        raise _ffi.VltfError("softmax_xent_ls: stats needs 3 floats")
-    if rows is not None:
-        _f32(rows)
-        if rows.numel() < 3 * b:
-            raise _ffi.VltfError("softmax_xent_ls: rows workspace needs 3*batch floats")
-    sl, t = None, 1
-    if seq_len is not None:
-        if not T or T < 1 or b % int(T):
-            raise _ffi.VltfError("softmax_xent_ls: seq_len needs T with rows = clips * T (rows %d, T %s)" % (b, T))
-        sl, t = _seq_len(seq_len, b // int(T), "softmax_xent_ls"), int(T)
+    b, c, sl, t = _xent_args("softmax_xent_ls", 3, logits, labels, dlogits, stats, rows, seq_len, T)
     _ffi.call("vl_softmax_xent_ls", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, _p(sl), t,
               float(smoothing), int(top_k), stream())
 
@@ -775,18 +773,7 @@ def softmax_xent_mix(logits, labels, dlogits, stats, grad_scale, rows, rows_per_
     """softmax_xent_ls on the labels of clips blended by mixup_pairs (vl_softmax_xent_mix): y' = lam y + (1 - lam) y_partner ahead of
     the smoothing, the partner being the same row of the clip mirrored in the batch; hits against the row's own label.  logits are
     clips of rows_per_clip rows.  stats: 3 floats; rows: None or >= 3*batch floats; lam as in mixup_pairs."""
-    _f32(logits, dlogits, stats); _dense(logits, labels, dlogits)
-    if labels.dtype != torch.int32:
-        raise _ffi.VltfError("softmax_xent_mix: labels must be int32 one-hot")
-    b, c = logits.shape
-    if tuple(labels.shape) != (b, c):
-        raise _ffi.VltfError("softmax_xent_mix: labels must have the logits' shape (the partner's row is found by index)")
-    if stats.numel() < 3:
-        raise _ffi.VltfError("softmax_xent_mix: stats needs 3 floats")
-    if rows is not None:
-        _f32(rows)
-        if rows.numel() < 3 * b:
-            raise _ffi.VltfError("softmax_xent_mix: rows workspace needs 3*batch floats")
+    b, c, _, _ = _xent_args("softmax_xent_mix", 3, logits, labels, dlogits, stats, rows, partner=True)
     lam_host, lam_dev = _lam(lam, "softmax_xent_mix")
     _ffi.call("vl_softmax_xent_mix", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, int(rows_per_clip),
               float(smoothing), int(top_k), lam_host, lam_dev, stream())
