@@ -18,7 +18,8 @@
  *     [kh][kw][cin/group][cout] (alexnet.py:73,113), fc weights [in][out] (alexnet.py:225),
  *     LSTM kernel [D+H][4H] with gate order i, j, f, o (TF BasicLSTMCell; lstm.py:17).
  *   - Thread-compatible: one stream/descriptor set per host thread (exceptions, both process-wide words: vl_set_conv_math
- *     and the test hooks vl_lstm_seq_test_hooks, vl_pool_lrn_bwd_test_ranges, vl_conv_set_row_classes).
+ *     and the test hooks vl_lstm_seq_test_hooks, vl_pool_lrn_bwd_test_ranges, vl_conv_set_row_classes,
+ *     vl_conv_set_stage_depth / vl_conv_last_launch).
  */
 #ifndef VLTF_H
 #define VLTF_H
@@ -129,6 +130,15 @@ int vl_conv_math(void);
  * The one difference: with on = 0 a non-finite weight reaches every output through its padding taps as well (inf * 0 = NaN); with
  * on = 1 it no longer poisons the border rows through the kernel rows left out. */
 int vl_conv_set_row_classes(int on);
+/* Test hook of the same launches, process-wide, default 0.  The 16x16-MFMA LDS-DMA kernel (48- and 96-channel tiles: conv1 / conv4
+ * forward, conv2 / conv4 / conv5 dgrad) exists with reduction stages of 32 rows (two workgroups per CU) and of 16 rows (three).
+ * rows = 16 or 32 forces that form on every launch of the kernel, 0 returns the choice to the dispatcher.  The stage depth moves
+ * barriers only, never the order of a sum: the two forms agree bit for bit.  Launches of other kernels ignore it. */
+int vl_conv_set_stage_depth(int rows);
+/* Kernel form of the latest vl_conv_fwd / vl_conv_dgrad call in fp32 arithmetic: tile height * 100 + stage depth for an LDS-DMA
+ * launch (4816, 4832, 9616, 9632: the 16x16-MFMA kernel; 12832: the 32x32-MFMA kernel), 0 for any other kernel.  A call that splits
+ * into two launches reports the second. */
+int vl_conv_last_launch(void);
 /* y[n][cout][oh][ow] = conv(x[n][cin][h][w], w_hwio) + bias, optional fused ReLU (alexnet.py:77). */
 int vl_conv_fwd(const vl_conv_desc* d, const float* x, const float* w_hwio, const float* bias, float* y,
                 int n, int relu, vl_stream_t stream);

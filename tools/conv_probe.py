@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Runs one AlexNet conv layer's fwd / dgrad / wgrad kernels in isolation (for rocprofv3 / timing).
 usage: conv_probe.py <conv1..conv5> <fwd|dgrad|wgrad> [frames] [iters]
-VL_PROBE_ROW_CLASSES=0: the flat pixel order of fwd / dgrad (ops.conv_set_row_classes)."""
+VL_PROBE_ROW_CLASSES=0: the flat pixel order of fwd / dgrad (ops.conv_set_row_classes).
+VL_PROBE_MASK=1: dgrad with the fused ReluGrad mask (the engine's conv4 / conv5 dgrad).
+VL_PROBE_DEPTHS=32,16 [VL_PROBE_PAIRS=5]: the stage depths of the 16x16 LDS-DMA kernel (ops.conv_set_stage_depth) timed alternately
+in this one process, PAIRS rounds, one line per timing with the kernel form that ran (ops.conv_last_launch)."""
 import os
 import sys
 import time
@@ -60,6 +63,7 @@ def main():
     dw = torch.empty_like(wt)
     wtt = torch.empty(wt.numel(), device=dev)
     ws = torch.empty(max(conv.wgrad_ws_bytes(n) // 4, 1), device=dev)
+    mask = haloed(cin, h, w, xh) if os.environ.get("VL_PROBE_MASK") else None
     if what == "dgrad":
         conv.wt_transpose(wt, wtt)
 
@@ -67,7 +71,7 @@ def main():
         if what == "fwd":
             conv.fwd(x, wt, b, y, relu=True)
         elif what == "dgrad":
-            conv.dgrad(dy, wtt, dx)
+            conv.dgrad(dy, wtt, dx, relu_mask=mask)
         else:
             conv.wgrad(x, dy, dw, ws)
 
@@ -80,11 +84,26 @@ def main():
         got = {"fwd": y, "dgrad": dx, "wgrad": dw}[what].cpu()
         print("  vs %s: rel L2 %.3e  max abs %.3e (ref max %.3e)" % (os.environ["VL_PROBE_CMP"], float((got - ref).norm() / ref.norm()),
                                                                   float((got - ref).abs().max()), float(ref.abs().max())))
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        run()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / iters
+
+    def timed():
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            run()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    depths = [int(d) for d in os.environ.get("VL_PROBE_DEPTHS", "").split(",") if d]
+    if depths:
+        for _ in range(int(os.environ.get("VL_PROBE_PAIRS", "5"))):
+            for d in depths:
+                ops.conv_set_stage_depth(d)
+                run()                                   # the form's first launch (its LDS attribute) outside the timing
+                dt = timed()
+                print("%s.%s n=%d depth=%d form=%d: %.4f ms  %.1f TFLOP/s" % (layer, what, n, d, ops.conv_last_launch(), dt * 1e3,
+                                                                             2 * MACS[layer] * n / dt / 1e12))
+        ops.conv_set_stage_depth(0)
+        return
+    dt = timed()
     print("%s.%s n=%d: %.3f ms  %.1f TFLOP/s" % (layer, what, n, dt * 1e3, 2 * MACS[layer] * n / dt / 1e12))
 
 

@@ -27,6 +27,8 @@ SIGNATURES = {
     "vl_set_conv_math": (i32, [i32]),
     "vl_conv_math": (i32, []),
     "vl_conv_set_row_classes": (i32, [i32]),
+    "vl_conv_set_stage_depth": (i32, [i32]),
+    "vl_conv_last_launch": (i32, []),
     "vl_gemm_split_ws_bytes": (C.c_size_t, [i32, i32, i32]),
     "vl_conv_fwd": (i32, [p, p, p, p, p, i32, i32, p]),
     "vl_conv_wt_transpose": (i32, [p, p, p, p]),

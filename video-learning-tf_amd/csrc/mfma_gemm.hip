@@ -2001,6 +2001,21 @@ extern "C" int vl_conv_set_row_classes(int on) {
     return 0;
 }
 
+// tests and measurements: vl_conv_set_stage_depth(16 | 32) forces the stage depth of the 16x16 LDS-DMA kernel (conv_dma16_kernel:
+// 16-row stages, three workgroups per CU; 32-row stages, two), 0 gives the choice back to conv16_stage_depth.  vl_conv_last_launch
+// reports the kernel form of the latest fp32 conv forward / dgrad call: tile height * 100 + stage depth for an LDS-DMA launch
+// (4816, 4832, 9616, 9632, 12832), 0 for any other kernel.
+static int g_conv_stage_depth = 0;
+static int g_conv_last_launch = 0;
+
+extern "C" int vl_conv_set_stage_depth(int rows) {
+    VL_CHECK(rows == 0 || rows == 16 || rows == 32, "vl_conv_set_stage_depth: 0 (dispatcher's choice), 16 or 32");
+    g_conv_stage_depth = rows;
+    return 0;
+}
+
+extern "C" int vl_conv_last_launch(void) { return g_conv_last_launch; }
+
 // ---- convolution descriptor -------------------------------------------------------------------
 // struct vl_conv_desc: conv_desc.h (shared with conv_c8.hip)
 
@@ -2287,16 +2302,34 @@ static int launch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_gr
 // strides 80 / 144 floats (= 16 mod 32) keep the four 16-lane groups of a fragment read -- lane group g reads row 4 s + g --
 // on disjoint banks.  Lane l holds A[co = l & 15][r = l >> 4], B[r = l >> 4][pixel = l & 15]; D register q is
 // y[co = 4 (l >> 4) + q][pixel = l & 15].
+//
+// Stage depth SR and residency OCC (workgroups per CU) go together: <TA, 32, 2> holds 2 x 32 reduction rows in LDS (56 / 72 KB: two
+// workgroups per CU), <TA, 16, 3> 2 x 16 rows (28 / 36 KB, 49.5 KB with the [96][132] wide-store staging tile: three per CU within
+// 168 VGPRs).  A stage of 16 rows is ONE block of the reduction order, each wave fetches 4 rows of it.  The depth only moves the
+// barriers: the products enter every accumulator in the same order, so the two forms agree bit for bit (conv16_lds_bytes,
+// conv16_stage_depth; vl_conv_set_stage_depth forces one).
+#ifndef VL_CONV16_SPREAD
+#define VL_CONV16_SPREAD 0   // measurements only: 1 spreads the 16-row form's fetches over all of a stage's MFMAs (one per three, TA = 3: two)
+#endif
 
-template <int TA>   // channel tiles of 16 per workgroup: 3 (48 channels: conv2 dgrad) or 6 (96: the 192-channel layers)
-__global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe, const ConvRowClasses rc,
-                                                           int tiles_i, int wide) {
-    constexpr int BM = 16 * TA, BN = 128, SR = 32;
+template <int TA, int SR, int OCC>   // TA: channel tiles of 16 per workgroup: 3 (48 channels: conv2 dgrad) or 6 (96: the 192-channel layers)
+__global__ __launch_bounds__(NT, OCC) void conv_dma16_kernel(const ConvDmaParams pa, const ConvGeom g, const EpiConvNCHW::Params pe, const ConvRowClasses rc,
+                                                             int tiles_i, int wide) {
+    constexpr int BM = 16 * TA, BN = 128;
+    static_assert((SR == 32 && OCC == 2) || (SR == 16 && OCC == 3), "stage depth and residency");
     constexpr int NA = (BM + 63) / 64;                                // 64-lane fetches per weight row
     constexpr int SA = NA * 64 + 16, SB = 144;                        // LDS row strides (floats), both = 16 mod 32
     constexpr int ABUF = SR * SA, BUF = SR * (SA + SB);
     constexpr int RW = SR / 4, FPR = NA + 2, NF = RW * FPR, NSTEP = SR / 4;   // rows per wave, fetches per row / per wave, k4-steps
     constexpr int NM = 2 * TA;                                        // MFMAs per k4-step
+    // fetch f rides in the shadow of the stage's MFMA number f * FSP.  The table of the stage after next replaces the current one
+    // after k4-step LT, which is not before the step of the last fetch (that fetch still reads the current table), and is pinned
+    // at the stage's last step: SR = 32 loads after step 5 of 8, SR = 16 after step 1 of 4 (FSP = 3: after the last step)
+    constexpr int FSP = (SR == 16 && VL_CONV16_SPREAD) ? NM * NSTEP / NF : 1;
+    constexpr int FLAST = (NF - 1) * FSP / NM;                        // k4-step of the last fetch
+    constexpr int LT = FLAST > NSTEP - 3 ? FLAST : NSTEP - 3;
+    static_assert(SR % KBLK == 0 && KBLK % RW == 0, "a wave's rows lie within one 16-row block");
+    static_assert((NF - 1) * FSP < NM * NSTEP && LT <= NSTEP - 1 && FLAST <= LT, "fetches must end before the table is replaced");
     extern __shared__ __attribute__((aligned(16))) float ldsc[];
     const ConvTile tl = conv_pick_tile(rc, g, pa);
     const int ti_blk = tl.bid % tiles_i, tj_blk = tl.bid / tiles_i;   // tj_blk: pixel tile within the class segment
@@ -2405,8 +2438,8 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
                 for (int m = 0; m < NM; ++m) {
                     const int a = m >> 1, b = m & 1;
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[c][a], bf[c][b], acc[a][b], 0, 0, 0);
-                    const int f = t * NM + m;
-                    if (f < NF) {
+                    const int i = t * NM + m, f = i / FSP;
+                    if (i % FSP == 0 && f < NF) {
                         if (fast) dma_fast(cur ^ 1, f, st_next);
                         else dma(cur ^ 1, f, st_next);
                         __builtin_amdgcn_sched_barrier(0);
@@ -2415,12 +2448,11 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
             } else {                                               // rows past K: no products; the (zero) fetches of the stage after the last keep the counters in step
 #pragma unroll
                 for (int m = 0; m < NM; ++m) {
-                    const int f = t * NM + m;
-                    if (f < NF) dma(cur ^ 1, f, st_next);
+                    const int i = t * NM + m, f = i / FSP;
+                    if (i % FSP == 0 && f < NF) dma(cur ^ 1, f, st_next);
                 }
             }
-            static_assert(NF <= NM * (NSTEP - 3), "fetches must end before the table is replaced");
-            if (t == NSTEP - 3) {
+            if (t == LT) {
                 load_table(st_next + 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -2528,21 +2560,38 @@ __global__ __launch_bounds__(NT, 2) void conv_dma16_kernel(const ConvDmaParams p
 }
 
 
-template <int BM>   // 128: conv_dma_kernel (32x32 MFMA tiles); 48 / 96: conv_dma16_kernel (16x16 tiles)
-static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
-                           int Cout_total, const ConvOut& o, hipStream_t s, const vl_conv_rowcls* rcd = nullptr) {
-    constexpr int BN = 128, SR = 32;
+// LDS of a conv_dma16_kernel launch: the two stage buffers of SR rows x (weight row of roundup(BM, 64) + 16 floats | 128 + 16 pixels),
+// or the [BM][132] staging tile of the wide-store epilogue, whichever is larger.  A CU has 163,840 B:
+//   BM  SR   stage buffers   staging tile   allocation   workgroups that fit
+//   48  32        57,344         25,344        57,344        2
+//   48  16        28,672         25,344        28,672        5 (the kernel is built for 3)
+//   96  32        73,728         50,688        73,728        2
+//   96  16        36,864         50,688        50,688        3
+// (tests/test_conv_stage_depth_gpu.py holds this table)
+constexpr size_t conv16_stage_bytes(int BM, int SR) { return (size_t)2 * SR * ((BM + 63) / 64 * 64 + 16 + 144) * sizeof(float); }
+constexpr size_t conv16_staging_bytes(int BM) { return (size_t)BM * (128 + 4) * sizeof(float); }
+constexpr size_t conv16_lds_bytes(int BM, int SR) {
+    return conv16_stage_bytes(BM, SR) > conv16_staging_bytes(BM) ? conv16_stage_bytes(BM, SR) : conv16_staging_bytes(BM);
+}
+static_assert(3 * conv16_lds_bytes(96, 16) <= 163840 && 3 * conv16_lds_bytes(48, 16) <= 163840, "three 16-row workgroups per CU");
+static_assert(2 * conv16_lds_bytes(96, 32) <= 163840 && 2 * conv16_lds_bytes(48, 32) <= 163840, "two 32-row workgroups per CU");
+
+template <int BM, int SR>   // 128: conv_dma_kernel (32x32 MFMA tiles); 48 / 96: conv_dma16_kernel (16x16 tiles) at stage depth SR
+static int launch_conv_dma_sr(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
+                              int Cout_total, const ConvOut& o, hipStream_t s, const vl_conv_rowcls* rcd) {
+    constexpr int BN = 128;
+    static_assert(BM != 128 || SR == 32, "the 32x32 kernel launches with 32-row stages");
     // 128-wide: 64 KB of stage buffers, 66 KB with the wide-store staging tile [128][132] (two workgroups per CU either way)
-    constexpr size_t lds = BM == 128 ? (size_t)BM * (BN + 4) * sizeof(float)
-                                     : (size_t)2 * SR * ((BM + 63) / 64 * 64 + 16 + 144) * sizeof(float);   // 56 / 72 KB
+    constexpr size_t lds = BM == 128 ? (size_t)BM * (BN + 4) * sizeof(float) : conv16_lds_bytes(BM, SR);
     static_assert(BM != 128 || (size_t)2 * SR * (BM + BN) * sizeof(float) <= (size_t)BM * (BN + 4) * sizeof(float), "stage buffers fit");
+    static_assert(BM == 128 || conv16_stage_bytes(BM, SR) <= lds, "stage buffers fit");
     ConvDmaParams pa{w, w_ld, (int64_t)w_grp_stride, (int64_t)g.K * w_ld * 4, row_tab, ceil_div(g.K, KBLK)};
     const EpiConvNCHW::Params pe = make_epi(g, Cog, Cout_total, o);
-    static bool attr_set = false;
+    static bool attr_set = false;                                     // one per instantiation (BM, SR): each form has its own size
     if (!attr_set) {
         const void* kern;
         if constexpr (BM == 128) kern = reinterpret_cast<const void*>(conv_dma_kernel<SR>);
-        else kern = reinterpret_cast<const void*>(conv_dma16_kernel<BM / 16>);
+        else kern = reinterpret_cast<const void*>(conv_dma16_kernel<BM / 16, SR, SR == 16 ? 3 : 2>);
         VL_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
@@ -2569,10 +2618,37 @@ static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int 
     if constexpr (BM == 128) {
         hipLaunchKernelGGL(conv_dma_kernel<SR>, grid, dim3(NT), lds, s, pa, g, pe, rc, tiles_i, wide);
     } else {
-        hipLaunchKernelGGL((conv_dma16_kernel<BM / 16>), grid, dim3(NT), lds, s, pa, g, pe, rc, tiles_i, wide);
+        hipLaunchKernelGGL((conv_dma16_kernel<BM / 16, SR, SR == 16 ? 3 : 2>), grid, dim3(NT), lds, s, pa, g, pe, rc, tiles_i, wide);
     }
     VL_LAUNCH_CHECK();
+    g_conv_last_launch = BM * 100 + SR;
     return 0;
+}
+
+// Stage depth of a conv_dma16_kernel launch: 16 (three workgroups per CU) or 32 (two).  vl_conv_set_stage_depth forces one.
+// Measured (profiles/conv_stage_depth.txt: both depths alternately in one process, 5 pairs, ms as min..max, depth 32 | depth 16):
+//                      1024 frames (many-frames branch)      128 frames (few-frames branch, one rank's shard)
+//   conv1 fwd   96     2.004..2.027 | 1.894..1.895           0.2565..0.2638 | 0.2412..0.2421     23 blocks of 16 rows per tile
+//   conv4 fwd   96     1.698..1.735 | 1.643..1.645           0.2497..0.2577 | 0.2395..0.2399     72..108 (row classes)
+//   conv4 dgrad 96     1.746..1.792 | 1.677..1.679           0.2535..0.2613 | 0.2443..0.2446     72..108, masked epilogue
+//   conv5 dgrad 96     1.230..1.273 | 1.170..1.175           0.1785..0.1850 | 0.1696..0.1698     48..72, masked epilogue
+//   conv2 dgrad 48     3.423..3.458 | 3.314..3.324           0.5082..0.5156 | 0.4977..0.4978     120..200
+// Every launch's depth-16 range lies wholly below its depth-32 range, for both tile heights, both epilogues, tile lives from 23 to
+// 200 blocks and both dispatcher branches; the gain shrinks with the tile's life (6.5 % at 23 blocks, 3 % at 200), as a cost paid
+// once per tile would.  Alone, nothing measured favours 32 rows.  Inside the step the branches part: the 64-clip step (every launch
+// in the many-frames branch) went 33.67..33.69 -> 33.21..33.28 ms, the 8-clip step (every launch in the few-frames branch, each
+// 0.17..0.5 ms long beside the weight gradients of the second stream) 5.093..5.106 -> 5.115..5.144 ms with 16 rows everywhere.
+// So the rule is the branch: 16 rows for a many-frames launch, 32 rows, as before, for a few-frames one.
+static int conv16_stage_depth(bool few) { return g_conv_stage_depth ? g_conv_stage_depth : few ? 32 : 16; }
+
+template <int BM>
+static int launch_conv_dma(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
+                           int Cout_total, const ConvOut& o, hipStream_t s, const vl_conv_rowcls* rcd = nullptr, bool few = false) {
+    if constexpr (BM != 128) {
+        if (conv16_stage_depth(few) == 16)
+            return launch_conv_dma_sr<BM, 16>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
+    }
+    return launch_conv_dma_sr<BM, 32>(g, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, o, s, rcd);
 }
 
 template <int BM>
@@ -2619,6 +2695,7 @@ static int launch_conv_ring(const ConvGeom& g, const float* w, int64_t w_ld, int
 template <bool PADDED>
 static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_grp_stride, const int* row_tab, int Cog,
                          int Cout_total, const ConvOut& o, uint32_t* wsplit, hipStream_t s, const vl_conv_rowcls* rcd) {
+    g_conv_last_launch = 0;
     // output-channel tile: 128 when it divides well, else 96 (conv1: 96, conv4: 192) or 64 (conv2 dgrad: 48)
     const int w128 = ceil_div(Cog, 128) * 128, w96 = ceil_div(Cog, 96) * 96, w64 = ceil_div(Cog, 64) * 64;
     // split products: the ring kernel (128-channel tiles; its 16-byte im2col fetches need unit column stride in memory)
@@ -2631,7 +2708,10 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
     // Few frames (one rank's shard of a multi-GPU job): the tile with the fewest padded rows can leave CUs idle or half of them
     // with two workgroups and the rest with one.  Per-CU load of a tile width = ceil(workgroups / CUs) x its rows; take the
     // LDS-DMA kernel (128 / 96 / 48 rows) with the smallest load, ties to the wider tile.  With many frames the widths agree
-    // with the padded-row rule below (loads differ by the padding only), which then decides alone.
+    // with the padded-row rule below (loads differ by the padding only), which then decides alone.  (The load counts the rows of matrix
+    // work a CU is handed, which its resident workgroups share -- two of the 128-row kernel, three of the 96 / 48-row kernel's 16-row
+    // form: the slots change how well a CU hides a tile's prologue and epilogue, not this sum, so the pick is the same for both depths.
+    // This branch launches the 32-row form: conv16_stage_depth.)
     const int64_t px = ceil_div(g.M, 128), cus = vl_device_cus(), ngrp = Cout_total / Cog;
     const bool few = px * ceil_div(Cog, 128) * ngrp < 8 * cus;        // under 8 workgroups per CU at the widest tile: quantisation matters
     // (the few-frames branch keeps the flat pixel order: its width pick and tail split count flat tiles)
@@ -2646,9 +2726,9 @@ static int dispatch_conv(const ConvGeom& g, const float* w, int64_t w_ld, int w_
             return b;
         };
         auto run = [&](int wi, const ConvGeom& gg, const ConvOut& oo) {
-            if (wi == 0) return launch_conv_dma<128>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s);
-            if (wi == 1) return launch_conv_dma<96>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s);
-            return launch_conv_dma<48>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s);
+            if (wi == 0) return launch_conv_dma<128>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s, nullptr, true);
+            if (wi == 1) return launch_conv_dma<96>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s, nullptr, true);
+            return launch_conv_dma<48>(gg, w, w_ld, w_grp_stride, row_tab, Cog, Cout_total, oo, s, nullptr, true);
         };
         int64_t best_load = 0;
         const int best = pick(px, best_load);

@@ -1261,6 +1261,18 @@ def conv_set_row_classes(on=True):
     _ffi.call("vl_conv_set_row_classes", int(bool(on)))
 
 
+def conv_set_stage_depth(rows=0):
+    """Test hook: 16 or 32 forces the reduction-stage depth of the 16x16-MFMA LDS-DMA conv kernel (three or two workgroups per CU),
+    0 returns the choice to the dispatcher; results are bitwise the same."""
+    _ffi.call("vl_conv_set_stage_depth", int(rows))
+
+
+def conv_last_launch():
+    """Kernel form of the latest fp32 conv forward / dgrad call: tile height * 100 + stage depth for an LDS-DMA launch (4816, 4832,
+    9616, 9632, 12832), 0 for any other kernel."""
+    return int(_ffi.lib().vl_conv_last_launch())
+
+
 def relu_grad(d, y, count=None):
     """d = y > 0 ? d : 0 in place over the first `count` elements."""
     _f32(d, y); _dense(d, y)
