@@ -458,6 +458,22 @@ int vl_mixup_pairs(void* x, int dtype, int clips, int64_t clip_elems, float lam,
 int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
                         float grad_scale, int rows_per_clip, float smoothing, int top_k, float lam, const float* lam_dev,
                         vl_stream_t stream);
+/* Class weights and the focal loss (Lin et al. 2017) on top of both, one launch.  With p = softmax(z), y' the label row
+ * after the mixup blend and then the smoothing exactly as above, w = class_weights (float[classes] on the device, read when the
+ * kernel runs; NULL = all ones) and m_c = (1 - p_c)^gamma (gamma == 0: m_c = 1 exactly, no pow):
+ *     loss = sum_c w_c y'_c m_c (-log p_c)
+ *     a_c  = w_c y'_c (m_c - gamma (1 - p_c)^(gamma - 1) p_c log p_c),  A = sum_c a_c,  dlogits_j = (p_j A - a_j) * grad_scale
+ * with log p_c = z_c - lse, 1 - p_c = -expm1(log p_c), and the second term of a_c 0 where 1 - p_c == 0 (its limit: a saturated row
+ * stays finite at every gamma).  The weights sit inside the class sum (PyTorch's rule for probability targets), so a smoothed or
+ * mixed row is weighted by the classes it carries.  The normaliser stays the row count: grad_scale is the caller's 1 / live rows
+ * (Keras' class_weight, tf.losses' SUM_OVER_BATCH_SIZE), NOT 1 / sum of the rows' weights as in PyTorch's hard-label mean.
+ * seq_len / T as in vl_softmax_xent_ls; rows_per_clip, lam, lam_dev as in vl_softmax_xent_mix (rows_per_clip 1, lam 1 and lam_dev
+ * NULL: no partner row is read); lengths together with rows_per_clip > 1 or a lambda are refused.  gamma must be finite and >= 0.
+ * Hits and top-k hits are unweighted, against the row's own labels.  stats float[3], rows float[3*batch] or NULL, both launch forms,
+ * no atomics: as there.  All weights 1 and gamma 0 computes what _ls / _mix compute (not bit for bit: p A and p round differently). */
+int vl_softmax_xent_wf(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
+                       float grad_scale, const int32_t* seq_len, int T, int rows_per_clip, float smoothing, int top_k, float lam,
+                       const float* lam_dev, const float* class_weights, float gamma, vl_stream_t stream);
 
 /* ---- CutMix / VideoMix (Yun et al. 2019, 2020): one box swapped between clip i and clip clips - 1 - i ---------------
  * The box is {t0, t1, y0, y1, x0, x1}, half-open, in frames of the clip and pixels of the out_h x out_w frame conv1 sees; all channels

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """The bytes the loss launches write, as one SHA-256 per case: for comparing two builds of the library.
 
-Every entry point (vl_softmax_xent, vl_softmax_xent_len, vl_softmax_xent_ls, vl_softmax_xent_mix) is launched over a fixed list of
+Every entry point (vl_softmax_xent, vl_softmax_xent_len, vl_softmax_xent_ls, vl_softmax_xent_mix, and vl_softmax_xent_wf where the
+library has it) is launched over a fixed list of
 cases: the shapes of tests/test_label_smoothing_gpu.py and the two that tools/bench_label_smoothing.py times, both launch forms,
 lengths off and on, smoothing {0, 0.1}, top_k {0, 5}, rows_per_clip {1, 2} where it divides the batch, lam {1, 0.5, 0.8} as a host
 argument and as a device word.  The inputs are those of case() of that test file; dlogits and the rows workspace hold NaN beforehand
 and stats holds 1, 2, 3 (a sum that is left alone shows).  A case's digest is over the raw bytes of dlogits, stats and rows, in that order.
+The vl_softmax_xent_wf cases (weights off / on, gamma {0, 2}, smoothing 0.1, top_k 5, lengths, a lambda) come after the last case of the last shape,
+so the file of a build from before that entry point is the head of this one's, name for name.
 
 The launches are deterministic, so two builds that compute the same thing write the same file:
 
@@ -74,6 +77,19 @@ def cases(b, c):
                                ops.softmax_xent_mix(z, y, dz, st, 1.0 / b, ws, rpc, eps, k, lam))
 
 
+def wf_cases(b, c):
+    """cases() for vl_softmax_xent_wf"""
+    lens, T = lengths(b, c)
+    sl = torch.from_numpy(lens).to(DEV)
+    w = torch.from_numpy(np.random.default_rng(b * c + 2).uniform(0.25, 4.0, c).astype(np.float32)).to(DEV)
+    for weights in (False, True):
+        for gamma in (0.0, 2.0):
+            for name, kw in (("plain", {}), ("len", dict(seq_len=sl, T=T)), ("lam 0.8", dict(lam=0.8))):
+                yield ("wf weights %d gamma %g %s" % (weights, gamma, name),
+                       lambda z, y, dz, st, ws, weights=weights, gamma=gamma, kw=kw:
+                       ops.softmax_xent_wf(z, y, dz, st, 1.0 / b, ws, 0.1, 5, w if weights else None, gamma, **kw))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="the digests as JSON (default: standard output)")
@@ -81,10 +97,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("loss_bits.py needs a HIP device; there is no CPU fallback")
     digests = {}
-    for b, c in SHAPES:
+    for b, c, cases_of in [s + (cases,) for s in SHAPES] + [s + (wf_cases,) for s in SHAPES]:
         z, onehot = case(b, c)
         zd, yd = torch.from_numpy(z).to(DEV), torch.from_numpy(np.ascontiguousarray(onehot)).to(DEV, torch.int32)
-        for name, launch in cases(b, c):
+        for name, launch in cases_of(b, c):
             for form in ("one-workgroup", "rows"):
                 dz = torch.full((b, c), NAN, device=DEV)
                 stats = torch.tensor([1.0, 2.0, 3.0], device=DEV)

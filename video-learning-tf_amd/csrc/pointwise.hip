@@ -1785,8 +1785,18 @@ extern "C" int vl_dropout_bwd(const float* dy, const uint8_t* mask, float* dx, i
 //        label's rank among the logits (top_k == 0: no pass), a third workspace column and stats[2].
 //   MIX  mixup / CutMix labels (vl_softmax_xent_mix; with LS): y' = lam y + (1 - lam) yp ahead of the smoothing, yp the
 //        partner's label row.  At lam == 1 y' is y exactly (labels are small non-negative integers): the bits of LS alone.
+//   WF   class weights + focal loss (vl_softmax_xent_wf; with LS, with or without MIX): with p = softmax(z), w the class
+//        weights (NULL: ones) and m_c = (1 - p_c)^gamma,
+//            loss = sum_c w_c y'_c m_c (-log p_c)
+//            a_c  = w_c y'_c (m_c - gamma (1 - p_c)^(gamma - 1) p_c log p_c),   A = sum_c a_c,   dz_j = (p_j A - a_j) gscale
+//        log p_c = z_c - lse and 1 - p_c = -expm1f(log p_c); the second term of a_c is 0 where 1 - p_c == 0 (its limit), so a saturated
+//        row stays finite at every gamma.  The weights sit inside the class sum; the normaliser stays the caller's row count (gscale),
+//        not sum w.  gamma == 0 (uniform over the launch): m = 1 exactly, no pow / expm1; a_c = w_c y'_c does not depend on z, so A is
+//        summed beside the exponentials and reduced with them, and dz is written once.  gamma > 0: A needs lse first, so a_c is parked
+//        in dz and a last pass turns it into dz (each lane rereads only what it wrote).  An element with w_c y'_c == 0 skips the pow.
 // The switches are template parameters and not launch arguments: the plain launch holds neither the smoothing arithmetic nor a second
-// label load, and writes two workspace columns and stats[0..1] only (an ls launch costs 1.12 x a plain one at 1344 x 1000).
+// label load, and writes two workspace columns and stats[0..1] only (an ls launch costs 1.12 x a plain one at 1344 x 1000); no launch
+// without WF holds a weight load, a pow or the reduction of A.
 
 // One element of a mixup blend, used by the label loop below and by every loop of both dtypes of vl_mixup_pairs: the rounding steps are
 // spelled out (1 - lam by the caller, two products, one sum), so an element's bits do not depend on which loop reached it.
@@ -1798,10 +1808,10 @@ __device__ __forceinline__ float mix_elem(float a, float b, float lam, float oml
 // yp (MIX only): the partner's label row (nullptr: the row is its own partner and reads no other label row than its own).  The hits
 // are counted against the row's OWN labels.  hitk (LS only): rank = #{c : z_c > z_t} + #{c < t : z_c == z_t}, t the first arg-max of
 // the label row; a top-k hit iff rank < k.
-template <bool LS, bool MIX>
+template <bool LS, bool MIX, bool WF>
 __device__ __forceinline__ void xent_row(const float* __restrict__ z, const int32_t* __restrict__ y, const int32_t* __restrict__ yp,
-                                         float* __restrict__ dz, int C, float gscale, float eps, int top_k, float lam, int lane,
-                                         float& loss, float& hit, float& hitk) {
+                                         float* __restrict__ dz, int C, float gscale, float eps, int top_k, float lam,
+                                         const float* __restrict__ cw, float gamma, int lane, float& loss, float& hit, float& hitk) {
     float mx = -INFINITY;
     int am = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
@@ -1816,9 +1826,24 @@ __device__ __forceinline__ void xent_row(const float* __restrict__ z, const int3
     int cand = (mx == gmx) ? am : 0x7fffffff;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    float se = 0.f;
-    for (int c = lane; c < C; c += 64) se += expf(z[c] - gmx);
+    const bool focal = WF && gamma != 0.f;            // (uniform over the launch)
+    float se = 0.f, A = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        se += expf(z[c] - gmx);
+        if constexpr (WF) {
+            if (!focal && dz) {                       // A = sum_c w_c y'_c: the same y' as the label loop below forms, from the same words
+                const int32_t* yq = yp ? yp : y;
+                const float lam_r = yp ? lam : 1.0f;
+                float ys = (float)y[c];
+                if constexpr (MIX) ys = mix_elem(ys, (float)yq[c], lam_r, 1.0f - lam_r);
+                if constexpr (LS) ys = ys * (1.0f - eps) + eps / (float)C;
+                A += (cw ? cw[c] : 1.0f) * ys;
+            }
+        }
+    }
     se = wave_sum(se);
+    if constexpr (WF)
+        if (!focal && dz) A = wave_sum(A);
     const float lse = logf(se) + gmx;
     const float on = 1.0f - eps, off = eps / (float)C;
     float l = 0.f;
@@ -1833,14 +1858,37 @@ __device__ __forceinline__ void xent_row(const float* __restrict__ z, const int3
         float ys = (float)yv;
         if constexpr (MIX) ys = mix_elem(ys, (float)yq[c], lam_r, oml);
         if constexpr (LS) ys = ys * on + off;
-        l += ys * (lse - z[c]);
+        if constexpr (!WF) l += ys * (lse - z[c]);
         if (yv > ymax) {
             ymax = yv;
             yarg = c;
         }
-        if (dz) dz[c] = (expf(z[c] - lse) - ys) * gscale;
+        if constexpr (!WF) {
+            if (dz) dz[c] = (expf(z[c] - lse) - ys) * gscale;
+        } else {
+            const float wy = (cw ? cw[c] : 1.0f) * ys, lp = z[c] - lse;
+            if (!focal) {
+                l += wy * (lse - z[c]);
+                if (dz) dz[c] = (expf(lp) * A - wy) * gscale;
+            } else {
+                float a = 0.f;
+                if (wy != 0.f) {
+                    const float q = fmaxf(-expm1f(lp), 0.f), m = powf(q, gamma);        // q = 1 - p, m = q^gamma
+                    l += wy * m * (lse - z[c]);
+                    a = wy * (m - (q > 0.f ? gamma * (m / q) * expf(lp) * lp : 0.f));
+                }
+                A += a;
+                if (dz) dz[c] = a;                    // parked until A is known
+            }
+        }
     }
     l = wave_sum(l);
+    if constexpr (WF) {
+        if (focal && dz) {
+            A = wave_sum(A);
+            for (int c = lane; c < C; c += 64) dz[c] = (expf(z[c] - lse) * A - dz[c]) * gscale;
+        }
+    }
     int gy = ymax;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) gy = max(gy, __shfl_xor(gy, o, 64));
@@ -1884,12 +1932,14 @@ __device__ __forceinline__ const int32_t* mix_partner_labels(const int32_t* __re
 }
 
 // Both kernels take the same arguments but for stats / rows.  seq_len, T: !MIX only; rpc, lam_arg, lam_dev: MIX only (lam is read from
-// lam_dev, when given, as the kernel runs: a captured step replays with the lambda the host wrote before the replay); eps, top_k: LS.
+// lam_dev, when given, as the kernel runs: a captured step replays with the lambda the host wrote before the replay); eps, top_k: LS;
+// cw (nullable, float[C], read as the kernel runs), gamma: WF only -- last, so the arguments of the launches without WF stay where they were.
 // Without a workspace: wave w walks rows w, w + 4, ...; stats += ((w0 + w1) + w2) + w3 per column.
-template <bool LS, bool MIX>
+template <bool LS, bool MIX, bool WF>
 __global__ void xent_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
                             float* __restrict__ stats, int batch, int C, float gscale, const int32_t* __restrict__ seq_len, int T, int rpc,
-                            float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
+                            float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev, const float* __restrict__ cw,
+                            float gamma) {
     __shared__ float sl[4], sc[4], sk[4];
     const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1901,8 +1951,8 @@ __global__ void xent_kernel(const float* __restrict__ logits, const int32_t* __r
             xent_zero_row(dz, C, lane);
             continue;
         }
-        xent_row<LS, MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
-                          dz, C, gscale, eps, top_k, lam, lane, l, h, hk);
+        xent_row<LS, MIX, WF>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
+                          dz, C, gscale, eps, top_k, lam, cw, gamma, lane, l, h, hk);
         loss_acc += l;
         corr_acc += h;
         topk_acc += hk;
@@ -1922,10 +1972,11 @@ __global__ void xent_kernel(const float* __restrict__ logits, const int32_t* __r
 }
 
 // With a workspace: row b's loss, hit and (LS) top-k hit to rows[b], rows[batch + b], rows[2 batch + b]; zeros for a dead row.
-template <bool LS, bool MIX>
+template <bool LS, bool MIX, bool WF>
 __global__ void xent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
                                  float* __restrict__ rows, int batch, int C, float gscale, const int32_t* __restrict__ seq_len, int T,
-                                 int rpc, float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev) {
+                                 int rpc, float eps, int top_k, float lam_arg, const float* __restrict__ lam_dev,
+                                 const float* __restrict__ cw, float gamma) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= batch) return;
     const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
@@ -1934,8 +1985,8 @@ __global__ void xent_rows_kernel(const float* __restrict__ logits, const int32_t
     if (!MIX && xent_row_dead(seq_len, T, b))
         xent_zero_row(dz, C, lane);
     else
-        xent_row<LS, MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
-                          dz, C, gscale, eps, top_k, lam, lane, l, h, hk);
+        xent_row<LS, MIX, WF>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr,
+                          dz, C, gscale, eps, top_k, lam, cw, gamma, lane, l, h, hk);
     if (lane == 0) {
         rows[b] = l;
         rows[batch + b] = h;
@@ -1988,20 +2039,23 @@ struct xent_args {
     int top_k = 0;
     float lam = 1.f;
     const float* lam_dev = nullptr;
+    const float* class_weights = nullptr;
+    float gamma = 0.f;
 };
 
-template <bool LS, bool MIX>
+template <bool LS, bool MIX, bool WF = false>
 static int xent_launch(xent_args a, vl_stream_t stream) {
     if (!a.seq_len) a.T = 1;
     if (!a.rows) {
-        hipLaunchKernelGGL((xent_kernel<LS, MIX>), dim3(1), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels, a.dlogits, a.stats,
-                           a.batch, a.classes, a.grad_scale, a.seq_len, a.T, a.rows_per_clip, a.smoothing, a.top_k, a.lam, a.lam_dev);
+        hipLaunchKernelGGL((xent_kernel<LS, MIX, WF>), dim3(1), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels, a.dlogits, a.stats,
+                           a.batch, a.classes, a.grad_scale, a.seq_len, a.T, a.rows_per_clip, a.smoothing, a.top_k, a.lam, a.lam_dev,
+                           a.class_weights, a.gamma);
         VL_LAUNCH_CHECK();
         return 0;
     }
-    hipLaunchKernelGGL((xent_rows_kernel<LS, MIX>), dim3((a.batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels,
+    hipLaunchKernelGGL((xent_rows_kernel<LS, MIX, WF>), dim3((a.batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, a.logits, a.labels,
                        a.dlogits, a.rows, a.batch, a.classes, a.grad_scale, a.seq_len, a.T, a.rows_per_clip, a.smoothing, a.top_k, a.lam,
-                       a.lam_dev);
+                       a.lam_dev, a.class_weights, a.gamma);
     VL_LAUNCH_CHECK();
     hipLaunchKernelGGL((xent_sum_kernel<LS>), dim3(1), dim3(256), 0, (hipStream_t)stream, a.rows, a.stats, a.batch, a.top_k);
     VL_LAUNCH_CHECK();
@@ -2043,6 +2097,27 @@ extern "C" int vl_softmax_xent_mix(const float* logits, const int32_t* labels, f
     VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_softmax_xent_mix: lam must lie in [0, 1], got %g", (double)lam);
     return xent_launch<true, true>(
         {logits, labels, dlogits, stats, rows, batch, classes, grad_scale, nullptr, 1, rows_per_clip, smoothing, top_k, lam, lam_dev}, stream);
+}
+
+// Class weights and the focal loss on top of _ls / _mix.  rows_per_clip 1, lam 1 and no lam_dev: no partner row is read
+// and seq_len may mask rows; otherwise the labels are mixed as in _mix, which takes no lengths.
+extern "C" int vl_softmax_xent_wf(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                                  int classes, float grad_scale, const int32_t* seq_len, int T, int rows_per_clip, float smoothing,
+                                  int top_k, float lam, const float* lam_dev, const float* class_weights, float gamma,
+                                  vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_softmax_xent_wf: bad argument");
+    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_softmax_xent_wf: batch (%d rows) is not whole sequences of T = %d", batch, T);
+    VL_CHECK(rows_per_clip > 0 && batch % rows_per_clip == 0, "vl_softmax_xent_wf: batch (%d rows) is not whole clips of %d rows", batch,
+             rows_per_clip);
+    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_softmax_xent_wf: smoothing must lie in [0, 1), got %g", (double)smoothing);
+    VL_CHECK(top_k >= 0, "vl_softmax_xent_wf: top_k must be >= 0, got %d", top_k);
+    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_softmax_xent_wf: lam must lie in [0, 1], got %g", (double)lam);
+    VL_CHECK(gamma >= 0.f && gamma <= 3.0e38f, "vl_softmax_xent_wf: gamma must be finite and >= 0, got %g", (double)gamma);
+    const bool mix = rows_per_clip > 1 || lam_dev || lam != 1.f;
+    VL_CHECK(!(mix && seq_len), "vl_softmax_xent_wf: seq_len cannot be combined with mixed labels (rows_per_clip > 1 or a lambda)");
+    const xent_args a = {logits, labels, dlogits, stats, rows, batch, classes, grad_scale, seq_len, T, rows_per_clip, smoothing, top_k, lam,
+                         lam_dev, class_weights, gamma};
+    return mix ? xent_launch<true, true, true>(a, stream) : xent_launch<true, false, true>(a, stream);
 }
 
 // ---- mixup (Zhang et al. 2018): the paired in-place blend of the clips (the loss on the mixed labels: xent_row<., MIX>) --

@@ -15,7 +15,7 @@ data-parallel all-reduce of the first (large: fc6 = 85 % of bytes) bucket overla
 import collections
 import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import contextlib
 import gc
@@ -80,6 +80,8 @@ class NetConfig:
     cutmix_seed: int = 0                        # train.cutmix_seed: the key of the box draws (cutmix_box)
     cutmix_mode: Optional[str] = None           # train.cutmix_mode: spatial | temporal | cuboid; None = spatial when cutmix is on
     cutmix_prob: Optional[float] = None         # train.cutmix_prob: with mixup on too, the chance that a batch is cut; None = 0.5
+    class_weights: Optional[Sequence[float]] = None   # train.class_weights: num_classes weights inside the loss's class sum; None = ones
+    focal_gamma: float = 0.0                    # train.focal_gamma: the focal loss's focusing parameter (Lin et al. 2017), >= 0; 0 = off
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -326,6 +328,48 @@ def check_label_smoothing(label_smoothing):
     if not (0.0 <= s < 1.0):                      # (NaN fails both, inf the second)
         raise VltfError("label_smoothing must be a number in [0, 1) (0 / None = off), got %r" % (label_smoothing,))
     return s
+
+
+def check_class_weights(class_weights, num_classes):
+    """The class weights of the loss as a float32 array of num_classes entries, or None (off: every class weighs 1).  Refused: anything
+    but a sequence of numbers (strings and booleans included), a length other than num_classes, a negative, NaN or infinite entry, and
+    weights that are all zero (no row would carry a loss)."""
+    if class_weights is None:
+        return None
+    msg = "class_weights must be %d finite numbers >= 0, not all zero (None = off), got %%s" % num_classes
+    if isinstance(class_weights, (str, bytes)) or np.isscalar(class_weights):
+        raise VltfError(msg % repr(class_weights))
+    try:
+        vals = list(class_weights)
+    except TypeError:
+        raise VltfError(msg % repr(class_weights))
+    if len(vals) != num_classes:
+        raise VltfError(msg % ("%d entries" % len(vals)))
+    for v in vals:
+        if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise VltfError(msg % ("the entry %r" % (v,)))
+        if not (math.isfinite(float(v)) and float(v) >= 0.0):
+            raise VltfError(msg % ("the entry %r" % (v,)))
+    with np.errstate(over="ignore"):
+        w = np.asarray(vals, np.float64).astype(np.float32)
+    if not np.isfinite(w).all():                  # (a number beyond float32's range)
+        raise VltfError(msg % "an entry beyond float32")
+    if not (w > 0).any():
+        raise VltfError(msg % "all zeros")
+    return w
+
+
+def check_focal_gamma(focal_gamma):
+    """The focusing parameter of the focal loss as a float, None read as 0 (off).  Accepted: finite and >= 0.  Refused: negative, NaN,
+    infinite, not a number (booleans included)."""
+    if focal_gamma is None:
+        return 0.0
+    if isinstance(focal_gamma, (bool, np.bool_, str, bytes)) or not isinstance(focal_gamma, (int, float, np.integer, np.floating)):
+        raise VltfError("focal_gamma must be a finite number >= 0 (0 / None = off), got %r" % (focal_gamma,))
+    g = float(focal_gamma)
+    if not (math.isfinite(g) and 0.0 <= g <= 3.0e38):
+        raise VltfError("focal_gamma must be a finite number >= 0 (0 / None = off), got %r" % (focal_gamma,))
+    return g
 
 
 def check_top_k(top_k):
@@ -1078,7 +1122,7 @@ class LRCNEngine:
         self.rows_out = self.logits.shape[0]
         if training:
             self.dlogits = buf(*self.logits.shape)
-        self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out)
+        self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out, cfg.class_weights, cfg.focal_gamma)
         self._mix_setup(cfg.mixup_alpha, cfg.mixup_seed, self.rows_out)
         self.ss = torch.zeros(1, device=dev)
         # L2 weight decay: ops.l2_regularize takes the norm's place in _finish_step and returns {sum g'^2, regulariser}; the update calls
@@ -1270,20 +1314,30 @@ class LRCNEngine:
         return None if self._stats_last is None else self._stats_last["tensor_stats"]
 
     # ---- label smoothing / top-k accuracy (label_smoothing, top_k; setup and fetch shared with GraphEngine) -------------------------------------
-    def _loss_setup(self, label_smoothing, top_k, rows):
-        """Both off (or an engine that does not train: validation computes no loss): the two sums and the 2 * rows workspace of
-        ops.softmax_xent, as ever.  Either on: three sums and 3 * rows, for ops.softmax_xent_ls."""
+    def _loss_setup(self, label_smoothing, top_k, rows, class_weights=None, focal_gamma=0.0, num_classes=None):
+        """All off (or an engine that does not train: validation computes no loss): the two sums and the 2 * rows workspace of
+        ops.softmax_xent, as ever.  Label smoothing or top-k on: three sums and 3 * rows, for ops.softmax_xent_ls.  Class weights or a
+        focal gamma on (xent_wf): the same three columns, for ops.softmax_xent_wf, and the weights on the device
+        (class_weights_dev; None = ones), read by the launch as it runs."""
         self.label_smoothing, self.top_k = check_label_smoothing(label_smoothing), check_top_k(top_k)
+        self.class_weights = check_class_weights(class_weights, self.cfg.num_classes if num_classes is None else num_classes)
+        self.focal_gamma = check_focal_gamma(focal_gamma)
         if not self.training:
-            self.label_smoothing, self.top_k = 0.0, 0
+            self.label_smoothing, self.top_k, self.class_weights, self.focal_gamma = 0.0, 0, None, 0.0
         self.xent_ls = self.label_smoothing > 0.0 or self.top_k > 0
-        cols = 3 if self.xent_ls else 2
+        self.xent_wf = self.class_weights is not None or self.focal_gamma > 0.0
+        self.class_weights_dev = None if self.class_weights is None else torch.from_numpy(self.class_weights).to(self.dev)
+        cols = 3 if self.xent_ls or self.xent_wf else 2
         self.stats = torch.zeros(cols, device=self.dev)
         self.loss_rows = torch.zeros(cols * rows, device=self.dev)      # per-row losses | hits (| top-k hits): the loss launch's workspace
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale):
         """The loss launch of a train step: stats += {loss sum, hits (, top-k hits)}, dlogits = (softmax - labels') * grad_scale."""
-        if self.mix_lam is not None:              # mixup: the labels of the blended clips, the weight read from the device
+        if self.xent_wf:                          # class weights / focal loss, on mixed labels when mixup or CutMix is on
+            ops.softmax_xent_wf(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k,
+                                self.class_weights_dev, self.focal_gamma,
+                                **({} if self.mix_lam is None else dict(rows_per_clip=self.rows_out // self.B, lam=self.mix_lam)))
+        elif self.mix_lam is not None:              # mixup: the labels of the blended clips, the weight read from the device
             ops.softmax_xent_mix(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.rows_out // self.B,
                                  self.label_smoothing, self.top_k, self.mix_lam)
         elif self.xent_ls:
@@ -1323,7 +1377,7 @@ class LRCNEngine:
             self.cut_box_last = (0, 0, 0, 0, 0, 0)
             if self.mixup_alpha > 0.0:
                 self.blend_lam = torch.ones(1, device=self.dev)
-        if not self.xent_ls:
+        if not (self.xent_ls or self.xent_wf):
             self.stats = torch.zeros(3, device=self.dev)
             self.loss_rows = torch.zeros(3 * rows, device=self.dev)
 

@@ -40,7 +40,8 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_ema, check_fc_dropout, check_label_smoothing,
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
+                     check_label_smoothing,
                      check_cutmix, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
 
@@ -756,7 +757,7 @@ class GraphEngine:
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
                  lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0,
-                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0):
+                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0, class_weights=None, focal_gamma=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -775,7 +776,10 @@ class GraphEngine:
         (tfa.optimizers.LAMB) in the place of the Adam update -- Adam's moments, a trust ratio |w| / |u| per trained weight tensor of rank
         >= 2 of every pipeline, weight_decay decoupled (engine.check_lamb, engine.lamb_ranges, LRCNEngine._lamb_setup); optimizer adam
         only; False = off.  mixup_alpha: refused when > 0 -- mixup pairs the clips of ONE dcnn pipeline (LRCNEngine).
-        cutmix_alpha: refused when > 0 for the same reason."""
+        cutmix_alpha: refused when > 0 for the same reason.  class_weights, focal_gamma: num_classes weights inside the
+        class sum of the loss and the focal loss's focusing parameter, in the loss launch of the last pipeline with its seq_len
+        (engine.check_class_weights, engine.check_focal_gamma, LRCNEngine._loss_setup); a forward-only engine ignores
+        them; None / 0 = off."""
         if check_cutmix(cutmix_alpha)[0] > 0.0:
             raise VltfError("cutmix_alpha = %s is refused by GraphEngine: frame towers, vector inputs, clips-per-video ratios and word-level "
                             "losses have no one clip to pair; CutMix runs on single-pipeline models (LRCNEngine, NetConfig.cutmix_alpha)"
@@ -785,6 +789,7 @@ class GraphEngine:
                             "losses have no one clip to pair; mixup runs on single-pipeline models (LRCNEngine, NetConfig.mixup_alpha)"
                             % (mixup_alpha,))
         self._loss_opts = (check_label_smoothing(label_smoothing), check_top_k(top_k))
+        self._loss_wf = (check_class_weights(class_weights, int(num_classes)), check_focal_gamma(focal_gamma))
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
@@ -908,7 +913,7 @@ class GraphEngine:
         self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None   # LRCNEngine.__init__: the running sum
         self.ema = torch.zeros(total, device=dev) if self.ema_decay > 0.0 and training else None   # LRCNEngine.__init__: the shadow weights
         rows = self.last.max_rows
-        self._loss_setup(*self._loss_opts, rows)
+        self._loss_setup(*self._loss_opts, rows, *self._loss_wf, num_classes=self.num_classes)
         self.ss = torch.zeros(1, device=dev)
         self.ss2 = None
         if self.decay is not None:                # L2 weight decay (LRCNEngine.__init__): {sum g'^2, regulariser}, self.ss its first word
@@ -985,7 +990,10 @@ class GraphEngine:
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale, **lengths):
         """LRCNEngine._xent_launch through this module's ops (lengths: seq_len and T of a loss masked by seq_len, or nothing)."""
-        if self.xent_ls:
+        if self.xent_wf:
+            ops.softmax_xent_wf(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k,
+                                self.class_weights_dev, self.focal_gamma, **lengths)
+        elif self.xent_ls:
             ops.softmax_xent_ls(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k, **lengths)
         else:
             ops.softmax_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, **lengths)

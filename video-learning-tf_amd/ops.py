@@ -779,6 +779,24 @@ def softmax_xent_mix(logits, labels, dlogits, stats, grad_scale, rows, rows_per_
               float(smoothing), int(top_k), lam_host, lam_dev, stream())
 
 
+def softmax_xent_wf(logits, labels, dlogits, stats, grad_scale, rows, smoothing, top_k, class_weights=None, gamma=0.0, seq_len=None,
+                    T=None, rows_per_clip=1, lam=1.0):
+    """softmax_xent_ls / softmax_xent_mix with class weights and the focal loss in the same launch (vl_softmax_xent_wf):
+    loss = sum_c w_c y'_c (1 - p_c)^gamma (-log p_c), normalised by the caller's row count (grad_scale).  class_weights: None (ones) or
+    a float32 device tensor of `classes` elements, read when the kernel runs; gamma >= 0.  seq_len / T as in softmax_xent_ls;
+    rows_per_clip / lam as in softmax_xent_mix (1 and 1.0: no partner row); the two do not combine.  stats: 3 floats; rows: None or
+    >= 3*batch floats."""
+    mixed = int(rows_per_clip) != 1 or torch.is_tensor(lam) or float(lam) != 1.0
+    b, c, sl, t = _xent_args("softmax_xent_wf", 3, logits, labels, dlogits, stats, rows, seq_len, T, partner=mixed)
+    if class_weights is not None:
+        _f32(class_weights); _dense(class_weights)
+        if class_weights.numel() != c:
+            raise _ffi.VltfError("softmax_xent_wf: class_weights holds %d floats for %d classes" % (class_weights.numel(), c))
+    lam_host, lam_dev = _lam(lam, "softmax_xent_wf")
+    _ffi.call("vl_softmax_xent_wf", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, _p(sl), t,
+              int(rows_per_clip), float(smoothing), int(top_k), lam_host, lam_dev, _p(class_weights), float(gamma), stream())
+
+
 def sumsq(g, out, ws, accumulate=False):
     _f32(g, out, ws)
     if ws.numel() < 1024:

@@ -62,6 +62,7 @@ def pipeline_net_config(settings, p, dataset):
               ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
               label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
               lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0], mixup_seed=settings.get_mixup()[1],
+              class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma(),
               **dict(zip(("cutmix_alpha", "cutmix_seed", "cutmix_mode", "cutmix_prob"), settings.get_cutmix())))
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
@@ -310,6 +311,8 @@ def do_test(settings, val, feeder, engine, rank=0, world=1):
         if val.save_interval is not None:
             with open(os.path.join(settings.run_folder, "accuracy_top%d_%s" % (top_k, settings.run_id)), "w") as f:
                 f.write(str(topk))
+    if getattr(settings.val, "per_class", False):         # val.per_class: recall per class and their mean (Validation.get_per_class)
+        val.report_per_class(write=val.save_interval is not None)
     return accuracy
 
 
@@ -369,7 +372,8 @@ def main(init_file, seed=0, device=None):
                              tensor_stats_interval=settings.get_tensor_stats_interval(), ema_decay=settings.get_ema()[0],
                              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
                              label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
-                             lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0])
+                             lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0],
+                             class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma())
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

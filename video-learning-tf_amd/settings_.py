@@ -29,6 +29,7 @@ class TrainSettings:
     label_smoothing, top_k = 0.0, 0
     mixup_alpha, mixup_seed = 0.0, 0
     cutmix_alpha, cutmix_seed, cutmix_mode, cutmix_prob = 0.0, 0, None, None
+    class_weights, focal_gamma = None, 0.0
 
 
 class ValSettings:
@@ -36,6 +37,25 @@ class ValSettings:
     clip_fusion_type, clip_fusion_method = defs.fusion_type.late, defs.fusion_method.avg
     use_ema = False
     top_k = 0
+    per_class = False
+
+
+def balanced_class_weights(item_labels, num_classes):
+    """`train: class_weights: balanced`: w_c = N / (C n_c), n_c the occurrences of class c among the labels of the item list (one list
+    of labels per item, as Dataset.read_frames_metadata keeps them; a multi-label item counts once per label) and N their total --
+    sklearn's compute_class_weight("balanced").  A class without an occurrence gets 1.0.  -> (weights, the absent classes)."""
+    counts = [0] * num_classes
+    for labels in item_labels:
+        for l in labels:
+            c = int(l)
+            if not 0 <= c < num_classes:
+                error("train.class_weights: balanced: the item list holds the label %s, outside the %d classes" % (l, num_classes))
+            counts[c] += 1
+    total = sum(counts)
+    if total == 0:
+        error("train.class_weights: balanced: the training item list holds no label")
+    absent = [c for c, n in enumerate(counts) if n == 0]
+    return [total / (num_classes * n) if n else 1.0 for n in counts], absent
 
 
 class Settings:
@@ -75,6 +95,19 @@ class Settings:
         """train.top_k: the k of the top-k accuracy a training step also counts; 0 = off, and outside the train phase (validation ranks
         its fused logits on the host under val.top_k, Validation.get_topk_accuracy)."""
         return self.train.top_k if self.phase == defs.phase.train else 0
+
+    def get_class_weights(self):
+        """train.class_weights as the numbers the engine takes (a list, or the balanced weights of the training item list, formed by
+        initialize once the datasets are read); None = off, and outside the train phase."""
+        if self.phase != defs.phase.train or self.train.class_weights is None:
+            return None
+        if isinstance(self.train.class_weights, str):
+            error("train.class_weights: balanced needs the training datasets, which are not read yet")
+        return self.train.class_weights
+
+    def get_focal_gamma(self):
+        """train.focal_gamma (the focal loss's focusing parameter); 0 = off, and outside the train phase."""
+        return self.train.focal_gamma if self.phase == defs.phase.train else 0.0
 
     def get_mixup(self):
         """(train.mixup_alpha, train.mixup_seed): mixup's Beta(alpha, alpha) and the key of its draws (engine.check_mixup,
@@ -197,6 +230,50 @@ class Settings:
             return check_top_k(None if k == "None" else k)
         except VltfError as ex:
             error("%s.top_k: %s" % (where, ex))
+
+    def read_loss_weights(self, obj):
+        """`train: class_weights: [w_0, ..]` | `balanced` and `train: focal_gamma: G` (this project's extension): absent /
+        None = off; quoted numbers are read as numbers.  -> (a list of num_classes floats | "balanced" | None, gamma)."""
+        from .engine import VltfError, check_class_weights, check_focal_gamma
+
+        def number(v):
+            if isinstance(v, str) and v != "None":      # a quoted number; nan / inf come as strings too
+                try:
+                    return float(v)
+                except ValueError:
+                    pass
+            return v
+
+        cw = obj.get("class_weights")
+        if cw in (None, "None"):
+            cw = None
+        elif isinstance(cw, str) and cw.strip().lower() == "balanced":
+            cw = "balanced"
+        else:
+            if isinstance(cw, str):                      # "1, 2.5, 1" / "[1, 2.5, 1]"
+                cw = [x for x in cw.replace("[", " ").replace("]", " ").replace(",", " ").split()]
+            try:
+                w = check_class_weights([number(v) for v in cw] if isinstance(cw, (list, tuple)) else cw, self.num_classes)
+                cw = [float(v) for v in w]
+            except VltfError as ex:
+                error("train.class_weights: %s" % ex)
+        g = number(obj.get("focal_gamma"))
+        try:
+            return cw, check_focal_gamma(None if g == "None" else g)
+        except VltfError as ex:
+            error("train.focal_gamma: %s" % ex)
+
+    def resolve_balanced_weights(self):
+        """After the datasets are read: `class_weights: balanced` becomes the numbers, from the main training dataset's item list."""
+        if not self.train or self.train.class_weights != "balanced":
+            return
+        main = [d for d in self.feeder.datasets.get(defs.phase.train, []) if d.tag == defs.dataset_tag.main]
+        if not main:
+            error("train.class_weights: balanced: there is no [%s] training dataset to count the labels of" % defs.dataset_tag.main)
+        weights, absent = balanced_class_weights(main[0].labels, self.num_classes)
+        if absent:
+            warning("train.class_weights: balanced: no item of class(es) %s in [%s]: their weight is 1.0" % (absent, main[0].id))
+        self.train.class_weights = weights
 
     # ---- run block (settings_.py:210-366) -------------------------------------------------------------------
     def read_config(self, config, init_file):
@@ -368,6 +445,9 @@ class Settings:
                     t.cutmix_mode, t.cutmix_prob = (md, pr) if a > 0.0 else (None, None)
                 except VltfError as ex:
                     error("train.cutmix_alpha / train.cutmix_seed / train.cutmix_mode / train.cutmix_prob: %s" % ex)
+                # class weights inside the loss's class sum and the focal loss (engine.check_class_weights, engine.check_focal_gamma;
+                # `balanced` is resolved by initialize, from the training item list): absent / None = off
+                t.class_weights, t.focal_gamma = self.read_loss_weights(obj)
                 if obj.get("lr_decay") in (None, "None"):
                     t.lr_decay = None
                 else:
@@ -389,6 +469,11 @@ class Settings:
                 v.use_ema = ue
                 # top-k accuracy of the fused per-video logits beside the top-1 one (Validation.get_topk_accuracy): absent / None = off
                 v.top_k = self.read_top_k(obj, "val")
+                # recall per class and the mean-class accuracy of the fused per-video logits (Validation.get_per_class): absent / None = off
+                pc = obj.get("per_class") if obj.get("per_class") not in (None, "None") else False
+                if not isinstance(pc, bool):
+                    error("val.per_class must be a boolean, got [%s]" % (pc,))
+                v.per_class = pc
 
         self.feeder = Feeder(defs.input_mode.video, self.phases, (self.train, self.val), self.save_freq_per_epoch, self.run_folder,
                              self.should_resume())
@@ -468,6 +553,7 @@ class Settings:
         self.tensorboard_folder = os.path.join(self.run_folder, self.tensorboard_folder, self.phase)
         self.feeder.set_phase(self.phase)
         self.feeder.initialize_datasets()
+        self.resolve_balanced_weights()
         if self.should_resume():
             if self.train:
                 info("Resuming training.")

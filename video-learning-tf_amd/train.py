@@ -156,6 +156,11 @@ class Train:
         if getattr(engine, "xent_ls", False):
             info("Loss: label smoothing %s (labels y (1 - eps) + eps / %d; the logged loss is the smoothed one), top-k accuracy %s" %
                  (engine.label_smoothing, settings.num_classes, ("k = %d" % engine.top_k) if engine.top_k > 0 else "off"))
+        if getattr(engine, "xent_wf", False):
+            w = engine.class_weights
+            info("Loss: focal gamma %s, class weights %s; rows are normalised by their count, not by their weights, and the logged loss is "
+                 "the weighted one" % (engine.focal_gamma, "off" if w is None else "min %g (class %d), max %g (class %d)" %
+                                       (w.min(), int(w.argmin()), w.max(), int(w.argmax()))))
 
         if getattr(engine, "mix_lam", None) is not None:
             info("Mixup: alpha %s, seed %d (one Beta(alpha, alpha) weight per batch, folded to max(lam, 1 - lam)); clip i is blended with "

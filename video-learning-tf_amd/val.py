@@ -109,5 +109,46 @@ class Validation:
             accuracies.append(np.mean(topk_hits(self.item_logits, self.item_labels[cur:cur + n, :], k)))
         return float(np.mean(accuracies))
 
+    def get_per_class(self):
+        """val.per_class: -> (mean-class accuracy, hits [classes], items [classes]) over the fused per-video logits of every saved
+        chunk and the rows still in memory.  An item counts under the first arg-max of its label row (the rule of topk_hits, so a
+        multi-hot item has one class); hits and items are SUMMED over the chunks -- a chunk may hold no item of a class, so there is
+        no mean of chunk means here.  A class's recall is hits / items; the mean-class accuracy is the mean recall over the classes
+        that have at least one item."""
+        classes = self.item_labels.shape[1]
+        hits, items = np.zeros(classes, np.int64), np.zeros(classes, np.int64)
+        chunks, cur = [], 0
+        for c in range(self.save_counter):
+            chunks.append(self.load_validation_logits_chunk(c))
+        if len(self.item_logits) > 0:
+            chunks.append(self.item_logits)
+        for logits in chunks:
+            t = np.argmax(self.item_labels[cur:cur + len(logits), :], axis=1)
+            cur += len(logits)
+            items += np.bincount(t, minlength=classes)
+            hits += np.bincount(t[np.argmax(logits, axis=1) == t], minlength=classes)
+        present = items > 0
+        if not present.any():
+            error("val.per_class: there are no validation items")
+        return float(np.mean(hits[present] / items[present])), hits, items
+
+    def report_per_class(self, write=True):
+        """get_per_class logged -- the mean-class accuracy and the three classes of lowest recall -- and, with write, stored beside the
+        accuracy file: accuracy_mean_class_<run_id> (the number) and accuracy_per_class_<run_id>, one line `class hits items recall`
+        per class (a class without items has recall nan).  -> the mean-class accuracy."""
+        mean_class, hits, items = self.get_per_class()
+        recall = np.where(items > 0, hits / np.maximum(items, 1), np.nan)
+        present = np.flatnonzero(items > 0)
+        worst = present[np.argsort(recall[present], kind="stable")[:3]]
+        info("Validation mean-class accuracy: %2.5f over %d of %d classes with items; lowest recall: %s" %
+             (mean_class, len(present), len(items), ", ".join("class %d %d/%d" % (c, hits[c], items[c]) for c in worst)))
+        if write:
+            with open(os.path.join(self.run_folder, "accuracy_mean_class_" + self.run_id), "w") as f:
+                f.write(str(mean_class))
+            with open(os.path.join(self.run_folder, "accuracy_per_class_" + self.run_id), "w") as f:
+                for c in range(len(items)):
+                    f.write("%d %d %d %s\n" % (c, hits[c], items[c], repr(float(recall[c]))))
+        return mean_class
+
     def get_chunk_accuracy(self, logits, labels):
         return np.mean(np.equal(np.argmax(logits, axis=1), np.argmax(labels, axis=1)))
