@@ -2295,21 +2295,20 @@ struct tier_table {
     int n;
 };
 
-// sorted, disjoint, inside [0, count), multipliers finite and > 0 (the kernels rely on it: an element outside every tier is never
-// addressed, and no element is addressed twice)
-static int tier_table_make(const char* who, const vl_lr_tier* tiers, int n_tiers, int64_t count, tier_table* out) {
-    VL_CHECK(tiers && n_tiers >= 1 && n_tiers <= VL_MAX_LR_TIERS, "%s: 1 .. %d tiers, got %d", who, VL_MAX_LR_TIERS, n_tiers);
-    int64_t prev = 0;
-    for (int k = 0; k < n_tiers; ++k) {
-        const vl_lr_tier& t = tiers[k];
-        VL_CHECK(t.begin >= prev && t.end > t.begin && t.end <= count,
-                 "%s: tier %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)t.begin,
-                 (long long)t.end, (long long)count);
-        VL_CHECK(t.lr_mult > 0.f && t.lr_mult <= 3.402823466e38f, "%s: tier %d: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
-        out->t[k] = t;
-        prev = t.end;
-    }
-    out->n = n_tiers;
+// The rules every range table keeps (tier, decay, LARS and LAMB tables alike; the kernels rely on them: an element outside every range
+// is never addressed, and no element is addressed twice).  An entry is named `open`k`close` in the messages: "tier 2", "ranges[2]".
+// Entry k begins at or after `prev` (its predecessor's end), is not empty and ends inside [0, count); count < 0: the bound is not known.
+static int range_bounds_check(const char* who, const char* open, int k, const char* close, int64_t begin, int64_t end, int64_t prev,
+                              int64_t count) {
+    VL_CHECK(begin >= prev && end > begin && (count < 0 || end <= count),
+             "%s: %s%d%s = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, open, k, close,
+             (long long)begin, (long long)end, (long long)count);
+    return 0;
+}
+// a multiplier is finite and > 0, a decay finite and >= 0 (NaN fails both comparisons)
+static int range_factor_check(const char* who, const char* open, int k, const char* close, const char* name, float x, bool positive) {
+    VL_CHECK((positive ? x > 0.f : x >= 0.f) && x <= 3.402823466e38f, "%s: %s%d%s: %s must be finite and %s", who, open, k, close, name,
+             positive ? "> 0" : ">= 0");
     return 0;
 }
 
@@ -2320,6 +2319,25 @@ static tier_table tier_table_full(int64_t count) {
     tt.t[0].lr_mult = 1.f;
     tt.n = 1;
     return tt;
+}
+
+// null_is_full: a NULL table of 0 entries is the full range (vl_momentum_apply, vl_grad_accumulate, vl_ema_update)
+static int tier_table_make(const char* who, const vl_lr_tier* tiers, int n_tiers, int64_t count, tier_table* out, bool null_is_full = false) {
+    if (null_is_full && !tiers && n_tiers == 0) {
+        *out = tier_table_full(count);
+        return 0;
+    }
+    VL_CHECK(tiers && n_tiers >= 1 && n_tiers <= VL_MAX_LR_TIERS, "%s: 1 .. %d tiers, got %d", who, VL_MAX_LR_TIERS, n_tiers);
+    int64_t prev = 0;
+    for (int k = 0; k < n_tiers; ++k) {
+        const vl_lr_tier& t = tiers[k];
+        if (int rc = range_bounds_check(who, "tier ", k, "", t.begin, t.end, prev, count)) return rc;
+        if (int rc = range_factor_check(who, "tier ", k, "", "lr_mult", t.lr_mult, true)) return rc;
+        out->t[k] = t;
+        prev = t.end;
+    }
+    out->n = n_tiers;
+    return 0;
 }
 
 // [begin, end) = scalar head [begin, v0) + 16-byte interior [v0, v1) + scalar tail [v1, end).  The interior exists where every one of the
@@ -2339,6 +2357,22 @@ __device__ __forceinline__ void tier_split(int64_t begin, int64_t end, int phase
     if (v0 > end) v0 = end;
     v1 = v0 + ((end - v0) & ~(int64_t)3);
 }
+// The one walk of a range, for a lane that starts at i0 and strides by `step`: f1(i) for element i of the head and of the tail, f4(v0, i)
+// for 16-byte vector i of the interior, whose vector 0 begins at element v0.  Every ranged kernel below goes through here, so which
+// elements a range addresses, and which loop reaches each, is stated once; f1 and f4 share an element function, so an element's result
+// does not depend on the loop that reached it.
+template <class F1, class F4>
+__device__ __forceinline__ void range_walk(int64_t begin, int64_t end, int phase, int64_t i0, int64_t step, F1 f1, F4 f4) {
+    int64_t v0, v1;
+    tier_split(begin, end, phase, v0, v1);
+    for (int64_t i = begin + i0; i < v0; i += step) f1(i);
+    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) f4(v0, i);
+    for (int64_t i = v1 + i0; i < end; i += step) f1(i);
+}
+// 16-byte vector i counted from element v0 of p.  (One element offset on purpose: as `((float4*)(p + v0))[i]` hipcc keeps a pointer per
+// array through the interiors of grad_accumulate_kernel and l2_regularize_stage1, one more 64-bit add per pass: DESIGN.md 4.4.)
+__device__ __forceinline__ float4& vec4(float* p, int64_t v0, int64_t i) { return *reinterpret_cast<float4*>(p + v0 + 4 * i); }
+__device__ __forceinline__ const float4& vec4(const float* p, int64_t v0, int64_t i) { return *reinterpret_cast<const float4*>(p + v0 + 4 * i); }
 
 __global__ void sumsq_stage1(const float* __restrict__ g, int64_t count, float* __restrict__ ws) {
     __shared__ float sm[4];
@@ -2386,18 +2420,12 @@ __global__ void sumsq_tiers_stage1(const float* __restrict__ g, tier_table tt, f
     float acc = 0.f;
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
     const int phase = align_phase(g, nullptr, nullptr, nullptr);
-    for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) acc += g[i] * g[i];
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            const float4 v = g4[i];
-            acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) acc += g[i] * g[i];
-    }
+    for (int k = 0; k < tt.n; ++k)
+        range_walk(tt.t[k].begin, tt.t[k].end, phase, i0, step, [&](int64_t i) { acc += g[i] * g[i]; },
+                   [&](int64_t v0, int64_t i) {
+                       const float4 v = vec4(g, v0, i);
+                       acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+                   });
     acc = block_sum_256(acc, sm);
     if (threadIdx.x == 0) ws[blockIdx.x] = acc;
 }
@@ -2429,10 +2457,8 @@ static int decay_table_make(const char* who, const vl_decay_range* ranges, int n
     int64_t prev = 0;
     for (int k = 0; k < n_ranges; ++k) {
         const vl_decay_range& r = ranges[k];
-        VL_CHECK(r.begin >= prev && r.end > r.begin && r.end <= count,
-                 "%s: range %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
-                 (long long)r.end, (long long)count);
-        VL_CHECK(r.decay >= 0.f && r.decay <= 3.402823466e38f, "%s: range %d: decay must be finite and >= 0", who, k);   // (NaN fails both)
+        if (int rc = range_bounds_check(who, "range ", k, "", r.begin, r.end, prev, count)) return rc;
+        if (int rc = range_factor_check(who, "range ", k, "", "decay", r.decay, false)) return rc;
         out->r[k] = r;
         prev = r.end;
     }
@@ -2468,36 +2494,25 @@ __global__ __launch_bounds__(256) void l2_regularize_stage1(const float* __restr
     for (int k = 0; k < dt.n; ++k) {
         const int64_t begin = dt.r[k].begin, end = dt.r[k].end;
         const float decay = dt.r[k].decay, half_decay = 0.5f * decay;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        const int64_t nvec = (v1 - v0) / 4;
         if (decay > 0.f) {
-            for (int64_t i = begin + i0; i < v0; i += step) {
-                float gi = g[i];
-                l2_elem(w[i], gi, decay, half_decay, ss, rs);
-                g[i] = gi;
-            }
-            const float4* __restrict__ w4 = reinterpret_cast<const float4*>(w + v0);
-            float4* __restrict__ g4 = reinterpret_cast<float4*>(g + v0);
-            for (int64_t i = i0; i < nvec; i += step) {
-                const float4 wv = w4[i];
-                float4 gv = g4[i];
-                l2_elem4(wv, gv, decay, half_decay, ss, rs);
-                g4[i] = gv;
-            }
-            for (int64_t j = v1 + i0; j < end; j += step) {
-                float gi = g[j];
-                l2_elem(w[j], gi, decay, half_decay, ss, rs);
-                g[j] = gi;
-            }
-        } else {
-            for (int64_t i = begin + i0; i < v0; i += step) ss += g[i] * g[i];
-            const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-            for (int64_t i = i0; i < nvec; i += step) {
-                const float4 v = g4[i];
-                ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-            }
-            for (int64_t i = v1 + i0; i < end; i += step) ss += g[i] * g[i];
+            range_walk(begin, end, phase, i0, step,
+                       [&](int64_t i) {
+                           float gi = g[i];
+                           l2_elem(w[i], gi, decay, half_decay, ss, rs);
+                           g[i] = gi;
+                       },
+                       [&](int64_t v0, int64_t i) {
+                           const float4 wv = vec4(w, v0, i);
+                           float4 gv = vec4(g, v0, i);
+                           l2_elem4(wv, gv, decay, half_decay, ss, rs);
+                           vec4(g, v0, i) = gv;
+                       });
+        } else {                              // a read-only sum: w is never loaded, g never stored
+            range_walk(begin, end, phase, i0, step, [&](int64_t i) { ss += g[i] * g[i]; },
+                       [&](int64_t v0, int64_t i) {
+                           const float4 v = vec4(g, v0, i);
+                           ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+                       });
         }
     }
     ss = block_sum_256(ss, sm);
@@ -2544,10 +2559,8 @@ __device__ __forceinline__ float clip_scale(float clip_norm, const float* sumsq,
     return gscale * clip_norm / fmaxf(norm, clip_norm);
 }
 
-// the update bodies, shared by the eager kernels and the step-state ones (vl_sgd_apply_st / vl_adam_apply_st): only where lr / the
-// Adam step size comes from differs, so a replayed update and the eager one get the same bits
-// (grid-stride start and step from the kernel, as dropout_fwd_body).  One element function each, used by the scalar and the 16-byte
-// loops alike: an element's result does not depend on which loop reached it.
+// the update bodies (grid-stride start and step from the kernel, as dropout_fwd_body).  One element function each, used by the scalar
+// and the 16-byte callable of range_walk alike: an element's result does not depend on which loop reached it.
 // The rounding steps are spelled out (no contraction left to the compiler, which chose differently per loop): the forms are the
 // ones the one-loop kernels were built with, so every loop here -- and the plain entry points before there were tiers -- give the same bits.
 __device__ __forceinline__ float sgd_elem(float w, float g, float a) {
@@ -2560,23 +2573,17 @@ __device__ __forceinline__ void sgd_apply_body(float* __restrict__ w, const floa
     const float sc = clip_scale(clip_norm, sumsq, gscale);
     const int phase = align_phase(w, g, nullptr, nullptr);
     for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
         const float a = (lr * tt.t[k].lr_mult) * sc;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) w[i] = sgd_elem(w[i], g[i], a);
-        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            float4 wv = w4[i];
-            const float4 gv = g4[i];
-            wv.x = sgd_elem(wv.x, gv.x, a);
-            wv.y = sgd_elem(wv.y, gv.y, a);
-            wv.z = sgd_elem(wv.z, gv.z, a);
-            wv.w = sgd_elem(wv.w, gv.w, a);
-            w4[i] = wv;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) w[i] = sgd_elem(w[i], g[i], a);
+        range_walk(tt.t[k].begin, tt.t[k].end, phase, i0, step, [&](int64_t i) { w[i] = sgd_elem(w[i], g[i], a); },
+                   [&](int64_t v0, int64_t i) {
+                       float4 wv = vec4(w, v0, i);
+                       const float4 gv = vec4(g, v0, i);
+                       wv.x = sgd_elem(wv.x, gv.x, a);
+                       wv.y = sgd_elem(wv.y, gv.y, a);
+                       wv.z = sgd_elem(wv.z, gv.z, a);
+                       wv.w = sgd_elem(wv.w, gv.w, a);
+                       vec4(w, v0, i) = wv;
+                   });
     }
 }
 
@@ -2596,27 +2603,19 @@ __device__ __forceinline__ void adam_apply_body(float* __restrict__ w, const flo
     const float sc = clip_scale(clip_norm, sumsq, gscale);
     const int phase = align_phase(w, g, m, v);
     for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
         const float lr_k = lr_t * tt.t[k].lr_mult;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) adam_elem(w[i], g[i], m[i], v[i], sc, lr_k);
-        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-        float4* __restrict__ m4 = reinterpret_cast<float4*>(m + v0);
-        float4* __restrict__ q4 = reinterpret_cast<float4*>(v + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            float4 wv = w4[i], mv = m4[i], qv = q4[i];
-            const float4 gv = g4[i];
-            adam_elem(wv.x, gv.x, mv.x, qv.x, sc, lr_k);
-            adam_elem(wv.y, gv.y, mv.y, qv.y, sc, lr_k);
-            adam_elem(wv.z, gv.z, mv.z, qv.z, sc, lr_k);
-            adam_elem(wv.w, gv.w, mv.w, qv.w, sc, lr_k);
-            m4[i] = mv;
-            q4[i] = qv;
-            w4[i] = wv;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) adam_elem(w[i], g[i], m[i], v[i], sc, lr_k);
+        range_walk(tt.t[k].begin, tt.t[k].end, phase, i0, step, [&](int64_t i) { adam_elem(w[i], g[i], m[i], v[i], sc, lr_k); },
+                   [&](int64_t v0, int64_t i) {
+                       float4 wv = vec4(w, v0, i), mv = vec4(m, v0, i), qv = vec4(v, v0, i);
+                       const float4 gv = vec4(g, v0, i);
+                       adam_elem(wv.x, gv.x, mv.x, qv.x, sc, lr_k);
+                       adam_elem(wv.y, gv.y, mv.y, qv.y, sc, lr_k);
+                       adam_elem(wv.z, gv.z, mv.z, qv.z, sc, lr_k);
+                       adam_elem(wv.w, gv.w, mv.w, qv.w, sc, lr_k);
+                       vec4(m, v0, i) = mv;
+                       vec4(v, v0, i) = qv;
+                       vec4(w, v0, i) = wv;
+                   });
     }
 }
 
@@ -2629,28 +2628,22 @@ __device__ __forceinline__ void momentum_elem(float& w, float g, float& a, float
     w = __builtin_fmaf(-lr_k, nesterov ? __builtin_fmaf(momentum, ai, gi) : ai, w);
 }
 
-// one range [begin, end) of the momentum update with its own lr_k: scalar head, 16-byte interior, scalar tail (tier_split).  Shared by the
-// tier walk below and by the LARS walk (lars_apply_body), so a range's bits do not depend on which table named it.
+// one range [begin, end) of the momentum update with its own lr_k (range_walk).  Shared by the tier walk below and by the LARS walk
+// (lars_apply_body), so a range's bits do not depend on which table named it.
 __device__ __forceinline__ void momentum_range(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, int64_t begin,
                                                int64_t end, int phase, float sc, float lr_k, float momentum, bool nesterov, int64_t i0,
                                                int64_t step) {
-    int64_t v0, v1;
-    tier_split(begin, end, phase, v0, v1);
-    for (int64_t i = begin + i0; i < v0; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
-    float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + v0);
-    float4* __restrict__ a4 = reinterpret_cast<float4*>(a + v0);
-    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-        float4 wv = w4[i], av = a4[i];
-        const float4 gv = g4[i];
-        momentum_elem(wv.x, gv.x, av.x, sc, lr_k, momentum, nesterov);
-        momentum_elem(wv.y, gv.y, av.y, sc, lr_k, momentum, nesterov);
-        momentum_elem(wv.z, gv.z, av.z, sc, lr_k, momentum, nesterov);
-        momentum_elem(wv.w, gv.w, av.w, sc, lr_k, momentum, nesterov);
-        a4[i] = av;
-        w4[i] = wv;
-    }
-    for (int64_t i = v1 + i0; i < end; i += step) momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov);
+    range_walk(begin, end, phase, i0, step, [&](int64_t i) { momentum_elem(w[i], g[i], a[i], sc, lr_k, momentum, nesterov); },
+               [&](int64_t v0, int64_t i) {
+                   float4 wv = vec4(w, v0, i), av = vec4(a, v0, i);
+                   const float4 gv = vec4(g, v0, i);
+                   momentum_elem(wv.x, gv.x, av.x, sc, lr_k, momentum, nesterov);
+                   momentum_elem(wv.y, gv.y, av.y, sc, lr_k, momentum, nesterov);
+                   momentum_elem(wv.z, gv.z, av.z, sc, lr_k, momentum, nesterov);
+                   momentum_elem(wv.w, gv.w, av.w, sc, lr_k, momentum, nesterov);
+                   vec4(a, v0, i) = av;
+                   vec4(w, v0, i) = wv;
+               });
 }
 
 __device__ __forceinline__ void momentum_apply_body(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a,
@@ -2662,25 +2655,35 @@ __device__ __forceinline__ void momentum_apply_body(float* __restrict__ w, const
         momentum_range(w, g, a, tt.t[k].begin, tt.t[k].end, phase, sc, lr * tt.t[k].lr_mult, momentum, nesterov, i0, step);
 }
 
+// One kernel per rule for the eager and the step-state (_st) entry points.  st != nullptr: lr / Adam's step size / the rate is read from
+// the step state (vltf.h: vl_step_state), a uniform load, in place of the argument; nothing else differs, so a replayed update and the
+// eager one get the same bits.  The state is read ahead of the skip word so that the two device loads are in flight together: read
+// after it, the test of st cost every wave one more scalar round trip (+2 % on the Adam launch alone).
 __global__ void momentum_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, tier_table tt, float lr,
-                                      float momentum, int nesterov, float clip_norm, const float* __restrict__ sumsq, float gscale,
-                                      const uint32_t* __restrict__ skip) {
+                                      const vl_step_state* __restrict__ st, float momentum, int nesterov, float clip_norm,
+                                      const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (st) lr = st->lr;                                              // ahead of the skip word: the two loads share a round trip
     if (skip && *skip) return;
-    momentum_apply_body(w, g, a, tt, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                        (int64_t)gridDim.x * blockDim.x);
+    momentum_apply_body(w, g, a, tt, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
+                        (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, float lr, float clip_norm,
-                                 const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+__global__ void sgd_apply_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, float lr,
+                                 const vl_step_state* __restrict__ st, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                 const uint32_t* __restrict__ skip) {
+    if (st) lr = st->lr;
     if (skip && *skip) return;                                        // the step's results are invalid (vl_status_or): no update
-    sgd_apply_body(w, g, tt, lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    sgd_apply_body(w, g, tt, lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                   (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void adam_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                  tier_table tt, float lr_t, float clip_norm, const float* __restrict__ sumsq, float gscale,
-                                  const uint32_t* __restrict__ skip) {
+                                  tier_table tt, float lr_t, const vl_step_state* __restrict__ st, float clip_norm,
+                                  const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+    if (st) lr_t = st->adam_lr;
     if (skip && *skip) return;
-    adam_apply_body(w, g, m, v, tt, lr_t, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    adam_apply_body(w, g, m, v, tt, lr_t, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                    (int64_t)gridDim.x * blockDim.x);
 }
 
 // *dst |= first word of an LSTM cluster workspace (its sticky time-out word, lstm_cluster.hip): the optimizer's `skip` word of a step
@@ -2695,9 +2698,10 @@ extern "C" int vl_status_or(uint32_t* dst, const void* lstm_ws, int init, vl_str
     return 0;
 }
 
-static int sgd_apply_launch(float* w, const float* g, int64_t count, const tier_table& tt, float lr, float clip_norm, const float* sumsq,
-                            float gscale, const uint32_t* skip, vl_stream_t stream) {
-    hipLaunchKernelGGL(sgd_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, tt, lr,
+// state: nullptr (the eager entry points: lr / lr_t counts) or the step state the kernel reads in its place
+static int sgd_apply_launch(float* w, const float* g, int64_t count, const tier_table& tt, float lr, const vl_step_state* state,
+                            float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+    hipLaunchKernelGGL(sgd_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, tt, lr, state,
                        clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
@@ -2706,7 +2710,7 @@ static int sgd_apply_launch(float* w, const float* g, int64_t count, const tier_
 extern "C" int vl_sgd_apply(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq, float gscale,
                             const uint32_t* skip, vl_stream_t stream) {
     VL_CHECK(w && g && count > 0, "vl_sgd_apply: bad argument");
-    return sgd_apply_launch(w, g, count, tier_table_full(count), lr, clip_norm, sumsq, gscale, skip, stream);
+    return sgd_apply_launch(w, g, count, tier_table_full(count), lr, nullptr, clip_norm, sumsq, gscale, skip, stream);
 }
 
 extern "C" int vl_sgd_apply_tiers(float* w, const float* g, int64_t count, float lr, float clip_norm, const float* sumsq, float gscale,
@@ -2714,7 +2718,7 @@ extern "C" int vl_sgd_apply_tiers(float* w, const float* g, int64_t count, float
     VL_CHECK(w && g && count > 0, "vl_sgd_apply_tiers: bad argument");
     tier_table tt;
     if (int rc = tier_table_make("vl_sgd_apply_tiers", tiers, n_tiers, count, &tt)) return rc;
-    return sgd_apply_launch(w, g, count, tt, lr, clip_norm, sumsq, gscale, skip, stream);
+    return sgd_apply_launch(w, g, count, tt, lr, nullptr, clip_norm, sumsq, gscale, skip, stream);
 }
 
 // Adam's bias-corrected step size at count `step` (TF: lr * sqrt(1 - beta2^t) / (1 - beta1^t)); host code, shared by vl_adam_apply and
@@ -2724,10 +2728,11 @@ static float adam_step_size(float lr, int step) {
     return (float)(lr * sqrt(b2t) / b1t);
 }
 
-static int adam_apply_launch(float* w, const float* g, float* m, float* v, int64_t count, const tier_table& tt, float lr_t, float clip_norm,
-                             const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
+static int adam_apply_launch(float* w, const float* g, float* m, float* v, int64_t count, const tier_table& tt, float lr_t,
+                             const vl_step_state* state, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                             vl_stream_t stream) {
     hipLaunchKernelGGL(adam_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, tt,
-                       lr_t, clip_norm, sumsq, gscale, skip);
+                       lr_t, state, clip_norm, sumsq, gscale, skip);
     VL_LAUNCH_CHECK();
     return 0;
 }
@@ -2735,7 +2740,8 @@ static int adam_apply_launch(float* w, const float* g, float* m, float* v, int64
 extern "C" int vl_adam_apply(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
                              const float* sumsq, float gscale, int step, const uint32_t* skip, vl_stream_t stream) {
     VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply: bad argument");
-    return adam_apply_launch(w, g, m, v, count, tier_table_full(count), adam_step_size(lr, step), clip_norm, sumsq, gscale, skip, stream);
+    return adam_apply_launch(w, g, m, v, count, tier_table_full(count), adam_step_size(lr, step), nullptr, clip_norm, sumsq, gscale, skip,
+                             stream);
 }
 
 extern "C" int vl_adam_apply_tiers(float* w, const float* g, float* m, float* v, int64_t count, float lr, float clip_norm,
@@ -2744,7 +2750,7 @@ extern "C" int vl_adam_apply_tiers(float* w, const float* g, float* m, float* v,
     VL_CHECK(w && g && m && v && count > 0 && step >= 1, "vl_adam_apply_tiers: bad argument");
     tier_table tt;
     if (int rc = tier_table_make("vl_adam_apply_tiers", tiers, n_tiers, count, &tt)) return rc;
-    return adam_apply_launch(w, g, m, v, count, tt, adam_step_size(lr, step), clip_norm, sumsq, gscale, skip, stream);
+    return adam_apply_launch(w, g, m, v, count, tt, adam_step_size(lr, step), nullptr, clip_norm, sumsq, gscale, skip, stream);
 }
 
 // ---- step state (vltf.h: vl_step_state): the scalars a replayed step reads from device memory -------------------------------
@@ -2792,47 +2798,17 @@ extern "C" int vl_step_state_set_ema(vl_step_state* state, float rate, vl_stream
     return 0;
 }
 
-// the update kernels above with lr / Adam's step size read from the step state
-__global__ void sgd_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, tier_table tt, const vl_step_state* __restrict__ st,
-                                    float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
-    sgd_apply_body(w, g, tt, st->lr, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-__global__ void adam_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                     tier_table tt, const vl_step_state* __restrict__ st, float clip_norm, const float* __restrict__ sumsq,
-                                     float gscale, const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
-    adam_apply_body(w, g, m, v, tt, st->adam_lr, clip_norm, sumsq, gscale,
-                    (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-static int sgd_apply_st_launch(float* w, const float* g, int64_t count, const tier_table& tt, const vl_step_state* state, float clip_norm,
-                               const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
-    hipLaunchKernelGGL(sgd_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, tt, state,
-                       clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
-}
-
-static int adam_apply_st_launch(float* w, const float* g, float* m, float* v, int64_t count, const tier_table& tt, const vl_step_state* state,
-                                float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
-    hipLaunchKernelGGL(adam_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, tt,
-                       state, clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
-}
-
+// the update entry points above with lr / Adam's step size read from the step state: the same kernels, handed the state
 extern "C" int vl_sgd_apply_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
                                float gscale, const uint32_t* skip, vl_stream_t stream) {
     VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_st: bad argument");
-    return sgd_apply_st_launch(w, g, count, tier_table_full(count), state, clip_norm, sumsq, gscale, skip, stream);
+    return sgd_apply_launch(w, g, count, tier_table_full(count), 0.f, state, clip_norm, sumsq, gscale, skip, stream);
 }
 
 extern "C" int vl_adam_apply_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
                                 const float* sumsq, float gscale, const uint32_t* skip, vl_stream_t stream) {
     VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_st: bad argument");
-    return adam_apply_st_launch(w, g, m, v, count, tier_table_full(count), state, clip_norm, sumsq, gscale, skip, stream);
+    return adam_apply_launch(w, g, m, v, count, tier_table_full(count), 0.f, state, clip_norm, sumsq, gscale, skip, stream);
 }
 
 extern "C" int vl_sgd_apply_tiers_st(float* w, const float* g, int64_t count, const vl_step_state* state, float clip_norm, const float* sumsq,
@@ -2840,7 +2816,7 @@ extern "C" int vl_sgd_apply_tiers_st(float* w, const float* g, int64_t count, co
     VL_CHECK(w && g && state && count > 0, "vl_sgd_apply_tiers_st: bad argument");
     tier_table tt;
     if (int rc = tier_table_make("vl_sgd_apply_tiers_st", tiers, n_tiers, count, &tt)) return rc;
-    return sgd_apply_st_launch(w, g, count, tt, state, clip_norm, sumsq, gscale, skip, stream);
+    return sgd_apply_launch(w, g, count, tt, 0.f, state, clip_norm, sumsq, gscale, skip, stream);
 }
 
 extern "C" int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float* v, int64_t count, const vl_step_state* state, float clip_norm,
@@ -2849,55 +2825,41 @@ extern "C" int vl_adam_apply_tiers_st(float* w, const float* g, float* m, float*
     VL_CHECK(w && g && m && v && state && count > 0, "vl_adam_apply_tiers_st: bad argument");
     tier_table tt;
     if (int rc = tier_table_make("vl_adam_apply_tiers_st", tiers, n_tiers, count, &tt)) return rc;
-    return adam_apply_st_launch(w, g, m, v, count, tt, state, clip_norm, sumsq, gscale, skip, stream);
+    return adam_apply_launch(w, g, m, v, count, tt, 0.f, state, clip_norm, sumsq, gscale, skip, stream);
 }
 
 // ---- momentum / Nesterov update (vltf.h: vl_momentum_apply): two entry points, a NULL table is the full range ---------------------
-__global__ void momentum_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, tier_table tt,
-                                         const vl_step_state* __restrict__ st, float momentum, int nesterov, float clip_norm,
-                                         const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
-    momentum_apply_body(w, g, a, tt, st->lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
-                        (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-static int momentum_args(const char* who, const float* w, const float* g, const float* accum, int64_t count, float momentum,
-                         const vl_lr_tier* tiers, int n_tiers, tier_table* tt) {
+static int momentum_apply_launch(const char* who, float* w, const float* g, float* accum, int64_t count, float lr, const vl_step_state* state,
+                                 float momentum, int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                                 const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream) {
     VL_CHECK(w && g && accum && count > 0, "%s: bad argument", who);
     VL_CHECK(momentum > 0.f && momentum < 1.f, "%s: momentum must lie in (0, 1), got %g", who, (double)momentum);   // (NaN fails)
-    if (!tiers && n_tiers == 0) {
-        *tt = tier_table_full(count);
-        return 0;
-    }
-    return tier_table_make(who, tiers, n_tiers, count, tt);
+    tier_table tt;
+    if (int rc = tier_table_make(who, tiers, n_tiers, count, &tt, true)) return rc;
+    hipLaunchKernelGGL(momentum_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt, lr, state,
+                       momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int vl_momentum_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov,
                                  float clip_norm, const float* sumsq, float gscale, const uint32_t* skip, const vl_lr_tier* tiers,
                                  int n_tiers, vl_stream_t stream) {
-    tier_table tt;
-    if (int rc = momentum_args("vl_momentum_apply", w, g, accum, count, momentum, tiers, n_tiers, &tt)) return rc;
-    hipLaunchKernelGGL(momentum_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt, lr,
-                       momentum, nesterov, clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return momentum_apply_launch("vl_momentum_apply", w, g, accum, count, lr, nullptr, momentum, nesterov, clip_norm, sumsq, gscale, skip,
+                                 tiers, n_tiers, stream);
 }
 
 extern "C" int vl_momentum_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
                                     int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
                                     const vl_lr_tier* tiers, int n_tiers, vl_stream_t stream) {
     VL_CHECK(state, "vl_momentum_apply_st: bad argument");
-    tier_table tt;
-    if (int rc = momentum_args("vl_momentum_apply_st", w, g, accum, count, momentum, tiers, n_tiers, &tt)) return rc;
-    hipLaunchKernelGGL(momentum_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, tt,
-                       state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return momentum_apply_launch("vl_momentum_apply_st", w, g, accum, count, 0.f, state, momentum, nesterov, clip_norm, sumsq, gscale, skip,
+                                 tiers, n_tiers, stream);
 }
 
 // ---- gradient accumulation over micro-batches (vltf.h: vl_grad_accumulate) ------------------------------------------------------------
 // MODE 0: acc = g.  MODE 1: acc = acc + g.  MODE 2: g = acc + g (acc stays).  One fp32 add per element, shared by the scalar head / tail
-// and the 16-byte interior; the ranges are walked as in sgd_apply_body, so an element outside every range is never addressed.
+// and the 16-byte interior; the ranges go through range_walk, so an element outside every range is never addressed.
 __device__ __forceinline__ float acc_elem(float a, float g) {
 #pragma clang fp contract(off)
     return a + g;
@@ -2907,38 +2869,28 @@ template <int MODE>
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ g, tier_table tt) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
     const int phase = align_phase(acc, g, nullptr, nullptr);
-    for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) {
-            if (MODE == 0) acc[i] = g[i];
-            else if (MODE == 1) acc[i] = acc_elem(acc[i], g[i]);
-            else g[i] = acc_elem(acc[i], g[i]);
-        }
-        float4* __restrict__ a4 = reinterpret_cast<float4*>(acc + v0);
-        float4* __restrict__ g4 = reinterpret_cast<float4*>(g + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            const float4 gv = g4[i];
-            if (MODE == 0) {
-                a4[i] = gv;
-            } else {
-                const float4 av = a4[i];
-                float4 r;
-                r.x = acc_elem(av.x, gv.x);
-                r.y = acc_elem(av.y, gv.y);
-                r.z = acc_elem(av.z, gv.z);
-                r.w = acc_elem(av.w, gv.w);
-                if (MODE == 1) a4[i] = r;
-                else g4[i] = r;
-            }
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) {
-            if (MODE == 0) acc[i] = g[i];
-            else if (MODE == 1) acc[i] = acc_elem(acc[i], g[i]);
-            else g[i] = acc_elem(acc[i], g[i]);
-        }
-    }
+    for (int k = 0; k < tt.n; ++k)
+        range_walk(tt.t[k].begin, tt.t[k].end, phase, i0, step,
+                   [&](int64_t i) {
+                       if (MODE == 0) acc[i] = g[i];
+                       else if (MODE == 1) acc[i] = acc_elem(acc[i], g[i]);
+                       else g[i] = acc_elem(acc[i], g[i]);
+                   },
+                   [&](int64_t v0, int64_t i) {
+                       const float4 gv = vec4(g, v0, i);
+                       if (MODE == 0) {
+                           vec4(acc, v0, i) = gv;
+                       } else {
+                           const float4 av = vec4(acc, v0, i);
+                           float4 r;
+                           r.x = acc_elem(av.x, gv.x);
+                           r.y = acc_elem(av.y, gv.y);
+                           r.z = acc_elem(av.z, gv.z);
+                           r.w = acc_elem(av.w, gv.w);
+                           if (MODE == 1) vec4(acc, v0, i) = r;
+                           else vec4(g, v0, i) = r;
+                       }
+                   });
 }
 
 extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode, const vl_lr_tier* ranges, int n_ranges,
@@ -2946,11 +2898,7 @@ extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode,
     VL_CHECK(acc && g && count > 0, "vl_grad_accumulate: bad argument");
     VL_CHECK(mode >= 0 && mode <= 2, "vl_grad_accumulate: mode must be 0 (store), 1 (add) or 2 (final), got %d", mode);
     tier_table tt;
-    if (!ranges && n_ranges == 0) {
-        tt = tier_table_full(count);
-    } else if (int rc = tier_table_make("vl_grad_accumulate", ranges, n_ranges, count, &tt)) {
-        return rc;
-    }
+    if (int rc = tier_table_make("vl_grad_accumulate", ranges, n_ranges, count, &tt, true)) return rc;
     const dim3 grid(grid_for(count, 256, 4096)), block(256);
     if (mode == 0) hipLaunchKernelGGL(grad_accumulate_kernel<0>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
     else if (mode == 1) hipLaunchKernelGGL(grad_accumulate_kernel<1>, grid, block, 0, (hipStream_t)stream, acc, g, tt);
@@ -2961,7 +2909,7 @@ extern "C" int vl_grad_accumulate(float* acc, float* g, int64_t count, int mode,
 
 // ---- exponential moving average of the weights (vltf.h: vl_ema_update) ------------------------------------------------------------------
 // s' = fma(rate, w - s, s): two roundings, spelled out, shared by the scalar head / tail and the 16-byte interior; the ranges are walked
-// as in sgd_apply_body, so an element outside every range is never addressed.
+// by range_walk, so an element outside every range is never addressed.
 __device__ __forceinline__ float ema_elem(float s, float w, float rate) {
 #pragma clang fp contract(off)
     const float d = w - s;
@@ -2971,66 +2919,49 @@ __device__ __forceinline__ float ema_elem(float s, float w, float rate) {
 __device__ __forceinline__ void ema_update_body(float* __restrict__ s, const float* __restrict__ w, const tier_table& tt, float rate, int64_t i0,
                                                 int64_t step) {
     const int phase = align_phase(s, w, nullptr, nullptr);
-    for (int k = 0; k < tt.n; ++k) {
-        const int64_t begin = tt.t[k].begin, end = tt.t[k].end;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) s[i] = ema_elem(s[i], w[i], rate);
-        float4* __restrict__ s4 = reinterpret_cast<float4*>(s + v0);
-        const float4* __restrict__ w4 = reinterpret_cast<const float4*>(w + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            float4 sv = s4[i];
-            const float4 wv = w4[i];
-            sv.x = ema_elem(sv.x, wv.x, rate);
-            sv.y = ema_elem(sv.y, wv.y, rate);
-            sv.z = ema_elem(sv.z, wv.z, rate);
-            sv.w = ema_elem(sv.w, wv.w, rate);
-            s4[i] = sv;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) s[i] = ema_elem(s[i], w[i], rate);
-    }
+    for (int k = 0; k < tt.n; ++k)
+        range_walk(tt.t[k].begin, tt.t[k].end, phase, i0, step, [&](int64_t i) { s[i] = ema_elem(s[i], w[i], rate); },
+                   [&](int64_t v0, int64_t i) {
+                       float4 sv = vec4(s, v0, i);
+                       const float4 wv = vec4(w, v0, i);
+                       sv.x = ema_elem(sv.x, wv.x, rate);
+                       sv.y = ema_elem(sv.y, wv.y, rate);
+                       sv.z = ema_elem(sv.z, wv.z, rate);
+                       sv.w = ema_elem(sv.w, wv.w, rate);
+                       vec4(s, v0, i) = sv;
+                   });
 }
 
+// st != nullptr: the rate from the state (momentum_apply_kernel)
 __global__ void ema_update_kernel(float* __restrict__ s, const float* __restrict__ w, tier_table tt, float rate,
-                                  const uint32_t* __restrict__ skip) {
+                                  const vl_step_state* __restrict__ st, const uint32_t* __restrict__ skip) {
+    if (st) rate = st->ema_rate;
     if (skip && *skip) return;
     ema_update_body(s, w, tt, rate, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-__global__ void ema_update_st_kernel(float* __restrict__ s, const float* __restrict__ w, tier_table tt, const vl_step_state* __restrict__ st,
-                                     const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
-    ema_update_body(s, w, tt, st->ema_rate, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-static int ema_args(const char* who, const float* shadow, const float* w, int64_t count, const vl_lr_tier* ranges, int n_ranges,
-                    tier_table* tt) {
+// state == nullptr: the rate counts, and is checked
+static int ema_update_launch(const char* who, float* shadow, const float* w, int64_t count, float rate, const vl_step_state* state,
+                             const uint32_t* skip, const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream) {
     VL_CHECK(shadow && w && count > 0, "%s: bad argument", who);
-    if (!ranges && n_ranges == 0) {
-        *tt = tier_table_full(count);
-        return 0;
-    }
-    return tier_table_make(who, ranges, n_ranges, count, tt);
+    tier_table tt;
+    if (int rc = tier_table_make(who, ranges, n_ranges, count, &tt, true)) return rc;
+    VL_CHECK(state || (rate > 0.f && rate <= 1.f), "%s: rate must lie in (0, 1], got %g", who, (double)rate);   // (NaN fails)
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, shadow, w, tt, rate, state,
+                       skip);
+    VL_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int vl_ema_update(float* shadow, const float* w, int64_t count, float rate, const uint32_t* skip, const vl_lr_tier* ranges,
                              int n_ranges, vl_stream_t stream) {
-    tier_table tt;
-    if (int rc = ema_args("vl_ema_update", shadow, w, count, ranges, n_ranges, &tt)) return rc;
-    VL_CHECK(rate > 0.f && rate <= 1.f, "vl_ema_update: rate must lie in (0, 1], got %g", (double)rate);   // (NaN fails)
-    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, shadow, w, tt, rate, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return ema_update_launch("vl_ema_update", shadow, w, count, rate, nullptr, skip, ranges, n_ranges, stream);
 }
 
 extern "C" int vl_ema_update_st(float* shadow, const float* w, int64_t count, const vl_step_state* state, const uint32_t* skip,
                                 const vl_lr_tier* ranges, int n_ranges, vl_stream_t stream) {
     VL_CHECK(state, "vl_ema_update_st: bad argument");
-    tier_table tt;
-    if (int rc = ema_args("vl_ema_update_st", shadow, w, count, ranges, n_ranges, &tt)) return rc;
-    hipLaunchKernelGGL(ema_update_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, shadow, w, tt, state, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return ema_update_launch("vl_ema_update_st", shadow, w, count, 0.f, state, skip, ranges, n_ranges, stream);
 }
 
 // ---- per-variable gradient / weight statistics (vltf.h: vl_tensor_stats) ----------------------------------------------------------------
@@ -3332,10 +3263,8 @@ static int lars_table_make(const char* who, const vl_lars_range* ranges, int n_r
     int64_t prev = 0;
     for (int k = 0; k < n_ranges; ++k) {
         const vl_lars_range& r = ranges[k];
-        VL_CHECK(r.begin >= prev && r.end > r.begin && r.end <= count,
-                 "%s: range %d = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
-                 (long long)r.end, (long long)count);
-        VL_CHECK(r.lr_mult > 0.f && r.lr_mult <= 3.402823466e38f, "%s: range %d: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
+        if (int rc = range_bounds_check(who, "range ", k, "", r.begin, r.end, prev, count)) return rc;
+        if (int rc = range_factor_check(who, "range ", k, "", "lr_mult", r.lr_mult, true)) return rc;
         VL_CHECK(r.trust_index >= -1 && r.trust_index < n_trust, "%s: range %d: trust_index %d is neither -1 nor inside the %d trust entries",
                  who, k, r.trust_index, n_trust);
         out->r[k] = r;
@@ -3358,50 +3287,43 @@ __device__ __forceinline__ void lars_apply_body(float* __restrict__ w, const flo
     }
 }
 
+// st != nullptr: lr from the state (momentum_apply_kernel)
 __global__ void lars_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, lars_table lt,
-                                  const float* __restrict__ trust, float lr, float momentum, int nesterov, float clip_norm,
-                                  const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
+                                  const float* __restrict__ trust, float lr, const vl_step_state* __restrict__ st, float momentum,
+                                  int nesterov, float clip_norm, const float* __restrict__ sumsq, float gscale,
+                                  const uint32_t* __restrict__ skip) {
+    if (st) lr = st->lr;
     if (skip && *skip) return;
-    lars_apply_body(w, g, a, lt, trust, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                    (int64_t)gridDim.x * blockDim.x);
-}
-
-__global__ void lars_apply_st_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ a, lars_table lt,
-                                     const float* __restrict__ trust, const vl_step_state* __restrict__ st, float momentum, int nesterov,
-                                     float clip_norm, const float* __restrict__ sumsq, float gscale, const uint32_t* __restrict__ skip) {
-    if (skip && *skip) return;
-    lars_apply_body(w, g, a, lt, trust, st->lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
+    lars_apply_body(w, g, a, lt, trust, lr, momentum, nesterov != 0, clip_norm, sumsq, gscale,
                     (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
-static int lars_args(const char* who, const float* w, const float* g, const float* accum, int64_t count, float momentum,
-                     const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, lars_table* lt) {
+static int lars_apply_launch(const char* who, float* w, const float* g, float* accum, int64_t count, float lr, const vl_step_state* state,
+                             float momentum, int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
+                             const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream) {
     VL_CHECK(w && g && accum && count > 0, "%s: bad argument", who);
     VL_CHECK(momentum > 0.f && momentum < 1.f, "%s: momentum must lie in (0, 1), got %g", who, (double)momentum);   // (NaN fails)
-    return lars_table_make(who, ranges, n_ranges, count, trust, n_trust, lt);
+    lars_table lt;
+    if (int rc = lars_table_make(who, ranges, n_ranges, count, trust, n_trust, &lt)) return rc;
+    hipLaunchKernelGGL(lars_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, lt, trust, lr,
+                       state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
+    VL_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int vl_lars_apply(float* w, const float* g, float* accum, int64_t count, float lr, float momentum, int nesterov, float clip_norm,
                              const float* sumsq, float gscale, const uint32_t* skip, const vl_lars_range* ranges, int n_ranges,
                              const float* trust, int n_trust, vl_stream_t stream) {
-    lars_table lt;
-    if (int rc = lars_args("vl_lars_apply", w, g, accum, count, momentum, ranges, n_ranges, trust, n_trust, &lt)) return rc;
-    hipLaunchKernelGGL(lars_apply_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, lt, trust, lr,
-                       momentum, nesterov, clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return lars_apply_launch("vl_lars_apply", w, g, accum, count, lr, nullptr, momentum, nesterov, clip_norm, sumsq, gscale, skip, ranges,
+                             n_ranges, trust, n_trust, stream);
 }
 
 extern "C" int vl_lars_apply_st(float* w, const float* g, float* accum, int64_t count, const vl_step_state* state, float momentum,
                                 int nesterov, float clip_norm, const float* sumsq, float gscale, const uint32_t* skip,
                                 const vl_lars_range* ranges, int n_ranges, const float* trust, int n_trust, vl_stream_t stream) {
     VL_CHECK(state, "vl_lars_apply_st: bad argument");
-    lars_table lt;
-    if (int rc = lars_args("vl_lars_apply_st", w, g, accum, count, momentum, ranges, n_ranges, trust, n_trust, &lt)) return rc;
-    hipLaunchKernelGGL(lars_apply_st_kernel, dim3(grid_for(count, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, accum, lt, trust,
-                       state, momentum, nesterov, clip_norm, sumsq, gscale, skip);
-    VL_LAUNCH_CHECK();
-    return 0;
+    return lars_apply_launch("vl_lars_apply_st", w, g, accum, count, 0.f, state, momentum, nesterov, clip_norm, sumsq, gscale, skip, ranges,
+                             n_ranges, trust, n_trust, stream);
 }
 
 // ---- LAMB (vltf.h: vl_lamb_moments, vl_lamb_apply): Adam's moments, a per-tensor trust ratio |w| / |u| on the device, decoupled decay -----
@@ -3421,12 +3343,10 @@ static int lamb_table_make(const char* who, const vl_lamb_range* ranges, int n_r
     int64_t prev = 0, chunks = 0;
     for (int k = 0; k < n_ranges; ++k) {
         const vl_lamb_range& r = ranges[k];
-        VL_CHECK(r.begin >= prev && r.end > r.begin && (count < 0 || r.end <= count),
-                 "%s: ranges[%d] = [%lld, %lld) is empty, unsorted, overlaps its predecessor or leaves [0, %lld)", who, k, (long long)r.begin,
-                 (long long)r.end, (long long)count);
+        if (int rc = range_bounds_check(who, "ranges[", k, "]", r.begin, r.end, prev, count)) return rc;
         VL_CHECK(r.end - r.begin <= 0x7FFFFFFFll, "%s: ranges[%d] has %lld elements, more than 2^31 - 1", who, k, (long long)(r.end - r.begin));
-        VL_CHECK(r.lr_mult > 0.f && r.lr_mult <= 3.402823466e38f, "%s: ranges[%d]: lr_mult must be finite and > 0", who, k);   // (NaN fails both)
-        VL_CHECK(r.decay >= 0.f && r.decay <= 3.402823466e38f, "%s: ranges[%d]: decay must be finite and >= 0", who, k);
+        if (int rc = range_factor_check(who, "ranges[", k, "]", "lr_mult", r.lr_mult, true)) return rc;
+        if (int rc = range_factor_check(who, "ranges[", k, "]", "decay", r.decay, false)) return rc;
         VL_CHECK(r.trust_index >= -1 && (count < 0 || r.trust_index < n_trust),
                  "%s: ranges[%d]: trust_index %d is neither -1 nor inside the %d entries of trust", who, k, r.trust_index, n_trust);
         out->r[k] = r;
@@ -3725,26 +3645,19 @@ __global__ void lamb_apply_kernel(float* __restrict__ w, const float* __restrict
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
     const int phase = align_phase(w, m, v, nullptr);
     for (int k = 0; k < lt.n; ++k) {
-        const int64_t begin = lt.r[k].begin, end = lt.r[k].end;
         const int ti = lt.r[k].trust_index;
         const float a = (lr * lt.r[k].lr_mult) * (ti < 0 ? 1.f : trust[ti]);
         const float decay = lt.r[k].decay;
-        int64_t v0, v1;
-        tier_split(begin, end, phase, v0, v1);
-        for (int64_t i = begin + i0; i < v0; i += step) lamb_apply_elem(w[i], m[i], v[i], a, c1, c2, eps, decay);
-        float4* __restrict__ w4 = reinterpret_cast<float4*>(w + v0);
-        const float4* __restrict__ m4 = reinterpret_cast<const float4*>(m + v0);
-        const float4* __restrict__ q4 = reinterpret_cast<const float4*>(v + v0);
-        for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-            float4 wv = w4[i];
-            const float4 mv = m4[i], qv = q4[i];
-            lamb_apply_elem(wv.x, mv.x, qv.x, a, c1, c2, eps, decay);
-            lamb_apply_elem(wv.y, mv.y, qv.y, a, c1, c2, eps, decay);
-            lamb_apply_elem(wv.z, mv.z, qv.z, a, c1, c2, eps, decay);
-            lamb_apply_elem(wv.w, mv.w, qv.w, a, c1, c2, eps, decay);
-            w4[i] = wv;
-        }
-        for (int64_t i = v1 + i0; i < end; i += step) lamb_apply_elem(w[i], m[i], v[i], a, c1, c2, eps, decay);
+        range_walk(lt.r[k].begin, lt.r[k].end, phase, i0, step, [&](int64_t i) { lamb_apply_elem(w[i], m[i], v[i], a, c1, c2, eps, decay); },
+                   [&](int64_t v0, int64_t i) {
+                       float4 wv = vec4(w, v0, i);
+                       const float4 mv = vec4(m, v0, i), qv = vec4(v, v0, i);
+                       lamb_apply_elem(wv.x, mv.x, qv.x, a, c1, c2, eps, decay);
+                       lamb_apply_elem(wv.y, mv.y, qv.y, a, c1, c2, eps, decay);
+                       lamb_apply_elem(wv.z, mv.z, qv.z, a, c1, c2, eps, decay);
+                       lamb_apply_elem(wv.w, mv.w, qv.w, a, c1, c2, eps, decay);
+                       vec4(w, v0, i) = wv;
+                   });
     }
 }
 
@@ -3824,20 +3737,16 @@ __device__ __forceinline__ float fc_dropout_elem(float y, uint64_t s, int64_t e,
 }
 
 __device__ __forceinline__ void fc_dropout_body(float* __restrict__ y, int64_t count, float keep, uint64_t s, int64_t i0, int64_t step) {
-    int64_t v0, v1;
-    tier_split(0, count, align_phase(y, nullptr, nullptr, nullptr), v0, v1);
-    for (int64_t e = i0; e < v0; e += step) y[e] = fc_dropout_elem(y[e], s, e, keep);
-    float4* __restrict__ y4 = reinterpret_cast<float4*>(y + v0);
-    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-        const int64_t e = v0 + 4 * i;
-        float4 v = y4[i];
-        v.x = fc_dropout_elem(v.x, s, e, keep);
-        v.y = fc_dropout_elem(v.y, s, e + 1, keep);
-        v.z = fc_dropout_elem(v.z, s, e + 2, keep);
-        v.w = fc_dropout_elem(v.w, s, e + 3, keep);
-        y4[i] = v;
-    }
-    for (int64_t e = v1 + i0; e < count; e += step) y[e] = fc_dropout_elem(y[e], s, e, keep);
+    range_walk(0, count, align_phase(y, nullptr, nullptr, nullptr), i0, step, [&](int64_t e) { y[e] = fc_dropout_elem(y[e], s, e, keep); },
+               [&](int64_t v0, int64_t i) {
+                   const int64_t e = v0 + 4 * i;
+                   float4 v = vec4(y, v0, i);
+                   v.x = fc_dropout_elem(v.x, s, e, keep);
+                   v.y = fc_dropout_elem(v.y, s, e + 1, keep);
+                   v.z = fc_dropout_elem(v.z, s, e + 2, keep);
+                   v.w = fc_dropout_elem(v.w, s, e + 3, keep);
+                   vec4(y, v0, i) = v;
+               });
 }
 
 __global__ __launch_bounds__(256) void fc_dropout_fwd_kernel(float* __restrict__ y, int64_t count, float keep, uint64_t seed, uint32_t salt) {
@@ -3880,21 +3789,16 @@ __device__ __forceinline__ float relu_dropout_grad_elem(float d, float y, float 
 
 __global__ __launch_bounds__(256) void relu_dropout_grad_kernel(float* __restrict__ d, const float* __restrict__ y, int64_t count, float keep) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
-    int64_t v0, v1;
-    tier_split(0, count, align_phase(d, y, nullptr, nullptr), v0, v1);
-    for (int64_t e = i0; e < v0; e += step) d[e] = relu_dropout_grad_elem(d[e], y[e], keep);
-    float4* __restrict__ d4 = reinterpret_cast<float4*>(d + v0);
-    const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + v0);
-    for (int64_t i = i0; i < (v1 - v0) / 4; i += step) {
-        float4 dv = d4[i];
-        const float4 yv = y4[i];
-        dv.x = relu_dropout_grad_elem(dv.x, yv.x, keep);
-        dv.y = relu_dropout_grad_elem(dv.y, yv.y, keep);
-        dv.z = relu_dropout_grad_elem(dv.z, yv.z, keep);
-        dv.w = relu_dropout_grad_elem(dv.w, yv.w, keep);
-        d4[i] = dv;
-    }
-    for (int64_t e = v1 + i0; e < count; e += step) d[e] = relu_dropout_grad_elem(d[e], y[e], keep);
+    range_walk(0, count, align_phase(d, y, nullptr, nullptr), i0, step, [&](int64_t e) { d[e] = relu_dropout_grad_elem(d[e], y[e], keep); },
+               [&](int64_t v0, int64_t i) {
+                   float4 dv = vec4(d, v0, i);
+                   const float4 yv = vec4(y, v0, i);
+                   dv.x = relu_dropout_grad_elem(dv.x, yv.x, keep);
+                   dv.y = relu_dropout_grad_elem(dv.y, yv.y, keep);
+                   dv.z = relu_dropout_grad_elem(dv.z, yv.z, keep);
+                   dv.w = relu_dropout_grad_elem(dv.w, yv.w, keep);
+                   vec4(d, v0, i) = dv;
+               });
 }
 
 extern "C" int vl_relu_dropout_grad(float* d, const float* y, int64_t count, float keep, vl_stream_t stream) {
