@@ -77,7 +77,9 @@ int vl_input_prep_u8(const uint8_t* src, float* dst, int n, int raw_h, int raw_w
  * (y0, x0) bit for bit.  mirror, mean_bgr may be NULL; src, dst, box may not. */
 int vl_input_prep_u8_box(const uint8_t* src, float* dst, int n, int raw_h, int raw_w, int out_h, int out_w, const int32_t* box,
                          const uint8_t* mirror, const float* mean_bgr, int dst_halo, int dst_phase, vl_stream_t stream);
-/* The reference's own feed format: fp32 NHWC placeholder (models/model.py:54) -> NCHW (+halo, dst_phase as above). */
+/* The reference's own feed format: fp32 NHWC placeholder (models/model.py:54) -> NCHW (+halo, dst_phase as above).  A copy of the
+ * pixels, bit for bit, and of nothing else: unlike vl_input_prep_u8 it writes NO halo or phase-padding column, in the interior rows
+ * either -- the whole halo must have been zeroed once (tests/test_feed_geometry_gpu.py holds it to that). */
 int vl_nhwc_to_nchw(const float* src, float* dst, int n, int h, int w, int c, int dst_halo, int dst_phase, vl_stream_t stream);
 int vl_nchw_to_nhwc(const float* src, float* dst, int n, int c, int h, int w, vl_stream_t stream);
 
