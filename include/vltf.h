@@ -349,6 +349,42 @@ int vl_lstm_seq_fwd_st(const float* gx, const float* kh, const float* h0, const 
 int vl_lstm_seq_bwd_st(const float* dout, const float* kh, const float* act, const float* cseq, const float* c0, float* dz,
                        float* dh0, float* dc0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
                        uint32_t tag_offset, vl_stream_t stream);
+/* ---- bidirectional layer: both directions in ONE launch (tf.nn.bidirectional_dynamic_rnn, outputs concatenated) -------------------------
+ * A forward cell (_fw) and a backward cell (_bw) of the same hidden size H read the same clips.  The backward cell runs over the reversed
+ * live prefix (tf.reverse_sequence with seq_len): its processing step s of clip b works on time index L_b - 1 - s for s < L_b, and every
+ * per-row tensor of the _bw set is addressed by that TIME index, so row r of hseq_fw and of hseq_bw belong to the same frame.  Steps
+ * s >= L_b are dead and sit on row s: the dead-row contract above holds for both sets (every row written, dead rows of gx / dout never
+ * read).  hprev_bw[r] is the h that entered the step of row r -- the backward cell's output of the row AFTER it in time, h0_bw on the last
+ * live row -- so hprev_bw^T dz_bw is the recurrent weight gradient; the cell-state predecessor in the backward launch is likewise the
+ * previous processing step.  seq_len == NULL: L_b = T.
+ * Each argument set is dense as in vl_lstm_seq_fwd / _bwd, except hseq_fw / hseq_bw (written) and dout_fw / dout_bw (read, nullable),
+ * whose rows are hseq_ld / dout_ld floats apart (>= H): with hseq_bw = hseq_fw + H and a stride of 2H a layer's output is one
+ * [batch T][2H] tensor, and its gradient is read in place.
+ * H <= 512 only (the cluster form; no per-clip form), and the device must hold both directions of one group: CUs >= 2 ceil(H/16).
+ * Otherwise the calls return an error and launch nothing.  A launch runs 2 G ceil(H/16) workgroups, G <= CUs / (2 ceil(H/16)) groups of
+ * <= 8 clips per direction; larger batches take further launches.  `ws` is a workspace of vl_lstm_seq_ws_bytes (the exchange words of the
+ * two directions are disjoint slices of it); a launch uses T + 1 tags.  The eager pair refuses a stream that is being captured. */
+int vl_lstm_seq_bi_fwd(const float* gx_fw, const float* gx_bw, const float* kh_fw, const float* kh_bw, const float* h0_fw,
+                       const float* h0_bw, const float* c0_fw, const float* c0_bw, float* act_fw, float* act_bw, float* cseq_fw,
+                       float* cseq_bw, float* hseq_fw, float* hseq_bw, int64_t hseq_ld, float* hprev_fw, float* hprev_bw, int batch, int T,
+                       int H, float forget_bias, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream);
+int vl_lstm_seq_bi_bwd(const float* dout_fw, const float* dout_bw, int64_t dout_ld, const float* kh_fw, const float* kh_bw,
+                       const float* act_fw, const float* act_bw, const float* cseq_fw, const float* cseq_bw, const float* c0_fw,
+                       const float* c0_bw, float* dz_fw, float* dz_bw, float* dh0_fw, float* dh0_bw, float* dc0_fw, float* dc0_bw, int batch,
+                       int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream);
+/* Replay-safe forms (no lengths), tags as vl_lstm_seq_fwd_st: launch k of a call uses base origin + tag_offset + k (T + 1);
+ * vl_lstm_seq_bi_tag_span = launches x (T + 1), launches = ceil(batch / (8 (CUs / (2 ceil(H/16))))); 0 where the calls are refused. */
+size_t vl_lstm_seq_bi_tag_span(int batch, int T, int H);
+int vl_lstm_seq_bi_fwd_st(const float* gx_fw, const float* gx_bw, const float* kh_fw, const float* kh_bw, const float* h0_fw,
+                          const float* h0_bw, const float* c0_fw, const float* c0_bw, float* act_fw, float* act_bw, float* cseq_fw,
+                          float* cseq_bw, float* hseq_fw, float* hseq_bw, int64_t hseq_ld, float* hprev_fw, float* hprev_bw, int batch,
+                          int T, int H, float forget_bias, void* ws, size_t ws_bytes, const vl_step_state* state, uint32_t tag_offset,
+                          vl_stream_t stream);
+int vl_lstm_seq_bi_bwd_st(const float* dout_fw, const float* dout_bw, int64_t dout_ld, const float* kh_fw, const float* kh_bw,
+                          const float* act_fw, const float* act_bw, const float* cseq_fw, const float* cseq_bw, const float* c0_fw,
+                          const float* c0_bw, float* dz_fw, float* dz_bw, float* dh0_fw, float* dh0_bw, float* dc0_fw, float* dc0_bw,
+                          int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state, uint32_t tag_offset,
+                          vl_stream_t stream);
 /* Zeroes the exchange words of `ws` (not its time-out word), on the stream: lets the owner of a workspace restart its tags. */
 int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream);
 /* Synchronous read-and-reset of the time-out flag in `ws`: *timed_out = 1 if a workgroup of ANY cluster-form launch on `ws` since

@@ -73,6 +73,10 @@ class ComposedEngine(GraphEngine):
                             % head.input_fusion)
         if enc_cfg.classifier not in ("lstm", "fc"):
             raise VltfError("pipeline 1 of the two-pipeline model needs a classifier (lstm | fc)")
+        if getattr(enc_cfg, "lstm_bidirectional", False) or getattr(head, "lstm_bidirectional", False):
+            raise VltfError("lstm_bidirectional is not built for the two-pipeline model: its decoder takes pipeline 1's output as the "
+                            "state of a unidirectional LSTM, and its heads are specified by HeadConfig, which has no such option "
+                            "(use GraphEngine with PipelineSpec(lstm_bidirectional=True) for a pipeline without a state input)")
         self.h = head
         pipes, datasets = two_pipelines(enc_cfg, head, max_clips, scopes)
         super().__init__(pipes, datasets, head.num_classes, device, training, dp, optimizer=enc_cfg.optimizer,

@@ -124,17 +124,49 @@ struct LstmClusterArgs {
     const vl_step_state* state;   // ST kernels: the tag origin, read when the kernel runs (vl_lstm_seq_fwd_st / _bwd_st)
 };
 
+// ---- bidirectional: both directions of a layer in one launch ----------------------------------------------------------------------------
+// tf.nn.bidirectional_dynamic_rnn: a forward and a backward cell over the same clips; the backward cell runs over the reversed live
+// prefix (tf.reverse_sequence) and its outputs are stored at the time index they belong to.  The two directions are independent chains of
+// T dependent steps, and the cluster form already splits the device into groups that never talk to each other: so the grid holds
+// 2 G W workgroups, G groups per direction with the SAME clip plan, and the chain is paid once.  blockIdx.x -> virtual group
+// vg = blockIdx.x % 2G (direction vg / G, group vg % G; a virtual group's workgroups share blockIdx.x % 8 when 2G is a multiple of 8),
+// workgroup blockIdx.x / 2G.  Each direction has its own argument set (its tensors and weights; B, T, H, G, cpg, the workspace and the
+// tag base are the same in both); the exchange words of (direction, group) are those of virtual group vg in the [parity][group]...
+// layout, 2 G <= maxG of them, so vl_lstm_seq_ws_bytes is unchanged.  The protocol is untouched: a launch uses T + 1 tags, shared by
+// its directions because their words are disjoint, and every workgroup publishes and gathers at every epoch -- no wait depends on the
+// lengths or on the direction (only WHICH ROW a gate thread reads and writes does).
+struct LstmBiArgs {
+    LstmClusterArgs d[2];     // [0] forward in time, [1] backward
+    int64_t ld;               // row stride of hseq (forward launch) / dout (backward launch): a layer's [B T][2H] output, no concat copy
+};
+
+// the argument type of a kernel, and a workgroup's own argument set in it
+template <bool BI> struct ClusterArgsOf { typedef LstmClusterArgs type; };
+template <> struct ClusterArgsOf<true> { typedef LstmBiArgs type; };
+__device__ __forceinline__ const LstmClusterArgs& own_args(const LstmClusterArgs& q, bool) { return q; }
+__device__ __forceinline__ const LstmClusterArgs& own_args(const LstmBiArgs& q, bool rev) { return rev ? q.d[1] : q.d[0]; }
+__device__ __forceinline__ int64_t own_stride(const LstmClusterArgs& q) { return q.H; }
+__device__ __forceinline__ int64_t own_stride(const LstmBiArgs& q) { return q.ld; }
+
 // ---- forward ------------------------------------------------------------------------------------------------------------
-template <bool ST>
-__global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmClusterArgs p) {
+// BI = false: the unidirectional kernels, what they were before the bidirectional launch existed (vgrp = the group, VG = p.G).  BI = true:
+// p = the workgroup's direction's arguments, vgrp = direction * G + group indexes the exchange (VG = 2 G virtual groups per parity
+// block), rev = the backward direction: processing step t of a clip of length len works on the row of time index len - 1 - t (a dead
+// step, t >= len, on row t); hseq has its own row stride.  t below is always the PROCESSING step: epochs, parities and waits are functions of
+// t alone.
+template <bool ST, bool BI = false>
+__global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const typename ClusterArgsOf<BI>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    const bool rev = BI && (int)(blockIdx.x % (2 * own_args(ka, false).G)) >= own_args(ka, false).G;
+    const LstmClusterArgs& p = own_args(ka, rev);
     const int H = p.H, Hp = p.Hp, H4 = 4 * p.H, T = p.T;
     const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
     float* Ks = sm;                   // [Hp][LC]  (rows H .. Hp - 1: zeros)
     float* hb = Ks + (size_t)Hp * LC; // [CPG][Hp]   h_{t-1} of the group's clips
     float* zb = hb + CPG * Hp;        // [KP][2 S][LC] recurrent part of the own columns' pre-activations per reduction slice (KP * 2 S = 8 rows)
     const int tid = threadIdx.x;
-    const int grp = blockIdx.x % p.G, w = blockIdx.x / p.G;
+    const int VG = BI ? 2 * p.G : p.G, vgrp = blockIdx.x % VG;
+    const int grp = BI ? vgrp % p.G : blockIdx.x % p.G, w = blockIdx.x / VG;
     const int clip0 = grp * p.cpg;
     const int nclips = min(p.cpg, p.B - clip0);
     // the weight slice, once
@@ -162,13 +194,13 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
     const int ngran = nclips * H;
     constexpr int MAXG = CPG * LH_MAX / LNT;
     const int myn = ngran > tid ? (ngran - tid + LNT - 1) / LNT : 0;
-    u64* xg = p.xch + (size_t)grp * CPG * Hp;                  // + parity * G * CPG * Hp
-    const size_t xpar = (size_t)p.G * CPG * Hp;
+    u64* xg = p.xch + (size_t)vgrp * CPG * Hp;                 // + parity * VG * CPG * Hp
+    const size_t xpar = (size_t)VG * CPG * Hp;
     __syncthreads();
 
     for (int t = 0; t < T; ++t) {
         float zx[4] = {0.f, 0.f, 0.f, 0.f};
-        const int64_t r = (int64_t)(clip0 + gc) * T + t;
+        const int64_t r = (int64_t)(clip0 + gc) * T + ((BI && rev && t < len) ? len - 1 - t : t);
         const bool alive = t < len;
         if (glive && alive) {                                  // a dead row of gx is never read (it may hold anything)
 #pragma unroll
@@ -241,7 +273,9 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
                     for (int q = 0; q < 4; ++q) zr[q] += zb[(kp_ * 2 * S + gc) * LC + q * LU + gul];
                 const float zi = zx[0] + zr[0], zj = zx[1] + zr[1], zf = zx[2] + zr[2], zo = zx[3] + zr[3];
                 gi = sigm(zi); gj = tanhf(zj); gf = sigm(zf + p.forget_bias); go = sigm(zo);
-                cst = cst * gf + gi * gj;
+                // BI: the contraction the compiler chooses for the unidirectional kernels, spelled out -- left to itself it fuses the OTHER
+                // product here, and the forward half would differ from the unidirectional launch in the last bits
+                cst = BI ? __builtin_fmaf(cst, gf, gi * gj) : cst * gf + gi * gj;
                 h = tanhf(cst) * go;
                 hpub = h;
             }
@@ -250,13 +284,14 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const LstmCluster
             float* a = p.act + r * H4 + gu;
             a[0] = gi; a[H] = gj; a[2 * H] = gf; a[3 * H] = go;
             p.cseq[r * H + gu] = cst;
-            p.hseq[r * H + gu] = h;
+            p.hseq[BI ? r * own_stride(ka) + gu : r * H + gu] = h;
             p.hprev[r * H + gu] = hp;
         }
         // no barrier needed here: the next iteration writes hb only after its gather, and every read of hb of this iteration
         // precedes the barrier above; zb is rewritten only after the next iteration's first barrier
     }
 }
+
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
 // partial[c][k] = sum over the own 64 columns of dz[c][j] Kh[k][j], for the first NC clips, published as granules
@@ -297,15 +332,21 @@ __device__ __forceinline__ void publish_partials(const float* KsT, const float* 
     }
 }
 
-template <bool ST>
-__global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmClusterArgs p) {
+// BI, vgrp, VG, rev as in the forward kernel; dout has its own row stride.  The loop runs over PROCESSING steps t = T - 1 .. 0; the cell
+// state that entered step t is the one of processing step t - 1: the row before in time for the forward direction, the row after for the
+// backward one (c0 at t == 0 for both).
+template <bool ST, bool BI = false>
+__global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const typename ClusterArgsOf<BI>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    const bool rev = BI && (int)(blockIdx.x % (2 * own_args(ka, false).G)) >= own_args(ka, false).G;
+    const LstmClusterArgs& p = own_args(ka, rev);
     const int H = p.H, Hp = p.Hp, H4 = 4 * p.H, T = p.T, W = p.W;
     const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
     float* KsT = sm;                      // [LC][Hp]  KsT[j][k] = kh[k][column j of this workgroup]
     float* zl = KsT + (size_t)LC * Hp;    // [CPG][LC] dz_t of the own columns
     const int tid = threadIdx.x;
-    const int grp = blockIdx.x % p.G, w = blockIdx.x / p.G;
+    const int VG = BI ? 2 * p.G : p.G, vgrp = blockIdx.x % VG;
+    const int grp = BI ? vgrp % p.G : blockIdx.x % p.G, w = blockIdx.x / VG;
     const int clip0 = grp * p.cpg;
     const int nclips = min(p.cpg, p.B - clip0);
     for (int i = tid; i < LC * Hp; i += LNT) {
@@ -318,8 +359,8 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
     float dc = 0.f, dh = 0.f;
     const int len = (glive && p.seq_len) ? min(max(p.seq_len[clip0 + gc], 0), T) : T;   // as in the forward
     // exchange: P[parity][group][source workgroup][clip][k]
-    const size_t pgrp = (size_t)W * CPG * Hp, ppar = (size_t)p.G * pgrp;
-    u64* pg = p.xch + (size_t)grp * pgrp;
+    const size_t pgrp = (size_t)W * CPG * Hp, ppar = (size_t)VG * pgrp;
+    u64* pg = p.xch + (size_t)vgrp * pgrp;
     constexpr int MAXW = LH_MAX / LU;
     auto gather_dh = [&](unsigned epoch) {                      // sum over source workgroups of their partial for (gc, gu)
         const u64* src = pg + (epoch & 1) * ppar + (size_t)gc * Hp + gu;
@@ -341,16 +382,16 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_bwd_kernel(const LstmCluster
     __syncthreads();
 
     for (int t = T - 1; t >= 0; --t) {
-        const int64_t r = (int64_t)(clip0 + gc) * T + t;
+        const int64_t r = (int64_t)(clip0 + gc) * T + ((BI && rev && t < len) ? len - 1 - t : t);
         const unsigned epoch = (unsigned)(T - t);               // 1 .. T
         float din = 0.f, gi = 0.f, gj = 0.f, gf = 0.f, go = 0.f, cc = 0.f, cp = 0.f;
         const bool alive = t < len;
         if (glive && alive) {                                   // a dead row of dout / act is never read
-            din = p.dout ? p.dout[r * H + gu] : 0.f;
+            din = p.dout ? p.dout[BI ? r * own_stride(ka) + gu : r * H + gu] : 0.f;
             const float* a = p.act + r * H4 + gu;
             gi = a[0]; gj = a[H]; gf = a[2 * H]; go = a[3 * H];
             cc = p.cseq[r * H + gu];
-            cp = t > 0 ? p.cseq[(r - 1) * H + gu] : (p.c0 ? p.c0[(int64_t)(clip0 + gc) * H + gu] : 0.f);
+            cp = t > 0 ? p.cseq[((BI && rev) ? r + 1 : r - 1) * H + gu] : (p.c0 ? p.c0[(int64_t)(clip0 + gc) * H + gu] : 0.f);
         }
         if (t < T - 1) dh = gather_dh(epoch - 1);               // published by every workgroup of the group at step t + 1
         if (glive) {
@@ -425,6 +466,20 @@ size_t vl_lstm_cluster_ws_bytes(int H) {
     return STATUS_BYTES + sizeof(u64) * (c.xch_fwd > c.xch_bwd ? c.xch_fwd : c.xch_bwd);
 }
 
+// The LDS limit of all eight kernels at the first call of any: a graph's first (captured) call of the replay-safe ones then sets nothing
+static int cluster_lds_attrs() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        const void* kerns[8] = {reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<false>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<false>),
+                                reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<true>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<true>),
+                                reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<false, true>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<false, true>),
+                                reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<true, true>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<true, true>)};
+        for (const void* k : kerns) VL_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr_set = true;
+    }
+    return 0;
+}
+
 // Runs one direction over all clips, in chunks of at most maxG * 8 clips (one launch each).  st == nullptr: tag bases from the
 // process-wide counter; else the replay-safe kernels, launch k with base tag_offset + k (T + 1) over st->tag_origin.
 static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws, size_t ws_bytes, const vl_step_state* st,
@@ -438,14 +493,7 @@ static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws,
     a.xch = (u64*)((char*)ws + STATUS_BYTES);
     a.state = st;
     const size_t lds = bwd ? sizeof(float) * ((size_t)LC * c.Hp + CPG * LC) : sizeof(float) * ((size_t)c.Hp * LC + CPG * c.Hp + CPG * LC);   // zb: KP * clips <= 8 rows
-    // all four kernels at the first call of any: a graph's first (captured) call of the replay-safe ones then sets nothing
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* kerns[4] = {reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<false>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<false>),
-                                reinterpret_cast<const void*>(lstm_cluster_fwd_kernel<true>), reinterpret_cast<const void*>(lstm_cluster_bwd_kernel<true>)};
-        for (const void* k : kerns) VL_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set = true;
-    }
+    if (cluster_lds_attrs()) return 1;
     a.spin_limit = g_spin_limit;
     a.mute = g_mute_workgroup;
     const float *gx = a.gx, *h0 = a.h0, *c0 = a.c0, *dout = a.dout;
@@ -488,6 +536,73 @@ static int vl_lstm_cluster_run(bool bwd, LstmClusterArgs a, int batch, void* ws,
         }
         if (bwd) hipLaunchKernelGGL(lstm_cluster_bwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
         else hipLaunchKernelGGL(lstm_cluster_fwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
+        VL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// Both directions of a layer, in chunks of at most mg_bi * 8 clips (one launch each; mg_bi = CUs / 2W groups per direction, so that the
+// 2 G W workgroups of a launch are resident at once).  q.d[0] / q.d[1]: the forward / backward direction's tensors for the whole batch.
+static int cluster_mg_bi(int H) { return cluster_cus() / (2 * ((H + LU - 1) / LU)); }
+
+static int vl_lstm_cluster_run_bi(bool bwd, LstmBiArgs q, int batch, void* ws, size_t ws_bytes, const vl_step_state* st, unsigned tag_offset,
+                                  hipStream_t s) {
+    const int T = q.d[0].T, H = q.d[0].H;
+    const ClusterPlan c = cluster_plan(H);
+    const int mg = cluster_mg_bi(H), chunk = mg * CPG;
+    VL_CHECK(mg >= 1, "vl_lstm_seq_bi: the device has too few compute units for both directions of H = %d in one launch", H);
+    VL_CHECK(ws && ws_bytes >= vl_lstm_cluster_ws_bytes(H), "vl_lstm_seq_bi: workspace too small (%zu < %zu bytes)", ws_bytes,
+             vl_lstm_cluster_ws_bytes(H));
+    const size_t lds = bwd ? sizeof(float) * ((size_t)LC * c.Hp + CPG * LC) : sizeof(float) * ((size_t)c.Hp * LC + CPG * c.Hp + CPG * LC);
+    if (cluster_lds_attrs()) return 1;
+    const LstmBiArgs whole = q;
+    for (int b0 = 0, k = 0; b0 < batch; b0 += chunk, ++k) {
+        const int nb = batch - b0 < chunk ? batch - b0 : chunk;
+        int G = nb < mg ? nb : mg;
+        const int cpg = (nb + G - 1) / G;
+        G = (nb + cpg - 1) / cpg;
+        const int64_t ro = (int64_t)b0 * T, so = (int64_t)b0 * H;
+        unsigned ebase;
+        if (st) ebase = tag_offset + (unsigned)k * ((unsigned)T + 1u);    // over st->tag_origin (vl_lstm_seq_bi_tag_span counts these launches)
+        else {
+            ebase = __atomic_fetch_add(&g_epoch_base, (unsigned)T + 1u, __ATOMIC_RELAXED);
+            if (ebase > 0xfff00000u) {                                     // as in vl_lstm_cluster_run
+                VL_HIP(hipMemsetAsync((char*)ws + STATUS_BYTES, 0, ws_bytes - STATUS_BYTES, s));
+                __atomic_store_n(&g_epoch_base, (unsigned)T + 1u, __ATOMIC_RELAXED);
+                ebase = 0;
+            }
+        }
+        for (int d = 0; d < 2; ++d) {
+            const LstmClusterArgs& f = whole.d[d];
+            LstmClusterArgs& a = q.d[d];
+            a.W = c.W; a.Hp = c.Hp; a.B = nb; a.G = G; a.cpg = cpg;
+            a.status = (unsigned*)ws;
+            a.xch = (u64*)((char*)ws + STATUS_BYTES);
+            a.state = st;
+            a.spin_limit = g_spin_limit;
+            a.mute = g_mute_workgroup;
+            a.ebase = ebase;
+            a.gx = f.gx ? f.gx + ro * 4 * H : nullptr;
+            a.h0 = f.h0 ? f.h0 + so : nullptr;
+            a.c0 = f.c0 ? f.c0 + so : nullptr;
+            a.act = f.act + ro * 4 * H;
+            a.cseq = f.cseq + ro * H;
+            a.hseq = f.hseq ? f.hseq + ro * q.ld : nullptr;
+            a.hprev = f.hprev ? f.hprev + ro * H : nullptr;
+            a.dout = f.dout ? f.dout + ro * q.ld : nullptr;
+            a.dz = f.dz ? f.dz + ro * 4 * H : nullptr;
+            a.dh0 = f.dh0 ? f.dh0 + so : nullptr;
+            a.dc0 = f.dc0 ? f.dc0 + so : nullptr;
+            a.seq_len = f.seq_len ? f.seq_len + b0 : nullptr;
+        }
+        const dim3 grid(2 * G * c.W);
+        if (st) {
+            if (bwd) hipLaunchKernelGGL((lstm_cluster_bwd_kernel<true, true>), grid, dim3(LNT), lds, s, q);
+            else hipLaunchKernelGGL((lstm_cluster_fwd_kernel<true, true>), grid, dim3(LNT), lds, s, q);
+        } else {
+            if (bwd) hipLaunchKernelGGL((lstm_cluster_bwd_kernel<false, true>), grid, dim3(LNT), lds, s, q);
+            else hipLaunchKernelGGL((lstm_cluster_fwd_kernel<false, true>), grid, dim3(LNT), lds, s, q);
+        }
         VL_LAUNCH_CHECK();
     }
     return 0;
@@ -592,6 +707,98 @@ extern "C" int vl_lstm_seq_bwd_st(const float* dout, const float* kh, const floa
                                   uint32_t tag_offset, vl_stream_t stream) {
     VL_CHECK(state, "vl_lstm_seq_bwd_st: null state");
     return lstm_seq_bwd(dout, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, nullptr, ws, ws_bytes, state, tag_offset, (hipStream_t)stream);
+}
+
+// ---- bidirectional entry points (vltf.h) -------------------------------------------------------------------------------------------------
+static int lstm_seq_bi_fwd(const char* what, const float* const gx[2], const float* const kh[2], const float* const h0[2], const float* const c0[2],
+                           float* const act[2], float* const cseq[2], float* const hseq[2], float* const hprev[2], int64_t hseq_ld, int batch,
+                           int T, int H, float forget_bias, const int32_t* seq_len, void* ws, size_t ws_bytes, const vl_step_state* st,
+                           unsigned tag_offset, hipStream_t stream) {
+    for (int d = 0; d < 2; ++d) VL_CHECK(gx[d] && kh[d] && act[d] && cseq[d] && hseq[d] && hprev[d], "%s: null argument", what);
+    VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= LH_MAX, "%s: bad shape (the bidirectional launch needs a hidden size <= %d)", what, LH_MAX);
+    VL_CHECK(hseq_ld >= H, "%s: hseq row stride %lld below H", what, (long long)hseq_ld);
+    VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "%s: workspace smaller than vl_lstm_seq_ws_bytes", what);
+    LstmBiArgs q = {};
+    for (int d = 0; d < 2; ++d) {
+        LstmClusterArgs& a = q.d[d];
+        a.gx = gx[d]; a.kh = kh[d]; a.h0 = h0[d]; a.c0 = c0[d]; a.act = act[d]; a.cseq = cseq[d]; a.hseq = hseq[d]; a.hprev = hprev[d];
+        a.T = T; a.H = H; a.forget_bias = forget_bias; a.seq_len = seq_len;
+    }
+    q.ld = hseq_ld;
+    return vl_lstm_cluster_run_bi(false, q, batch, ws, ws_bytes, st, tag_offset, stream);
+}
+
+static int lstm_seq_bi_bwd(const char* what, const float* const dout[2], int64_t dout_ld, const float* const kh[2], const float* const act[2],
+                           const float* const cseq[2], const float* const c0[2], float* const dz[2], float* const dh0[2], float* const dc0[2],
+                           int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, const vl_step_state* st,
+                           unsigned tag_offset, hipStream_t stream) {
+    for (int d = 0; d < 2; ++d) VL_CHECK(kh[d] && act[d] && cseq[d] && dz[d], "%s: null argument", what);
+    VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= LH_MAX, "%s: bad shape (the bidirectional launch needs a hidden size <= %d)", what, LH_MAX);
+    VL_CHECK((!dout[0] && !dout[1]) || dout_ld >= H, "%s: dout row stride %lld below H", what, (long long)dout_ld);
+    VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "%s: workspace smaller than vl_lstm_seq_ws_bytes", what);
+    LstmBiArgs q = {};
+    for (int d = 0; d < 2; ++d) {
+        LstmClusterArgs& a = q.d[d];
+        a.kh = kh[d]; a.c0 = c0[d]; a.act = const_cast<float*>(act[d]); a.cseq = const_cast<float*>(cseq[d]); a.dout = dout[d]; a.dz = dz[d];
+        a.dh0 = dh0[d]; a.dc0 = dc0[d]; a.T = T; a.H = H; a.seq_len = seq_len;
+    }
+    q.ld = dout_ld;
+    return vl_lstm_cluster_run_bi(true, q, batch, ws, ws_bytes, st, tag_offset, stream);
+}
+
+#define BI_FWD_ARGS const float* const gx[2] = {gx_fw, gx_bw}; const float* const kh[2] = {kh_fw, kh_bw}; const float* const h0[2] = {h0_fw, h0_bw}; \
+    const float* const c0[2] = {c0_fw, c0_bw}; float* const act[2] = {act_fw, act_bw}; float* const cseq[2] = {cseq_fw, cseq_bw};                 \
+    float* const hseq[2] = {hseq_fw, hseq_bw}; float* const hprev[2] = {hprev_fw, hprev_bw}
+#define BI_BWD_ARGS const float* const dout[2] = {dout_fw, dout_bw}; const float* const kh[2] = {kh_fw, kh_bw}; const float* const act[2] = {act_fw, act_bw}; \
+    const float* const cseq[2] = {cseq_fw, cseq_bw}; const float* const c0[2] = {c0_fw, c0_bw}; float* const dz[2] = {dz_fw, dz_bw};                       \
+    float* const dh0[2] = {dh0_fw, dh0_bw}; float* const dc0[2] = {dc0_fw, dc0_bw}
+
+extern "C" int vl_lstm_seq_bi_fwd(const float* gx_fw, const float* gx_bw, const float* kh_fw, const float* kh_bw, const float* h0_fw,
+                                  const float* h0_bw, const float* c0_fw, const float* c0_bw, float* act_fw, float* act_bw, float* cseq_fw,
+                                  float* cseq_bw, float* hseq_fw, float* hseq_bw, int64_t hseq_ld, float* hprev_fw, float* hprev_bw, int batch,
+                                  int T, int H, float forget_bias, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_bi_fwd", seq_len == nullptr)) return 1;
+    BI_FWD_ARGS;
+    return lstm_seq_bi_fwd("vl_lstm_seq_bi_fwd", gx, kh, h0, c0, act, cseq, hseq, hprev, hseq_ld, batch, T, H, forget_bias, seq_len, ws, ws_bytes,
+                           nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_bi_bwd(const float* dout_fw, const float* dout_bw, int64_t dout_ld, const float* kh_fw, const float* kh_bw,
+                                  const float* act_fw, const float* act_bw, const float* cseq_fw, const float* cseq_bw, const float* c0_fw,
+                                  const float* c0_bw, float* dz_fw, float* dz_bw, float* dh0_fw, float* dh0_bw, float* dc0_fw, float* dc0_bw,
+                                  int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_lstm_seq_bi_bwd", seq_len == nullptr)) return 1;
+    BI_BWD_ARGS;
+    return lstm_seq_bi_bwd("vl_lstm_seq_bi_bwd", dout, dout_ld, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, seq_len, ws, ws_bytes, nullptr, 0,
+                           (hipStream_t)stream);
+}
+
+extern "C" size_t vl_lstm_seq_bi_tag_span(int batch, int T, int H) {
+    if (batch < 1 || T < 1 || !vl_lstm_cluster_ok(H) || cluster_mg_bi(H) < 1) return 0;
+    const int chunk = cluster_mg_bi(H) * CPG;
+    return (size_t)((batch + chunk - 1) / chunk) * ((size_t)T + 1);
+}
+
+extern "C" int vl_lstm_seq_bi_fwd_st(const float* gx_fw, const float* gx_bw, const float* kh_fw, const float* kh_bw, const float* h0_fw,
+                                     const float* h0_bw, const float* c0_fw, const float* c0_bw, float* act_fw, float* act_bw, float* cseq_fw,
+                                     float* cseq_bw, float* hseq_fw, float* hseq_bw, int64_t hseq_ld, float* hprev_fw, float* hprev_bw,
+                                     int batch, int T, int H, float forget_bias, void* ws, size_t ws_bytes, const vl_step_state* state,
+                                     uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_lstm_seq_bi_fwd_st: null state");
+    BI_FWD_ARGS;
+    return lstm_seq_bi_fwd("vl_lstm_seq_bi_fwd_st", gx, kh, h0, c0, act, cseq, hseq, hprev, hseq_ld, batch, T, H, forget_bias, nullptr, ws,
+                           ws_bytes, state, tag_offset, (hipStream_t)stream);
+}
+
+extern "C" int vl_lstm_seq_bi_bwd_st(const float* dout_fw, const float* dout_bw, int64_t dout_ld, const float* kh_fw, const float* kh_bw,
+                                     const float* act_fw, const float* act_bw, const float* cseq_fw, const float* cseq_bw, const float* c0_fw,
+                                     const float* c0_bw, float* dz_fw, float* dz_bw, float* dh0_fw, float* dh0_bw, float* dc0_fw,
+                                     float* dc0_bw, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                                     uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_lstm_seq_bi_bwd_st: null state");
+    BI_BWD_ARGS;
+    return lstm_seq_bi_bwd("vl_lstm_seq_bi_bwd_st", dout, dout_ld, kh, act, cseq, c0, dz, dh0, dc0, batch, T, H, nullptr, ws, ws_bytes, state,
+                           tag_offset, (hipStream_t)stream);
 }
 
 extern "C" int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream) {

@@ -52,6 +52,7 @@ class NetConfig:
     lstm_hidden: int = 256
     lstm_layers: int = 1
     fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state}
+    lstm_bidirectional: bool = False            # every LSTM layer a forward and a backward cell, outputs concatenated (blstm_names); H <= 512
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
@@ -95,6 +96,35 @@ def tf_same_out(n, s):
     return -(-n // s)
 
 
+BLSTM_MAX_HIDDEN = 512      # the bidirectional launch exists in the cluster form only (vltf.h: vl_lstm_seq_bi_fwd)
+
+
+def blstm_names(layer, scope=""):
+    """TF's variable names of one bidirectional layer (stack_bidirectional_dynamic_rnn's scopes), in flat-buffer order: forward kernel
+    and bias, backward kernel and bias.  Kernels are (d + H, 4H) with d the encode width for layer 0 and 2H above it."""
+    return [scope + "bidirectional_rnn/%s/multi_rnn_cell/cell_%d/basic_lstm_cell/%s" % (d, layer, v) for d in ("fw", "bw") for v in ("kernel", "bias")]
+
+
+def check_blstm(hidden, what="lstm_bidirectional"):
+    """Refuses a bidirectional LSTM whose hidden size the one-launch form cannot take."""
+    if not 1 <= int(hidden) <= BLSTM_MAX_HIDDEN:
+        raise VltfError("%s: the bidirectional recurrence runs both directions in one cluster launch and needs a hidden size <= %d, got %d"
+                        % (what, BLSTM_MAX_HIDDEN, hidden))
+
+
+def blstm_buffers(buf, rows, H, training):
+    """The device buffers of one bidirectional layer.  Per direction, as (forward, backward) pairs: projections gx, gates act, cell
+    states cseq, entering outputs hprev (and dz when training); ONE [rows][2H] output hseq and ONE gradient dout of it, whose halves
+    (hhalf, dhalf: views at row stride 2H) the recurrence launch writes and reads in place."""
+    pair = lambda w: (buf(rows, w), buf(rows, w))
+    S = dict(gx=pair(4 * H), act=pair(4 * H), cseq=pair(H), hprev=pair(H), hseq=buf(rows, 2 * H))
+    S["hhalf"] = (S["hseq"][:, :H], S["hseq"][:, H:])
+    if training:
+        S.update(dz=pair(4 * H), dout=buf(rows, 2 * H))
+        S["dhalf"] = (S["dout"][:, :H], S["dout"][:, H:])
+    return S
+
+
 def param_specs(cfg: NetConfig):
     """[(tf_variable_name, shape)] in flat-buffer order (classifier, fc8..fc6, conv5..conv1)."""
     h, w, c = cfg.image_shape
@@ -106,7 +136,19 @@ def param_specs(cfg: NetConfig):
             h, w = ops.pool_out(h), ops.pool_out(w)
     specs = []
     dim = cfg.encode_dim()
-    if cfg.classifier == "lstm":
+    if cfg.lstm_bidirectional and cfg.classifier != "lstm":
+        raise VltfError("lstm_bidirectional needs classifier lstm, not [%s]" % cfg.classifier)
+    if cfg.classifier == "lstm" and cfg.lstm_bidirectional:
+        check_blstm(cfg.lstm_hidden)
+        H = cfg.lstm_hidden
+        if 2 * H != cfg.num_classes:                      # the head reads the 2H-wide fused vector
+            head = "fc_convert" if cfg.fusion == "state" else "output_fc"
+            specs += [(head + "_w", (2 * H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+        d = dim
+        for l in range(cfg.lstm_layers):
+            specs += [(n, (d + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l)]
+            d = 2 * H
+    elif cfg.classifier == "lstm":
         if cfg.lstm_hidden != cfg.num_classes:
             # fusion `state`: logits = convert_dim_fc(final h) under its default name (model.py:137-141), else "output_fc" (lstm.py:90)
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
@@ -1084,8 +1126,16 @@ class LRCNEngine:
             self.lstm_fusion = "last" if cfg.fusion == "state" else cfg.fusion
             self.per_step = cfg.fusion == "reshape"
             self.head = "fc_convert" if cfg.fusion == "state" else "output_fc"
-            self.lstm = []
+            self.lstm, self.blstm = [], []                              # per-layer buffers: unidirectional layers, or bidirectional ones
+            self.bi = bool(cfg.lstm_bidirectional)
+            HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
+            if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
+                raise VltfError("lstm_bidirectional: this device has too few compute units to hold both directions of hidden size %d in "
+                                "one launch" % H)
             for l in range(cfg.lstm_layers):
+                if self.bi:
+                    self.blstm.append(blstm_buffers(buf, N, H, training))
+                    continue
                 S = dict(gx=buf(N, 4 * H), act=buf(N, 4 * H), cseq=buf(N, H), hseq=buf(N, H), hprev=buf(N, H))
                 if training:
                     S.update(dz=buf(N, 4 * H), dout=buf(N, H))
@@ -1093,13 +1143,15 @@ class LRCNEngine:
             self.gh = buf(B, 4 * H)
             self.lstm_ws = ops.lstm_seq_ws(B, T, H, dev) if H <= 1024 else None
             R = N if self.per_step else B                             # logits rows
-            self.fused = buf(R, H)
-            self.dropped = buf(R, H)
-            self.drop_mask = buf(R, H, dtype=torch.uint8)
-            self.logits = buf(R, C) if H != C else self.dropped
+            self.fused = buf(R, HO)
+            self.dropped = buf(R, HO)
+            self.drop_mask = buf(R, HO, dtype=torch.uint8)
+            self.logits = buf(R, C) if HO != C else self.dropped
             if training:
                 self.dh, self.dc = buf(B, H), buf(B, H)
-                self.dfused, self.ddropped = buf(R, H), buf(R, H)
+                self.dfused, self.ddropped = buf(R, HO), buf(R, HO)
+                if self.bi:
+                    self.dx_bw = buf(N, max(D, HO))                   # the backward direction's share of a layer's input gradient
         else:
             ff = cfg.frame_fusion
             if cfg.classifier == "none" and ff and ff[0] == "late":
@@ -1666,6 +1718,8 @@ class LRCNEngine:
         packed-operand kernel too (bf16 path): the same arithmetic as the split-product GEMM in mode 1 -- operands rounded to bf16, fp32
         accumulation -- without its operand images.  They reuse fc6's operand buffers (the launches are serial on one stream)."""
         D, H4 = self.cfg.encode_dim(), 4 * self.cfg.lstm_hidden
+        if getattr(self, "bi", False):                       # a bidirectional layer's dense products run on ops.gemm
+            return False
         return (l == 0 and self._fc6_kc8(n) and os.environ.get("VLTF_LSTM_KC8", "1") != "0" and D % 8 == 0 and H4 % 8 == 0
                 and D * H4 <= self.k_w.numel() and n * max(D, H4) <= self.k_act.numel() and (not self.training or n * H4 <= self.k_d6.numel()))
 
@@ -1727,6 +1781,19 @@ class LRCNEngine:
         D, C, H, T = cfg.encode_dim(), cfg.num_classes, cfg.lstm_hidden, self.T
         if cfg.classifier == "lstm":
             xin, d = self.feat, D
+            HO = self.lstm_out
+            for l, S in enumerate(self.blstm):
+                # both input projections, then both recurrences in ONE launch, the halves of hseq written in place
+                Kf, bf, Kb, bb = (P[k] for k in blstm_names(l))
+                ops.gemm(xin, Kf, S["gx"][0], n, 4 * H, d, bias=bf, ws=self.ws)
+                ops.gemm(xin, Kb, S["gx"][1], n, 4 * H, d, bias=bb, ws=self.ws)
+                st = {}
+                if self._tag_off is not None:                         # captured: replay-safe tags on the graph workspace
+                    st = dict(state=self.state, tag_offset=self._tag_off)
+                    self._tag_off += ops.lstm_seq_bi_tag_span(b, T, H)
+                ops.lstm_seq_bi_fwd(S["gx"], (Kf[d:], Kb[d:]), S["act"], S["cseq"], S["hhalf"], S["hprev"], b, T, H, FORGET_BIAS,
+                                    ws=self.lstm_ws_graph if st else self.lstm_ws, hseq_ld=HO, **st)
+                xin, d = S["hseq"], HO
             for l, S in enumerate(self.lstm):
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 K = P[pre + "kernel"]
@@ -1755,8 +1822,14 @@ class LRCNEngine:
             r = n if self.per_step else b
             if self.per_step:
                 v = xin                                                  # every step's output of the last layer
+            elif self.bi and self.lstm_fusion == "last":
+                # each direction's FINAL output: the forward half at t = T - 1, the backward half at t = 0
+                o3 = xin[:b * T].view(b, T, HO)
+                ops.copy2d(o3[:, T - 1, :H], self.fused, b, H, src_ld=T * HO, dst_ld=HO)
+                ops.copy2d(o3[:, 0, H:], self.fused[:, H:], b, H, src_ld=T * HO, dst_ld=HO)
+                v = self.fused
             else:
-                ops.temporal_fusion_fwd(xin, self.fused, b, T, H, self.lstm_fusion)
+                ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, self.lstm_fusion)
                 v = self.fused
             self._dropout = train and cfg.dropout_keep_prob > 0 and cfg.fusion != "state"
             if self._dropout and self._tag_off is not None:          # captured: the seed follows the step state's count
@@ -1767,8 +1840,8 @@ class LRCNEngine:
                                 (self._draw_index() << 20) ^ 0x5DEECE66D)
                 v = self.dropped
             self._v = v
-            if H != C:
-                ops.gemm(v, P[self.head + "_w"], self.logits, r, C, H, bias=P[self.head + "_b"])
+            if HO != C:
+                ops.gemm(v, P[self.head + "_w"], self.logits, r, C, HO, bias=P[self.head + "_b"])
             elif v is not self.logits:
                 self.logits[:r].copy_(v[:r])
             self._rows = r
@@ -1839,22 +1912,57 @@ class LRCNEngine:
 
         if cfg.classifier == "lstm":
             d, r = self.dlogits, self._rows
-            if H != C:
+            HO = self.lstm_out
+            if HO != C:
                 def head_grads(ws, sws, r=r):
-                    ops.gemm(self._v, self.dlogits, G[self.head + "_w"], H, C, r, transa=True)
+                    ops.gemm(self._v, self.dlogits, G[self.head + "_w"], HO, C, r, transa=True)
                     ops.colsum(self.dlogits, G[self.head + "_b"], sws, r, C)
                 param_grads(head_grads)
-                ops.gemm(self.dlogits, P[self.head + "_w"], self.ddropped, r, H, C, transb=True)
+                ops.gemm(self.dlogits, P[self.head + "_w"], self.ddropped, r, HO, C, transb=True)
                 d = self.ddropped
             if self._dropout:
                 ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], cfg.dropout_keep_prob)
                 d = self.dfused
-            top = self.lstm[-1]
+            top = (self.blstm or self.lstm)[-1]
             if self.per_step:
                 top["dout"][:r].copy_(d[:r])
+            elif self.bi and self.lstm_fusion == "last":
+                ops.fill(top["dout"][:b * T], 0.0)
+                g3 = top["dout"][:b * T].view(b, T, HO)
+                ops.copy2d(d, g3[:, T - 1, :H], b, H, src_ld=HO, dst_ld=T * HO)
+                ops.copy2d(d[:, H:], g3[:, 0, H:], b, H, src_ld=HO, dst_ld=T * HO)
             else:
-                ops.temporal_fusion_bwd(d, top["dout"], b, T, H, self.lstm_fusion)
-            for l in reversed(range(cfg.lstm_layers)):
+                ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, self.lstm_fusion)
+            for l in reversed(range(len(self.blstm))):
+                S = self.blstm[l]
+                names = blstm_names(l)
+                Kf, Kb = P[names[0]], P[names[2]]
+                din = D if l == 0 else HO
+                xin = self.feat if l == 0 else self.blstm[l - 1]["hseq"]
+                st = {}
+                if self._tag_off is not None:
+                    st = dict(state=self.state, tag_offset=self._tag_off)
+                    self._tag_off += ops.lstm_seq_bi_tag_span(b, T, H)
+                ops.lstm_seq_bi_bwd(S["dhalf"], (Kf[din:], Kb[din:]), S["act"], S["cseq"], S["dz"], b, T, H,
+                                    ws=self.lstm_ws_graph if st else self.lstm_ws, dout_ld=HO, **st)
+
+                def blstm_grads(ws, sws, S=S, names=names, din=din, xin=xin):
+                    for k in range(2):                                                    # each direction's three products and bias sum
+                        gK, gb = G[names[2 * k]], G[names[2 * k + 1]]
+                        ops.gemm(xin, S["dz"][k], gK, din, 4 * H, n, transa=True, ws=ws)
+                        ops.gemm(S["hprev"][k], S["dz"][k], gK[din:], H, 4 * H, n, transa=True, ws=ws)
+                        ops.colsum(S["dz"][k], gb, sws, n, 4 * H)
+                param_grads(blstm_grads)
+                if l == 0 and not self.dcnn_trains:
+                    continue                                                              # frozen tower: nobody reads dfeat
+                # the input gradient is the SUM of both directions' dz Kx^T; the ReluGrad of fc6 / fc7 applies to the sum
+                target = self.dfeat if l == 0 else self.blstm[l - 1]["dout"]
+                ops.gemm(S["dz"][0], Kf, target, n, din, 4 * H, transb=True, ldb=4 * H, ws=self.ws)
+                ops.gemm(S["dz"][1], Kb, self.dx_bw, n, din, 4 * H, transb=True, ldb=4 * H, ws=self.ws)
+                ops.eltwise2(target, self.dx_bw, target, "add", n * din)
+                if l == 0 and self.f8 is None:
+                    self._relu_grad(self.dfeat, self.feat, n * D)
+            for l in reversed(range(len(self.lstm))):
                 S = self.lstm[l]
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 K = P[pre + "kernel"]

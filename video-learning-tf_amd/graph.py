@@ -40,7 +40,7 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
                      check_label_smoothing,
                      check_cutmix, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -56,6 +56,7 @@ class PipelineSpec:
     fc_output_dim: Optional[int] = None             # fc
     classifier: Optional[str] = None                # None | fc | lstm
     lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state)
+    lstm_bidirectional: bool = False                # classifier lstm: a forward and a backward cell per layer, outputs concatenated (2H wide)
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
     train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
@@ -214,9 +215,19 @@ class PipeNode:
                     raise VltfError("Undefined frame fusion type : %s" % self.lfusion)
                 self.per_step = self.lfusion == "reshape"
                 self.head_name = "fc_convert" if self.lfusion == "state" else "output_fc"
-                if self.H != C and self.head_name == "fc_convert" and self.rep_fc:
+                self.bi = bool(s.lstm_bidirectional)
+                self.HO = 2 * self.H if self.bi else self.H       # width of the LSTM's output and of the head's input
+                if self.bi:
+                    check_blstm(self.H, "pipeline [%s]: lstm_bidirectional" % s.name)
+                    if self.state_src is not None:
+                        raise VltfError("pipeline [%s]: a bidirectional LSTM takes no state input ([%s]): the reference hands ONE vector to "
+                                        "every cell as c = h, and which of the two directions it would initialise is not defined" %
+                                        (s.name, self.state_src.ref))
+                if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
+            if s.lstm_bidirectional and self.cls != "lstm":
+                raise VltfError("pipeline [%s]: lstm_bidirectional needs classifier lstm, not [%s]" % (s.name, self.cls))
             self.late = ftype == "late" and self.fpc > 1 and fmethod != "reshape"
             if self.late:
                 if self.cls == "lstm" or rows % self.fpc:
@@ -239,11 +250,14 @@ class PipeNode:
         if self.cls == "fc" and self.cls_fc:
             specs += [(sc + "fc_convert_w", (self.feat_dim, C)), (sc + "fc_convert_b", (C,))]
         if self.cls == "lstm":
-            H = self.H
-            if H != C:
-                specs += [(sc + self.head_name + "_w", (H, C)), (sc + self.head_name + "_b", (C,))]
-            dims = [self.feat_dim] + [H] * (self.L - 1)
+            H, HO = self.H, self.HO
+            if HO != C:
+                specs += [(sc + self.head_name + "_w", (HO, C)), (sc + self.head_name + "_b", (C,))]
+            dims = [self.feat_dim] + [HO] * (self.L - 1)
             for l in reversed(range(self.L)):
+                if self.bi:
+                    specs += [(n, (dims[l] + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l, sc)]
+                    continue
                 pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 specs += [(pre + "kernel", (dims[l] + H, 4 * H)), (pre + "bias", (4 * H,))]
             if self.state_src is not None and self.state_src.dim != H:
@@ -306,10 +320,16 @@ class PipeNode:
             if tr and self.cls_fc:
                 self.dcls_in = buf(rows_cls, self.feat_dim)
         elif self.cls == "lstm":
-            H, T = self.H, self.fpc
+            H, T, HO = self.H, self.fpc, self.HO
             B = R0 // T
-            self.lstm = []
+            self.lstm, self.blstm = [], []                              # per-layer buffers: unidirectional layers, or bidirectional ones
+            if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:
+                raise VltfError("pipeline [%s]: lstm_bidirectional: this device has too few compute units to hold both directions of "
+                                "hidden size %d in one launch" % (self.spec.name, H))
             for l in range(self.L):
+                if self.bi:
+                    self.blstm.append(blstm_buffers(buf, R0, H, tr))
+                    continue
                 S = dict(gx=buf(R0, 4 * H), act=buf(R0, 4 * H), cseq=buf(R0, H), hseq=buf(R0, H), hprev=buf(R0, H))
                 if tr:
                     S.update(dz=buf(R0, 4 * H), dout=buf(R0, H), dh0=buf(B, H), dc0=buf(B, H))
@@ -319,10 +339,10 @@ class PipeNode:
                 raise VltfError("GraphEngine: LSTM hidden size above 1024 is not built")
             self.seq_len_buf = torch.zeros(B, dtype=torch.int32, device=dev)     # per-clip lengths of a call that gives them
             r = R0 if self.per_step else B
-            self.fused = buf(r, H) if not self.per_step else None
-            self.dropped = buf(r, H)
-            self.drop_mask = buf(r, H, dtype=torch.uint8)
-            self.cls_out = buf(r, C) if H != C else None
+            self.fused = buf(r, HO) if not self.per_step else None
+            self.dropped = buf(r, HO)
+            self.drop_mask = buf(r, HO, dtype=torch.uint8)
+            self.cls_out = buf(r, C) if HO != C else None
             if self.state_src is not None:
                 sd = self.state_src.dim
                 self.rep_state = buf(B, sd) if self.state_ratio > 1 else None
@@ -331,8 +351,11 @@ class PipeNode:
                     self.dstate = buf(B, H)
                     self.drep_state = buf(B, sd) if (sd != H and self.state_src.kind == "pipe") else None
             if tr:
-                self.dpre, self.dfused = buf(r, H), buf(r, H)
+                self.dpre, self.dfused = buf(r, HO), buf(r, HO)
                 self.dxseq = buf(R0, self.feat_dim)
+                if self.bi:
+                    self.dx_bw = buf(R0, max(self.feat_dim, HO))      # the backward direction's share of a layer's input gradient
+                    self.dlast = buf(B, HO)                           # fusion last / state: the fused gradient with its backward half zeroed
             sw = max(sw, 64 * 4 * H, 64 * H)
         if self.late:
             self.late_out = buf(self.max_rows, C)
@@ -539,6 +562,14 @@ class PipeNode:
                 s0 = self.state
         self._s0, self._b = s0, b
         xin, d = x, self.feat_dim
+        HO, last = self.HO, "last" if self.lfusion == "state" else self.lfusion
+        for l, S in enumerate(self.blstm):
+            Kf, bf, Kb, bb = (P[k] for k in blstm_names(l, sc))
+            ops.gemm(xin, Kf, S["gx"][0], rows, 4 * H, d, bias=bf, ws=g.ws)
+            ops.gemm(xin, Kb, S["gx"][1], rows, 4 * H, d, bias=bb, ws=g.ws)
+            ops.lstm_seq_bi_fwd(S["gx"], (Kf[d:], Kb[d:]), S["act"], S["cseq"], S["hhalf"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws,
+                                hseq_ld=HO, **lk)
+            xin, d = S["hseq"], HO
         for l, S in enumerate(self.lstm):
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]
@@ -551,7 +582,10 @@ class PipeNode:
             v = xin                                                     # reshape fusion: every step's output (tf_util.py:26-27)
         else:
             # with lengths `state` and `last` are h of step len - 1 (dynamic_rnn's final state), `avg` the mean over the live steps
-            ops.temporal_fusion_fwd(xin, self.fused, b, T, H, "last" if self.lfusion == "state" else self.lfusion, **lk)
+            ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, last, **lk)
+            if self.bi and last == "last":
+                # each direction's FINAL output: the forward half at step len - 1 (just fused), the backward half at step 0
+                ops.copy2d(xin[:, H:], self.fused[:, H:], b, H, src_ld=T * HO, dst_ld=HO)
             v = self.fused
         self._dropout = train and g.dropout_keep_prob > 0 and self.lfusion != "state"       # lstm.py:80-93
         if self._dropout:
@@ -559,8 +593,8 @@ class PipeNode:
                             (g._draw_index() << 20) ^ (0x2545F4914F6CDD1D + 0x9E3779B9 * self.index))
             v = self.dropped
         self._v = v
-        if H != C:
-            ops.gemm(v, P[sc + self.head_name + "_w"], self.cls_out, r, C, H, bias=P[sc + self.head_name + "_b"])
+        if HO != C:
+            ops.gemm(v, P[sc + self.head_name + "_w"], self.cls_out, r, C, HO, bias=P[sc + self.head_name + "_b"])
             v = self.cls_out
         return v, r
 
@@ -614,21 +648,47 @@ class PipeNode:
         b = self._b
         rows = b * T
         r = rows if self.per_step else b
-        if H != C:
-            ops.gemm(self._v, d, G[sc + self.head_name + "_w"], H, C, r, transa=True)
+        HO, last = self.HO, "last" if self.lfusion == "state" else self.lfusion
+        if HO != C:
+            ops.gemm(self._v, d, G[sc + self.head_name + "_w"], HO, C, r, transa=True)
             ops.colsum(d, G[sc + self.head_name + "_b"], sw, r, C)
-            ops.gemm(d, P[sc + self.head_name + "_w"], self.dpre, r, H, C, transb=True)
+            ops.gemm(d, P[sc + self.head_name + "_w"], self.dpre, r, HO, C, transb=True)
             d = self.dpre
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
             d = self.dfused
-        top = self.lstm[-1]
+        top = (self.blstm or self.lstm)[-1]
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
+        elif self.bi and last == "last":
+            # the forward half's gradient lands on step len - 1 (the fusion's own backward, on a copy whose backward half is zero), the
+            # backward half's on step 0
+            ops.fill(self.dlast[:b], 0.0)
+            ops.copy2d(d, self.dlast, b, H, src_ld=HO, dst_ld=HO)
+            ops.temporal_fusion_bwd(self.dlast, top["dout"], b, T, HO, last, **self._len_kw())
+            ops.copy2d(d[:, H:], top["dout"][:, H:], b, H, src_ld=HO, dst_ld=T * HO)
         else:
-            ops.temporal_fusion_bwd(d, top["dout"], b, T, H, "last" if self.lfusion == "state" else self.lfusion, **self._len_kw())
+            ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, last, **self._len_kw())
         has_state = self._s0 is not None
-        for l in reversed(range(self.L)):
+        for l in reversed(range(len(self.blstm))):
+            S = self.blstm[l]
+            names = blstm_names(l, sc)
+            Kf, Kb = P[names[0]], P[names[2]]
+            din = self.feat_dim if l == 0 else HO
+            xin = self._xcls if l == 0 else self.blstm[l - 1]["hseq"]
+            ops.lstm_seq_bi_bwd(S["dhalf"], (Kf[din:], Kb[din:]), S["act"], S["cseq"], S["dz"], b, T, H, ws=self.lstm_ws, dout_ld=HO,
+                                **self._len_kw())
+            for k in range(2):
+                gK = G[names[2 * k]]
+                ops.gemm(xin, S["dz"][k], gK, din, 4 * H, rows, transa=True, ws=g.ws)
+                ops.gemm(S["hprev"][k], S["dz"][k], gK[din:], H, 4 * H, rows, transa=True, ws=g.ws)
+                ops.colsum(S["dz"][k], G[names[2 * k + 1]], sw, rows, 4 * H)
+            if l > 0 or self.wants_feat:                                # the input gradient: the sum of both directions' dz Kx^T
+                target = self.blstm[l - 1]["dout"] if l > 0 else self.dxseq
+                ops.gemm(S["dz"][0], Kf, target, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
+                ops.gemm(S["dz"][1], Kb, self.dx_bw, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
+                ops.eltwise2(target, self.dx_bw, target, "add", rows * din)
+        for l in reversed(range(len(self.lstm))):
             S = self.lstm[l]
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]

@@ -576,6 +576,71 @@ def lstm_seq_bwd_st(dout, kh, act, cseq, dz, batch, T, H, ws=None, state=None, t
               ws.numel() * 4, _state(state), int(tag_offset), stream())
 
 
+def _pair(v, what):
+    """A (forward, backward) pair of the bidirectional entry points; None = (None, None)."""
+    if v is None:
+        return (None, None)
+    if not (isinstance(v, (tuple, list)) and len(v) == 2):
+        raise _ffi.VltfError("%s: expected a (forward, backward) pair of tensors" % what)
+    return tuple(v)
+
+
+def _row_stride(pair, H, ld, what):
+    """Row stride (floats) of a strided pair (hseq / dout): `ld`, or H for two dense tensors."""
+    ld = int(H if ld is None else ld)
+    for t in pair:
+        if t is not None and ld == H and not t.is_contiguous():
+            raise _ffi.VltfError("%s: a view into a wider tensor needs its row stride (ld)" % what)
+    return ld
+
+
+def lstm_seq_bi_fwd(gx, kh, act, cseq, hseq, hprev, batch, T, H, forget_bias=1.0, ws=None, h0=None, c0=None, seq_len=None,
+                    hseq_ld=None, state=None, tag_offset=0):
+    """Both directions of a bidirectional layer in one launch (vl_lstm_seq_bi_fwd).  gx, kh, act, cseq, hseq, hprev, h0, c0 are
+    (forward, backward) pairs; the backward cell runs over the reversed live prefix and stores by time index.  hseq_ld: row stride
+    of both hseq tensors (2 H with hseq = (out[:, :H], out[:, H:]) of one [batch T, 2H] tensor).  state: a step state -> the
+    replay-safe form (vl_lstm_seq_bi_fwd_st: no lengths), its tags from tag_offset."""
+    what = "lstm_seq_bi_fwd"
+    gx, kh, act, cseq, hseq, hprev, h0, c0 = (_pair(v, what) for v in (gx, kh, act, cseq, hseq, hprev, h0, c0))
+    _f32(*gx, *kh, *act, *cseq, *hseq, *hprev, *h0, *c0, ws)
+    _dense(*gx, *kh, *act, *cseq, *hprev, *h0, *c0)
+    if ws is None:
+        raise _ffi.VltfError("lstm_seq_bi_fwd: a workspace from lstm_seq_ws() is required")
+    ptrs = [_p(t) for pr in (gx, kh, h0, c0, act, cseq, hseq) for t in pr] + [_row_stride(hseq, H, hseq_ld, what), _p(hprev[0]), _p(hprev[1])]
+    if state is not None:
+        if seq_len is not None:
+            raise _ffi.VltfError("lstm_seq_bi_fwd: the replay-safe form takes no lengths")
+        _ffi.call("vl_lstm_seq_bi_fwd_st", *ptrs, batch, T, H, forget_bias, _p(ws), ws.numel() * 4, _state(state), int(tag_offset), stream())
+        return
+    _ffi.call("vl_lstm_seq_bi_fwd", *ptrs, batch, T, H, forget_bias, _p(None if seq_len is None else _seq_len(seq_len, batch, what)),
+              _p(ws), ws.numel() * 4, stream())
+
+
+def lstm_seq_bi_bwd(dout, kh, act, cseq, dz, batch, T, H, ws=None, c0=None, dh0=None, dc0=None, seq_len=None, dout_ld=None, state=None,
+                    tag_offset=0):
+    """BPTT of both directions in one launch (vl_lstm_seq_bi_bwd); pairs as in lstm_seq_bi_fwd, dout (nullable, each half too) with row
+    stride dout_ld; dh0 / dc0: optional output pairs.  state: the replay-safe form (vl_lstm_seq_bi_bwd_st)."""
+    what = "lstm_seq_bi_bwd"
+    dout, kh, act, cseq, dz, c0, dh0, dc0 = (_pair(v, what) for v in (dout, kh, act, cseq, dz, c0, dh0, dc0))
+    _f32(*dout, *kh, *act, *cseq, *dz, *c0, *dh0, *dc0, ws)
+    _dense(*kh, *act, *cseq, *dz, *c0, *dh0, *dc0)
+    if ws is None:
+        raise _ffi.VltfError("lstm_seq_bi_bwd: a workspace from lstm_seq_ws() is required")
+    ptrs = [_p(dout[0]), _p(dout[1]), _row_stride(dout, H, dout_ld, what)] + [_p(t) for pr in (kh, act, cseq, c0, dz, dh0, dc0) for t in pr]
+    if state is not None:
+        if seq_len is not None:
+            raise _ffi.VltfError("lstm_seq_bi_bwd: the replay-safe form takes no lengths")
+        _ffi.call("vl_lstm_seq_bi_bwd_st", *ptrs, batch, T, H, _p(ws), ws.numel() * 4, _state(state), int(tag_offset), stream())
+        return
+    _ffi.call("vl_lstm_seq_bi_bwd", *ptrs, batch, T, H, _p(None if seq_len is None else _seq_len(seq_len, batch, what)), _p(ws),
+              ws.numel() * 4, stream())
+
+
+def lstm_seq_bi_tag_span(batch, T, H):
+    """Exchange tags one replay-safe bidirectional call uses above its tag offset (0: H or the device cannot take the launch)."""
+    return int(_ffi.lib().vl_lstm_seq_bi_tag_span(int(batch), int(T), int(H)))
+
+
 def lstm_seq_ws_clear(ws):
     """Zeroes the exchange words of a workspace (not its time-out word), on the stream: its owner restarts its tags."""
     _f32(ws)

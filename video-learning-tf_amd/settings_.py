@@ -174,6 +174,7 @@ class Settings:
         if network.classifier == defs.classifier.lstm:
             params = parse_seq(self.read_field(content, "lstm_params", required=True))
             network.lstm_params = [int(params[0]), int(params[1]), defs.check(params[2], defs.fusion_method)]
+        network.lstm_bidirectional = self.read_lstm_bidirectional(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         network.input_shape = self.read_field(content, "input_shape", listify=True)
@@ -183,6 +184,24 @@ class Settings:
         if unread:
             error("Undefined pipeline field(s):" + str(unread))
         return network
+
+    def read_lstm_bidirectional(self, content, network):
+        """`lstm_bidirectional: True` beside lstm_params (this project's extension of the pipeline schema): every LSTM layer gets a
+        forward and a backward cell whose outputs are concatenated (tf.nn.bidirectional_dynamic_rnn).  Absent / None / False = off.
+        Refused without the LSTM classifier and for a hidden size the one-launch recurrence cannot take."""
+        v = self.read_field(content, "lstm_bidirectional")
+        if v in (None, "None", False, "False"):
+            return False
+        if v not in (True, "True"):
+            error("lstm_bidirectional must be True or False, got [%s]" % (v,))
+        if network.classifier != defs.classifier.lstm:
+            error("lstm_bidirectional needs classifier lstm, but the pipeline's classifier is [%s]" % network.classifier)
+        from .engine import VltfError, check_blstm
+        try:
+            check_blstm(network.lstm_params[0])
+        except VltfError as ex:
+            error(str(ex))
+        return True
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
