@@ -385,6 +385,35 @@ int vl_lstm_seq_bi_bwd_st(const float* dout_fw, const float* dout_bw, int64_t do
                           const float* c0_bw, float* dz_fw, float* dz_bw, float* dh0_fw, float* dh0_bw, float* dc0_fw, float* dc0_bw,
                           int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state, uint32_t tag_offset,
                           vl_stream_t stream);
+/* ---- GRU recurrence, reset-after form (Keras GRU(reset_after=True), CudnnGRU, torch.nn.GRU), gate blocks z | r | n of width H -------------
+ *   gh_t = h_{t-1} . rk + rb        z = sigmoid(gx_z + gh_z)   r = sigmoid(gx_r + gh_r)   n = tanh(gx_n + r * gh_n)
+ *   h_t  = z * h_{t-1} + (1 - z) * n
+ * gx [batch T][3H]: the input projections x . kernel + bias of all rows (one GEMM, the caller's); rk = recurrent_kernel [H][3H];
+ * rb = recurrent_bias [3H] (nullable: zeros); h0 (nullable, [batch][H]: zeros).  The forward writes act [batch T][3H] (the ACTIVATED
+ * z, r, n), hcand [batch T][H] (= gh_n with its bias: the backward needs it for the reset gate), hseq and hprev (h_{t-1} of every row).
+ * The backward, with din = dout_t + dh (dout nullable: zeros):
+ *   dn = din (1 - z)(1 - n^2)   dz' = din (h_{t-1} - n) z (1 - z)   dr' = dn gh_n r (1 - r)
+ *   dgx_t = [dz', dr', dn]   dgh_t = [dz', dr', dn r]   dh_{t-1} = din z + dgh_t . rk^T
+ * writes dgx and dgh [batch T][3H] (the caller's GEMMs give d kernel = x^T dgx, d bias = colsum dgx, d rk = hprev^T dgh,
+ * d rb = colsum dgh, dx = dgx kernel^T) and, when asked, dh0 [batch][H].
+ * The cluster form of vl_lstm_seq_fwd only, H <= 512 (larger: an error, nothing launched; there is no per-clip form): a workgroup keeps the
+ * 48 columns of rk of its 16 units in LDS.  Launch plan, workspace (vl_lstm_seq_ws_bytes), status word (vl_lstm_seq_status) and test
+ * hooks are the LSTM's, and a launch takes its T + 1 tags from the SAME process-wide counter as the LSTM launches, so GRU and LSTM
+ * launches may share a workspace.  seq_len (nullable, device int32 [batch]): the dead-row contract above -- a dead step carries h,
+ * writes act = hcand = hseq = dgx = dgh = 0 and hprev = the carried h, and never reads its row of gx or dout.
+ * The eager pair refuses a stream that is being captured; the _st pair (no lengths) takes its tags as vl_lstm_seq_fwd_st does, and
+ * vl_gru_seq_tag_span = launches x (T + 1) counts them (0 where the calls are refused). */
+int vl_gru_seq_fwd(const float* gx, const float* rk, const float* rb, const float* h0, float* act, float* hcand, float* hseq,
+                   float* hprev, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream);
+int vl_gru_seq_bwd(const float* dout, const float* rk, const float* act, const float* hcand, const float* hprev, float* dgx, float* dgh,
+                   float* dh0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream);
+size_t vl_gru_seq_tag_span(int batch, int T, int H);
+int vl_gru_seq_fwd_st(const float* gx, const float* rk, const float* rb, const float* h0, float* act, float* hcand, float* hseq,
+                      float* hprev, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state, uint32_t tag_offset,
+                      vl_stream_t stream);
+int vl_gru_seq_bwd_st(const float* dout, const float* rk, const float* act, const float* hcand, const float* hprev, float* dgx,
+                      float* dgh, float* dh0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                      uint32_t tag_offset, vl_stream_t stream);
 /* Zeroes the exchange words of `ws` (not its time-out word), on the stream: lets the owner of a workspace restart its tags. */
 int vl_lstm_seq_ws_clear(void* ws, size_t ws_bytes, vl_stream_t stream);
 /* Synchronous read-and-reset of the time-out flag in `ws`: *timed_out = 1 if a workgroup of ANY cluster-form launch on `ws` since

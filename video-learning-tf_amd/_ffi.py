@@ -79,6 +79,11 @@ SIGNATURES = {
     "vl_lstm_seq_bi_tag_span": (sz, [i32, i32, i32]),
     "vl_lstm_seq_bi_fwd_st": (i32, [p] * 14 + [i64, p, p, i32, i32, i32, f32, p, sz, p, u32, p]),
     "vl_lstm_seq_bi_bwd_st": (i32, [p, p, i64] + [p] * 14 + [i32, i32, i32, p, sz, p, u32, p]),
+    "vl_gru_seq_fwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, p, sz, p]),
+    "vl_gru_seq_bwd": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, p, sz, p]),
+    "vl_gru_seq_tag_span": (sz, [i32, i32, i32]),
+    "vl_gru_seq_fwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p, u32, p]),
+    "vl_gru_seq_bwd_st": (i32, [p, p, p, p, p, p, p, p, i32, i32, i32, p, sz, p, u32, p]),
     "vl_lstm_seq_ws_clear": (i32, [p, sz, p]),
     "vl_lstm_seq_status": (i32, [p, C.POINTER(i32)]),
     "vl_lstm_seq_test_hooks": (i32, [C.c_uint, i32]),

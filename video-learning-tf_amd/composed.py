@@ -77,6 +77,11 @@ class ComposedEngine(GraphEngine):
             raise VltfError("lstm_bidirectional is not built for the two-pipeline model: its decoder takes pipeline 1's output as the "
                             "state of a unidirectional LSTM, and its heads are specified by HeadConfig, which has no such option "
                             "(use GraphEngine with PipelineSpec(lstm_bidirectional=True) for a pipeline without a state input)")
+        if getattr(enc_cfg, "rnn_cell", "lstm") != "lstm" or getattr(head, "rnn_cell", "lstm") != "lstm":
+            raise VltfError("rnn_cell [%s] is not built for the two-pipeline model: its decoder takes pipeline 1's output as the state of "
+                            "an LSTM (use LRCNEngine, or GraphEngine with PipelineSpec(rnn_cell=\"gru\") for a pipeline without a state "
+                            "input)" % (getattr(enc_cfg, "rnn_cell", "lstm") if getattr(enc_cfg, "rnn_cell", "lstm") != "lstm"
+                                        else getattr(head, "rnn_cell", "lstm")))
         self.h = head
         pipes, datasets = two_pipelines(enc_cfg, head, max_clips, scopes)
         super().__init__(pipes, datasets, head.num_classes, device, training, dp, optimizer=enc_cfg.optimizer,

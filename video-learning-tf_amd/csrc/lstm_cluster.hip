@@ -295,7 +295,8 @@ __global__ __launch_bounds__(LNT) void lstm_cluster_fwd_kernel(const typename Cl
 
 // ---- backward -----------------------------------------------------------------------------------------------------------
 // partial[c][k] = sum over the own 64 columns of dz[c][j] Kh[k][j], for the first NC clips, published as granules
-template <int NC>
+// (NCOL: the workgroup's column count -- 64 for the LSTM, 48 for the GRU kernels below)
+template <int NC, int NCOL = LC>
 __device__ __forceinline__ void publish_partials(const float* KsT, const float* zl, u64* dst, int H, int Hp, int nclips, unsigned epoch,
                                                  int tid) {
     for (int k = tid; k < H; k += LNT) {
@@ -304,15 +305,15 @@ __device__ __forceinline__ void publish_partials(const float* KsT, const float* 
         for (int c = 0; c < NC; ++c) acc[c] = 0.f;
         // eight columns per pass, their LDS reads (8 weights, NC x 2 quads of dz -- broadcast reads) issued together: as in the forward
         // product the loop is LDS latency, not bandwidth; the sums keep the one-column-per-pass order (same bits)
-        for (int jj = 0; jj < LC; jj += 8) {
+        for (int jj = 0; jj < NCOL; jj += 8) {
             float wv[8];
             float4 za[NC], zc[NC];
 #pragma unroll
             for (int e = 0; e < 8; ++e) wv[e] = KsT[(jj + e) * Hp + k];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                za[c] = *reinterpret_cast<const float4*>(zl + c * LC + jj);
-                zc[c] = *reinterpret_cast<const float4*>(zl + c * LC + jj + 4);
+                za[c] = *reinterpret_cast<const float4*>(zl + c * NCOL + jj);
+                zc[c] = *reinterpret_cast<const float4*>(zl + c * NCOL + jj + 4);
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -820,4 +821,384 @@ extern "C" int vl_lstm_seq_test_hooks(unsigned spin_limit, int mute_workgroup) {
     g_spin_limit = spin_limit ? spin_limit : SPIN_LIMIT;
     g_mute_workgroup = mute_workgroup;
     return 0;
+}
+
+// ---- GRU (reset-after form: Keras GRU(reset_after=True), CudnnGRU, torch.nn.GRU; gate blocks z | r | n) -------------------------------------
+//   gh_t = h_{t-1} . recurrent_kernel + recurrent_bias      z = s(gx_z + gh_z)   r = s(gx_r + gh_r)   n = tanh(gx_n + r gh_n)
+//   h_t = z h_{t-1} + (1 - z) n
+// Every pre-activation is a function of h_{t-1} alone, so a step needs the ONE all-gather of h the LSTM step needs: the protocol above --
+// granules, T + 1 tags per launch from g_epoch_base, two parities, the length-blind exchange, the sticky status word, the launch plan of
+// vl_lstm_cluster_run and the workspace of vl_lstm_seq_ws_bytes -- is used as it stands.  (The reset-before form needs r h of ALL units before
+// the candidate: two dependent exchanges per step.  Not built.)  What differs from the LSTM kernels:
+//   * a workgroup owns the GC = 48 columns {q H + u} of its 16 units: Ks is [Hp][48] (bwd: [48][Hp]), plus its 48 entries of recurrent_bias.
+//     Column j of the product belongs to lane j of each wave; LANES 48..63 IDLE in the product (the slice is not padded to 64: the loop is LDS
+//     latency, an idle quarter wave costs nothing, and the padded slice would only take LDS);
+//   * there is no cell state: the gate thread of (clip, unit) reads its own h_{t-1} from the gathered copy;
+//   * the forward stores hcand = gh_n (with its bias) beside the activated gates: the backward needs it for dr';
+//   * backward: dgx_t = [dz', dr', dn] and dgh_t = [dz', dr', dn r] of the own columns are local; din z is carried in a register (as dc is in
+//     the LSTM kernel) and dgh_t . recurrent_kernel^T is the reduce-scatter of publish_partials.
+static constexpr int GC = 3 * LU;    // gate columns per workgroup
+
+struct GruClusterArgs {
+    const float* gx;      // fwd: [B T][3H] input projections (+bias)
+    const float* rk;      // [H][3H] recurrent_kernel
+    const float* rb;      // fwd: nullable [3H] recurrent_bias
+    const float* h0;      // fwd: nullable [B][H]
+    float* act;           // [B T][3H] activated z, r, n (fwd: out, bwd: in)
+    float* hcand;         // [B T][H] gh_n (fwd: out, bwd: in)
+    float* hseq;          // fwd out
+    float* hprev;         // [B T][H] h_{t-1} (fwd: out, bwd: in)
+    const float* dout;    // bwd: nullable [B T][H]
+    float* dgx;           // bwd out [B T][3H]
+    float* dgh;           // bwd out [B T][3H]
+    float* dh0;           // bwd: nullable out [B][H]
+    const int32_t* seq_len;   // nullable [B], as in LstmClusterArgs
+    u64* xch;
+    unsigned* status;
+    int B, T, H, Hp, G, W, cpg;
+    unsigned spin_limit;
+    int mute;
+    unsigned ebase;
+    const vl_step_state* state;
+};
+
+template <bool ST>
+__global__ __launch_bounds__(LNT) void gru_cluster_fwd_kernel(const GruClusterArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int H = p.H, Hp = p.Hp, H3 = 3 * p.H, T = p.T;
+    const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
+    float* Ks = sm;                   // [Hp][GC]  (rows H .. Hp - 1: zeros)
+    float* hb = Ks + (size_t)Hp * GC; // [CPG][Hp]   h_{t-1} of the group's clips
+    float* zb = hb + CPG * Hp;        // [KP][2 S][GC] the own columns of h_{t-1} . recurrent_kernel per reduction slice (8 rows)
+    float* bs = zb + CPG * GC;        // [GC] the own columns of recurrent_bias
+    const int tid = threadIdx.x;
+    const int grp = blockIdx.x % p.G, w = blockIdx.x / p.G;
+    const int clip0 = grp * p.cpg;
+    const int nclips = min(p.cpg, p.B - clip0);
+    for (int i = tid; i < Hp * GC; i += LNT) {
+        const int k = i / GC, j = i - k * GC, q = j / LU, u = w * LU + (j - q * LU);
+        Ks[i] = (u < H && k < H) ? p.rk[(int64_t)k * H3 + q * H + u] : 0.f;
+    }
+    if (tid < GC) {
+        const int q = tid / LU, u = w * LU + (tid - q * LU);
+        bs[tid] = (p.rb && u < H) ? p.rb[q * H + u] : 0.f;
+    }
+    for (int i = tid; i < CPG * Hp; i += LNT) {
+        const int c = i / Hp, k = i - c * Hp;
+        hb[i] = (p.h0 && c < nclips && k < H) ? p.h0[(int64_t)(clip0 + c) * H + k] : 0.f;
+    }
+    // gate threads: (clip gc, unit gul) for tid < CPG * LU
+    const int gc = tid / LU, gul = tid - gc * LU, gu = w * LU + gul;
+    const bool glive = tid < CPG * LU && gc < nclips && gu < H;
+    const int len = (glive && p.seq_len) ? min(max(p.seq_len[clip0 + gc], 0), T) : T;
+    // product threads: lane j < GC of wave wv works on column j for the clip pair (slot, slot + S) over the kpart-th slice (as in the LSTM kernel)
+    const int j = tid & 63, wv = tid >> 6;
+    const int S = nclips > 4 ? 4 : (nclips > 2 ? 2 : 1), KP = 4 / S;
+    const int slot = wv & (S - 1), kpart = wv / S;
+    const int klen = ((H + KP - 1) / KP + 3) / 4 * 4, kbeg = kpart * klen, kend = min(H, kbeg + klen);
+    const int ngran = nclips * H;
+    constexpr int MAXG = CPG * LH_MAX / LNT;
+    const int myn = ngran > tid ? (ngran - tid + LNT - 1) / LNT : 0;
+    u64* xg = p.xch + (size_t)grp * CPG * Hp;
+    const size_t xpar = (size_t)p.G * CPG * Hp;
+    __syncthreads();
+
+    for (int t = 0; t < T; ++t) {
+        float xz = 0.f, xr = 0.f, xn = 0.f;
+        const int64_t r = (int64_t)(clip0 + gc) * T + t;
+        const bool alive = t < len;
+        if (glive && alive) {                                  // a dead row of gx is never read
+            const float* g = p.gx + r * H3 + gu;
+            xz = g[0]; xr = g[H]; xn = g[2 * H];
+        }
+        if (t > 0) {
+            const u64* src = xg + ((t - 1) & 1) * xpar;
+            auto run = [&](auto tag) {
+                constexpr int N = decltype(tag)::value;
+                float v[N];
+                gather_granules<N>(src, myn, [&](int m) { const int i = tid + LNT * m; const int c = i / H; return c * Hp + (i - c * H); },
+                                   ebase + (unsigned)t, v, p.status, p.spin_limit);
+#pragma unroll
+                for (int m = 0; m < N; ++m)
+                    if (m < myn) {
+                        const int i = tid + LNT * m, c = i / H;
+                        hb[c * Hp + (i - c * H)] = v[m];
+                    }
+            };
+            if (myn <= 1) run(IntK<1>{});
+            else if (myn <= 2) run(IntK<2>{});
+            else if (myn <= 8) run(IntK<8>{});
+            else run(IntK<MAXG>{});
+        }
+        __syncthreads();                                       // h_{t-1} complete in LDS
+        const float hp = glive ? hb[gc * Hp + gu] : 0.f;
+        if (j < GC) {
+            float z0 = 0.f, z1 = 0.f;
+            const float* h0p = hb + slot * Hp;
+            const float* h1p = hb + (slot + S) * Hp;
+            const float* kp = Ks + j;
+            int k = kbeg;
+            for (; k + 16 <= kend; k += 16) {                  // four reduction quads per pass, as in the LSTM kernel
+                float4 a[4], b[4];
+                float wq[4][4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    a[u] = *reinterpret_cast<const float4*>(h0p + k + 4 * u);
+                    b[u] = *reinterpret_cast<const float4*>(h1p + k + 4 * u);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) wq[u][e] = kp[(k + 4 * u + e) * GC];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    z0 += a[u].x * wq[u][0] + a[u].y * wq[u][1] + a[u].z * wq[u][2] + a[u].w * wq[u][3];
+                    z1 += b[u].x * wq[u][0] + b[u].y * wq[u][1] + b[u].z * wq[u][2] + b[u].w * wq[u][3];
+                }
+            }
+            for (; k < kend; k += 4) {
+                const float4 a = *reinterpret_cast<const float4*>(h0p + k);
+                const float4 b = *reinterpret_cast<const float4*>(h1p + k);
+                const float w0 = kp[(k + 0) * GC], w1 = kp[(k + 1) * GC], w2 = kp[(k + 2) * GC], w3 = kp[(k + 3) * GC];
+                z0 += a.x * w0 + a.y * w1 + a.z * w2 + a.w * w3;
+                z1 += b.x * w0 + b.y * w1 + b.z * w2 + b.w * w3;
+            }
+            zb[(kpart * 2 * S + slot) * GC + j] = z0;
+            zb[(kpart * 2 * S + slot + S) * GC + j] = z1;
+        }
+        __syncthreads();                                       // own columns complete; everyone has consumed h_{t-1}
+        if (glive) {
+            // dead step: gates, candidate and output 0; the carried h (= hp) is what the peers get
+            float az = 0.f, ar = 0.f, an = 0.f, hc = 0.f, h = 0.f, hpub = hp;
+            if (alive) {
+                float gh[3] = {0.f, 0.f, 0.f};
+                for (int kp_ = 0; kp_ < KP; ++kp_)             // fixed order: reproducible
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) gh[q] += zb[(kp_ * 2 * S + gc) * GC + q * LU + gul];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) gh[q] += bs[q * LU + gul];
+                az = sigm(xz + gh[0]); ar = sigm(xr + gh[1]); hc = gh[2];
+                an = tanhf(xn + ar * hc);
+                h = az * hp + (1.f - az) * an;
+                hpub = h;
+            }
+            if (t + 1 < T && (int)blockIdx.x != p.mute) store_granule(xg + (t & 1) * xpar + gc * Hp + gu, ebase + (unsigned)(t + 1), hpub);
+            float* a = p.act + r * H3 + gu;
+            a[0] = az; a[H] = ar; a[2 * H] = an;
+            p.hcand[r * H + gu] = hc;
+            p.hseq[r * H + gu] = h;
+            p.hprev[r * H + gu] = hp;
+        }
+        // (no barrier here: see the LSTM kernel)
+    }
+}
+
+template <bool ST>
+__global__ __launch_bounds__(LNT) void gru_cluster_bwd_kernel(const GruClusterArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int H = p.H, Hp = p.Hp, H3 = 3 * p.H, T = p.T, W = p.W;
+    const unsigned ebase = ST ? p.ebase + p.state->tag_origin : p.ebase;
+    float* KsT = sm;                      // [GC][Hp]  KsT[j][k] = rk[k][column j of this workgroup]
+    float* zl = KsT + (size_t)GC * Hp;    // [CPG][GC] dgh_t of the own columns
+    const int tid = threadIdx.x;
+    const int grp = blockIdx.x % p.G, w = blockIdx.x / p.G;
+    const int clip0 = grp * p.cpg;
+    const int nclips = min(p.cpg, p.B - clip0);
+    for (int i = tid; i < GC * Hp; i += LNT) {
+        const int jj = i / Hp, k = i - jj * Hp, q = jj / LU, u = w * LU + (jj - q * LU);
+        KsT[i] = (u < H && k < H) ? p.rk[(int64_t)k * H3 + q * H + u] : 0.f;
+    }
+    for (int i = tid; i < CPG * GC; i += LNT) zl[i] = 0.f;
+    const int gc = tid / LU, gul = tid - gc * LU, gu = w * LU + gul;
+    const bool glive = tid < CPG * LU && gc < nclips && gu < H;
+    float dhz = 0.f, dh = 0.f;                                  // din_{t+1} z_{t+1} (local) and dgh_{t+1} . rk^T (gathered)
+    const int len = (glive && p.seq_len) ? min(max(p.seq_len[clip0 + gc], 0), T) : T;
+    // exchange: P[parity][group][source workgroup][clip][k]
+    const size_t pgrp = (size_t)W * CPG * Hp, ppar = (size_t)p.G * pgrp;
+    u64* pg = p.xch + (size_t)grp * pgrp;
+    constexpr int MAXW = LH_MAX / LU;
+    auto gather_dh = [&](unsigned epoch) {
+        const u64* src = pg + (epoch & 1) * ppar + (size_t)gc * Hp + gu;
+        const size_t wstride = (size_t)CPG * Hp;
+        auto run = [&](auto tag) {
+            constexpr int N = decltype(tag)::value;
+            float v[N];
+            gather_granules<N>(src, glive ? W : 0, [&](int m) { return (size_t)m * wstride; }, ebase + epoch, v, p.status, p.spin_limit);
+            float s = 0.f;
+#pragma unroll
+            for (int m = 0; m < N; ++m)
+                if (m < W) s += v[m];                           // fixed order: reproducible
+            return s;
+        };
+        if (W <= 4) return run(IntK<4>{});
+        if (W <= 16) return run(IntK<16>{});
+        return run(IntK<MAXW>{});
+    };
+    __syncthreads();
+
+    for (int t = T - 1; t >= 0; --t) {
+        const int64_t r = (int64_t)(clip0 + gc) * T + t;
+        const unsigned epoch = (unsigned)(T - t);               // 1 .. T
+        float din = 0.f, az = 0.f, ar = 0.f, an = 0.f, hc = 0.f, hp = 0.f;
+        const bool alive = t < len;
+        if (glive && alive) {                                   // a dead row of dout / act / hcand / hprev is never read
+            din = p.dout ? p.dout[r * H + gu] : 0.f;
+            const float* a = p.act + r * H3 + gu;
+            az = a[0]; ar = a[H]; an = a[2 * H];
+            hc = p.hcand[r * H + gu];
+            hp = p.hprev[r * H + gu];
+        }
+        if (t < T - 1) dh = gather_dh(epoch - 1);
+        if (glive) {
+            // dead step: dgx = dgh = 0 exactly; dhz stays 0 and the gathered dh is a sum of zeros (dead steps are a suffix)
+            float dzp = 0.f, drp = 0.f, dn = 0.f, dnr = 0.f;
+            if (alive) {
+                din += dhz + dh;
+                dn = din * (1.f - az) * (1.f - an * an);
+                dzp = din * (hp - an) * az * (1.f - az);
+                drp = dn * hc * ar * (1.f - ar);
+                dnr = dn * ar;
+                dhz = din * az;
+            }
+            float* xp = p.dgx + r * H3 + gu;
+            xp[0] = dzp; xp[H] = drp; xp[2 * H] = dn;
+            float* hq = p.dgh + r * H3 + gu;
+            hq[0] = dzp; hq[H] = drp; hq[2 * H] = dnr;
+            float* zz = zl + gc * GC + gul;
+            zz[0] = dzp; zz[LU] = drp; zz[2 * LU] = dnr;
+        }
+        __syncthreads();                                        // own dgh_t in LDS
+        if ((t > 0 || p.dh0) && (int)blockIdx.x != p.mute) {
+            u64* dst = pg + (epoch & 1) * ppar + (size_t)w * CPG * Hp;
+            if (nclips > 4) publish_partials<8, GC>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else if (nclips > 2) publish_partials<4, GC>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else if (nclips > 1) publish_partials<2, GC>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+            else publish_partials<1, GC>(KsT, zl, dst, H, Hp, nclips, ebase + epoch, tid);
+        }
+        __syncthreads();                                        // zl consumed before the next step rewrites it
+    }
+    if (p.dh0) {
+        dh = gather_dh((unsigned)T);
+        if (glive) p.dh0[(int64_t)(clip0 + gc) * H + gu] = dhz + dh;
+    }
+}
+
+static int gru_lds_attrs() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        const void* kerns[4] = {reinterpret_cast<const void*>(gru_cluster_fwd_kernel<false>), reinterpret_cast<const void*>(gru_cluster_bwd_kernel<false>),
+                                reinterpret_cast<const void*>(gru_cluster_fwd_kernel<true>), reinterpret_cast<const void*>(gru_cluster_bwd_kernel<true>)};
+        for (const void* k : kerns) VL_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr_set = true;
+    }
+    return 0;
+}
+
+// The launch plan of vl_lstm_cluster_run (chunks of at most maxG * 8 clips, one launch each), tags from the same counter.
+static int vl_gru_cluster_run(bool bwd, GruClusterArgs a, int batch, void* ws, size_t ws_bytes, const vl_step_state* st, unsigned tag_offset,
+                              hipStream_t s) {
+    const ClusterPlan c = cluster_plan(a.H);
+    a.W = c.W;
+    a.Hp = c.Hp;
+    a.status = (unsigned*)ws;
+    a.xch = (u64*)((char*)ws + STATUS_BYTES);
+    a.state = st;
+    const size_t lds = bwd ? sizeof(float) * ((size_t)GC * c.Hp + CPG * GC) : sizeof(float) * ((size_t)c.Hp * GC + CPG * c.Hp + CPG * GC + GC);
+    if (gru_lds_attrs()) return 1;
+    a.spin_limit = g_spin_limit;
+    a.mute = g_mute_workgroup;
+    const GruClusterArgs whole = a;
+    for (int b0 = 0, k = 0; b0 < batch; b0 += c.chunk, ++k) {
+        const int nb = batch - b0 < c.chunk ? batch - b0 : c.chunk;
+        int G = nb < c.maxG ? nb : c.maxG;
+        const int cpg = (nb + G - 1) / G;
+        G = (nb + cpg - 1) / cpg;
+        a.B = nb; a.G = G; a.cpg = cpg;
+        const int64_t ro = (int64_t)b0 * a.T, so = (int64_t)b0 * a.H;
+        a.gx = whole.gx ? whole.gx + ro * 3 * a.H : nullptr;
+        a.h0 = whole.h0 ? whole.h0 + so : nullptr;
+        a.act = whole.act + ro * 3 * a.H;
+        a.hcand = whole.hcand + ro * a.H;
+        a.hseq = whole.hseq ? whole.hseq + ro * a.H : nullptr;
+        a.hprev = whole.hprev + ro * a.H;
+        a.dout = whole.dout ? whole.dout + ro * a.H : nullptr;
+        a.dgx = whole.dgx ? whole.dgx + ro * 3 * a.H : nullptr;
+        a.dgh = whole.dgh ? whole.dgh + ro * 3 * a.H : nullptr;
+        a.dh0 = whole.dh0 ? whole.dh0 + so : nullptr;
+        a.seq_len = whole.seq_len ? whole.seq_len + b0 : nullptr;
+        if (st) {
+            a.ebase = tag_offset + (unsigned)k * ((unsigned)a.T + 1u);       // over st->tag_origin (vl_gru_seq_tag_span counts these launches)
+            if (bwd) hipLaunchKernelGGL(gru_cluster_bwd_kernel<true>, dim3(G * c.W), dim3(LNT), lds, s, a);
+            else hipLaunchKernelGGL(gru_cluster_fwd_kernel<true>, dim3(G * c.W), dim3(LNT), lds, s, a);
+            VL_LAUNCH_CHECK();
+            continue;
+        }
+        a.ebase = __atomic_fetch_add(&g_epoch_base, (unsigned)a.T + 1u, __ATOMIC_RELAXED);   // ONE counter for LSTM and GRU launches
+        if (a.ebase > 0xfff00000u) {                                         // as in vl_lstm_cluster_run
+            VL_HIP(hipMemsetAsync(a.xch, 0, ws_bytes - STATUS_BYTES, s));
+            __atomic_store_n(&g_epoch_base, (unsigned)a.T + 1u, __ATOMIC_RELAXED);
+            a.ebase = 0;
+        }
+        if (bwd) hipLaunchKernelGGL(gru_cluster_bwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
+        else hipLaunchKernelGGL(gru_cluster_fwd_kernel<false>, dim3(G * c.W), dim3(LNT), lds, s, a);
+        VL_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+static int gru_seq_fwd(const char* what, const float* gx, const float* rk, const float* rb, const float* h0, float* act, float* hcand, float* hseq,
+                       float* hprev, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, const vl_step_state* st,
+                       unsigned tag_offset, hipStream_t stream) {
+    VL_CHECK(gx && rk && act && hcand && hseq && hprev, "%s: null argument", what);
+    VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= LH_MAX, "%s: bad shape (the GRU recurrence needs a hidden size <= %d)", what, LH_MAX);
+    VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "%s: workspace smaller than vl_lstm_seq_ws_bytes", what);
+    GruClusterArgs a = {};
+    a.gx = gx; a.rk = rk; a.rb = rb; a.h0 = h0; a.act = act; a.hcand = hcand; a.hseq = hseq; a.hprev = hprev;
+    a.T = T; a.H = H; a.seq_len = seq_len;
+    return vl_gru_cluster_run(false, a, batch, ws, ws_bytes, st, tag_offset, stream);
+}
+
+static int gru_seq_bwd(const char* what, const float* dout, const float* rk, const float* act, const float* hcand, const float* hprev, float* dgx,
+                       float* dgh, float* dh0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes,
+                       const vl_step_state* st, unsigned tag_offset, hipStream_t stream) {
+    VL_CHECK(rk && act && hcand && hprev && dgx && dgh, "%s: null argument", what);
+    VL_CHECK(batch > 0 && T > 0 && H > 0 && H <= LH_MAX, "%s: bad shape (the GRU recurrence needs a hidden size <= %d)", what, LH_MAX);
+    VL_CHECK(ws && ws_bytes >= vl_lstm_seq_ws_bytes(batch, T, H), "%s: workspace smaller than vl_lstm_seq_ws_bytes", what);
+    GruClusterArgs a = {};
+    a.rk = rk; a.act = const_cast<float*>(act); a.hcand = const_cast<float*>(hcand); a.hprev = const_cast<float*>(hprev); a.dout = dout;
+    a.dgx = dgx; a.dgh = dgh; a.dh0 = dh0; a.T = T; a.H = H; a.seq_len = seq_len;
+    return vl_gru_cluster_run(true, a, batch, ws, ws_bytes, st, tag_offset, stream);
+}
+
+extern "C" int vl_gru_seq_fwd(const float* gx, const float* rk, const float* rb, const float* h0, float* act, float* hcand, float* hseq,
+                              float* hprev, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_gru_seq_fwd", seq_len == nullptr)) return 1;
+    return gru_seq_fwd("vl_gru_seq_fwd", gx, rk, rb, h0, act, hcand, hseq, hprev, batch, T, H, seq_len, ws, ws_bytes, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int vl_gru_seq_bwd(const float* dout, const float* rk, const float* act, const float* hcand, const float* hprev, float* dgx, float* dgh,
+                              float* dh0, int batch, int T, int H, const int32_t* seq_len, void* ws, size_t ws_bytes, vl_stream_t stream) {
+    if (refuse_capture((hipStream_t)stream, "vl_gru_seq_bwd", seq_len == nullptr)) return 1;
+    return gru_seq_bwd("vl_gru_seq_bwd", dout, rk, act, hcand, hprev, dgx, dgh, dh0, batch, T, H, seq_len, ws, ws_bytes, nullptr, 0,
+                       (hipStream_t)stream);
+}
+
+extern "C" size_t vl_gru_seq_tag_span(int batch, int T, int H) {
+    if (batch < 1 || T < 1 || !vl_lstm_cluster_ok(H)) return 0;
+    const ClusterPlan c = cluster_plan(H);
+    return (size_t)((batch + c.chunk - 1) / c.chunk) * ((size_t)T + 1);
+}
+
+extern "C" int vl_gru_seq_fwd_st(const float* gx, const float* rk, const float* rb, const float* h0, float* act, float* hcand, float* hseq,
+                                 float* hprev, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                                 uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_gru_seq_fwd_st: null state");
+    return gru_seq_fwd("vl_gru_seq_fwd_st", gx, rk, rb, h0, act, hcand, hseq, hprev, batch, T, H, nullptr, ws, ws_bytes, state, tag_offset,
+                       (hipStream_t)stream);
+}
+
+extern "C" int vl_gru_seq_bwd_st(const float* dout, const float* rk, const float* act, const float* hcand, const float* hprev, float* dgx,
+                                 float* dgh, float* dh0, int batch, int T, int H, void* ws, size_t ws_bytes, const vl_step_state* state,
+                                 uint32_t tag_offset, vl_stream_t stream) {
+    VL_CHECK(state, "vl_gru_seq_bwd_st: null state");
+    return gru_seq_bwd("vl_gru_seq_bwd_st", dout, rk, act, hcand, hprev, dgx, dgh, dh0, batch, T, H, nullptr, ws, ws_bytes, state, tag_offset,
+                       (hipStream_t)stream);
 }

@@ -53,6 +53,7 @@ class NetConfig:
     lstm_layers: int = 1
     fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state}
     lstm_bidirectional: bool = False            # every LSTM layer a forward and a backward cell, outputs concatenated (blstm_names); H <= 512
+    rnn_cell: str = "lstm"                      # the recurrent cell of classifier lstm: "lstm" (BasicLSTMCell) | "gru" (reset-after, gru_names); H <= 512
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
@@ -112,6 +113,49 @@ def check_blstm(hidden, what="lstm_bidirectional"):
                         % (what, BLSTM_MAX_HIDDEN, hidden))
 
 
+RNN_CELLS = ("lstm", "gru")
+GRU_MAX_HIDDEN = ops.GRU_MAX_HIDDEN     # the GRU recurrence exists in the cluster form only (vltf.h: vl_gru_seq_fwd)
+
+
+def gru_names(layer, scope=""):
+    """The variable names of one GRU layer (Keras GRU(reset_after=True) under multi_rnn_cell's scopes), in flat-buffer order: kernel
+    (d, 3H), recurrent_kernel (H, 3H), bias (3H,), recurrent_bias (3H,); gate blocks z | r | n.  The two biases are Keras' (2, 3H) bias
+    split into its rows ON PURPOSE: decay_ranges, LARS and LAMB treat rank >= 2 as a weight, and a rank-2 bias would be decayed and
+    trust-scaled."""
+    return [scope + "rnn/multi_rnn_cell/cell_%d/gru_cell/%s" % (layer, v) for v in ("kernel", "recurrent_kernel", "bias", "recurrent_bias")]
+
+
+def gru_specs(layer, d, H, scope=""):
+    """[(name, shape)] of gru_names(layer) for an input of width d."""
+    return list(zip(gru_names(layer, scope), ((d, 3 * H), (H, 3 * H), (3 * H,), (3 * H,))))
+
+
+def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state_input=False, what="rnn_cell"):
+    """Refuses what the GRU classifier is not built for; -> the cell.  `classifier`: "lstm" where the pipeline has the recurrent classifier."""
+    if cell not in RNN_CELLS:
+        raise VltfError("%s must be lstm or gru, got [%s]" % (what, cell))
+    if cell == "gru":
+        if classifier != "lstm":
+            raise VltfError("%s: gru is the recurrent cell of classifier lstm, but the classifier is [%s]" % (what, classifier))
+        if bidirectional:
+            raise VltfError("%s: gru with lstm_bidirectional is not built (the bidirectional launch runs LSTM cells)" % what)
+        if state_input:
+            raise VltfError("%s: gru takes no state input: the reference hands an LSTM ONE vector as c = h, and a GRU has no cell state" % what)
+        if not 1 <= int(hidden) <= GRU_MAX_HIDDEN:
+            raise VltfError("%s: the GRU recurrence runs in the cluster form only and needs a hidden size <= %d, got %d"
+                            % (what, GRU_MAX_HIDDEN, hidden))
+    return cell
+
+
+def gru_buffers(buf, rows, H, training):
+    """The device buffers of one GRU layer: projections gx, activated gates act, the candidate's recurrent term hcand, outputs hseq,
+    entering outputs hprev (and, training, the gradients dgx / dgh of the two pre-activation terms and dout of the output)."""
+    S = dict(gx=buf(rows, 3 * H), act=buf(rows, 3 * H), hcand=buf(rows, H), hseq=buf(rows, H), hprev=buf(rows, H))
+    if training:
+        S.update(dgx=buf(rows, 3 * H), dgh=buf(rows, 3 * H), dout=buf(rows, H))
+    return S
+
+
 def blstm_buffers(buf, rows, H, training):
     """The device buffers of one bidirectional layer.  Per direction, as (forward, backward) pairs: projections gx, gates act, cell
     states cseq, entering outputs hprev (and dz when training); ONE [rows][2H] output hseq and ONE gradient dout of it, whose halves
@@ -136,9 +180,19 @@ def param_specs(cfg: NetConfig):
             h, w = ops.pool_out(h), ops.pool_out(w)
     specs = []
     dim = cfg.encode_dim()
+    check_rnn_cell(cfg.rnn_cell, cfg.classifier, cfg.lstm_hidden, cfg.lstm_bidirectional)
     if cfg.lstm_bidirectional and cfg.classifier != "lstm":
         raise VltfError("lstm_bidirectional needs classifier lstm, not [%s]" % cfg.classifier)
-    if cfg.classifier == "lstm" and cfg.lstm_bidirectional:
+    if cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
+        H = cfg.lstm_hidden
+        if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
+            head = "fc_convert" if cfg.fusion == "state" else "output_fc"
+            specs += [(head + "_w", (H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+        d = dim
+        for l in range(cfg.lstm_layers):
+            specs += gru_specs(l, d, H)
+            d = H
+    elif cfg.classifier == "lstm" and cfg.lstm_bidirectional:
         check_blstm(cfg.lstm_hidden)
         H = cfg.lstm_hidden
         if 2 * H != cfg.num_classes:                      # the head reads the 2H-wide fused vector
@@ -1126,8 +1180,9 @@ class LRCNEngine:
             self.lstm_fusion = "last" if cfg.fusion == "state" else cfg.fusion
             self.per_step = cfg.fusion == "reshape"
             self.head = "fc_convert" if cfg.fusion == "state" else "output_fc"
-            self.lstm, self.blstm = [], []                              # per-layer buffers: unidirectional layers, or bidirectional ones
+            self.lstm, self.blstm, self.gru = [], [], []                # per-layer buffers: unidirectional, bidirectional or GRU layers
             self.bi = bool(cfg.lstm_bidirectional)
+            self.is_gru = cfg.rnn_cell == "gru"                         # (refusals: param_specs -> check_rnn_cell)
             HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
                 raise VltfError("lstm_bidirectional: this device has too few compute units to hold both directions of hidden size %d in "
@@ -1135,6 +1190,9 @@ class LRCNEngine:
             for l in range(cfg.lstm_layers):
                 if self.bi:
                     self.blstm.append(blstm_buffers(buf, N, H, training))
+                    continue
+                if self.is_gru:
+                    self.gru.append(gru_buffers(buf, N, H, training))
                     continue
                 S = dict(gx=buf(N, 4 * H), act=buf(N, 4 * H), cseq=buf(N, H), hseq=buf(N, H), hprev=buf(N, H))
                 if training:
@@ -1718,7 +1776,7 @@ class LRCNEngine:
         packed-operand kernel too (bf16 path): the same arithmetic as the split-product GEMM in mode 1 -- operands rounded to bf16, fp32
         accumulation -- without its operand images.  They reuse fc6's operand buffers (the launches are serial on one stream)."""
         D, H4 = self.cfg.encode_dim(), 4 * self.cfg.lstm_hidden
-        if getattr(self, "bi", False):                       # a bidirectional layer's dense products run on ops.gemm
+        if getattr(self, "bi", False) or getattr(self, "is_gru", False):   # a bidirectional or GRU layer's dense products run on ops.gemm
             return False
         return (l == 0 and self._fc6_kc8(n) and os.environ.get("VLTF_LSTM_KC8", "1") != "0" and D % 8 == 0 and H4 % 8 == 0
                 and D * H4 <= self.k_w.numel() and n * max(D, H4) <= self.k_act.numel() and (not self.training or n * H4 <= self.k_d6.numel()))
@@ -1794,6 +1852,17 @@ class LRCNEngine:
                 ops.lstm_seq_bi_fwd(S["gx"], (Kf[d:], Kb[d:]), S["act"], S["cseq"], S["hhalf"], S["hprev"], b, T, H, FORGET_BIAS,
                                     ws=self.lstm_ws_graph if st else self.lstm_ws, hseq_ld=HO, **st)
                 xin, d = S["hseq"], HO
+            for l, S in enumerate(self.gru):
+                # the input projection of all rows (z | r | n), then the recurrence with its own recurrent_kernel / recurrent_bias
+                K, U, bk, rb = (P[k] for k in gru_names(l))
+                ops.gemm(xin, K, S["gx"], n, 3 * H, d, bias=bk, ws=self.ws)
+                st = {}
+                if self._tag_off is not None:                         # captured: replay-safe tags on the graph workspace
+                    st = dict(state=self.state, tag_offset=self._tag_off)
+                    self._tag_off += ops.gru_seq_tag_span(b, T, H)
+                ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb,
+                                ws=self.lstm_ws_graph if st else self.lstm_ws, **st)
+                xin, d = S["hseq"], H
             for l, S in enumerate(self.lstm):
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 K = P[pre + "kernel"]
@@ -1923,7 +1992,7 @@ class LRCNEngine:
             if self._dropout:
                 ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], cfg.dropout_keep_prob)
                 d = self.dfused
-            top = (self.blstm or self.lstm)[-1]
+            top = (self.blstm or self.gru or self.lstm)[-1]
             if self.per_step:
                 top["dout"][:r].copy_(d[:r])
             elif self.bi and self.lstm_fusion == "last":
@@ -1962,6 +2031,33 @@ class LRCNEngine:
                 ops.eltwise2(target, self.dx_bw, target, "add", n * din)
                 if l == 0 and self.f8 is None:
                     self._relu_grad(self.dfeat, self.feat, n * D)
+            for l in reversed(range(len(self.gru))):
+                S = self.gru[l]
+                names = gru_names(l)
+                K, U = P[names[0]], P[names[1]]
+                din = D if l == 0 else H
+                xin = self.feat if l == 0 else self.gru[l - 1]["hseq"]
+                st = {}
+                if self._tag_off is not None:
+                    st = dict(state=self.state, tag_offset=self._tag_off)
+                    self._tag_off += ops.gru_seq_tag_span(b, T, H)
+                ops.gru_seq_bwd(S["dout"], U, S["act"], S["hcand"], S["hprev"], S["dgx"], S["dgh"], b, T, H,
+                                ws=self.lstm_ws_graph if st else self.lstm_ws, **st)
+
+                def gru_grads(ws, sws, S=S, names=names, din=din, xin=xin):
+                    ops.gemm(xin, S["dgx"], G[names[0]], din, 3 * H, n, transa=True, ws=ws)
+                    ops.gemm(S["hprev"], S["dgh"], G[names[1]], H, 3 * H, n, transa=True, ws=ws)
+                    ops.colsum(S["dgx"], G[names[2]], sws, n, 3 * H)
+                    ops.colsum(S["dgh"], G[names[3]], sws, n, 3 * H)
+                param_grads(gru_grads)
+                if l == 0 and not self.dcnn_trains:
+                    pass                                                              # frozen tower: nobody reads dfeat
+                elif l == 0:
+                    relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
+                    ops.gemm(S["dgx"], K, self.dfeat, n, D, 3 * H, transb=True, ldb=3 * H, relu_mask=self._fused_mask(relu_mask), ws=self.ws)
+                    self._relu_grad_behind(self.dfeat, relu_mask, n * D)
+                else:
+                    ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], n, H, 3 * H, transb=True, ldb=3 * H, ws=self.ws)
             for l in reversed(range(len(self.lstm))):
                 S = self.lstm[l]
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l

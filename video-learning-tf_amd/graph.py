@@ -41,6 +41,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs,
                      check_label_smoothing,
                      check_cutmix, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -57,6 +58,7 @@ class PipelineSpec:
     classifier: Optional[str] = None                # None | fc | lstm
     lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state)
     lstm_bidirectional: bool = False                # classifier lstm: a forward and a backward cell per layer, outputs concatenated (2H wide)
+    rnn_cell: str = "lstm"                          # classifier lstm: its cell, lstm | gru (engine.gru_names; no state input, H <= 512)
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
     train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
@@ -110,6 +112,8 @@ class PipeNode:
             raise VltfError("Specified late fusion with no classifier selected")          # model.py:36-37
         if s.classifier not in (None, "fc", "lstm"):
             raise VltfError("Undefined classifier [%s]" % s.classifier)
+        self.is_gru = check_rnn_cell(s.rnn_cell, s.classifier, s.lstm_params[0] if (s.classifier == "lstm" and s.lstm_params) else 1, s.lstm_bidirectional,
+                                     what="pipeline [%s]: rnn_cell" % s.name) == "gru"
         if s.representation not in ("dcnn", "nop", "fc"):
             raise VltfError("Undefined representation [%s]" % s.representation)
         if s.input_fusion not in (None, "avg", "maximum", "concat", "ibias"):
@@ -175,6 +179,7 @@ class PipeNode:
             if len(srcs) != 2:
                 raise VltfError("pipeline [%s]: an LSTM takes one state input (tf_util.py:184: too many values to unpack)" % s.name)
             self.state_src = srcs[1]
+            check_rnn_cell(s.rnn_cell, state_input=True, what="pipeline [%s]: rnn_cell" % s.name)
             if self.state_src.kind == "video":
                 raise VltfError("pipeline [%s]: the LSTM's state input must be vectors or a pipeline output, [%s] holds frames" %
                                 (s.name, self.state_src.ref))
@@ -258,6 +263,9 @@ class PipeNode:
                 if self.bi:
                     specs += [(n, (dims[l] + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l, sc)]
                     continue
+                if self.is_gru:
+                    specs += gru_specs(l, dims[l], H, sc)
+                    continue
                 pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 specs += [(pre + "kernel", (dims[l] + H, 4 * H)), (pre + "bias", (4 * H,))]
             if self.state_src is not None and self.state_src.dim != H:
@@ -322,13 +330,16 @@ class PipeNode:
         elif self.cls == "lstm":
             H, T, HO = self.H, self.fpc, self.HO
             B = R0 // T
-            self.lstm, self.blstm = [], []                              # per-layer buffers: unidirectional layers, or bidirectional ones
+            self.lstm, self.blstm, self.gru = [], [], []                # per-layer buffers: unidirectional, bidirectional or GRU layers
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:
                 raise VltfError("pipeline [%s]: lstm_bidirectional: this device has too few compute units to hold both directions of "
                                 "hidden size %d in one launch" % (self.spec.name, H))
             for l in range(self.L):
                 if self.bi:
                     self.blstm.append(blstm_buffers(buf, R0, H, tr))
+                    continue
+                if self.is_gru:
+                    self.gru.append(gru_buffers(buf, R0, H, tr))
                     continue
                 S = dict(gx=buf(R0, 4 * H), act=buf(R0, 4 * H), cseq=buf(R0, H), hseq=buf(R0, H), hprev=buf(R0, H))
                 if tr:
@@ -570,6 +581,11 @@ class PipeNode:
             ops.lstm_seq_bi_fwd(S["gx"], (Kf[d:], Kb[d:]), S["act"], S["cseq"], S["hhalf"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws,
                                 hseq_ld=HO, **lk)
             xin, d = S["hseq"], HO
+        for l, S in enumerate(self.gru):
+            K, U, bk, rb = (P[k] for k in gru_names(l, sc))
+            ops.gemm(xin, K, S["gx"], rows, 3 * H, d, bias=bk, ws=g.ws)
+            ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb, ws=self.lstm_ws, **lk)
+            xin, d = S["hseq"], H
         for l, S in enumerate(self.lstm):
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]
@@ -657,7 +673,7 @@ class PipeNode:
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
             d = self.dfused
-        top = (self.blstm or self.lstm)[-1]
+        top = (self.blstm or self.gru or self.lstm)[-1]
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
         elif self.bi and last == "last":
@@ -688,6 +704,21 @@ class PipeNode:
                 ops.gemm(S["dz"][0], Kf, target, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
                 ops.gemm(S["dz"][1], Kb, self.dx_bw, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
                 ops.eltwise2(target, self.dx_bw, target, "add", rows * din)
+        for l in reversed(range(len(self.gru))):
+            S = self.gru[l]
+            names = gru_names(l, sc)
+            K, U = P[names[0]], P[names[1]]
+            din = self.feat_dim if l == 0 else H
+            xin = self._xcls if l == 0 else self.gru[l - 1]["hseq"]
+            ops.gru_seq_bwd(S["dout"], U, S["act"], S["hcand"], S["hprev"], S["dgx"], S["dgh"], b, T, H, ws=self.lstm_ws, **self._len_kw())
+            ops.gemm(xin, S["dgx"], G[names[0]], din, 3 * H, rows, transa=True, ws=g.ws)
+            ops.gemm(S["hprev"], S["dgh"], G[names[1]], H, 3 * H, rows, transa=True, ws=g.ws)
+            ops.colsum(S["dgx"], G[names[2]], sw, rows, 3 * H)
+            ops.colsum(S["dgh"], G[names[3]], sw, rows, 3 * H)
+            if l > 0:
+                ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
+            elif self.wants_feat:
+                ops.gemm(S["dgx"], K, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
         for l in reversed(range(len(self.lstm))):
             S = self.lstm[l]
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l

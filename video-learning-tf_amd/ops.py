@@ -641,6 +641,51 @@ def lstm_seq_bi_tag_span(batch, T, H):
     return int(_ffi.lib().vl_lstm_seq_bi_tag_span(int(batch), int(T), int(H)))
 
 
+GRU_MAX_HIDDEN = 512        # the GRU recurrence exists in the cluster form only (vltf.h: vl_gru_seq_fwd)
+
+
+def gru_seq_fwd(gx, rk, act, hcand, hseq, hprev, batch, T, H, ws=None, rb=None, h0=None, seq_len=None, state=None, tag_offset=0):
+    """The reset-after GRU recurrence, all T steps in one launch (vl_gru_seq_fwd).  gx [batch T, 3H]: input projections (z | r | n);
+    rk = recurrent_kernel [H, 3H]; rb = recurrent_bias [3H] (None = zeros); h0 [batch, H] (None = zeros).  Writes act (activated z, r,
+    n), hcand (the candidate's recurrent term), hseq, hprev.  ws: a workspace from lstm_seq_ws().  seq_len: int32 device tensor [batch]
+    (dead steps carry h and write zeros).  state: a step state -> the replay-safe form (vl_gru_seq_fwd_st: no lengths), tags from
+    tag_offset."""
+    _f32(gx, rk, act, hcand, hseq, hprev, rb, h0, ws)
+    _dense(gx, rk, act, hcand, hseq, hprev, rb, h0)
+    if ws is None:
+        raise _ffi.VltfError("gru_seq_fwd: a workspace from lstm_seq_ws() is required")
+    ptrs = [_p(t) for t in (gx, rk, rb, h0, act, hcand, hseq, hprev)]
+    if state is not None:
+        if seq_len is not None:
+            raise _ffi.VltfError("gru_seq_fwd: the replay-safe form takes no lengths")
+        _ffi.call("vl_gru_seq_fwd_st", *ptrs, batch, T, H, _p(ws), ws.numel() * 4, _state(state), int(tag_offset), stream())
+        return
+    _ffi.call("vl_gru_seq_fwd", *ptrs, batch, T, H, _p(None if seq_len is None else _seq_len(seq_len, batch, "gru_seq_fwd")), _p(ws),
+              ws.numel() * 4, stream())
+
+
+def gru_seq_bwd(dout, rk, act, hcand, hprev, dgx, dgh, batch, T, H, ws=None, dh0=None, seq_len=None, state=None, tag_offset=0):
+    """BPTT of gru_seq_fwd in one launch (vl_gru_seq_bwd): reads dout (None = zeros) and the forward's act, hcand, hprev; writes dgx and dgh
+    [batch T, 3H] (the gradients of the two pre-activation terms) and, when given, dh0 [batch, H].  seq_len / state as in gru_seq_fwd."""
+    _f32(dout, rk, act, hcand, hprev, dgx, dgh, dh0, ws)
+    _dense(dout, rk, act, hcand, hprev, dgx, dgh, dh0)
+    if ws is None:
+        raise _ffi.VltfError("gru_seq_bwd: a workspace from lstm_seq_ws() is required")
+    ptrs = [_p(t) for t in (dout, rk, act, hcand, hprev, dgx, dgh, dh0)]
+    if state is not None:
+        if seq_len is not None:
+            raise _ffi.VltfError("gru_seq_bwd: the replay-safe form takes no lengths")
+        _ffi.call("vl_gru_seq_bwd_st", *ptrs, batch, T, H, _p(ws), ws.numel() * 4, _state(state), int(tag_offset), stream())
+        return
+    _ffi.call("vl_gru_seq_bwd", *ptrs, batch, T, H, _p(None if seq_len is None else _seq_len(seq_len, batch, "gru_seq_bwd")), _p(ws),
+              ws.numel() * 4, stream())
+
+
+def gru_seq_tag_span(batch, T, H):
+    """Exchange tags one replay-safe gru_seq_fwd / gru_seq_bwd call uses above its tag offset (0: H is refused)."""
+    return int(_ffi.lib().vl_gru_seq_tag_span(int(batch), int(T), int(H)))
+
+
 def lstm_seq_ws_clear(ws):
     """Zeroes the exchange words of a workspace (not its time-out word), on the stream: its owner restarts its tags."""
     _f32(ws)

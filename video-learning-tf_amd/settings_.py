@@ -175,6 +175,7 @@ class Settings:
             params = parse_seq(self.read_field(content, "lstm_params", required=True))
             network.lstm_params = [int(params[0]), int(params[1]), defs.check(params[2], defs.fusion_method)]
         network.lstm_bidirectional = self.read_lstm_bidirectional(content, network)
+        network.rnn_cell = self.read_rnn_cell(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         network.input_shape = self.read_field(content, "input_shape", listify=True)
@@ -202,6 +203,22 @@ class Settings:
         except VltfError as ex:
             error(str(ex))
         return True
+
+    def read_rnn_cell(self, content, network):
+        """`rnn_cell: gru` beside lstm_params (this project's extension of the pipeline schema): the layers of classifier lstm are
+        reset-after GRU cells (engine.gru_names) of lstm_params' hidden size.  Absent / None / lstm = BasicLSTMCell.  Refused without the
+        LSTM classifier, with lstm_bidirectional, with a second (state) input, above the hidden size the recurrence takes, and for any
+        other value (engine.check_rnn_cell)."""
+        v = self.read_field(content, "rnn_cell")
+        if v in (None, "None"):
+            return "lstm"
+        from .engine import VltfError, check_rnn_cell
+        lstm = network.classifier == defs.classifier.lstm
+        state_input = lstm and len(network.input) > 1 and self.read_field(content, "input_fusion") in (None, "None")
+        try:
+            return check_rnn_cell(v, network.classifier, network.lstm_params[0] if lstm else 1, network.lstm_bidirectional, state_input)
+        except VltfError as ex:
+            error(str(ex))
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
