@@ -194,7 +194,8 @@ int vl_bias_grad_c8(const void* dyb, float* db, float* ws, int n, int c, int h, 
 /* Dense products on the same pipeline (fc6 of the bf16 path): c[m][n] = sum_k a[k][m] b[k][n] (+ bias[n]) (ReLU) with both operands
  * reduction-major in 8-channel blocks, "kc8" = [ceil(channels / 8)][k][8] bf16 -- what the wgrad kernel consumes.
  *   vl_pack_kc8   dst = src[position * pos_stride + channel * ch_stride] (fp32, any strides: a matrix or its transpose) in kc8
- *   vl_gemm_kc8   the product (fp32 out, row-major; m, n multiples of 8); ws: vl_gemm_kc8_ws_bytes (split-k slabs, fixed order) */
+ *   vl_gemm_kc8   the product (fp32 out, row-major; m, n multiples of 8); ws: vl_gemm_kc8_ws_bytes (split-k slabs, fixed order)
+ * A kc8 address (dst, a_kc8, b_kc8) is a multiple of 16 -- 16-byte stores and fetches -- or the call is refused. */
 int vl_pack_kc8(const float* src, void* dst, int64_t positions, int channels, int64_t pos_stride, int64_t ch_stride, vl_stream_t stream);
 size_t vl_gemm_kc8_ws_bytes(int m, int n, int k);
 int vl_gemm_kc8(const void* a_kc8, const void* b_kc8, float* c, int m, int n, int k, const float* bias, int relu, void* ws,

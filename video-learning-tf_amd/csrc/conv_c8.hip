@@ -1485,6 +1485,7 @@ __global__ void pack_kc8_kernel(const float* __restrict__ src, uint4* __restrict
 /* dst (kc8: [ceil(channels / 8)][positions][8] bf16) = src[position * pos_stride + channel * ch_stride] rounded to bf16. */
 extern "C" int vl_pack_kc8(const float* src, void* dst, int64_t positions, int channels, int64_t pos_stride, int64_t ch_stride, vl_stream_t stream) {
     VL_CHECK(src && dst && positions > 0 && channels > 0, "vl_pack_kc8: bad argument");
+    VL_CHECK((uintptr_t)dst % 16 == 0, "vl_pack_kc8: dst must be 16-byte aligned (16-byte stores)");
     const int CB = (channels + 7) / 8;
     const int64_t total = ch_stride == 1 ? ((positions + 3) / 4) * CB : positions * CB;
     hipLaunchKernelGGL(pack_kc8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, (uint4*)dst, positions, channels,
@@ -1529,6 +1530,7 @@ extern "C" int vl_gemm_kc8(const void* a_kc8, const void* b_kc8, float* c, int m
                            size_t ws_bytes, vl_stream_t stream) {
     VL_CHECK(a_kc8 && b_kc8 && c && m > 0 && n > 0 && k > 0 && m % 8 == 0 && n % 8 == 0, "vl_gemm_kc8: bad argument (m, n multiples of 8)");
     VL_CHECK((int64_t)k * 16 * ((m > n ? m : n) / 8) < MAX_BUF_BYTES, "vl_gemm_kc8: operand too large for 32-bit offsets");
+    VL_CHECK((uintptr_t)a_kc8 % 16 == 0 && (uintptr_t)b_kc8 % 16 == 0, "vl_gemm_kc8: a and b must be 16-byte aligned (16-byte fetches)");
     C8WgPlan p;
     memset(&p, 0, sizeof(p));
     p.wa = 4; p.wb = 2; p.tb = 2;
