@@ -559,6 +559,32 @@ int vl_cutmix_pairs(float* x0, int clips, int fpc, int out_h, int out_w, int hal
 int vl_cutmix_pairs_s2d(const vl_conv_desc* d, void* xb, int clips, int fpc, const int32_t* box_host, const int32_t* box_dev,
                         vl_stream_t stream);
 
+/* ---- random erasing (Zhong et al. 2017): every clip's own box overwritten in place, write-only ----------------------
+ * table_dev: DEVICE int32 [clips][8] = {t0, t1, y0, y1, x0, x1, key_lo, key_hi} per clip, read when the kernel runs (capturable; the
+ * grid depends on clips, fpc and the frame height only).  The box is half-open, in frames of the clip and pixels of the frame conv1
+ * sees; every bound is clamped to its axis as a CutMix device box is, and a reversed or empty range writes nothing for that clip.
+ * All channels of the box are overwritten; no byte outside it changes (halo, phase padding, unused channel slots, other clips).
+ * mode 0 (zero): +0.0f, the mean colour of a mean-subtracted input (0x0000 packed).
+ * mode 1 (clip): one value per (clip, channel c), noise(key, 2^40 + c).
+ * mode 2 (pixel): noise(key, ((t C + c) H + y) W + x) with t the frame within the clip, c the stored channel, (y, x) the logical pixel
+ *   and C, H, W the channel count and frame size (3, out_h, out_w for x0; d's cin, h, w for the packed form) -- a function of the
+ *   logical coordinates, never of an address.
+ * noise(key, e): key = key_hi << 32 | key_lo (both as unsigned words); h = splitmix64(key ^ splitmix64(e)) with the splitmix64 of
+ *   vl_dropout_fwd; s = the sum of the four 16-bit fields of h; noise = (float)(s - 131070) * scale: an integer and ONE fp32 multiply.
+ *   s has mean 131070 and standard deviation sqrt(4 (65536^2 - 1) / 12) = 37837.22723720648, so scale = std / 37837.22723720648.
+ * The packed form rounds each value to bf16 to nearest even; a 16-byte chunk wholly inside the box is stored without being read, a
+ * chunk cut by a box edge is read, selected per element and written back.
+ * Contract: vl_erase_boxes followed by vl_s2d_c8_from_x0 equals vl_input_prep_u8_s2d followed by vl_erase_boxes_s2d bit for bit.
+ * Refused without a launch: null pointers, clips < 0, fpc outside [1, 65535], a bad size, mode outside 0..2, a non-finite scale.
+ * clips == 0 launches nothing.
+ * vl_erase_boxes: x0 is vl_input_prep_u8's destination for clips * fpc frames (dst_halo = halo, dst_phase = phase; the layout is
+ * stated at vl_cutmix_pairs). */
+int vl_erase_boxes(float* x0, int clips, int fpc, int out_h, int out_w, int halo, int phase, const int32_t* table_dev, int mode,
+                   float scale, vl_stream_t stream);
+/* The same on vl_input_prep_u8_s2d's destination for the descriptor d (the element map is stated at vl_cutmix_pairs_s2d). */
+int vl_erase_boxes_s2d(const vl_conv_desc* d, void* xb, int clips, int fpc, const int32_t* table_dev, int mode, float scale,
+                       vl_stream_t stream);
+
 /* ---- optimizer: clip_by_global_norm + GradientDescentOptimizer (train.py:199-222) ---------------
  * vl_sumsq: out[0] (+)= sum g^2 over count elements (ws: float[1024]); accumulate != 0 adds to out. */
 int vl_sumsq(const float* g, int64_t count, float* out, float* ws, int accumulate, vl_stream_t stream);

@@ -106,6 +106,8 @@ SIGNATURES = {
     "vl_softmax_xent_wf": (i32, [p, p, p, p, p, i32, i32, f32, p, i32, i32, f32, i32, f32, p, p, f32, p]),
     "vl_cutmix_pairs": (i32, [p, i32, i32, i32, i32, i32, i32, p, p, p]),
     "vl_cutmix_pairs_s2d": (i32, [p, p, i32, i32, p, p, p]),
+    "vl_erase_boxes": (i32, [p, i32, i32, i32, i32, i32, i32, p, i32, f32, p]),
+    "vl_erase_boxes_s2d": (i32, [p, p, i32, i32, p, i32, f32, p]),
     "vl_sumsq": (i32, [p, i64, p, p, i32, p]),
     "vl_sgd_apply": (i32, [p, p, i64, f32, f32, p, f32, p, p]),
     "vl_adam_apply": (i32, [p, p, p, p, i64, f32, f32, p, f32, i32, p, p]),

@@ -88,7 +88,8 @@ class ComposedEngine(GraphEngine):
                          dropout_keep_prob=head.dropout_keep_prob or enc_cfg.dropout_keep_prob, conv_math=enc_cfg.conv_math,
                          momentum=enc_cfg.momentum, nesterov=enc_cfg.nesterov, weight_decay=enc_cfg.weight_decay,
                          accumulate=enc_cfg.accumulate, ema_decay=enc_cfg.ema_decay, ema_warmup=enc_cfg.ema_warmup,
-                         class_weights=enc_cfg.class_weights, focal_gamma=enc_cfg.focal_gamma)      # (of the head's classes)
+                         class_weights=enc_cfg.class_weights, focal_gamma=enc_cfg.focal_gamma,      # (of the head's classes)
+                         erase_prob=enc_cfg.erase_prob)                    # (refused when > 0: GraphEngine)
         self.enc_cfg = enc_cfg
         self.Ts = self.last.fpc                  # steps the second LSTM runs (one more under ibias)
 

@@ -118,6 +118,36 @@ static inline int cut_box_host_check(const int32_t* box, int fpc, int H, int W, 
     return 0;
 }
 
+// ---- counter-based draws (dropout in pointwise.hip, random erasing below) -----------------------------------------------------------
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// ---- random erasing (vl_erase_boxes in pointwise.hip, vl_erase_boxes_s2d in conv_c8.hip) -------------------------------
+// A clip's row of the device table: {t0, t1, y0, y1, x0, x1, key_lo, key_hi}.  The box is clamped as a CutMix box is (cut_box_get), so
+// no content of the words reaches an address; false when an axis is then empty.  Wave-uniform.
+#define ERASE_ROW_WORDS 8
+#define ERASE_CLIP_ELEMENT (1ull << 40)          // mode 1: the element of channel c is 2^40 + c, above every pixel index of mode 2
+__device__ __forceinline__ bool erase_row_get(const int32_t* __restrict__ row, int fpc, int H, int W, int (&b)[6], uint64_t& key) {
+    const vl_cut_box none = {{0, 0, 0, 0, 0, 0}};
+    key = ((uint64_t)(uint32_t)row[7] << 32) | (uint64_t)(uint32_t)row[6];
+    return cut_box_get(none, row, fpc, H, W, b);
+}
+
+// host side of both launches: neither NaN nor an infinity (v - v is 0 for every finite v and NaN otherwise)
+static inline bool erase_scale_ok(float v) { return v - v == 0.f; }
+
+// noise(key, e): the four 16-bit fields of one hash summed (an Irwin-Hall sum: mean 131070, standard deviation 37837.227...), centred
+// as an integer, then ONE fp32 multiply -- a host restatement in integers and one fp32 product gives the same bits.
+__device__ __forceinline__ float erase_noise(uint64_t key, uint64_t e, float scale) {
+    const uint64_t h = splitmix64(key ^ splitmix64(e));
+    const int s = (int)(h & 0xffffu) + (int)((h >> 16) & 0xffffu) + (int)((h >> 32) & 0xffffu) + (int)(h >> 48);
+    return (float)(s - 131070) * scale;
+}
+
 // ---- random resized crop (vl_input_prep_u8_box in pointwise.hip, vl_input_prep_u8_box_s2d in conv_c8.hip) --------------
 // A frame's box {y0, x0, bh, bw} as a kernel uses it: sizes clamped into [1, raw] first, then the corner into [0, raw - size], so
 // that no content of the device words reaches an address outside the frame.

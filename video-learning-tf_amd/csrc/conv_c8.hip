@@ -1450,6 +1450,118 @@ extern "C" int vl_cutmix_pairs_s2d(const vl_conv_desc* d, void* xb, int clips, i
     return 0;
 }
 
+// Random erasing in that packed input (vl_erase_boxes in pointwise.hip is the fp32 form): every clip's own box, from its
+// row of the device table, is overwritten.  The element map, the grid and the masks are those of the CutMix kernel above, with z over
+// clips.  The fill is computed in fp32 exactly as the fp32 form computes it -- from the element's (t, c, y, x), never its address --
+// and rounded to nearest even, so erasing x0 and packing it gives these bits.  A chunk whose eight elements all lie in the box is one
+// 16-byte store with no load; a chunk cut by a box edge (on either axis: for s = 4 a chunk is 2 rows x 4 columns of one channel), or
+// with unused channel slots, is loaded, selected per element and stored whole.  In modes 0 and 1 the eight packed values of a chunk
+// are the same along a chunk row and are formed once per piece.
+__global__ __launch_bounds__(256) void erase_boxes_s2d_kernel(uint4* __restrict__ xb, int clips, int fpc, int C, int s, int H, int W, int pt,
+                                                              int pl, int OHp, int OWp, int CB, const int32_t* __restrict__ table, int mode,
+                                                              float scale) {
+    const int t = blockIdx.y;
+    const int64_t plane = (int64_t)OHp * OWp, frame = CB * plane;
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    for (int cj = blockIdx.z; cj < clips; cj += gridDim.z) {
+        int b[6];
+        uint64_t key;
+        if (!erase_row_get(table + (int64_t)cj * ERASE_ROW_WORDS, fpc, H, W, b, key)) continue;
+        if (t < b[0] || t >= b[1]) continue;
+        const int Rlo = max((b[2] + pt) / s, (int)blockIdx.x * CUT_S2D_ROWS);
+        const int Rhi = min(min((b[3] - 1 + pt) / s + 1, OHp), ((int)blockIdx.x + 1) * CUT_S2D_ROWS);
+        if (Rlo >= Rhi) continue;
+        const int Slo = (b[4] + pl) / s, Shi = min((b[5] - 1 + pl) / s + 1, OWp);
+        uint4* __restrict__ p = xb + ((int64_t)cj * fpc + t) * frame;
+        // blockDim.y == CUT_S2D_ROWS: a wave keeps its chunk row and walks the chunk planes, so the (c, py, px) of a chunk's elements are
+        // counted on from the previous chunk's -- no division per piece
+        const int R = Rlo + wv;
+        if (R >= Rhi) continue;
+        int px = 0, py = 0, c = 0;
+        float cur = mode == 1 ? erase_noise(key, ERASE_CLIP_ELEMENT, scale) : 0.f;
+        for (int cb = 0; cb < CB; ++cb) {
+            // per element of the chunk: its px, its fill of modes 0 / 1 and its row's index of mode 2; rows: those whose pixel row is in the box
+            int pxs[8];
+            float fill[8];
+            int64_t erow[8];
+            uint32_t rows = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int y = s * R + py - pt;
+                if (c < C && y >= b[2] && y < b[3]) rows |= 1u << j;
+                pxs[j] = px;
+                fill[j] = cur;
+                erow[j] = mode == 2 ? ((int64_t)(t * C + c) * H + y) * W : 0;
+                if (++px == s) {
+                    px = 0;
+                    if (++py == s) {
+                        py = 0;
+                        ++c;
+                        if (mode == 1) cur = erase_noise(key, ERASE_CLIP_ELEMENT + c, scale);
+                    }
+                }
+            }
+            if (!rows) continue;                                      // (uniform over the wave)
+            const uint32_t pw[4] = {pack_bf16(fill[0], fill[1]), pack_bf16(fill[2], fill[3]), pack_bf16(fill[4], fill[5]), pack_bf16(fill[6], fill[7])};
+            const int64_t row = cb * plane + (int64_t)R * OWp;
+            for (int S = Slo + lane; S < Shi; S += 64) {
+                const int xl = s * S - pl;                            // the chunk's columns are xl .. xl + s - 1
+                uint32_t m = rows;
+                if (xl < b[4] || xl + s > b[5]) {                     // a chunk on a vertical edge of the box: per element
+                    m = 0;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int x = xl + pxs[j];
+                        if (x >= b[4] && x < b[5]) m |= 1u << j;
+                    }
+                    m &= rows;
+                    if (!m) continue;
+                }
+                uint32_t nw[4] = {pw[0], pw[1], pw[2], pw[3]};
+                if (mode == 2) {
+                    float v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = erase_noise(key, (uint64_t)(erow[j] + xl + pxs[j]), scale);
+                    nw[0] = pack_bf16(v[0], v[1]);
+                    nw[1] = pack_bf16(v[2], v[3]);
+                    nw[2] = pack_bf16(v[4], v[5]);
+                    nw[3] = pack_bf16(v[6], v[7]);
+                }
+                if (m != 0xffu) {
+                    const uint4 ov = p[row + S];
+                    const uint32_t ow[4] = {ov.x, ov.y, ov.z, ov.w};
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const uint32_t sel = ((m >> (2 * w)) & 1u ? 0xffffu : 0u) | ((m >> (2 * w + 1)) & 1u ? 0xffff0000u : 0u);
+                        nw[w] = (ow[w] & ~sel) | (nw[w] & sel);
+                    }
+                }
+                p[row + S] = make_uint4(nw[0], nw[1], nw[2], nw[3]);
+            }
+        }
+    }
+}
+
+extern "C" int vl_erase_boxes_s2d(const vl_conv_desc* d, void* xb, int clips, int fpc, const int32_t* table_dev, int mode, float scale,
+                                  vl_stream_t stream) {
+    VL_CHECK(xb, "vl_erase_boxes_s2d: xb is null");
+    VL_CHECK(table_dev, "vl_erase_boxes_s2d: table_dev is null");
+    VL_CHECK(clips >= 0, "vl_erase_boxes_s2d: clips must be >= 0, got %d", clips);
+    VL_CHECK(fpc > 0 && fpc <= 65535, "vl_erase_boxes_s2d: fpc must lie in [1, 65535], got %d", fpc);
+    if (int rc = s2d_check(d, "vl_erase_boxes_s2d")) return rc;
+    VL_CHECK(mode >= 0 && mode <= 2, "vl_erase_boxes_s2d: mode must be 0 (zero), 1 (clip) or 2 (pixel), got %d", mode);
+    VL_CHECK(erase_scale_ok(scale), "vl_erase_boxes_s2d: scale must be finite");
+    VL_CHECK(((uintptr_t)xb & 15) == 0, "vl_erase_boxes_s2d: xb is not 16-byte aligned");
+    VL_CHECK(((uintptr_t)table_dev & 3) == 0, "vl_erase_boxes_s2d: table_dev is not 4-byte aligned");
+    if (clips == 0) return 0;
+    const int s = d->stride, ka = (d->kh - 1) / s + 1, OHp = d->oh + ka - 1, OWp = d->ow + ka - 1, CB = (d->cin * s * s + 7) / 8;
+    const dim3 grid((OHp + CUT_S2D_ROWS - 1) / CUT_S2D_ROWS, fpc, clips < 65535 ? clips : 65535);
+    hipLaunchKernelGGL(erase_boxes_s2d_kernel, grid, dim3(64, CUT_S2D_ROWS), 0, (hipStream_t)stream, (uint4*)xb, clips, fpc, d->cin, s, d->h, d->w, d->pt,
+                       d->pl, OHp, OWp, CB, table_dev, mode, scale);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- dense products on the wgrad kernel --------------------------------------------------------------------------------------------
 // C[m][n] = sum_k A[k][m] B[k][n] is what wgrad_c8_kernel computes when "positions" are k and both operands are stored position-major
 // in 8-channel blocks: "kc8" = [channel block][k][8] bf16 (one image, no halo, one tap per block of A).  fc6's three products are

@@ -1711,14 +1711,7 @@ extern "C" int vl_temporal_fusion_bwd_len(const float* dy, float* dx, int batch,
     return temporal_fusion_bwd(dy, dx, batch, T, H, method, seq_len, (hipStream_t)stream);
 }
 
-// ---- dropout (lstm.py:50-56) ------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// ---- dropout (lstm.py:50-56; splitmix64: common.h) ---------------------------------------------
 // one body for the eager kernel and the step-state one (vl_dropout_fwd_st): only where the seed comes from differs
 // (the grid-stride start and step come from the kernel: blockDim read there, where the compiler knows the work-group size is uniform)
 __device__ __forceinline__ void dropout_fwd_body(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ mask, int64_t count,
@@ -2284,6 +2277,72 @@ extern "C" int vl_cutmix_pairs(float* x0, int clips, int fpc, int out_h, int out
     const dim3 grid((out_h + CUT_ROWS - 1) / CUT_ROWS, fpc, pairs < 65535 ? pairs : 65535);
     hipLaunchKernelGGL(cutmix_pairs_f32_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, (uint32_t*)x0, clips, fpc, out_h, out_w, halo,
                        phase, wq, box, box_dev);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- random erasing (Zhong et al. 2017): every clip's own (t, y, x) box overwritten in place, in x0 ---------------------
+// The layout and the column runs are those of the CutMix kernel above; the launch is write-only and per clip.  A clip's box and key
+// come from its row of the device table (erase_row_get, common.h) when the kernel runs.  grid (x: tiles of CUT_ROWS rows, y: the
+// frame of the clip, z: clips), the same for every table; a workgroup whose frame or rows lie outside a clip's box goes on to its next
+// clip after a uniform branch.  mode 0 stores +0, mode 1 one value per (clip, channel), mode 2 a value per element from its LOGICAL
+// index ((t 3 + c) oh + y) ow + x, so that the packed form (vl_erase_boxes_s2d) draws the same value for the same pixel.
+__global__ __launch_bounds__(256) void erase_boxes_f32_kernel(float* __restrict__ x, int clips, int fpc, int oh, int ow, int halo, int phase,
+                                                              int wq, const int32_t* __restrict__ table, int mode, float scale) {
+    const int t = blockIdx.y;
+    const int64_t plane = (int64_t)(oh + 2 * halo) * wq, frame = 3 * phase * plane;
+    const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    for (int j = blockIdx.z; j < clips; j += gridDim.z) {
+        int b[6];
+        uint64_t key;
+        if (!erase_row_get(table + (int64_t)j * ERASE_ROW_WORDS, fpc, oh, ow, b, key)) continue;
+        if (t < b[0] || t >= b[1]) continue;
+        const int ylo = max(b[2], (int)blockIdx.x * CUT_ROWS), yhi = min(b[3], ((int)blockIdx.x + 1) * CUT_ROWS);
+        if (ylo >= yhi) continue;
+        float* __restrict__ p = x + ((int64_t)j * fpc + t) * frame;
+        float cv[3] = {0.f, 0.f, 0.f};               // mode 1: the clip's three channel values, once per workgroup
+        if (mode == 1) {                             // lanes 0 .. 2 hash one channel each, then every lane reads the three
+            const float mine = erase_noise(key, ERASE_CLIP_ELEMENT + (uint64_t)(lane < 3 ? lane : 0), scale);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cv[c] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine), c));
+        }
+        // the column run of a phase is formed once (two divisions); then a wave takes one (channel, row) piece of it at a time, with a
+        // few multiplies of index arithmetic per piece
+        for (int ph = 0; ph < phase; ++ph) {
+            const int qlo = (b[4] + halo - ph + phase - 1) / phase, qhi = (b[5] + halo - ph + phase - 1) / phase;
+            if (qlo >= qhi) continue;
+            for (int i = wv; i < 3 * CUT_ROWS; i += 4) {
+                const int c = i / CUT_ROWS, y = ylo + i % CUT_ROWS;
+                if (y >= yhi) continue;
+                const int64_t row = (int64_t)(c * phase + ph) * plane + (int64_t)(y + halo) * wq;
+                const uint64_t e0 = ((uint64_t)(t * 3 + c) * oh + y) * ow;
+                float v = c == 0 ? cv[0] : (c == 1 ? cv[1] : cv[2]);
+                for (int q = qlo + lane; q < qhi; q += 64) {
+                    if (mode == 2) v = erase_noise(key, e0 + (uint64_t)(q * phase + ph - halo), scale);
+                    p[row + q] = v;
+                }
+            }
+        }
+    }
+}
+
+extern "C" int vl_erase_boxes(float* x0, int clips, int fpc, int out_h, int out_w, int halo, int phase, const int32_t* table_dev, int mode,
+                              float scale, vl_stream_t stream) {
+    VL_CHECK(x0, "vl_erase_boxes: x0 is null");
+    VL_CHECK(table_dev, "vl_erase_boxes: table_dev is null");
+    VL_CHECK(clips >= 0, "vl_erase_boxes: clips must be >= 0, got %d", clips);
+    VL_CHECK(fpc > 0 && fpc <= 65535, "vl_erase_boxes: fpc must lie in [1, 65535], got %d", fpc);
+    VL_CHECK(out_h > 0 && out_w > 0, "vl_erase_boxes: bad frame size %d x %d", out_h, out_w);
+    VL_CHECK(halo >= 0, "vl_erase_boxes: halo must be >= 0, got %d", halo);
+    VL_CHECK(phase >= 1, "vl_erase_boxes: phase must be >= 1, got %d", phase);
+    VL_CHECK(mode >= 0 && mode <= 2, "vl_erase_boxes: mode must be 0 (zero), 1 (clip) or 2 (pixel), got %d", mode);
+    VL_CHECK(erase_scale_ok(scale), "vl_erase_boxes: scale must be finite");
+    VL_CHECK(((uintptr_t)x0 & 3) == 0 && ((uintptr_t)table_dev & 3) == 0, "vl_erase_boxes: x0 / table_dev is not 4-byte aligned");
+    if (clips == 0) return 0;
+    const int wq = (out_w + 2 * halo + phase - 1) / phase;
+    const dim3 grid((out_h + CUT_ROWS - 1) / CUT_ROWS, fpc, clips < 65535 ? clips : 65535);
+    hipLaunchKernelGGL(erase_boxes_f32_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, x0, clips, fpc, out_h, out_w, halo, phase, wq,
+                       table_dev, mode, scale);
     VL_LAUNCH_CHECK();
     return 0;
 }

@@ -84,6 +84,13 @@ class NetConfig:
     cutmix_prob: Optional[float] = None         # train.cutmix_prob: with mixup on too, the chance that a batch is cut; None = 0.5
     class_weights: Optional[Sequence[float]] = None   # train.class_weights: num_classes weights inside the loss's class sum; None = ones
     focal_gamma: float = 0.0                    # train.focal_gamma: the focal loss's focusing parameter (Lin et al. 2017), >= 0; 0 = off
+    erase_prob: float = 0.0                     # train.erase_prob: random erasing (Zhong et al. 2017), the chance that a clip gets a box; 0 = off
+    erase_scale: Optional[Sequence[float]] = None     # train.erase_scale: the box's share of the frame area (lo, hi); None = (0.02, 0.33)
+    erase_ratio: Optional[Sequence[float]] = None     # train.erase_ratio: its aspect ratio h / w, log-uniform in (lo, hi); None = (0.3, 3.3)
+    erase_frames: Optional[Sequence[float]] = None    # train.erase_frames: the share of the clip's frames it spans (lo, hi); None = (1, 1)
+    erase_mode: Optional[str] = None            # train.erase_mode: zero | clip | pixel, the fill; None = zero
+    erase_std: Optional[float] = None           # train.erase_std: the standard deviation of a noise fill; None = 57.63
+    erase_seed: int = 0                         # train.erase_seed: the key of the draws (erase_row)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -638,6 +645,146 @@ def cutmix_box(alpha, seed, mode, draw_index, fpc, h, w):
     return tuple(box), u
 
 
+ERASE_MODES = ops.ERASE_MODES                    # zero | clip | pixel: vl_erase_boxes' mode 0, 1, 2
+ERASE_DEFAULTS = dict(scale=(0.02, 0.33), ratio=(0.3, 3.3), frames=(1.0, 1.0), mode="zero", std=57.63, seed=0)
+ERASE_ATTEMPTS = 10                              # torchvision's RandomErasing.get_params tries as often
+EraseConfig = collections.namedtuple("EraseConfig", "prob scale ratio frames mode std seed")
+
+
+def check_erase(prob=None, scale=None, ratio=None, frames=None, mode=None, std=None, seed=None):
+    """The options of random erasing (Zhong et al. 2017; torchvision RandomErasing, timm reprob / remode) as an EraseConfig, None read
+    as off / the default.  prob: the chance in [0, 1] that a clip gets a box (0 = off).  scale: (lo, hi) of the box's share of the
+    frame's area, 0 < lo <= hi <= 1 (default (0.02, 0.33)).  ratio: (lo, hi) of its aspect ratio h / w, drawn log-uniformly,
+    0 < lo <= hi (default (0.3, 3.3)).  frames: (lo, hi) of the share of the clip's frames the box spans, 0 < lo <= hi <= 1 (default
+    (1, 1): every frame).  mode: the fill -- 'zero' (the mean colour of a mean-subtracted input; the default), 'clip' (one normal-like
+    value per clip and channel) or 'pixel' (one per element).  std: the standard deviation of a noise fill, finite and >= 0 (default
+    57.63: ImageNet's per-channel deviation on the 0..255 scale).  seed: a whole number in [0, 2^64), the key of the draws (erase_row).
+    Refused: bools and strings for a number, a prob outside [0, 1], a range that is not two numbers 0 < lo <= hi (<= 1 for scale and
+    frames), an unknown mode, a negative, NaN or infinite std, a seed that is not whole or outside [0, 2^64), and any other option
+    given while prob is 0 or absent."""
+    def number(v, name, what):
+        if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise VltfError("%s must be %s, got %r" % (name, what, v))
+        return v
+
+    def span(v, name, cap):
+        what = "two numbers 0 < lo <= hi%s" % (" <= 1" if cap else "")
+        if isinstance(v, (str, bytes)) or not isinstance(v, (list, tuple, np.ndarray)) or len(v) != 2:
+            raise VltfError("%s must be %s, got %r" % (name, what, v))
+        lo, hi = (float(number(x, name, what)) for x in v)
+        if not (0.0 < lo <= hi and math.isfinite(hi) and (not cap or hi <= 1.0)):
+            raise VltfError("%s must be %s, got %r" % (name, what, v))
+        return lo, hi
+
+    pr = 0.0
+    if prob is not None:
+        pr = float(number(prob, "erase_prob", "a number in [0, 1] (0 / None = off)"))
+        if not (0.0 <= pr <= 1.0):                # (NaN fails both)
+            raise VltfError("erase_prob must be a number in [0, 1] (0 / None = off), got %r" % (prob,))
+    sd = 0
+    if seed is not None:
+        number(seed, "erase_seed", "a whole number >= 0")
+        if isinstance(seed, (float, np.floating)) and not (math.isfinite(seed) and float(seed) == int(seed)):
+            raise VltfError("erase_seed must be a whole number >= 0, got %r" % (seed,))
+        sd = int(seed)
+        if not (0 <= sd < 2 ** 64):
+            raise VltfError("erase_seed must be a whole number >= 0 (below 2^64), got %r" % (seed,))
+    sc = span(scale, "erase_scale", True) if scale is not None else ERASE_DEFAULTS["scale"]
+    ra = span(ratio, "erase_ratio", False) if ratio is not None else ERASE_DEFAULTS["ratio"]
+    fr = span(frames, "erase_frames", True) if frames is not None else ERASE_DEFAULTS["frames"]
+    if mode is not None and (not isinstance(mode, str) or mode not in ERASE_MODES):
+        raise VltfError("erase_mode must be one of %s, got %r" % (" | ".join(ERASE_MODES), mode))
+    st = ERASE_DEFAULTS["std"]
+    if std is not None:
+        st = float(number(std, "erase_std", "a finite number >= 0"))
+        if not (math.isfinite(st) and st >= 0.0):
+            raise VltfError("erase_std must be a finite number >= 0, got %r" % (std,))
+    if pr == 0.0:
+        for name, given in (("erase_scale", scale is not None), ("erase_ratio", ratio is not None), ("erase_frames", frames is not None),
+                            ("erase_mode", mode is not None), ("erase_std", std is not None), ("erase_seed", sd != 0)):
+            if given:
+                raise VltfError("%s is given without erase_prob: random erasing is off and nothing would be drawn" % name)
+    return EraseConfig(pr, sc, ra, fr, mode if mode is not None else ERASE_DEFAULTS["mode"], st, sd)
+
+
+def erase_config(cfg):
+    """An EraseConfig from one, or from anything with NetConfig's erase_* fields."""
+    if isinstance(cfg, EraseConfig):
+        return cfg
+    return check_erase(cfg.erase_prob, cfg.erase_scale, cfg.erase_ratio, cfg.erase_frames, cfg.erase_mode, cfg.erase_std, cfg.erase_seed)
+
+
+def check_erase_boxes(boxes, clips, fpc, h, w):
+    """A caller's boxes, one (t0, t1, y0, y1, x0, x1) per clip, as a list of six-int tuples.  Refused: anything but `clips` rows of six
+    whole numbers, a range that leaves [0, fpc] x [0, h] x [0, w] or is reversed.  (CutMix's half-volume rule has no place here: the
+    labels do not change.)"""
+    try:
+        rows = [tuple(box) for box in boxes]
+    except TypeError:
+        rows = None
+    if rows is None or len(rows) != clips:
+        raise VltfError("erase_boxes must be %d boxes (t0, t1, y0, y1, x0, x1), one per clip, got %r" % (clips, boxes))
+    out = []
+    for i, box in enumerate(rows):
+        try:
+            vals = tuple(int(v) for v in box)
+            ok = len(vals) == 6 and all(not isinstance(v, (bool, np.bool_, str, bytes)) and float(v) == int(v) for v in box)
+        except (TypeError, ValueError):
+            vals, ok = (), False
+        if not ok:
+            raise VltfError("erase_boxes: box %d must be six whole numbers (t0, t1, y0, y1, x0, x1), got %r" % (i, box))
+        for a, (name, n) in enumerate((("t", fpc), ("y", h), ("x", w))):
+            lo, hi = vals[2 * a], vals[2 * a + 1]
+            if lo < 0 or hi > n or lo > n or hi < 0:
+                raise VltfError("erase_boxes: box %d: the %s range [%d, %d) leaves the frame's [0, %d]" % (i, name, lo, hi, n))
+            if lo > hi:
+                raise VltfError("erase_boxes: box %d: the %s range [%d, %d) is reversed" % (i, name, lo, hi))
+        out.append(vals)
+    return out
+
+
+def erase_row(cfg, draw_index, global_clip, fpc, h, w):
+    """The eight ints (t0, t1, y0, y1, x0, x1, key_lo, key_hi) of one clip's row of the erase table (vl_erase_boxes) in the step with
+    this draw index (LRCNEngine._draw_index).  cfg: an EraseConfig (check_erase) or a NetConfig.  One Philox generator with the key
+    (seed, draw_index) and the counter (global_clip, 0, 0, 0), drawn from in a fixed order: the 64-bit noise key (always, so that an
+    override of the boxes keeps the keys); u, the clip is erased iff u < prob; then up to ten attempts of torchvision's get_params --
+    area = h w U(scale), r = exp(U(log ratio)), bh = int(round(sqrt(area r))), bw = int(round(sqrt(area / r))), accepted iff
+    0 < bh < h and 0 < bw < w, then y0 = integers(h - bh + 1), x0 = integers(w - bw + 1); last the frame run, L = max(1,
+    int(round(fpc U(frames)))) frames from t0 = integers(fpc - L + 1).  A clip that is not erased, or with no attempt accepted, has the
+    empty box (six zeros) and its key.  The key words are int32 (the low and the high half's bits).  A pure function of its arguments:
+    rank r of a data-parallel run passes global_clip = r B + i, every micro-step its own draw index, and a resumed run continues the
+    sequence."""
+    e = erase_config(cfg)
+    fpc, h, w = int(fpc), int(h), int(w)
+    rng = np.random.Generator(np.random.Philox(key=np.array([e.seed, int(draw_index)], np.uint64),
+                                               counter=np.array([int(global_clip), 0, 0, 0], np.uint64)))
+    key = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+    words = tuple(int(np.uint32(v).astype(np.int32)) for v in (key & 0xFFFFFFFF, key >> 32))
+    box = (0, 0, 0, 0, 0, 0)
+    if float(rng.random()) < e.prob:
+        for _ in range(ERASE_ATTEMPTS):
+            area = h * w * float(rng.uniform(e.scale[0], e.scale[1]))
+            r = math.exp(float(rng.uniform(math.log(e.ratio[0]), math.log(e.ratio[1]))))
+            bh, bw = int(round(math.sqrt(area * r))), int(round(math.sqrt(area / r)))
+            if 0 < bh < h and 0 < bw < w:
+                y0, x0 = int(rng.integers(h - bh + 1)), int(rng.integers(w - bw + 1))
+                n = max(1, int(round(fpc * float(rng.uniform(e.frames[0], e.frames[1])))))
+                t0 = int(rng.integers(fpc - n + 1))
+                box = (t0, t0 + n, y0, y0 + bh, x0, x0 + bw)
+                break
+    return box + words
+
+
+def erase_table(cfg, draw_index, rank, batch, fpc, h, w, boxes=None, clips=None):
+    """int32 [clips][8]: erase_row of the global clips rank * batch + i, i < clips (default: batch), of a rank whose batch holds up to
+    `batch` clips; boxes (check_erase_boxes) replace the drawn boxes and leave the keys."""
+    clips = int(batch) if clips is None else int(clips)
+    rows = [erase_row(cfg, draw_index, int(rank) * int(batch) + i, fpc, h, w) for i in range(clips)]
+    if boxes is not None:
+        rows = [tuple(box) + row[6:] for box, row in zip(boxes, rows)]
+    return np.array(rows, np.int32).reshape(clips, 8)
+
+
 def dropout_seed(draw_index):
     """The seed of every dropout launch of the step with this draw index (LRCNEngine._draw_index); the _st launches of a captured
     step form the same value on the device from the step state's count."""
@@ -977,7 +1124,9 @@ class LRCNEngine:
     ops.step_state_set_ema writes it (engine.ema_rate of the host's step_count) before every replay that applies an update.
     With NetConfig.mixup_alpha > 0 the captured step holds the blend and the mixed-label loss launch; both read the blend weight from
     a one-float device word (mix_lam) the host fills before every step, eager or replayed (_mix_write): the block stays as it is.
-    With NetConfig.cutmix_alpha > 0 the captured step holds the box swap too, which reads its six-int32 box (cut_box) the same way."""
+    With NetConfig.cutmix_alpha > 0 the captured step holds the box swap too, which reads its six-int32 box (cut_box) the same way.
+    With NetConfig.erase_prob > 0 it holds the erase launch ahead of both, which reads its int32 [max_clips][8] table (erase_table,
+    _erase_write) the same way."""
     FC6_CHUNKS = FC6_CHUNKS
     GRAPH_TAG_LIMIT = 0xFFF00000    # tags of lstm_ws_graph stay below this (the eager counter's limit, csrc/lstm_cluster.hip)
 
@@ -1234,6 +1383,7 @@ class LRCNEngine:
             self.dlogits = buf(*self.logits.shape)
         self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out, cfg.class_weights, cfg.focal_gamma)
         self._mix_setup(cfg.mixup_alpha, cfg.mixup_seed, self.rows_out)
+        self._erase_setup()
         self.ss = torch.zeros(1, device=dev)
         # L2 weight decay: ops.l2_regularize takes the norm's place in _finish_step and returns {sum g'^2, regulariser}; the update calls
         # and _fetch read the first word through self.ss.  Off: nothing is allocated, the norm calls are the ones of before.
@@ -1545,6 +1695,46 @@ class LRCNEngine:
                 self.layers[0]["conv"].cutmix_pairs_s2d(self.layers[0]["xb"][:n], b, self.T, self.cut_box)
             else:
                 ops.cutmix_pairs(self.x0[:n], b, self.T, self.cfg.image_shape[:2], self.x0_halo, self.x0_phase, self.cut_box)
+
+    # ---- random erasing (erase_*) ------------------------------------------------------------------------------------------
+    def _erase_setup(self):
+        """Off (erase_prob 0, or an engine that does not train): nothing is allocated and no launch is added.  On: the int32
+        [max_clips][8] table the launch reads (erase_row per clip; written before every step, outside any capture)."""
+        self.erase = erase_config(self.cfg)
+        self.erase_table = self.erase_table_last = None
+        if not self.training or self.erase.prob == 0.0:
+            self.erase = None
+            return
+        self.erase_table = torch.zeros((self.B, 8), dtype=torch.int32, device=self.dev)
+        self.erase_mode_id, self.erase_scale = ERASE_MODES.index(self.erase.mode), ops.erase_scale(self.erase.std)
+
+    def _erase_write(self, erase_boxes, mi, frames):
+        """Before a train step, eager or replayed: the table of the step's clips goes to the device on the stream -- erase_row of the
+        step's draw index for the clips rank * max_clips + i, the caller's erase_boxes in the place of the drawn boxes (the keys stay
+        the drawn ones) -- and is kept as self.erase_table_last."""
+        if self.erase is None:
+            if erase_boxes is not None:
+                raise VltfError("erase_boxes is given, but random erasing is off on this engine (NetConfig.erase_prob is 0)")
+            return
+        b = self._check_frames(int(frames.shape[0]))
+        fpc, (h, w) = self.T, self.cfg.image_shape[:2]
+        boxes = check_erase_boxes(erase_boxes, b, fpc, h, w) if erase_boxes is not None else None
+        rank = self.dp.rank if self.dp is not None else 0
+        table = erase_table(self.erase, self._draw_index(mi), rank, self.B, fpc, h, w, boxes, clips=b)
+        self.erase_table[:b].copy_(torch.from_numpy(table))
+        self.erase_table_last = table
+
+    def _erase_launch(self, n, b):
+        """Every clip's box of the frames just fed is overwritten in place, in the layout conv1 reads (as _mix_launch chooses it), ahead
+        of the blend / the cut: erase each sample, then mix (timm's order)."""
+        if self.erase is None:
+            return
+        if self.c8 and self._xb_fed:
+            self.layers[0]["conv"].erase_boxes_s2d(self.layers[0]["xb"][:n], b, self.T, self.erase_table[:b], self.erase_mode_id,
+                                                   self.erase_scale)
+        else:
+            ops.erase_boxes(self.x0[:n], b, self.T, self.cfg.image_shape[:2], self.x0_halo, self.x0_phase, self.erase_table[:b],
+                            self.erase_mode_id, self.erase_scale)
 
     # ---- LARS (lars_eeta; shared with GraphEngine) ----------------------------------------------------------------------------------------
     def _lars_setup(self):
@@ -2384,6 +2574,7 @@ class LRCNEngine:
             raise VltfError("labels must be int32 one-hot of shape (%d, %d)" % (self._rows_for(b, n), self.cfg.num_classes))
         self._mi = mi
         try:
+            self._erase_launch(n, b)              # random erasing: each clip's own box, ahead of the blend / the cut
             self._mix_launch(n, b)                # mixup: the clips just fed are blended in pairs before conv1 reads them
             rows = self._forward(n, b, train=True)
             world = self.dp.world if self.dp is not None else 1
@@ -2504,7 +2695,8 @@ class LRCNEngine:
         return b if (self.early or self.late) else n
 
     def train_step_u8(self, frames_u8, onehot, lr, clip_norm=0.0, mean_bgr=None, crop_y=None, crop_x=None, mirror=None,
-                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None, cut_box=None, crop_box=None):
+                      fetch=True, global_rows=None, resize=None, micro=None, mix_lambda=None, cut_box=None, crop_box=None,
+                      erase_boxes=None):
         """sess.run([summaries, loss, lr, global_step, optimizer], fdict) (run_task.py:44).
         crop_box: a box per frame in the place of crop_y / crop_x (feed_u8); refused together with them.
         micro = (i, k): micro-step i of an update that sums k of them (k <= cfg.accumulate), called in order i = 0 .. k - 1.  Only the
@@ -2513,11 +2705,14 @@ class LRCNEngine:
         mix_lambda: with mixup on (cfg.mixup_alpha > 0), this step's blend weight in [0, 1] in the place of the draw (folded to
         max(lam, 1 - lam)); refused with mixup off.
         cut_box: with CutMix on (cfg.cutmix_alpha > 0), this step's box (t0, t1, y0, y1, x0, x1) in the place of the draw; refused with
-        CutMix off, outside the frame, reversed, above half the clip's volume, or together with mix_lambda (check_cut_box)."""
+        CutMix off, outside the frame, reversed, above half the clip's volume, or together with mix_lambda (check_cut_box).
+        erase_boxes: with random erasing on (cfg.erase_prob > 0), one box (t0, t1, y0, y1, x0, x1) per clip in the place of the drawn
+        ones (the noise keys are still drawn); refused with erasing off, outside the frame or reversed (check_erase_boxes)."""
         self._check_crop_box(crop_box, crop_y, crop_x)
         mi = self.micro.enter(micro)
         try:
             self._mix_write(mix_lambda, mi, cut_box)
+            self._erase_write(erase_boxes, mi, frames_u8)
             if self.step_graph:
                 done, out = self._graph_step(True, frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, onehot, lr, clip_norm, fetch,
                                              global_rows, mi, crop_box=crop_box)
@@ -2530,10 +2725,11 @@ class LRCNEngine:
             raise
 
     def train_step_f32(self, frames_nhwc, onehot, lr, clip_norm=0.0, fetch=True, global_rows=None, micro=None, mix_lambda=None,
-                       cut_box=None):
+                       cut_box=None, erase_boxes=None):
         mi = self.micro.enter(micro)
         try:
             self._mix_write(mix_lambda, mi, cut_box)
+            self._erase_write(erase_boxes, mi, frames_nhwc)
             n, b = self.feed_f32_nhwc(frames_nhwc)
             return self._train(n, b, onehot, lr, clip_norm, fetch, global_rows, mi)
         except VltfError:

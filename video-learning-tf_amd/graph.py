@@ -43,7 +43,7 @@ from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
                      check_rnn_cell, gru_buffers, gru_names, gru_specs,
                      check_label_smoothing,
-                     check_cutmix, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
+                     check_cutmix, check_erase, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
 
 
@@ -848,7 +848,7 @@ class GraphEngine:
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
                  lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0,
-                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0, class_weights=None, focal_gamma=0.0):
+                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0, class_weights=None, focal_gamma=0.0, erase_prob=0.0):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -870,7 +870,12 @@ class GraphEngine:
         cutmix_alpha: refused when > 0 for the same reason.  class_weights, focal_gamma: num_classes weights inside the
         class sum of the loss and the focal loss's focusing parameter, in the loss launch of the last pipeline with its seq_len
         (engine.check_class_weights, engine.check_focal_gamma, LRCNEngine._loss_setup); a forward-only engine ignores
-        them; None / 0 = off."""
+        them; None / 0 = off.  erase_prob: refused when > 0 -- random erasing draws one table per batch of ONE dcnn pipeline
+        (LRCNEngine); per-tower tables are a follow-up."""
+        if check_erase(erase_prob).prob > 0.0:
+            raise VltfError("erase_prob = %s is refused by GraphEngine: random erasing keeps one box table for the clips of one dcnn "
+                            "pipeline; per-tower tables are a follow-up (use a single-pipeline model: LRCNEngine, NetConfig.erase_prob)"
+                            % (erase_prob,))
         if check_cutmix(cutmix_alpha)[0] > 0.0:
             raise VltfError("cutmix_alpha = %s is refused by GraphEngine: frame towers, vector inputs, clips-per-video ratios and word-level "
                             "losses have no one clip to pair; CutMix runs on single-pipeline models (LRCNEngine, NetConfig.cutmix_alpha)"

@@ -281,6 +281,19 @@ class Conv:
         _ffi.call("vl_cutmix_pairs_s2d", self._d, _p(xb), clips, fpc, host, dev, stream())
         del keep
 
+    def erase_boxes_s2d(self, xb, clips, fpc, table, mode, scale):
+        """Random erasing in place in the packed space-to-depth input (vl_erase_boxes_s2d): xb is what input_prep_u8_s2d writes for
+        clips * fpc frames; clip i's box of the h x w frames is overwritten with the fill of `mode`, rounded to bf16.  table, mode,
+        scale: as in ops.erase_boxes."""
+        clips, fpc = int(clips), int(fpc)
+        s, ka = self.stride, (self.kh - 1) // self.stride + 1
+        if not torch.is_tensor(xb) or not xb.is_cuda or xb.dtype != torch.bfloat16 or not xb.is_contiguous() or \
+                (clips >= 0 and fpc > 0 and tuple(xb.shape) != c8_shape(clips * fpc, self.cin * s * s, self.oh, self.ow, (ka - 1) // 2)):
+            raise _ffi.VltfError("conv.erase_boxes_s2d: xb must be the contiguous bf16 packed input of %d clips of %d frames, got %s"
+                                 % (clips, fpc, tuple(xb.shape) if torch.is_tensor(xb) else type(xb)))
+        _erase_table(table, clips, "conv.erase_boxes_s2d")
+        _ffi.call("vl_erase_boxes_s2d", self._d, _p(xb), clips, fpc, _p(table), int(mode), float(scale), stream())
+
     def s2d_weights(self, src, dst, grad=False):
         """grad=False: w [k][k][cin][cout] -> [ka][ka][cin s^2][cout]; grad=True: the stride-1 layer's dw -> dw."""
         _f32(src, dst); _dense(src, dst)
@@ -877,6 +890,37 @@ def cutmix_pairs(x0, clips, fpc, out_hw, halo, phase, box):
     host, dev, keep = _cut_box(box, "cutmix_pairs")
     _ffi.call("vl_cutmix_pairs", _p(x0), clips, fpc, int(out_hw[0]), int(out_hw[1]), int(halo), int(phase), host, dev, stream())
     del keep
+
+
+ERASE_MODES = ("zero", "clip", "pixel")          # vl_erase_boxes' mode 0, 1, 2
+ERASE_SUM_STD = 37837.22723720648                # the standard deviation of the four-field sum: sqrt(4 (65536^2 - 1) / 12)
+
+
+def erase_scale(std):
+    """vl_erase_boxes' scale for a fill of this standard deviation: (float)(std / 37837.22723720648)."""
+    return float(np.float32(float(std) / ERASE_SUM_STD))
+
+
+def _erase_table(table, clips, what):
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int32 and table.is_contiguous()
+            and (clips < 0 or tuple(table.shape) == (clips, 8))):
+        raise _ffi.VltfError("%s: the table is a contiguous device int32 [%d][8] tensor (t0, t1, y0, y1, x0, x1, key_lo, key_hi per clip)"
+                             % (what, clips))
+
+
+def erase_boxes(x0, clips, fpc, out_hw, halo, phase, table, mode, scale):
+    """Random erasing in place in x0 (vl_erase_boxes): x0 is phase_split_shape(clips * fpc, 3, *out_hw, halo, phase), what
+    input_prep_u8 writes; clip i's half-open box (row i of table, read when the kernel runs and clamped to the frame) is overwritten
+    in all channels.  table: device int32 [clips][8] = (t0, t1, y0, y1, x0, x1, key_lo, key_hi).  mode: 0 zero, 1 one value per
+    (clip, channel), 2 one per element (ERASE_MODES).  scale: erase_scale(std)."""
+    _f32(x0); _dense(x0)
+    clips, fpc = int(clips), int(fpc)
+    if clips >= 0 and fpc > 0 and tuple(x0.shape) != phase_split_shape(clips * fpc, 3, out_hw[0], out_hw[1], halo, phase):
+        raise _ffi.VltfError("erase_boxes: x0 %s is not %d clips of %d frames %s (halo %d, phase %d)"
+                             % (tuple(x0.shape), clips, fpc, tuple(out_hw), halo, phase))
+    _erase_table(table, clips, "erase_boxes")
+    _ffi.call("vl_erase_boxes", _p(x0), clips, fpc, int(out_hw[0]), int(out_hw[1]), int(halo), int(phase), _p(table), int(mode), float(scale),
+              stream())
 
 
 def softmax_xent_mix(logits, labels, dlogits, stats, grad_scale, rows, rows_per_clip, smoothing, top_k, lam):

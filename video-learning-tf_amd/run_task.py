@@ -63,7 +63,9 @@ def pipeline_net_config(settings, p, dataset):
               label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
               lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0], mixup_seed=settings.get_mixup()[1],
               class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma(),
-              **dict(zip(("cutmix_alpha", "cutmix_seed", "cutmix_mode", "cutmix_prob"), settings.get_cutmix())))
+              **dict(zip(("cutmix_alpha", "cutmix_seed", "cutmix_mode", "cutmix_prob"), settings.get_cutmix())),
+              **dict(zip(("erase_prob", "erase_scale", "erase_ratio", "erase_frames", "erase_mode", "erase_std", "erase_seed"),
+                         settings.get_erase())))
     if p.classifier == defs.classifier.lstm:
         if p.frame_fusion and p.frame_fusion[0] != defs.fusion_type.none:
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
@@ -339,6 +341,9 @@ def main(init_file, seed=0, device=None):
     if settings.get_cutmix()[0] > 0 and not single:
         error("train.cutmix_alpha is refused for this model: it runs on the multi-pipeline GraphEngine, which has no CutMix (frame towers, "
               "vector inputs and word-level losses have no one clip to pair); use it with a single-pipeline model")
+    if settings.get_erase()[0] > 0 and not single:
+        error("train.erase_prob is refused for this model: it runs on the multi-pipeline GraphEngine, which has no random erasing (one "
+              "box table serves the clips of one dcnn pipeline; per-tower tables are a follow-up); use it with a single-pipeline model")
     if world > 1:
         batch = -(-batch // world)           # data parallel: `batch_size` stays the GLOBAL batch of the config
     if single:

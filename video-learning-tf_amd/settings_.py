@@ -29,6 +29,7 @@ class TrainSettings:
     label_smoothing, top_k = 0.0, 0
     mixup_alpha, mixup_seed = 0.0, 0
     cutmix_alpha, cutmix_seed, cutmix_mode, cutmix_prob = 0.0, 0, None, None
+    erase = (0.0, None, None, None, None, None, 0)     # erase_prob, _scale, _ratio, _frames, _mode, _std, _seed (NetConfig's fields)
     class_weights, focal_gamma = None, 0.0
 
 
@@ -113,6 +114,12 @@ class Settings:
         """(train.mixup_alpha, train.mixup_seed): mixup's Beta(alpha, alpha) and the key of its draws (engine.check_mixup,
         engine.mixup_lambda); (0, 0) = off, and outside the train phase (validation never blends)."""
         return (self.train.mixup_alpha, self.train.mixup_seed) if self.phase == defs.phase.train else (0.0, 0)
+
+    def get_erase(self):
+        """(train.erase_prob, erase_scale, erase_ratio, erase_frames, erase_mode, erase_std, erase_seed): random erasing's chance per
+        clip, the ranges of its box, its fill and the key of its draws, checked and with the defaults filled in (engine.check_erase,
+        engine.erase_row); (0, None, None, None, None, None, 0) = off, and outside the train phase (validation never erases)."""
+        return self.train.erase if self.phase == defs.phase.train else TrainSettings.erase
 
     def get_cutmix(self):
         """(train.cutmix_alpha, train.cutmix_seed, train.cutmix_mode, train.cutmix_prob): CutMix / VideoMix's Beta(alpha, alpha), the key
@@ -481,6 +488,22 @@ class Settings:
                     t.cutmix_mode, t.cutmix_prob = (md, pr) if a > 0.0 else (None, None)
                 except VltfError as ex:
                     error("train.cutmix_alpha / train.cutmix_seed / train.cutmix_mode / train.cutmix_prob: %s" % ex)
+                # random erasing (Zhong et al. 2017): every clip gets a box of its own, or none, filled with the mean colour or noise
+                # (engine.check_erase, engine.erase_row): absent / None = off
+                from .engine import check_erase
+                names = ("erase_prob", "erase_scale", "erase_ratio", "erase_frames", "erase_mode", "erase_std", "erase_seed")
+                er = [obj.get(k) for k in names]
+                for i, conv in enumerate((float, None, None, None, None, float, int)):
+                    if conv is not None and isinstance(er[i], str) and er[i] != "None":      # a quoted number
+                        try:
+                            er[i] = conv(er[i])
+                        except ValueError:
+                            pass
+                try:
+                    e = check_erase(*(None if v == "None" else v for v in er))
+                    t.erase = tuple(e) if e.prob > 0.0 else TrainSettings.erase
+                except VltfError as ex:
+                    error("train.%s: %s" % (" / train.".join(names), ex))
                 # class weights inside the loss's class sum and the focal loss (engine.check_class_weights, engine.check_focal_gamma;
                 # `balanced` is resolved by initialize, from the training item list): absent / None = off
                 t.class_weights, t.focal_gamma = self.read_loss_weights(obj)

@@ -174,6 +174,12 @@ class Train:
                   ("; with mixup on a batch is cut with probability %s, else blended" % engine.cutmix_prob)
                   if engine.blend_lam is not None else ""))
 
+        if getattr(engine, "erase", None) is not None:
+            e = engine.erase
+            info("Random erasing: prob %s, scale %s, ratio %s, frames %s, mode %s%s, seed %d; every clip of a batch draws a box of its own "
+                 "(or none), overwritten after the feed and ahead of mixup / CutMix; the labels stay as they are" %
+                 (e.prob, tuple(e.scale), tuple(e.ratio), tuple(e.frames), e.mode, "" if e.mode == "zero" else " (std %s)" % e.std, e.seed))
+
     def _stats_step(self, out, lr):
         """After a step: a stats step's result goes to the JSONL file and to the log."""
         if self.stats_log is None or "tensor_stats" not in out:
