@@ -441,6 +441,20 @@ int vl_temporal_fusion_fwd_len(const float* x, float* y, int batch, int T, int H
 int vl_temporal_fusion_bwd_len(const float* dy, float* dx, int batch, int T, int H, int method, const int32_t* seq_len,
                                vl_stream_t stream);
 
+/* ---- attention pooling over time (fusion `attn`: Raffel & Ellis 2015, Yang et al. 2016) ------------------------------
+ * Per clip b with L = min(max(seq_len[b], 1), T) live steps (seq_len NULL: L = T), rows h[b][t][HO] and projections u[b][t][A]
+ * (u = h W + bias, vl_gemm):  s = tanh(u),  e_t = s_t . c,  alpha = softmax(e_0 .. e_{L-1}) (max-subtracted),  y = sum_t alpha_t h_t.
+ * fwd writes s [batch][T][A] (may alias u; dead rows zero), alpha [batch][T] (dead steps zero) and y [batch][HO].
+ * bwd reads dy [batch][HO] and writes du [batch][T][A] = de_t c_a (1 - s^2) with de_t = alpha_t (dy . h_t - sum_r alpha_r dy . h_r),
+ * dh [batch][T][HO] = alpha_t dy (the direct term only: du W^T is the caller's product) and dcp [batch][A] = sum_t de_t s[t][a], the
+ * per-clip partials of c's gradient (vl_colsum them); dead rows of du and dh are zeros.
+ * One workgroup per clip, no atomics: a clip's outputs depend on that clip's inputs alone, bit for bit, in any batch.  Rows t >= L of
+ * h, u and s are never read.  T <= 1024 (the scores of a clip live in LDS). */
+int vl_attn_pool_fwd(const float* u, const float* c, const float* h, const int32_t* seq_len, float* s, float* alpha, float* y,
+                     int batch, int T, int HO, int A, vl_stream_t stream);
+int vl_attn_pool_bwd(const float* dy, const float* h, const float* s, const float* alpha, const float* c, const int32_t* seq_len,
+                     float* du, float* dh, float* dcp, int batch, int T, int HO, int A, vl_stream_t stream);
+
 /* ---- imresize: scipy.misc.imresize(image, shape) of Dataset.process_image (dataset_.py:481-495: imgproc `raw_resize` to the raw
  * shape, `resize` to the network input size; also serialize.py:424-425) = PIL Image.resize(BILINEAR) on uint8, bit-exact:
  * Pillow's two-pass fixed-point resample (22-bit coefficients, uint8 intermediate, horizontal pass first; csrc/resize.hip).

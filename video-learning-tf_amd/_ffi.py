@@ -92,6 +92,8 @@ SIGNATURES = {
     "vl_temporal_fusion_bwd": (i32, [p, p, i32, i32, i32, i32, p]),
     "vl_temporal_fusion_fwd_len": (i32, [p, p, i32, i32, i32, i32, p, p]),
     "vl_temporal_fusion_bwd_len": (i32, [p, p, i32, i32, i32, i32, p, p]),
+    "vl_attn_pool_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
+    "vl_attn_pool_bwd": (i32, [p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_dropout_fwd": (i32, [p, p, p, i64, f32, u64, p]),
     "vl_dropout_bwd": (i32, [p, p, p, i64, f32, p]),
     "vl_dropout_fwd_st": (i32, [p, p, p, i64, f32, p, p]),

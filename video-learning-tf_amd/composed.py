@@ -66,6 +66,9 @@ def init_head_params(enc_cfg: NetConfig, head: HeadConfig, scopes=("enc", "dec")
 class ComposedEngine(GraphEngine):
     def __init__(self, enc_cfg: NetConfig, head: HeadConfig, max_clips: int, device="cuda:0", training=True, dp=None,
                  scopes=("enc", "dec")):
+        if head.fusion == "attn" or (enc_cfg.classifier == "lstm" and enc_cfg.fusion == "attn") or getattr(enc_cfg, "attn_dim", None) is not None:
+            raise VltfError("lstm_params fusion attn / attn_dim are not built for the two-pipeline model, which keeps avg | last | reshape | "
+                            "state (use LRCNEngine, or GraphEngine with PipelineSpec(lstm_params=(H, layers, \"attn\")))")
         if head.fusion not in ("avg", "last", "reshape", "state"):
             raise VltfError("Undefined frame fusion type : %s" % head.fusion)
         if head.input_fusion not in (None, "concat", "ibias"):

@@ -1711,6 +1711,134 @@ extern "C" int vl_temporal_fusion_bwd_len(const float* dy, float* dx, int batch,
     return temporal_fusion_bwd(dy, dx, batch, T, H, method, seq_len, (hipStream_t)stream);
 }
 
+// ---- attention pooling over time (fusion `attn`; vltf.h) -----------------------------------------------------------
+// One workgroup of ATTN_THREADS per clip, no atomics, every sum in one fixed order: a clip's outputs are a function of that clip's
+// inputs alone.  Rows t >= L (fusion_len) of h, u and s are never read.  T <= ATTN_MAX_T: a clip's scores live in LDS.
+#define ATTN_THREADS 256
+#define ATTN_MAX_T 1024
+
+// softmax pieces of e[0..L) in LDS, computed by EVERY wave on its own (same order, same bits): no exchange between waves
+__device__ __forceinline__ void attn_softmax_stats(const float* e, int L, int lane, float& mx, float& sum) {
+    float m = -INFINITY;
+    for (int t = lane; t < L; t += 64) m = fmaxf(m, e[t]);
+    mx = wave_max(m);
+    float z = 0.f;
+    for (int t = lane; t < L; t += 64) z += expf(e[t] - mx);
+    sum = wave_sum(z);
+}
+
+__global__ __launch_bounds__(ATTN_THREADS) void attn_pool_fwd_kernel(const float* u, const float* __restrict__ c,
+                                                                     const float* __restrict__ h, const int32_t* __restrict__ seq_len,
+                                                                     float* s, float* __restrict__ alpha, float* __restrict__ y, int T,
+                                                                     int HO, int A) {
+    __shared__ float e[ATTN_MAX_T];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = fusion_len(seq_len, b, T);
+    const float* ub = u + (int64_t)b * T * A;              // (s may alias u: element [t][a] is read, then written, by one thread)
+    float* sb = s + (int64_t)b * T * A;
+    // scores: one wave per step, lanes over A in a fixed order, then the shuffle tree
+    for (int t = wave; t < T; t += ATTN_THREADS / 64) {
+        if (t < L) {
+            float acc = 0.f;
+            for (int a = lane; a < A; a += 64) {
+                const float v = tanhf(ub[(int64_t)t * A + a]);
+                sb[(int64_t)t * A + a] = v;
+                acc = __fmaf_rn(v, c[a], acc);
+            }
+            acc = wave_sum(acc);
+            if (lane == 0) e[t] = acc;
+        } else {
+            for (int a = lane; a < A; a += 64) sb[(int64_t)t * A + a] = 0.f;
+        }
+    }
+    __syncthreads();
+    float mx, z;
+    attn_softmax_stats(e, L, lane, mx, z);
+    __syncthreads();                                        // every wave has read the scores: they become the weights in place
+    for (int t = tid; t < T; t += ATTN_THREADS) {
+        const float w = t < L ? expf(e[t] - mx) / z : 0.f;
+        e[t] = w;
+        alpha[(int64_t)b * T + t] = w;
+    }
+    __syncthreads();
+    const float* hb = h + (int64_t)b * T * HO;
+    for (int col = tid; col < HO; col += ATTN_THREADS) {    // a thread per column, t ascending: coalesced rows of h
+        float acc = 0.f;
+        for (int t = 0; t < L; ++t) acc = __fmaf_rn(e[t], hb[(int64_t)t * HO + col], acc);
+        y[(int64_t)b * HO + col] = acc;
+    }
+}
+
+__global__ __launch_bounds__(ATTN_THREADS) void attn_pool_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ h,
+                                                                     const float* __restrict__ s, const float* __restrict__ alpha,
+                                                                     const float* __restrict__ c, const int32_t* __restrict__ seq_len,
+                                                                     float* __restrict__ du, float* __restrict__ dh,
+                                                                     float* __restrict__ dcp, int T, int HO, int A) {
+    __shared__ float al[ATTN_MAX_T], da[ATTN_MAX_T], de[ATTN_MAX_T];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = fusion_len(seq_len, b, T);
+    const float* hb = h + (int64_t)b * T * HO;
+    const float* dyb = dy + (int64_t)b * HO;
+    for (int t = tid; t < L; t += ATTN_THREADS) al[t] = alpha[(int64_t)b * T + t];
+    // da_t = dy . h_t: one wave per live step
+    for (int t = wave; t < L; t += ATTN_THREADS / 64) {
+        float acc = 0.f;
+        for (int col = lane; col < HO; col += 64) acc = __fmaf_rn(dyb[col], hb[(int64_t)t * HO + col], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) da[t] = acc;
+    }
+    __syncthreads();
+    float dot = 0.f;                                        // sum_r alpha_r da_r, by every wave on its own (same order, same bits)
+    for (int t = lane; t < L; t += 64) dot = __fmaf_rn(al[t], da[t], dot);
+    dot = wave_sum(dot);
+    for (int t = tid; t < L; t += ATTN_THREADS) de[t] = al[t] * (da[t] - dot);
+    __syncthreads();
+    const float* sb = s + (int64_t)b * T * A;
+    float* dub = du + (int64_t)b * T * A;
+    for (int a = tid; a < A; a += ATTN_THREADS) {           // a thread per column of s / du, t ascending
+        const float ca = c[a];
+        float acc = 0.f;
+        for (int t = 0; t < T; ++t) {
+            float g = 0.f;
+            if (t < L) {
+                const float v = sb[(int64_t)t * A + a];
+                g = de[t] * ca * (1.f - v * v);
+                acc = __fmaf_rn(de[t], v, acc);
+            }
+            dub[(int64_t)t * A + a] = g;
+        }
+        dcp[(int64_t)b * A + a] = acc;
+    }
+    float* dhb = dh + (int64_t)b * T * HO;
+    for (int col = tid; col < HO; col += ATTN_THREADS) {
+        const float g = dyb[col];
+        for (int t = 0; t < T; ++t) dhb[(int64_t)t * HO + col] = t < L ? al[t] * g : 0.f;
+    }
+}
+
+extern "C" int vl_attn_pool_fwd(const float* u, const float* c, const float* h, const int32_t* seq_len, float* s, float* alpha, float* y,
+                                int batch, int T, int HO, int A, vl_stream_t stream) {
+    VL_CHECK(u && c && h && s && alpha && y, "vl_attn_pool_fwd: null pointer");
+    VL_CHECK(batch > 0 && T > 0 && HO > 0 && A > 0, "vl_attn_pool_fwd: batch %d, T %d, HO %d, A %d must be positive", batch, T, HO, A);
+    VL_CHECK(T <= ATTN_MAX_T, "vl_attn_pool_fwd: T %d exceeds %d (a clip's scores live in LDS)", T, ATTN_MAX_T);
+    hipLaunchKernelGGL(attn_pool_fwd_kernel, dim3(batch), dim3(ATTN_THREADS), 0, (hipStream_t)stream, u, c, h, seq_len, s, alpha, y, T,
+                       HO, A);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_attn_pool_bwd(const float* dy, const float* h, const float* s, const float* alpha, const float* c,
+                                const int32_t* seq_len, float* du, float* dh, float* dcp, int batch, int T, int HO, int A,
+                                vl_stream_t stream) {
+    VL_CHECK(dy && h && s && alpha && c && du && dh && dcp, "vl_attn_pool_bwd: null pointer");
+    VL_CHECK(batch > 0 && T > 0 && HO > 0 && A > 0, "vl_attn_pool_bwd: batch %d, T %d, HO %d, A %d must be positive", batch, T, HO, A);
+    VL_CHECK(T <= ATTN_MAX_T, "vl_attn_pool_bwd: T %d exceeds %d (a clip's scores live in LDS)", T, ATTN_MAX_T);
+    hipLaunchKernelGGL(attn_pool_bwd_kernel, dim3(batch), dim3(ATTN_THREADS), 0, (hipStream_t)stream, dy, h, s, alpha, c, seq_len, du, dh,
+                       dcp, T, HO, A);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- dropout (lstm.py:50-56; splitmix64: common.h) ---------------------------------------------
 // one body for the eager kernel and the step-state one (vl_dropout_fwd_st): only where the seed comes from differs
 // (the grid-stride start and step come from the kernel: blockDim read there, where the compiler knows the work-group size is uniform)

@@ -51,7 +51,8 @@ class NetConfig:
     classifier: str = "lstm"                    # defs.classifier.{lstm, fc}; "none": a feature pipeline (classifier: None, model.py:110-112)
     lstm_hidden: int = 256
     lstm_layers: int = 1
-    fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state}
+    fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state, attn}
+    attn_dim: Optional[int] = None              # fusion attn: width A of the attention scorer (attn_specs); None = the recurrent output width
     lstm_bidirectional: bool = False            # every LSTM layer a forward and a backward cell, outputs concatenated (blstm_names); H <= 512
     rnn_cell: str = "lstm"                      # the recurrent cell of classifier lstm: "lstm" (BasicLSTMCell) | "gru" (reset-after, gru_names); H <= 512
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
@@ -154,6 +155,46 @@ def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state
     return cell
 
 
+ATTN_MAX_DIM = 1024
+
+
+def attn_names(scope=""):
+    """The variable names of the attention pooling of fusion `attn`, in flat-buffer order: kernel (HO, A), bias (A,), context (A, 1).
+    The context is rank 2 ON PURPOSE: it is a weight, and decay_ranges, LARS and LAMB treat rank >= 2 as one; the bias is exempt as
+    every bias is."""
+    return [scope + "attention_pool/" + v for v in ("kernel", "bias", "context")]
+
+
+def attn_specs(HO, A, scope=""):
+    """[(name, shape)] of attn_names for a recurrent output of width HO and an attention width A."""
+    return list(zip(attn_names(scope), ((HO, A), (A,), (A, 1))))
+
+
+def check_attn(fusion, attn_dim=None, classifier="lstm", out_width=1, what="attn_dim"):
+    """-> the attention width A of fusion `attn` (attn_dim, default out_width: the recurrent output width), or None for every other
+    fusion.  Refused: fusion attn without the recurrent classifier, attn_dim without fusion attn, attn_dim not an integer in 1..1024."""
+    if fusion == "attn" and classifier != "lstm":
+        raise VltfError("lstm_params: fusion attn pools the outputs of the recurrent classifier, but the classifier is [%s]" % classifier)
+    if fusion != "attn":
+        if attn_dim not in (None, "None"):
+            raise VltfError("%s is the width of fusion attn's scorer, but the fusion is [%s]" % (what, fusion))
+        return None
+    if attn_dim in (None, "None"):
+        return int(out_width)
+    if isinstance(attn_dim, bool) or not isinstance(attn_dim, (int, np.integer)) or not 1 <= int(attn_dim) <= ATTN_MAX_DIM:
+        raise VltfError("%s must be an integer in 1..%d, got [%s]" % (what, ATTN_MAX_DIM, attn_dim))
+    return int(attn_dim)
+
+
+def attn_buffers(buf, clips, T, HO, A, training):
+    """The device buffers of fusion attn: us (the projection u, then s = tanh(u) in place), the weights alpha (and, training, the
+    per-clip partials dcp of the context gradient, du, and dproj = du W^T)."""
+    S = dict(us=buf(clips * T, A), alpha=buf(clips, T))
+    if training:
+        S.update(dcp=buf(clips, A), du=buf(clips * T, A), dproj=buf(clips * T, HO))
+    return S
+
+
 def gru_buffers(buf, rows, H, training):
     """The device buffers of one GRU layer: projections gx, activated gates act, the candidate's recurrent term hcand, outputs hseq,
     entering outputs hprev (and, training, the gradients dgx / dgh of the two pre-activation terms and dout of the output)."""
@@ -190,11 +231,16 @@ def param_specs(cfg: NetConfig):
     check_rnn_cell(cfg.rnn_cell, cfg.classifier, cfg.lstm_hidden, cfg.lstm_bidirectional)
     if cfg.lstm_bidirectional and cfg.classifier != "lstm":
         raise VltfError("lstm_bidirectional needs classifier lstm, not [%s]" % cfg.classifier)
+    # fusion attn: its three variables sit between the head and the recurrent layers, the order in which the backward produces them
+    A = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, (2 if cfg.lstm_bidirectional else 1) * cfg.lstm_hidden)
+    if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "attn":
+        raise VltfError("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
     if cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
         H = cfg.lstm_hidden
         if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
             specs += [(head + "_w", (H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+        specs += attn_specs(H, A) if A else []
         d = dim
         for l in range(cfg.lstm_layers):
             specs += gru_specs(l, d, H)
@@ -205,6 +251,7 @@ def param_specs(cfg: NetConfig):
         if 2 * H != cfg.num_classes:                      # the head reads the 2H-wide fused vector
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
             specs += [(head + "_w", (2 * H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+        specs += attn_specs(2 * H, A) if A else []
         d = dim
         for l in range(cfg.lstm_layers):
             specs += [(n, (d + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l)]
@@ -214,6 +261,7 @@ def param_specs(cfg: NetConfig):
             # fusion `state`: logits = convert_dim_fc(final h) under its default name (model.py:137-141), else "output_fc" (lstm.py:90)
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
             specs += [(head + "_w", (cfg.lstm_hidden, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+        specs += attn_specs(cfg.lstm_hidden, A) if A else []
         d = dim
         for l in range(cfg.lstm_layers):
             pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
@@ -1090,7 +1138,7 @@ def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in param_specs(cfg):
-        if name.endswith("kernel"):
+        if name.endswith("kernel") or name.endswith("attention_pool/context"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias"):
@@ -1322,7 +1370,7 @@ class LRCNEngine:
             self.dfeat = self.df8 if self.df8 is not None else (self.df7 if self.df7 is not None else self.df6)
         # ---- classifier
         if cfg.classifier == "lstm":
-            if cfg.fusion not in ops.FUSION_CODE and cfg.fusion not in ("state", "reshape"):
+            if cfg.fusion not in ops.FUSION_CODE and cfg.fusion not in ("state", "reshape", "attn"):
                 raise VltfError("Undefined frame fusion type : %s" % cfg.fusion)          # tf_util.py:28-29
             # `state` = final h of the last layer = its output at t = T-1 (full-length sequences, lstm.py:136), no dropout;
             # `reshape` (tf_util.py:26-27) keeps every step: one logits row per frame, labels [clips * fpc, classes]
@@ -1354,6 +1402,10 @@ class LRCNEngine:
             self.dropped = buf(R, HO)
             self.drop_mask = buf(R, HO, dtype=torch.uint8)
             self.logits = buf(R, C) if HO != C else self.dropped
+            # fusion attn (check_attn: param_specs): learned attention pooling in the place of avg / last
+            self.attn_dim = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, HO)
+            self.attn = attn_buffers(buf, B, T, HO, self.attn_dim, training) if self.attn_dim else None
+            self._attn_clips = 0
             if training:
                 self.dh, self.dc = buf(B, H), buf(B, H)
                 self.dfused, self.ddropped = buf(R, HO), buf(R, HO)
@@ -2087,6 +2139,16 @@ class LRCNEngine:
                 ops.copy2d(o3[:, T - 1, :H], self.fused, b, H, src_ld=T * HO, dst_ld=HO)
                 ops.copy2d(o3[:, 0, H:], self.fused[:, H:], b, H, src_ld=T * HO, dst_ld=HO)
                 v = self.fused
+            elif self.attn is not None:
+                # u = hseq W + bias over all rows, then ONE launch: s = tanh(u) in place, scores, softmax, weighted sum.  The attention's
+                # three dense products are called as the head's are, WITHOUT a workspace: fp32 whatever conv_math says (vl_gemm takes its
+                # split-bf16 branch only when it is handed the workspace for the operand images)
+                Wa, ba, ca = (P[k] for k in attn_names())
+                At, S = self.attn_dim, self.attn
+                ops.gemm(xin, Wa, S["us"], n, At, HO, bias=ba)
+                ops.attn_pool_fwd(S["us"], ca, xin, S["us"], S["alpha"], self.fused, b, T, HO, At)
+                self._attn_clips = b
+                v = self.fused
             else:
                 ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, self.lstm_fusion)
                 v = self.fused
@@ -2128,6 +2190,12 @@ class LRCNEngine:
         n, b = self.feed_u8(frames_u8, mean_bgr, crop_y, crop_x, mirror, resize, crop_box)
         rows = self._forward(n, b, train=False)
         return self.logits[:rows]
+
+    def attention_weights(self):
+        """Device view [clips, T] of the weights alpha the last forward gave each time step (fusion attn); rows sum to 1."""
+        if getattr(self, "attn", None) is None:
+            raise VltfError("attention_weights: the model has no attention pooling (lstm_params fusion attn)")
+        return self.attn["alpha"][:self._attn_clips]
 
     def forward_f32(self, frames_nhwc):
         n, b = self.feed_f32_nhwc(frames_nhwc)
@@ -2190,6 +2258,19 @@ class LRCNEngine:
                 g3 = top["dout"][:b * T].view(b, T, HO)
                 ops.copy2d(d, g3[:, T - 1, :H], b, H, src_ld=HO, dst_ld=T * HO)
                 ops.copy2d(d[:, H:], g3[:, 0, H:], b, H, src_ld=HO, dst_ld=T * HO)
+            elif self.attn is not None:
+                # ONE launch: du, the direct term alpha_t dy straight into dout, the per-clip partials of the context gradient
+                names = attn_names()
+                At, S, hs = self.attn_dim, self.attn, top["hseq"]
+                ops.attn_pool_bwd(d, hs, S["us"], S["alpha"], P[names[2]], S["du"], top["dout"], S["dcp"], b, T, HO, At)
+
+                def attn_grads(ws, sws, S=S, names=names, hs=hs, At=At):
+                    ops.gemm(hs, S["du"], G[names[0]], HO, At, n, transa=True)
+                    ops.colsum(S["du"], G[names[1]], sws, n, At)
+                    ops.colsum(S["dcp"], G[names[2]], sws, b, At)
+                param_grads(attn_grads)
+                ops.gemm(S["du"], P[names[0]], S["dproj"], n, HO, At, transb=True)
+                ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", n * HO)
             else:
                 ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, self.lstm_fusion)
             for l in reversed(range(len(self.blstm))):

@@ -41,7 +41,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, attn_buffers, attn_names, attn_specs, check_attn,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -56,7 +56,8 @@ class PipelineSpec:
     frame_encoding_layer: Optional[str] = None      # dcnn
     fc_output_dim: Optional[int] = None             # fc
     classifier: Optional[str] = None                # None | fc | lstm
-    lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state)
+    lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state | attn)
+    attn_dim: Optional[int] = None                  # fusion attn: the width of the attention scorer (engine.attn_specs); None = the LSTM's output width
     lstm_bidirectional: bool = False                # classifier lstm: a forward and a backward cell per layer, outputs concatenated (2H wide)
     rnn_cell: str = "lstm"                          # classifier lstm: its cell, lstm | gru (engine.gru_names; no state input, H <= 512)
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
@@ -106,8 +107,17 @@ class PipeNode:
         ftype, fmethod = s.frame_fusion if s.frame_fusion else (None, None)
         if ftype == "none":
             ftype = None
+        if ftype is not None and fmethod == "attn":
+            raise VltfError("pipeline [%s]: frame_fusion attn is not built: attention pooling is a fusion of the recurrent classifier "
+                            "(lstm_params)" % s.name)
         if ftype is not None and fmethod not in ("avg", "last", "reshape"):
             raise VltfError("Undefined frame fusion type : %s" % fmethod)                 # apply_temporal_fusion, tf_util.py:28-29
+        if s.input_fusion == "attn":
+            raise VltfError("pipeline [%s]: input_fusion attn is not built: attention pooling is a fusion of the recurrent classifier "
+                            "(lstm_params)" % s.name)
+        lf = s.lstm_params[2] if (s.classifier == "lstm" and s.lstm_params) else None
+        if s.classifier != "lstm" and (s.attn_dim not in (None, "None") or (s.lstm_params and s.lstm_params[2] == "attn")):
+            raise VltfError("pipeline [%s]: lstm_params fusion attn / attn_dim need classifier lstm, not [%s]" % (s.name, s.classifier))
         if s.classifier is None and ftype == "late":
             raise VltfError("Specified late fusion with no classifier selected")          # model.py:36-37
         if s.classifier not in (None, "fc", "lstm"):
@@ -216,7 +226,7 @@ class PipeNode:
                 if ftype is not None:
                     raise VltfError("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % ftype)
                 self.H, self.L, self.lfusion = int(s.lstm_params[0]), int(s.lstm_params[1]), s.lstm_params[2]
-                if self.lfusion not in ("avg", "last", "reshape", "state"):
+                if self.lfusion not in ("avg", "last", "reshape", "state", "attn"):
                     raise VltfError("Undefined frame fusion type : %s" % self.lfusion)
                 self.per_step = self.lfusion == "reshape"
                 self.head_name = "fc_convert" if self.lfusion == "state" else "output_fc"
@@ -228,6 +238,8 @@ class PipeNode:
                         raise VltfError("pipeline [%s]: a bidirectional LSTM takes no state input ([%s]): the reference hands ONE vector to "
                                         "every cell as c = h, and which of the two directions it would initialise is not defined" %
                                         (s.name, self.state_src.ref))
+                # fusion attn: learned attention pooling (engine.check_attn); None for every other fusion
+                self.attn_dim = check_attn(lf, s.attn_dim, "lstm", self.HO, what="pipeline [%s]: attn_dim" % s.name)
                 if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
@@ -258,6 +270,8 @@ class PipeNode:
             H, HO = self.H, self.HO
             if HO != C:
                 specs += [(sc + self.head_name + "_w", (HO, C)), (sc + self.head_name + "_b", (C,))]
+            if self.attn_dim:
+                specs += attn_specs(HO, self.attn_dim, sc)
             dims = [self.feat_dim] + [HO] * (self.L - 1)
             for l in reversed(range(self.L)):
                 if self.bi:
@@ -354,6 +368,7 @@ class PipeNode:
             self.dropped = buf(r, HO)
             self.drop_mask = buf(r, HO, dtype=torch.uint8)
             self.cls_out = buf(r, C) if HO != C else None
+            self.attn = attn_buffers(buf, B, T, HO, self.attn_dim, tr) if self.attn_dim else None
             if self.state_src is not None:
                 sd = self.state_src.dim
                 self.rep_state = buf(B, sd) if self.state_ratio > 1 else None
@@ -367,7 +382,7 @@ class PipeNode:
                 if self.bi:
                     self.dx_bw = buf(R0, max(self.feat_dim, HO))      # the backward direction's share of a layer's input gradient
                     self.dlast = buf(B, HO)                           # fusion last / state: the fused gradient with its backward half zeroed
-            sw = max(sw, 64 * 4 * H, 64 * H)
+            sw = max(sw, 64 * 4 * H, 64 * H, 64 * (self.attn_dim or 0))
         if self.late:
             self.late_out = buf(self.max_rows, C)
             if tr:
@@ -596,6 +611,14 @@ class PipeNode:
         r = rows if self.per_step else b
         if self.per_step:
             v = xin                                                     # reshape fusion: every step's output (tf_util.py:26-27)
+        elif self.attn is not None:
+            # u = hseq W + bias over all rows (a dead row of hseq is zero, its u is never read), then the one pooling launch; the
+            # attention's dense products take no workspace, as the head's: fp32 whatever conv_math says
+            Wa, ba, ca = (P[k] for k in attn_names(sc))
+            S = self.attn
+            ops.gemm(xin, Wa, S["us"], rows, self.attn_dim, HO, bias=ba)
+            ops.attn_pool_fwd(S["us"], ca, xin, S["us"], S["alpha"], self.fused, b, T, HO, self.attn_dim, **lk)
+            v = self.fused
         else:
             # with lengths `state` and `last` are h of step len - 1 (dynamic_rnn's final state), `avg` the mean over the live steps
             ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, last, **lk)
@@ -683,6 +706,15 @@ class PipeNode:
             ops.copy2d(d, self.dlast, b, H, src_ld=HO, dst_ld=HO)
             ops.temporal_fusion_bwd(self.dlast, top["dout"], b, T, HO, last, **self._len_kw())
             ops.copy2d(d[:, H:], top["dout"][:, H:], b, H, src_ld=HO, dst_ld=T * HO)
+        elif self.attn is not None:
+            # du, the direct term alpha_t dy straight into dout (zeros in the dead rows of both), the context gradient's per-clip partials
+            names, S, At, hs = attn_names(sc), self.attn, self.attn_dim, top["hseq"]
+            ops.attn_pool_bwd(d, hs, S["us"], S["alpha"], P[names[2]], S["du"], top["dout"], S["dcp"], b, T, HO, At, **self._len_kw())
+            ops.gemm(hs, S["du"], G[names[0]], HO, At, rows, transa=True)
+            ops.colsum(S["du"], G[names[1]], sw, rows, At)
+            ops.colsum(S["dcp"], G[names[2]], sw, b, At)
+            ops.gemm(S["du"], P[names[0]], S["dproj"], rows, HO, At, transb=True)
+            ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", rows * HO)
         else:
             ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, last, **self._len_kw())
         has_state = self._s0 is not None
@@ -822,7 +854,7 @@ def init_params_for(specs, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in specs:
-        if name.endswith("kernel"):
+        if name.endswith("kernel") or name.endswith("attention_pool/context"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias"):

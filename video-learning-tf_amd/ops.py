@@ -754,6 +754,39 @@ def temporal_fusion_bwd(dy, dx, batch, T, H, method, seq_len=None):
     _ffi.call("vl_temporal_fusion_bwd", _p(dy), _p(dx), batch, T, H, FUSION_CODE[method], stream())
 
 
+ATTN_MAX_T = 1024       # vl_attn_pool_*: a clip's scores live in LDS
+
+
+def _attn_sizes(who, batch, T, HO, A, **tensors):
+    """Every tensor given holds at least what the launch reads or writes of it (None passes: the C side refuses a null pointer)."""
+    need = dict(u=batch * T * A, s=batch * T * A, du=batch * T * A, h=batch * T * HO, dh=batch * T * HO, alpha=batch * T,
+                y=batch * HO, dy=batch * HO, dcp=batch * A, c=A)
+    for k, t in tensors.items():
+        if t is not None and min(batch, T, HO, A) > 0 and t.numel() < need[k]:
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), need[k]))
+
+
+def attn_pool_fwd(u, c, h, s, alpha, y, batch, T, HO, A, seq_len=None):
+    """Attention pooling over time (vl_attn_pool_fwd): s = tanh(u) (s may be u), alpha = softmax over the live steps of s . c,
+    y = sum_t alpha_t h_t.  u, s [batch, T, A]; c [A]; h [batch, T, HO]; alpha [batch, T]; y [batch, HO]; seq_len as temporal_fusion_fwd."""
+    _f32(u, c, h, s, alpha, y)
+    _dense(u, c, h, s, alpha, y)
+    _attn_sizes("attn_pool_fwd", batch, T, HO, A, u=u, c=c, h=h, s=s, alpha=alpha, y=y)
+    _ffi.call("vl_attn_pool_fwd", _p(u), _p(c), _p(h), None if seq_len is None else _p(_seq_len(seq_len, batch, "attn_pool_fwd")),
+              _p(s), _p(alpha), _p(y), batch, T, HO, A, stream())
+
+
+def attn_pool_bwd(dy, h, s, alpha, c, du, dh, dcp, batch, T, HO, A, seq_len=None):
+    """Its backward (vl_attn_pool_bwd): du [batch, T, A], the direct term dh [batch, T, HO] = alpha_t dy and the per-clip partials
+    dcp [batch, A] of c's gradient; dead rows of du and dh are zeros."""
+    _f32(dy, h, s, alpha, c, du, dh, dcp)
+    _dense(dy, h, s, alpha, c, du, dh, dcp)
+    _attn_sizes("attn_pool_bwd", batch, T, HO, A, dy=dy, h=h, s=s, alpha=alpha, c=c, du=du, dh=dh, dcp=dcp)
+    _ffi.call("vl_attn_pool_bwd", _p(dy), _p(h), _p(s), _p(alpha), _p(c),
+              None if seq_len is None else _p(_seq_len(seq_len, batch, "attn_pool_bwd")), _p(du), _p(dh), _p(dcp), batch, T, HO, A,
+              stream())
+
+
 def dropout_fwd(x, y, mask, keep, seed):
     _f32(x, y)
     _ffi.call("vl_dropout_fwd", _p(x), _p(y), _p(mask), x.numel(), keep, seed, stream())

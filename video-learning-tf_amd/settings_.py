@@ -183,10 +183,15 @@ class Settings:
             network.lstm_params = [int(params[0]), int(params[1]), defs.check(params[2], defs.fusion_method)]
         network.lstm_bidirectional = self.read_lstm_bidirectional(content, network)
         network.rnn_cell = self.read_rnn_cell(content, network)
+        network.attn_dim = self.read_attn_dim(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
+        if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
+            error("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
         network.input_shape = self.read_field(content, "input_shape", listify=True)
         network.input_fusion = self.read_field(content, "input_fusion", validate=defs.fusion_method)
+        if network.input_fusion == defs.fusion_method.attn:
+            error("input_fusion: attn is a fusion of the recurrent classifier (lstm_params), not an input fusion")
         network.train_from = self.read_train_from(content, network)
         unread = [x for x in content if x not in self.pipeline_field_cache]
         if unread:
@@ -224,6 +229,22 @@ class Settings:
         state_input = lstm and len(network.input) > 1 and self.read_field(content, "input_fusion") in (None, "None")
         try:
             return check_rnn_cell(v, network.classifier, network.lstm_params[0] if lstm else 1, network.lstm_bidirectional, state_input)
+        except VltfError as ex:
+            error(str(ex))
+
+    def read_attn_dim(self, content, network):
+        """`attn_dim: <A>` beside lstm_params (this project's extension of the pipeline schema): the width of the scorer of fusion attn,
+        learned attention pooling over the recurrent outputs (engine.attn_specs).  Absent / None = the recurrent output width.  Refused
+        without fusion attn and unless an integer in 1..1024; fusion attn itself is refused without the recurrent classifier
+        (engine.check_attn).  -> the width, or None for every other fusion."""
+        v = self.read_field(content, "attn_dim")
+        lstm = network.classifier == defs.classifier.lstm
+        from .engine import VltfError, check_attn
+        try:
+            if not lstm:
+                return check_attn(None, v, network.classifier)
+            H = network.lstm_params[0] * (2 if network.lstm_bidirectional else 1)
+            return check_attn(network.lstm_params[2], v, network.classifier, H)
         except VltfError as ex:
             error(str(ex))
 
@@ -521,6 +542,8 @@ class Settings:
                 v.logits_save_interval = int(obj["logits_save_interval"])
                 cf = parse_seq(obj["clip_fusion"])
                 v.clip_fusion_type, v.clip_fusion_method = defs.check(cf[0], defs.fusion_type), defs.check(cf[1], defs.fusion_method)
+                if v.clip_fusion_method == defs.fusion_method.attn:
+                    error("val.clip_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a fusion of a video's clips")
                 # evaluate the averaged weights a training run with train.ema_decay stored beside its weights: absent / None = the weights
                 ue = obj.get("use_ema") if obj.get("use_ema") not in (None, "None") else False
                 if not isinstance(ue, bool):
