@@ -556,6 +556,26 @@ int vl_softmax_xent_mix(const float* logits, const int32_t* labels, float* dlogi
 int vl_softmax_xent_wf(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
                        float grad_scale, const int32_t* seq_len, int T, int rows_per_clip, float smoothing, int top_k, float lam,
                        const float* lam_dev, const float* class_weights, float gamma, vl_stream_t stream);
+/* The multi-label loss: independent sigmoids per class on multi-hot labels (0 / 1 per class, any number of ones, none
+ * included), one launch in the form of the softmax ones.  Per element, z the logit, y the label, yp the partner row's label as in
+ * vl_softmax_xent_mix, q = pos_weights[c] (float[classes] on the device, read when the kernel runs; NULL = ones):
+ *     t = lam y + (1 - lam) yp  (lam 1 or a row that is its own partner: y exactly),  then  t = t (1 - smoothing) + smoothing / 2
+ *     log p = -(max(-z, 0) + sp),  log(1 - p) = -(max(z, 0) + sp),  sp = log1p(exp(-|z|))
+ *   gamma == 0:  l = -(q t log p + (1 - t) log(1 - p))             (tf.nn.weighted_cross_entropy_with_logits; q = 1: torch's
+ *                dl/dz = p (q t + 1 - t) - q t                      BCEWithLogitsLoss, with pos_weight = q otherwise)
+ *   gamma > 0:   l = q t (1 - p)^g (-log p) + (1 - t) p^g (-log(1 - p))        (Lin et al. 2017, the sigmoid form)
+ *                dl/dz = q t (1 - p)^g (g p log p - (1 - p)) + (1 - t) p^g (p - g (1 - p) log(1 - p)),  finite at any z and gamma
+ * The row loss is the MEAN over the classes and dlogits = dl/dz * grad_scale / classes: with the caller's grad_scale = 1 / live rows
+ * the summed loss over the rows is the element mean of Keras / torch / tf.losses, and the gradients are `classes` times smaller than
+ * a softmax row's.  stats float[3] += {row losses, hit@1 rows (the first arg-max of the logits is a class with y > 0, the row's OWN
+ * labels), exact-match rows ((z_c > 0) == (y_c > 0) for every class; z == 0 predicts negative; a row without labels is never a hit
+ * and is exact iff no logit is positive)}, in xent_sum_kernel's fixed order; rows float[3*batch] or NULL (one workgroup walks the
+ * batch); no atomics, bitwise reproducible.  seq_len / T: the dead-row contract of vl_softmax_xent_ls (not read, nothing added,
+ * dlogits row zeros); lengths together with rows_per_clip > 1 or a lambda are refused.  dlogits may be NULL.  smoothing in [0, 1),
+ * lam in [0, 1] unless lam_dev is given, gamma finite and >= 0. */
+int vl_sigmoid_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
+                    float grad_scale, const int32_t* seq_len, int T, int rows_per_clip, float smoothing, float lam, const float* lam_dev,
+                    const float* pos_weights, float gamma, vl_stream_t stream);
 
 /* ---- CutMix / VideoMix (Yun et al. 2019, 2020): one box swapped between clip i and clip clips - 1 - i ---------------
  * The box is {t0, t1, y0, y1, x0, x1}, half-open, in frames of the clip and pixels of the out_h x out_w frame conv1 sees; all channels

@@ -106,6 +106,7 @@ SIGNATURES = {
     "vl_mixup_pairs": (i32, [p, i32, i32, i64, f32, p, p]),
     "vl_softmax_xent_mix": (i32, [p, p, p, p, p, i32, i32, f32, i32, f32, i32, f32, p, p]),
     "vl_softmax_xent_wf": (i32, [p, p, p, p, p, i32, i32, f32, p, i32, i32, f32, i32, f32, p, p, f32, p]),
+    "vl_sigmoid_xent": (i32, [p, p, p, p, p, i32, i32, f32, p, i32, i32, f32, f32, p, p, f32, p]),
     "vl_cutmix_pairs": (i32, [p, i32, i32, i32, i32, i32, i32, p, p, p]),
     "vl_cutmix_pairs_s2d": (i32, [p, p, i32, i32, p, p, p]),
     "vl_erase_boxes": (i32, [p, i32, i32, i32, i32, i32, i32, p, i32, f32, p]),

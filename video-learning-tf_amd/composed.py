@@ -18,7 +18,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 from ._ffi import VltfError
-from .engine import NetConfig
+from .engine import NetConfig, check_label_type
 from .graph import DatasetInfo, GraphEngine, PipelineSpec, init_params_for, model_specs
 
 
@@ -85,6 +85,9 @@ class ComposedEngine(GraphEngine):
                             "an LSTM (use LRCNEngine, or GraphEngine with PipelineSpec(rnn_cell=\"gru\") for a pipeline without a state "
                             "input)" % (getattr(enc_cfg, "rnn_cell", "lstm") if getattr(enc_cfg, "rnn_cell", "lstm") != "lstm"
                                         else getattr(head, "rnn_cell", "lstm")))
+        if check_label_type(getattr(enc_cfg, "label_type", None)) != "single":
+            raise VltfError("label_type multiple is not built for the two-pipeline model: its word-level loss ranks one word per step "
+                            "(use LRCNEngine, or GraphEngine(label_type=\"multiple\"))")
         self.h = head
         pipes, datasets = two_pipelines(enc_cfg, head, max_clips, scopes)
         super().__init__(pipes, datasets, head.num_classes, device, training, dp, optimizer=enc_cfg.optimizer,

@@ -2241,6 +2241,171 @@ extern "C" int vl_softmax_xent_wf(const float* logits, const int32_t* labels, fl
     return mix ? xent_launch<true, true, true>(a, stream) : xent_launch<true, false, true>(a, stream);
 }
 
+// ---- sigmoid cross-entropy for multi-label rows (vl_sigmoid_xent): independent sigmoids per class ----------------------
+// The other loss family, beside the softmax one above and in its form: one wave per row, a per-row workspace summed in a fixed order by
+// xent_sum_kernel<true> (three columns), a one-workgroup form without a workspace, no atomics, bitwise reproducible.  The classes of a row
+// do not couple, so ONE lane-strided pass does everything: the first arg-max of the logits, the loss, the gradient and the exact-match test.
+// Per element, z the logit, y the 0/1 label, yp the partner row's (MIX), q = cw[c] (NULL: 1):
+//     t  = mix_elem(y, yp, lam)               (lam == 1 or a row that is its own partner: y exactly)
+//     t  = t (1 - eps) + eps / 2              (tf.losses.sigmoid_cross_entropy's smoothing; eps == 0: t exactly)
+//     e  = exp(-|z|),  sp = log1p(e),  -log p = max(-z, 0) + sp,  -log(1 - p) = max(z, 0) + sp
+//     p and 1 - p are 1 / (1 + e) and e / (1 + e), in the order the sign of z says: neither is formed by a subtraction from 1
+//   gamma == 0 (uniform over the launch, no exp of a power):
+//     l = q t (-log p) + (1 - t) (-log(1 - p));   dl/dz = p (q t + 1 - t) - q t, summed as (1 - t) p - q t (1 - p)
+//   gamma > 0 (Lin et al. 2017 in its sigmoid form, separable in the two terms, so soft labels are well defined):
+//     l = q t (1 - p)^g (-log p) + (1 - t) p^g (-log(1 - p)),   (1 - p)^g = exp(g log(1 - p)),  p^g = exp(g log p)
+//     dl/dz = q t (1 - p)^g (g p log p - (1 - p)) + (1 - t) p^g (p - g (1 - p) log(1 - p))
+//   The limits relied on.  At z = +120: e = 0, sp = 0, log p = -0, p = 1, 1 - p = 0, log(1 - p) = -120: (1 - p)^g = exp(-120 g) is
+//   finite (0 for a large g), g p log p = 0 and g (1 - p) log(1 - p) = g 0 (-120) = 0 -- no division and no log of 0 anywhere, so every
+//   term is a product of finite factors; z = -120 is the mirror image.  A power that has underflowed to 0 drops its whole term
+//   (x^g g log x -> 0: the power falls faster than g grows), so a gamma near float's range cannot pair 0 with inf.
+// Row loss = (1 / C) sum_c l_c and dz = dl/dz * gscale / C: the logged loss is the element mean of Keras / torch / tf.losses, and the
+// gradients are C times smaller than a softmax row's under the same gscale.
+// hit: the first arg-max of the logits is a class with y_c > 0 (the row's OWN labels); exact: (z_c > 0) == (y_c > 0) for every class
+// (z == 0 predicts negative; a row without labels is never a hit and is exact iff no logit is positive).
+template <bool MIX>
+__device__ __forceinline__ void sxent_row(const float* __restrict__ z, const int32_t* __restrict__ y, const int32_t* __restrict__ yp,
+                                          float* __restrict__ dz, int C, float gs, float eps, float lam, const float* __restrict__ cw,
+                                          float gamma, int lane, float& loss, float& hit, float& exact) {
+    const bool focal = gamma != 0.f;                  // (uniform over the launch)
+    const float on = 1.0f - eps, off = 0.5f * eps;
+    const int32_t* yq = yp ? yp : y;                  // (no branch in the loop: see xent_row)
+    const float lam_r = yp ? lam : 1.0f, oml = 1.0f - lam_r;
+    float mx = -INFINITY, l = 0.f;
+    int am = 0x7fffffff, bad = 0;
+    for (int c = lane; c < C; c += 64) {
+        const float v = z[c];
+        const int yv = y[c];
+        float t = (float)yv;
+        if constexpr (MIX) t = mix_elem(t, (float)yq[c], lam_r, oml);
+        t = __fmaf_rn(t, on, off);                    // (one rounding, spelled out: the same bits with and without MIX; eps == 0: t)
+        if (v > mx) {
+            mx = v;
+            am = c;
+        }
+        bad += ((v > 0.f) != (yv > 0)) ? 1 : 0;
+        const float e = expf(-fabsf(v)), sp = log1pf(e), r = 1.0f / (1.0f + e), er = e * r;
+        const float p = v >= 0.f ? r : er, np = v >= 0.f ? er : r;                  // p, 1 - p
+        const float nlp = fmaxf(-v, 0.f) + sp, nlq = fmaxf(v, 0.f) + sp;            // -log p, -log(1 - p)
+        const float qt = (cw ? cw[c] : 1.0f) * t, ut = 1.0f - t;
+        float g;
+        if (!focal) {
+            l += qt * nlp + ut * nlq;
+            g = ut * p - qt * np;
+        } else {
+            const float m1 = expf(-gamma * nlq), m0 = expf(-gamma * nlp);           // (1 - p)^g, p^g
+            l += qt * m1 * nlp + ut * m0 * nlq;
+            const float g1 = m1 > 0.f ? m1 * (-gamma * p * nlp - np) : 0.f;
+            const float g0 = m0 > 0.f ? m0 * (p + gamma * np * nlq) : 0.f;
+            g = qt * g1 + ut * g0;
+        }
+        if (dz) dz[c] = g * gs;
+    }
+    const float gmx = wave_max(mx);
+    int cand = (mx == gmx) ? am : 0x7fffffff;         // first index attaining the maximum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    loss = wave_sum(l) / (float)C;
+    hit = (cand < C && y[cand] > 0) ? 1.f : 0.f;      // (cand < C unless no logit compares above -inf: never index past the row)
+    exact = bad == 0 ? 1.f : 0.f;
+}
+
+// The two kernels, as xent_kernel / xent_rows_kernel: seq_len, T: !MIX only; rpc, lam_arg, lam_dev: MIX only; gs = grad_scale / C.
+template <bool MIX>
+__global__ void sxent_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                             float* __restrict__ stats, int batch, int C, float gs, const int32_t* __restrict__ seq_len, int T, int rpc,
+                             float eps, float lam_arg, const float* __restrict__ lam_dev, const float* __restrict__ cw, float gamma) {
+    __shared__ float sl[4], sc[4], sk[4];
+    const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float loss_acc = 0.f, hit_acc = 0.f, exact_acc = 0.f;
+    for (int b = wv; b < batch; b += 4) {
+        float* dz = dlogits ? dlogits + (int64_t)b * C : nullptr;
+        float l, h, ex;
+        if (!MIX && xent_row_dead(seq_len, T, b)) {
+            xent_zero_row(dz, C, lane);
+            continue;
+        }
+        sxent_row<MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr, dz,
+                       C, gs, eps, lam, cw, gamma, lane, l, h, ex);
+        loss_acc += l;
+        hit_acc += h;
+        exact_acc += ex;
+    }
+    if (lane == 0) {
+        sl[wv] = loss_acc;
+        sc[wv] = hit_acc;
+        sk[wv] = exact_acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        stats[0] += sl[0] + sl[1] + sl[2] + sl[3];
+        stats[1] += sc[0] + sc[1] + sc[2] + sc[3];
+        stats[2] += sk[0] + sk[1] + sk[2] + sk[3];
+    }
+}
+
+template <bool MIX>
+__global__ void sxent_rows_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels, float* __restrict__ dlogits,
+                                  float* __restrict__ rows, int batch, int C, float gs, const int32_t* __restrict__ seq_len, int T, int rpc,
+                                  float eps, float lam_arg, const float* __restrict__ lam_dev, const float* __restrict__ cw, float gamma) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= batch) return;
+    const float lam = MIX && lam_dev ? *lam_dev : lam_arg;
+    float* dz = dlogits ? dlogits + (int64_t)b * C : nullptr;
+    float l = 0.f, h = 0.f, ex = 0.f;
+    if (!MIX && xent_row_dead(seq_len, T, b))
+        xent_zero_row(dz, C, lane);
+    else
+        sxent_row<MIX>(logits + (int64_t)b * C, labels + (int64_t)b * C, MIX ? mix_partner_labels(labels, b, batch, rpc, C) : nullptr, dz,
+                       C, gs, eps, lam, cw, gamma, lane, l, h, ex);
+    if (lane == 0) {
+        rows[b] = l;
+        rows[batch + b] = h;
+        rows[2 * (int64_t)batch + b] = ex;
+    }
+}
+
+template <bool MIX>
+static int sxent_launch(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch, int classes,
+                        float gs, const int32_t* seq_len, int T, int rows_per_clip, float smoothing, float lam, const float* lam_dev,
+                        const float* pos_weights, float gamma, vl_stream_t stream) {
+    if (!rows) {
+        hipLaunchKernelGGL((sxent_kernel<MIX>), dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, stats, batch, classes,
+                           gs, seq_len, T, rows_per_clip, smoothing, lam, lam_dev, pos_weights, gamma);
+        VL_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL((sxent_rows_kernel<MIX>), dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, labels, dlogits, rows,
+                       batch, classes, gs, seq_len, T, rows_per_clip, smoothing, lam, lam_dev, pos_weights, gamma);
+    VL_LAUNCH_CHECK();
+    hipLaunchKernelGGL((xent_sum_kernel<true>), dim3(1), dim3(256), 0, (hipStream_t)stream, rows, stats, batch, 1);    // (1: all three columns)
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_sigmoid_xent(const float* logits, const int32_t* labels, float* dlogits, float* stats, float* rows, int batch,
+                               int classes, float grad_scale, const int32_t* seq_len, int T, int rows_per_clip, float smoothing, float lam,
+                               const float* lam_dev, const float* pos_weights, float gamma, vl_stream_t stream) {
+    VL_CHECK(logits && labels && stats && batch > 0 && classes > 0, "vl_sigmoid_xent: bad argument");
+    VL_CHECK(!seq_len || (T > 0 && batch % T == 0), "vl_sigmoid_xent: batch (%d rows) is not whole sequences of T = %d", batch, T);
+    VL_CHECK(rows_per_clip > 0 && batch % rows_per_clip == 0, "vl_sigmoid_xent: batch (%d rows) is not whole clips of %d rows", batch,
+             rows_per_clip);
+    VL_CHECK(smoothing >= 0.f && smoothing < 1.f, "vl_sigmoid_xent: smoothing must lie in [0, 1), got %g", (double)smoothing);
+    VL_CHECK(lam_dev || (lam >= 0.f && lam <= 1.f), "vl_sigmoid_xent: lam must lie in [0, 1], got %g", (double)lam);
+    VL_CHECK(gamma >= 0.f && gamma <= 3.0e38f, "vl_sigmoid_xent: gamma must be finite and >= 0, got %g", (double)gamma);
+    const bool mix = rows_per_clip > 1 || lam_dev || lam != 1.f;
+    VL_CHECK(!(mix && seq_len), "vl_sigmoid_xent: seq_len cannot be combined with mixed labels (rows_per_clip > 1 or a lambda)");
+    const float gs = grad_scale / (float)classes;
+    if (!seq_len) T = 1;
+    return mix ? sxent_launch<true>(logits, labels, dlogits, stats, rows, batch, classes, gs, nullptr, 1, rows_per_clip, smoothing, lam,
+                                    lam_dev, pos_weights, gamma, stream)
+               : sxent_launch<false>(logits, labels, dlogits, stats, rows, batch, classes, gs, seq_len, T, 1, smoothing, 1.f, nullptr,
+                                     pos_weights, gamma, stream);
+}
+
 // ---- mixup (Zhang et al. 2018): the paired in-place blend of the clips (the loss on the mixed labels: xent_row<., MIX>) --
 // Clip i is paired with clip clips - 1 - i.  lam comes from the launch arguments or, when lam_dev is given, from the device when the
 // kernel runs (a captured step replays with the lambda the host wrote before the replay).  Every loop of both dtypes blends with

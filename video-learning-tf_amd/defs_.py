@@ -76,6 +76,9 @@ class defs:
     class periodicity:
         interval, drops = "interval", "drops"
 
+    class label_type:
+        single, multiple = "single", "multiple"      # multiple: multi-hot label rows under the sigmoid loss
+
     class names:
         global_step, latest_savefile = "global_step", "latest"
 

@@ -92,6 +92,7 @@ class NetConfig:
     erase_mode: Optional[str] = None            # train.erase_mode: zero | clip | pixel, the fill; None = zero
     erase_std: Optional[float] = None           # train.erase_std: the standard deviation of a noise fill; None = 57.63
     erase_seed: int = 0                         # train.erase_seed: the key of the draws (erase_row)
+    label_type: str = "single"                  # network.label_type: single (softmax loss) | multiple (sigmoid loss on multi-hot rows)
 
     def encode_dim(self):
         return FC_DIM if self.frame_encoding_layer in ("fc6", "fc7") else self.num_classes
@@ -521,6 +522,19 @@ def check_focal_gamma(focal_gamma):
     if not (math.isfinite(g) and 0.0 <= g <= 3.0e38):
         raise VltfError("focal_gamma must be a finite number >= 0 (0 / None = off), got %r" % (focal_gamma,))
     return g
+
+
+LABEL_TYPES = ("single", "multiple")
+
+
+def check_label_type(label_type):
+    """network.label_type as "single" (one class per row: the softmax loss launches) or "multiple" (multi-hot rows: independent
+    sigmoids per class, ops.sigmoid_xent).  None reads as "single".  Refused: anything else, other spellings included."""
+    if label_type is None:
+        return "single"
+    if not isinstance(label_type, str) or label_type not in LABEL_TYPES:
+        raise VltfError("label_type must be one of %s (None = single), got %r" % (", ".join(LABEL_TYPES), label_type))
+    return label_type
 
 
 def check_top_k(top_k):
@@ -1433,7 +1447,7 @@ class LRCNEngine:
         self.rows_out = self.logits.shape[0]
         if training:
             self.dlogits = buf(*self.logits.shape)
-        self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out, cfg.class_weights, cfg.focal_gamma)
+        self._loss_setup(cfg.label_smoothing, cfg.top_k, self.rows_out, cfg.class_weights, cfg.focal_gamma, label_type=cfg.label_type)
         self._mix_setup(cfg.mixup_alpha, cfg.mixup_seed, self.rows_out)
         self._erase_setup()
         self.ss = torch.zeros(1, device=dev)
@@ -1626,12 +1640,20 @@ class LRCNEngine:
         return None if self._stats_last is None else self._stats_last["tensor_stats"]
 
     # ---- label smoothing / top-k accuracy (label_smoothing, top_k; setup and fetch shared with GraphEngine) -------------------------------------
-    def _loss_setup(self, label_smoothing, top_k, rows, class_weights=None, focal_gamma=0.0, num_classes=None):
+    def _loss_setup(self, label_smoothing, top_k, rows, class_weights=None, focal_gamma=0.0, num_classes=None, label_type="single"):
         """All off (or an engine that does not train: validation computes no loss): the two sums and the 2 * rows workspace of
         ops.softmax_xent, as ever.  Label smoothing or top-k on: three sums and 3 * rows, for ops.softmax_xent_ls.  Class weights or a
         focal gamma on (xent_wf): the same three columns, for ops.softmax_xent_wf, and the weights on the device
-        (class_weights_dev; None = ones), read by the launch as it runs."""
+        (class_weights_dev; None = ones), read by the launch as it runs.  label_type "multiple" (DESIGN 4.26): always three sums and
+        3 * rows, for ops.sigmoid_xent -- {loss, hit@1 rows, exact-match rows}; the smoothing, the focal gamma and the mixed labels go
+        to that launch, the class weights are its positive-term weights, and top_k is refused (a multi-hot row has no one label to
+        rank)."""
         self.label_smoothing, self.top_k = check_label_smoothing(label_smoothing), check_top_k(top_k)
+        self.label_type = check_label_type(label_type)
+        self.multilabel = self.label_type == "multiple"
+        if self.multilabel and self.top_k > 0:
+            raise VltfError("top_k = %d is refused with label_type multiple: a multi-hot row has no one label whose rank could be "
+                            "counted (accuracy is hit@1, subset_accuracy the exact match)" % self.top_k)
         self.class_weights = check_class_weights(class_weights, self.cfg.num_classes if num_classes is None else num_classes)
         self.focal_gamma = check_focal_gamma(focal_gamma)
         if not self.training:
@@ -1639,13 +1661,17 @@ class LRCNEngine:
         self.xent_ls = self.label_smoothing > 0.0 or self.top_k > 0
         self.xent_wf = self.class_weights is not None or self.focal_gamma > 0.0
         self.class_weights_dev = None if self.class_weights is None else torch.from_numpy(self.class_weights).to(self.dev)
-        cols = 3 if self.xent_ls or self.xent_wf else 2
+        cols = 3 if self.xent_ls or self.xent_wf or self.multilabel else 2
         self.stats = torch.zeros(cols, device=self.dev)
         self.loss_rows = torch.zeros(cols * rows, device=self.dev)      # per-row losses | hits (| top-k hits): the loss launch's workspace
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale):
         """The loss launch of a train step: stats += {loss sum, hits (, top-k hits)}, dlogits = (softmax - labels') * grad_scale."""
-        if self.xent_wf:                          # class weights / focal loss, on mixed labels when mixup or CutMix is on
+        if self.multilabel:                       # multi-hot rows: sigmoids per class; stats += {loss sum, hit@1 rows, exact-match rows}
+            ops.sigmoid_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.class_weights_dev,
+                             self.focal_gamma,
+                             **({} if self.mix_lam is None else dict(rows_per_clip=self.rows_out // self.B, lam=self.mix_lam)))
+        elif self.xent_wf:                        # class weights / focal loss, on mixed labels when mixup or CutMix is on
             ops.softmax_xent_wf(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k,
                                 self.class_weights_dev, self.focal_gamma,
                                 **({} if self.mix_lam is None else dict(rows_per_clip=self.rows_out // self.B, lam=self.mix_lam)))
@@ -1661,6 +1687,8 @@ class LRCNEngine:
         """_fetch: with top_k > 0 the result gains the top-k accuracy of the rows so far and the count behind it."""
         if getattr(self, "top_k", 0) > 0:
             out["topk_accuracy"], out["topk_correct"] = float(st[2]) / max(rows, 1), float(st[2])
+        if getattr(self, "multilabel", False):    # label_type multiple: `accuracy` is hit@1; the third sum counts the exact-match rows
+            out["subset_accuracy"], out["subset_correct"] = float(st[2]) / max(rows, 1), float(st[2])
         return out
 
     # ---- mixup (mixup_alpha, mixup_seed; DESIGN 4.18) and CutMix / VideoMix (cutmix_*; DESIGN 4.19) -----------------------------------
@@ -1689,7 +1717,7 @@ class LRCNEngine:
             self.cut_box_last = (0, 0, 0, 0, 0, 0)
             if self.mixup_alpha > 0.0:
                 self.blend_lam = torch.ones(1, device=self.dev)
-        if not (self.xent_ls or self.xent_wf):
+        if not (self.xent_ls or self.xent_wf or self.multilabel):
             self.stats = torch.zeros(3, device=self.dev)
             self.loss_rows = torch.zeros(3 * rows, device=self.dev)
 

@@ -43,7 +43,7 @@ from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
                      check_rnn_cell, gru_buffers, gru_names, gru_specs, attn_buffers, attn_names, attn_specs, check_attn,
                      check_label_smoothing,
-                     check_cutmix, check_erase, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
+                     check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
 
 
@@ -880,7 +880,8 @@ class GraphEngine:
                  optimizer="sgd", dropout_keep_prob=0.0, conv_math="f32", lr_mult=None, momentum=0.0, nesterov=False, weight_decay=0.0,
                  accumulate=1, fc_dropout_keep_prob=0.0, tensor_stats_interval=0, ema_decay=0.0, ema_warmup=False,
                  lars_eeta=0.0, lars_epsilon=0.0, label_smoothing=0.0, top_k=0,
-                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0, class_weights=None, focal_gamma=0.0, erase_prob=0.0):
+                 lamb=False, lamb_epsilon=None, mixup_alpha=0.0, cutmix_alpha=0.0, class_weights=None, focal_gamma=0.0, erase_prob=0.0,
+                 label_type="single"):
         """lr_mult: train.lr_mult, the learning-rate factor of the `modified` variables (engine.is_regular); a pipeline's train_from
         freezes the first layers of its tower (engine.tier_plan).  momentum, nesterov: tf.train.MomentumOptimizer's, optimizer sgd only
         (engine.check_momentum); 0 = plain SGD.  weight_decay: the L2 coefficient of every trained weight tensor of rank >= 2 of every
@@ -903,7 +904,9 @@ class GraphEngine:
         class sum of the loss and the focal loss's focusing parameter, in the loss launch of the last pipeline with its seq_len
         (engine.check_class_weights, engine.check_focal_gamma, LRCNEngine._loss_setup); a forward-only engine ignores
         them; None / 0 = off.  erase_prob: refused when > 0 -- random erasing draws one table per batch of ONE dcnn pipeline
-        (LRCNEngine); per-tower tables are a follow-up."""
+        (LRCNEngine); per-tower tables are a follow-up.  label_type: "single" | "multiple" (engine.check_label_type):
+        with multiple the loss launch of the last pipeline, with its seq_len, is ops.sigmoid_xent on multi-hot rows -- class_weights
+        are its positive-term weights, top_k is refused (LRCNEngine._loss_setup)."""
         if check_erase(erase_prob).prob > 0.0:
             raise VltfError("erase_prob = %s is refused by GraphEngine: random erasing keeps one box table for the clips of one dcnn "
                             "pipeline; per-tower tables are a follow-up (use a single-pipeline model: LRCNEngine, NetConfig.erase_prob)"
@@ -918,6 +921,7 @@ class GraphEngine:
                             % (mixup_alpha,))
         self._loss_opts = (check_label_smoothing(label_smoothing), check_top_k(top_k))
         self._loss_wf = (check_class_weights(class_weights, int(num_classes)), check_focal_gamma(focal_gamma))
+        self._label_type = check_label_type(label_type)
         self.fc_dropout_keep_prob = check_fc_dropout(fc_dropout_keep_prob)
         self.accumulate = check_accumulate(accumulate)
         self.micro, self._mi = MicroSequence(self.accumulate), None
@@ -1041,7 +1045,7 @@ class GraphEngine:
         self.gacc = torch.empty(total, device=dev) if self.accumulate > 1 and training else None   # LRCNEngine.__init__: the running sum
         self.ema = torch.zeros(total, device=dev) if self.ema_decay > 0.0 and training else None   # LRCNEngine.__init__: the shadow weights
         rows = self.last.max_rows
-        self._loss_setup(*self._loss_opts, rows, *self._loss_wf, num_classes=self.num_classes)
+        self._loss_setup(*self._loss_opts, rows, *self._loss_wf, num_classes=self.num_classes, label_type=self._label_type)
         self.ss = torch.zeros(1, device=dev)
         self.ss2 = None
         if self.decay is not None:                # L2 weight decay (LRCNEngine.__init__): {sum g'^2, regulariser}, self.ss its first word
@@ -1118,7 +1122,10 @@ class GraphEngine:
 
     def _xent_launch(self, logits, onehot, dlogits, grad_scale, **lengths):
         """LRCNEngine._xent_launch through this module's ops (lengths: seq_len and T of a loss masked by seq_len, or nothing)."""
-        if self.xent_wf:
+        if self.multilabel:
+            ops.sigmoid_xent(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.class_weights_dev,
+                             self.focal_gamma, **lengths)
+        elif self.xent_wf:
             ops.softmax_xent_wf(logits, onehot, dlogits, self.stats, grad_scale, self.loss_rows, self.label_smoothing, self.top_k,
                                 self.class_weights_dev, self.focal_gamma, **lengths)
         elif self.xent_ls:

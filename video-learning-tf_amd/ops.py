@@ -984,6 +984,25 @@ def softmax_xent_wf(logits, labels, dlogits, stats, grad_scale, rows, smoothing,
               int(rows_per_clip), float(smoothing), int(top_k), lam_host, lam_dev, _p(class_weights), float(gamma), stream())
 
 
+def sigmoid_xent(logits, labels, dlogits, stats, grad_scale, rows, smoothing=0.0, pos_weights=None, gamma=0.0, seq_len=None, T=None,
+                 rows_per_clip=1, lam=1.0):
+    """The multi-label loss launch (vl_sigmoid_xent): independent sigmoids per class on multi-hot int32 labels, the row loss the MEAN
+    over the classes, dlogits = dl/dz * grad_scale / classes.  smoothing: t' = t (1 - smoothing) + smoothing / 2, after the mixup
+    blend.  pos_weights: None (ones) or a float32 device tensor of `classes` elements, the weight of each class's positive term, read
+    when the kernel runs; gamma >= 0: the sigmoid focal loss.  seq_len / T as in softmax_xent_ls; rows_per_clip / lam as in
+    softmax_xent_mix (1 and 1.0: no partner row); the two do not combine.  stats: 3 floats (loss sum, hit@1 rows, exact-match rows);
+    rows: None or >= 3*batch floats."""
+    mixed = int(rows_per_clip) != 1 or torch.is_tensor(lam) or float(lam) != 1.0
+    b, c, sl, t = _xent_args("sigmoid_xent", 3, logits, labels, dlogits, stats, rows, seq_len, T, partner=mixed)
+    if pos_weights is not None:
+        _f32(pos_weights); _dense(pos_weights)
+        if pos_weights.numel() != c:
+            raise _ffi.VltfError("sigmoid_xent: pos_weights holds %d floats for %d classes" % (pos_weights.numel(), c))
+    lam_host, lam_dev = _lam(lam, "sigmoid_xent")
+    _ffi.call("vl_sigmoid_xent", _p(logits), _p(labels), _p(dlogits), _p(stats), _p(rows), b, c, grad_scale, _p(sl), t,
+              int(rows_per_clip), float(smoothing), lam_host, lam_dev, _p(pos_weights), float(gamma), stream())
+
+
 def sumsq(g, out, ws, accumulate=False):
     _f32(g, out, ws)
     if ws.numel() < 1024:

@@ -62,7 +62,7 @@ def pipeline_net_config(settings, p, dataset):
               ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
               label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
               lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0], mixup_seed=settings.get_mixup()[1],
-              class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma(),
+              class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma(), label_type=settings.label_type,
               **dict(zip(("cutmix_alpha", "cutmix_seed", "cutmix_mode", "cutmix_prob"), settings.get_cutmix())),
               **dict(zip(("erase_prob", "erase_scale", "erase_ratio", "erase_frames", "erase_mode", "erase_std", "erase_seed"),
                          settings.get_erase())))
@@ -231,6 +231,8 @@ def do_train(settings, train, feeder, engine):
                 reg += " gradient norm : %.8g, mean per variable : %.8g" % (train.last["grad_norm"], train.last["grads_norm_mean"])
             if "topk_accuracy" in train.last:        # train.top_k: of the batch (the update so far), global under data parallelism
                 reg += " top-%d accuracy : %2.5f" % (engine.top_k, train.last["topk_accuracy"])
+            if "subset_accuracy" in train.last:      # label_type multiple: the rows predicted exactly, beside the hit@1 `accuracy`
+                reg += " hit@1 : %2.5f subset accuracy : %2.5f" % (train.last["accuracy"], train.last["subset_accuracy"])
             info("Learning rate %2.8f, global step: %d, batch loss/nats : %2.5f / %2.3f %s" %
                  (learning_rate, settings.global_step, batch_loss, nats, reg))
             info("Dataset global step %d, epoch index %d, batch sizes %s, batch index train %d" %
@@ -305,7 +307,11 @@ def do_test(settings, val, feeder, engine, rank=0, world=1):
     if rank != 0:
         return None
     val.save_validation_logits_chunk(save_all=True)
-    accuracy = val.get_accuracy()
+    multilabel = getattr(val, "multilabel", False)
+    if multilabel:     # label_type multiple: mAP, F1 and subset accuracy over all items at once; `accuracy` is their hit@1
+        accuracy = val.report_multilabel(write=val.save_interval is not None)["hit1"]
+    else:
+        accuracy = val.get_accuracy()
     info("Validation run complete in [%s], accuracy: %2.5f" % (elapsed_str(tic), accuracy))
     if val.save_interval is not None:
         with open(os.path.join(settings.run_folder, "accuracy_" + settings.run_id), "w") as f:
@@ -382,7 +388,8 @@ def main(init_file, seed=0, device=None):
                              ema_warmup=settings.get_ema()[1], lars_eeta=settings.get_lars()[0], lars_epsilon=settings.get_lars()[1],
                              label_smoothing=settings.get_label_smoothing(), top_k=settings.get_top_k(), lamb=settings.get_lamb()[0],
                              lamb_epsilon=settings.get_lamb()[1], mixup_alpha=settings.get_mixup()[0],
-                             class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma())
+                             class_weights=settings.get_class_weights(), focal_gamma=settings.get_focal_gamma(),
+                             label_type=settings.label_type)
         for name in engine.skipped:
             warning("Pipeline [%s] does not feed the output pipeline [%s]: it is never evaluated and is not built." %
                     (name, settings.pipeline_names[-1]))

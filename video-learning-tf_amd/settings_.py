@@ -59,7 +59,27 @@ def balanced_class_weights(item_labels, num_classes):
     return [total / (num_classes * n) if n else 1.0 for n in counts], absent
 
 
+def balanced_pos_weights(item_labels, num_classes):
+    """`train: class_weights: balanced` under `network: label_type: multiple`: the positive-term weight q_c = (N - n_c) / n_c, N the
+    number of items of the list and n_c the number of items that carry class c (a label repeated inside one item counts once) -- the
+    negatives-to-positives ratio that torch documents for BCEWithLogitsLoss's pos_weight.  A class no item carries gets 1.0.
+    -> (weights, the absent classes)."""
+    counts, items = [0] * num_classes, 0
+    for labels in item_labels:
+        items += 1
+        for c in sorted(set(int(l) for l in labels)):
+            if not 0 <= c < num_classes:
+                error("train.class_weights: balanced: the item list holds the label %s, outside the %d classes" % (c, num_classes))
+            counts[c] += 1
+    if items == 0 or sum(counts) == 0:
+        error("train.class_weights: balanced: the training item list holds no label")
+    absent = [c for c, n in enumerate(counts) if n == 0]
+    return [(items - n) / n if n else 1.0 for n in counts], absent
+
+
 class Settings:
+    label_type = defs.label_type.single
+
     def __init__(self):
         self.run_id, self.resume_file, self.run_folder = "", None, None
         self.tensor_stats_interval = 0
@@ -327,6 +347,33 @@ class Settings:
         except VltfError as ex:
             error("train.focal_gamma: %s" % ex)
 
+    @staticmethod
+    def read_label_type(network):
+        """`network: label_type: defs.label_type.multiple` (the reference's name for the case; a plain `multiple` / `single` is read
+        too): absent / None = single.  multiple: multi-hot label rows under the sigmoid loss (engine.check_label_type)."""
+        from .engine import VltfError, check_label_type
+        v = network.get("label_type")
+        if v in (None, "None"):
+            return defs.label_type.single
+        if isinstance(v, str) and v.startswith("defs."):
+            return defs.check(v, defs.label_type)
+        try:
+            return check_label_type(v)
+        except VltfError as ex:
+            error("network.label_type: %s" % ex)
+
+    def check_multilabel_options(self):
+        """The options label_type multiple refuses: a top-k count (a multi-hot row has no one label to rank) and the per-class recall
+        (it files an item under one class); validation reports AP per class and mAP instead (Validation.get_multilabel)."""
+        if self.label_type != defs.label_type.multiple:
+            return
+        for where, s in (("train", self.train), ("val", self.val)):
+            if s is not None and s.top_k > 0:
+                error("%s.top_k: %d is refused with network.label_type multiple: a multi-hot row has no one label to rank" % (where, s.top_k))
+        if self.val is not None and self.val.per_class:
+            error("val.per_class is refused with network.label_type multiple: it files an item under one class; a multiple run writes "
+                  "ap_per_class_<run_id> and map_<run_id>")
+
     def resolve_balanced_weights(self):
         """After the datasets are read: `class_weights: balanced` becomes the numbers, from the main training dataset's item list."""
         if not self.train or self.train.class_weights != "balanced":
@@ -334,7 +381,8 @@ class Settings:
         main = [d for d in self.feeder.datasets.get(defs.phase.train, []) if d.tag == defs.dataset_tag.main]
         if not main:
             error("train.class_weights: balanced: there is no [%s] training dataset to count the labels of" % defs.dataset_tag.main)
-        weights, absent = balanced_class_weights(main[0].labels, self.num_classes)
+        balanced = balanced_pos_weights if self.label_type == defs.label_type.multiple else balanced_class_weights
+        weights, absent = balanced(main[0].labels, self.num_classes)
         if absent:
             warning("train.class_weights: balanced: no item of class(es) %s in [%s]: their weight is 1.0" % (absent, main[0].id))
         self.train.class_weights = weights
@@ -366,6 +414,7 @@ class Settings:
             self.pipelines[pname] = self.read_network(content)
             self.pipeline_names.append(pname)
         self.num_classes = int(config["network"]["num_classes"])
+        self.label_type = self.read_label_type(config["network"])
 
         for phase in self.phases:
             obj = config[phase]
@@ -556,6 +605,7 @@ class Settings:
                 if not isinstance(pc, bool):
                     error("val.per_class must be a boolean, got [%s]" % (pc,))
                 v.per_class = pc
+        self.check_multilabel_options()
 
         self.feeder = Feeder(defs.input_mode.video, self.phases, (self.train, self.val), self.save_freq_per_epoch, self.run_folder,
                              self.should_resume())

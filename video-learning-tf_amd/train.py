@@ -110,18 +110,25 @@ class TensorStatsLog:
 
 def dp_scalars(out):
     """The per-rank sums a data-parallel step adds over the ranks (dp.sum_scalars): loss sum, hits, rows -- and the top-k hits as a
-    fourth only when the engine counts them (train.top_k), so that a run without them exchanges the vector it always did."""
+    fourth only when the engine counts them (train.top_k), so that a run without them exchanges the vector it always did.  The
+    exact-match rows of a multi-label run (label_type multiple, which refuses top_k) travel the same way, after them."""
     v = [out["loss_sum"], out["correct"], float(out["rows"])]
     if "topk_correct" in out:
         v.append(out["topk_correct"])
+    if "subset_correct" in out:
+        v.append(out["subset_correct"])
     return v
 
 
 def dp_global(out, tot):
-    """out with loss / accuracy (/ topk_accuracy) of the GLOBAL batch, from the summed dp_scalars vector."""
+    """out with loss / accuracy (/ topk_accuracy / subset_accuracy) of the GLOBAL batch, from the summed dp_scalars vector."""
     g = dict(out, loss=float(tot[0] / max(tot[2], 1)), accuracy=float(tot[1] / max(tot[2], 1)))
+    i = 3
     if "topk_correct" in out:
-        g["topk_accuracy"] = float(tot[3] / max(tot[2], 1))
+        g["topk_accuracy"] = float(tot[i] / max(tot[2], 1))
+        i += 1
+    if "subset_correct" in out:
+        g["subset_accuracy"] = float(tot[i] / max(tot[2], 1))
     return g
 
 
@@ -153,10 +160,17 @@ class Train:
         if getattr(engine, "lamb", None) is not None:
             info("LAMB on the Adam update: epsilon %s, decoupled weight decay %s; %d weight tensors get a trust ratio |w| / |u|, the biases "
                  "learn with the plain rate and no decay" % (engine.lamb_epsilon, engine.weight_decay, len(engine.lamb["segs"])))
-        if getattr(engine, "xent_ls", False):
+        if getattr(engine, "xent_ls", False) and not getattr(engine, "multilabel", False):
             info("Loss: label smoothing %s (labels y (1 - eps) + eps / %d; the logged loss is the smoothed one), top-k accuracy %s" %
                  (engine.label_smoothing, settings.num_classes, ("k = %d" % engine.top_k) if engine.top_k > 0 else "off"))
-        if getattr(engine, "xent_wf", False):
+        if getattr(engine, "multilabel", False):
+            w = engine.class_weights
+            info("Loss: label_type multiple -- sigmoid cross-entropy per class, the row loss the mean over the %d classes (gradients are "
+                 "%d times smaller than a softmax row's); smoothing %s (labels t (1 - eps) + eps / 2), focal gamma %s, positive-term "
+                 "weights %s; accuracy is hit@1, subset accuracy the rows predicted exactly" %
+                 (settings.num_classes, settings.num_classes, engine.label_smoothing, engine.focal_gamma,
+                  "off" if w is None else "min %g (class %d), max %g (class %d)" % (w.min(), int(w.argmin()), w.max(), int(w.argmax()))))
+        elif getattr(engine, "xent_wf", False):
             w = engine.class_weights
             info("Loss: focal gamma %s, class weights %s; rows are normalised by their count, not by their weights, and the logged loss is "
                  "the weighted one" % (engine.focal_gamma, "off" if w is None else "min %g (class %d), max %g (class %d)" %

@@ -21,8 +21,61 @@ def topk_hits(logits, labels, k):
     return rank < int(k)
 
 
+def average_precision(scores, positives):
+    """sklearn's average_precision_score for one class: sum_n (R_n - R_{n-1}) P_n over the distinct score thresholds in descending
+    order -- the rows of a tied score enter together and form ONE threshold.  nan without a positive."""
+    scores, pos = np.asarray(scores, np.float64), np.asarray(positives) > 0
+    total = int(pos.sum())
+    if total == 0:
+        return float("nan")
+    order = np.argsort(-scores, kind="stable")
+    s, hit = scores[order], pos[order]
+    last = np.flatnonzero(np.append(s[1:] != s[:-1], True))      # the last row of every run of equal scores
+    tp = np.cumsum(hit)[last].astype(np.float64)
+    precision, recall = tp / (last + 1.0), tp / total
+    return float(np.sum(np.diff(np.append(0.0, recall)) * precision))
+
+
+def _f1(tp, fp, fn):
+    """2 tp / (2 tp + fp + fn); an empty denominator counts as 0."""
+    den = 2.0 * tp + fp + fn
+    return float(2.0 * tp / den) if den > 0 else 0.0
+
+
+def hit1_rows(logits, labels):
+    """Per row: the first arg-max of the logits is a class the row carries (the loss launch's hit@1; a row without labels never hits)."""
+    logits, labels = np.asarray(logits), np.asarray(labels)
+    return labels[np.arange(len(logits)), np.argmax(logits, axis=1)] > 0 if len(logits) else np.zeros(0, bool)
+
+
+def multilabel_metrics(logits, labels):
+    """The metrics of a multi-label run (network.label_type multiple) over ALL rows at once.  logits, labels: [N, C], a
+    label > 0 is a positive; the prediction of class c is z_c > 0 (p > 0.5; z == 0 predicts negative, as in the loss launch).
+    -> dict: ap [C] (average_precision per class, nan for a class without a positive), positives [C], map (the mean AP over the
+    classes with a positive; nan when there is none), f1_micro (tp, fp, fn summed over every class), f1_macro (the mean F1 over the
+    classes with a positive; an F1 with an empty denominator counts as 0), hit1 (hit1_rows' mean) and subset_accuracy (the rows
+    predicted exactly)."""
+    logits, pos = np.asarray(logits, np.float64), np.asarray(labels) > 0
+    if logits.ndim != 2 or logits.shape != pos.shape:
+        error("multilabel_metrics: logits %s and labels %s are not two [N, C] arrays of one shape" % (logits.shape, pos.shape))
+    n, classes = logits.shape
+    ap = np.array([average_precision(logits[:, c], pos[:, c]) for c in range(classes)], np.float64).reshape(classes)
+    positives = pos.sum(axis=0).astype(np.int64)
+    present = positives > 0
+    pred = logits > 0
+    tp, fp, fn = (pred & pos).sum(axis=0), (pred & ~pos).sum(axis=0), (~pred & pos).sum(axis=0)
+    f1 = np.array([_f1(tp[c], fp[c], fn[c]) for c in range(classes)], np.float64).reshape(classes)
+    return {"ap": ap, "positives": positives,
+            "map": float(np.mean(ap[present])) if present.any() else float("nan"),
+            "f1_micro": _f1(tp.sum(), fp.sum(), fn.sum()),
+            "f1_macro": float(np.mean(f1[present])) if present.any() else 0.0,
+            "hit1": float(np.mean(hit1_rows(logits, pos))) if n else 0.0,
+            "subset_accuracy": float(np.mean(np.all(pred == pos, axis=1))) if n else 0.0}
+
+
 class Validation:
     def __init__(self, settings):
+        self.multilabel = getattr(settings, "label_type", defs.label_type.single) == defs.label_type.multiple
         self.item_logits = np.zeros([0, settings.num_classes], np.float32)
         self.item_labels = np.zeros([0, settings.num_classes], np.float32)
         self.save_counter = 0
@@ -150,5 +203,37 @@ class Validation:
                     f.write("%d %d %d %s\n" % (c, hits[c], items[c], repr(float(recall[c]))))
         return mean_class
 
+    def get_multilabel(self):
+        """multilabel_metrics over the fused per-video logits of every saved chunk and the rows still in memory, CONCATENATED as
+        get_per_class walks them: AP ranks all items of a class against each other, so there is no mean of chunk means here."""
+        chunks = [self.load_validation_logits_chunk(c) for c in range(self.save_counter)]
+        if len(self.item_logits) > 0:
+            chunks.append(self.item_logits)
+        if not chunks:
+            error("multilabel validation: there are no validation items")
+        logits = np.concatenate(chunks)
+        return multilabel_metrics(logits, self.item_labels[:len(logits), :])
+
+    def report_multilabel(self, write=True):
+        """get_multilabel logged and, with write, stored beside the accuracy file: map_<run_id>, f1_micro_<run_id>, f1_macro_<run_id>,
+        subset_accuracy_<run_id> (a number each) and ap_per_class_<run_id>, one line `class positives ap` per class (a class
+        without a positive has ap nan).  -> the metrics."""
+        m = self.get_multilabel()
+        present = np.flatnonzero(m["positives"] > 0)
+        worst = present[np.argsort(m["ap"][present], kind="stable")[:3]]
+        info("Validation mAP: %2.5f over %d of %d classes with positives, micro-F1 %2.5f, macro-F1 %2.5f, hit@1 %2.5f, subset accuracy "
+             "%2.5f; lowest AP: %s" % (m["map"], len(present), len(m["ap"]), m["f1_micro"], m["f1_macro"], m["hit1"],
+                                        m["subset_accuracy"], ", ".join("class %d %.4f" % (c, m["ap"][c]) for c in worst)))
+        if write:
+            for name in ("map", "f1_micro", "f1_macro", "subset_accuracy"):
+                with open(os.path.join(self.run_folder, "%s_%s" % (name, self.run_id)), "w") as f:
+                    f.write(str(m[name]))
+            with open(os.path.join(self.run_folder, "ap_per_class_" + self.run_id), "w") as f:
+                for c in range(len(m["ap"])):
+                    f.write("%d %d %s\n" % (c, m["positives"][c], repr(float(m["ap"][c]))))
+        return m
+
     def get_chunk_accuracy(self, logits, labels):
+        if getattr(self, "multilabel", False):    # label_type multiple: hit@1 -- the arg-max of the logits is a class the item carries
+            return np.mean(hit1_rows(logits, labels))
         return np.mean(np.equal(np.argmax(logits, axis=1), np.argmax(labels, axis=1)))
