@@ -455,6 +455,31 @@ int vl_attn_pool_fwd(const float* u, const float* c, const float* h, const int32
 int vl_attn_pool_bwd(const float* dy, const float* h, const float* s, const float* alpha, const float* c, const int32_t* seq_len,
                      float* du, float* dh, float* dcp, int batch, int T, int HO, int A, vl_stream_t stream);
 
+/* ---- multi-head self-attention over the frames of a clip (rnn_cell `mhsa`; csrc/self_attention.hip) --------------------
+ * qkv [batch T][3H]: a row is Q(H) | K(H) | V(H) (the caller's projection x Wqkv + bqkv, vl_gemm); head h of `heads` owns columns
+ * h dh .. (h + 1) dh of each block, dh = H / heads.  Per clip b with L = min(max(seq_len[b], 0), T) live steps (seq_len NULL: L = T)
+ * and per head:
+ *   S[q][k] = (Q_q . K_k) / sqrt(dh) + pos[h][k - q + T - 1]      pos [heads][2T - 1], nullable: no position term
+ *   P[q]    = softmax over the live keys k < L of S[q]            (max-subtracted)
+ *   ctx_q   = sum_k P[q][k] V_k                                    head h writes its dh columns of ctx [batch T][H]
+ * fwd writes P [batch][heads][T][T] and ctx; a dead query row (q >= L) and a dead key column (k >= L) of P are zeros, a dead row of ctx
+ * is zeros.  bwd reads dctx [batch T][H], qkv and P as the forward stored it and writes
+ *   dV = P^T dctx,  dP = dctx V^T,  dS = P o (dP - rowsum(dP o P)),  dQ = dS K / sqrt(dh),  dK = dS^T Q / sqrt(dh)
+ * into dqkv [batch T][3H] (dead rows zeros) and, when dposp is not NULL, dposp [batch][heads][2T - 1][r] = sum over q, k with
+ * k - q + T - 1 = r of dS[q][k]: the per-clip partials of pos's gradient (vl_colsum them over the batch rows).
+ * DEAD-ROW CONTRACT: rows t >= L of qkv and dctx are never read (they may hold NaN).  One workgroup per (clip, head), no atomics,
+ * every sum in a fixed order: a clip's outputs depend on that clip's inputs alone, bit for bit, in any batch.
+ * Limits (an error names the one missed, nothing is launched): 1 <= T <= 64, H <= 1024, heads divides H, 8 <= dh <= 128.
+ * The launches take no host-varying scalar (1 / sqrt(dh) follows from the shape), so a captured step replays them as they are: there
+ * is no _st form. */
+int vl_mhsa_fwd(const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch, int T, int H, int heads,
+                vl_stream_t stream);
+int vl_mhsa_bwd(const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv, float* dposp, int batch, int T,
+                int H, int heads, vl_stream_t stream);
+/* y = x in the live rows t < L of x [batch T][W] and 0 in the dead ones (L as above; seq_len not NULL): the input of the first
+ * self-attention layer under seq_len, so that a padded frame's features reach no product (x^T dqkv reads every row). */
+int vl_live_rows(const float* x, const int32_t* seq_len, float* y, int batch, int T, int W, vl_stream_t stream);
+
 /* ---- imresize: scipy.misc.imresize(image, shape) of Dataset.process_image (dataset_.py:481-495: imgproc `raw_resize` to the raw
  * shape, `resize` to the network input size; also serialize.py:424-425) = PIL Image.resize(BILINEAR) on uint8, bit-exact:
  * Pillow's two-pass fixed-point resample (22-bit coefficients, uint8 intermediate, horizontal pass first; csrc/resize.hip).

@@ -55,6 +55,9 @@ class NetConfig:
     attn_dim: Optional[int] = None              # fusion attn: width A of the attention scorer (attn_specs); None = the recurrent output width
     lstm_bidirectional: bool = False            # every LSTM layer a forward and a backward cell, outputs concatenated (blstm_names); H <= 512
     rnn_cell: str = "lstm"                      # the recurrent cell of classifier lstm: "lstm" (BasicLSTMCell) | "gru" (reset-after, gru_names); H <= 512
+                                                # | "mhsa": every layer a multi-head self-attention layer over the fpc frames (mhsa_names)
+    sa_heads: Optional[int] = None              # rnn_cell mhsa: heads (divides lstm_hidden); None = 4 where 4 divides it, else 1
+    sa_positions: Optional[str] = None          # rnn_cell mhsa: "relative" (None: a learned bias per head and offset) | "none"
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
@@ -122,7 +125,7 @@ def check_blstm(hidden, what="lstm_bidirectional"):
                         % (what, BLSTM_MAX_HIDDEN, hidden))
 
 
-RNN_CELLS = ("lstm", "gru")
+RNN_CELLS = ("lstm", "gru", "mhsa")
 GRU_MAX_HIDDEN = ops.GRU_MAX_HIDDEN     # the GRU recurrence exists in the cluster form only (vltf.h: vl_gru_seq_fwd)
 
 
@@ -142,7 +145,16 @@ def gru_specs(layer, d, H, scope=""):
 def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state_input=False, what="rnn_cell"):
     """Refuses what the GRU classifier is not built for; -> the cell.  `classifier`: "lstm" where the pipeline has the recurrent classifier."""
     if cell not in RNN_CELLS:
-        raise VltfError("%s must be lstm or gru, got [%s]" % (what, cell))
+        raise VltfError("%s must be lstm or gru (or mhsa, the self-attention layer), got [%s]" % (what, cell))
+    if cell == "mhsa":
+        if classifier != "lstm":
+            raise VltfError("%s: mhsa is the temporal layer of classifier lstm, but the classifier is [%s]" % (what, classifier))
+        if bidirectional:
+            raise VltfError("%s: mhsa with lstm_bidirectional is not built (self-attention reads both directions already; the "
+                            "bidirectional launch runs LSTM cells)" % what)
+        if state_input:
+            raise VltfError("%s: mhsa takes no state input: the reference hands an LSTM ONE vector as c = h, and a self-attention layer "
+                            "has no state" % what)
     if cell == "gru":
         if classifier != "lstm":
             raise VltfError("%s: gru is the recurrent cell of classifier lstm, but the classifier is [%s]" % (what, classifier))
@@ -154,6 +166,67 @@ def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state
             raise VltfError("%s: the GRU recurrence runs in the cluster form only and needs a hidden size <= %d, got %d"
                             % (what, GRU_MAX_HIDDEN, hidden))
     return cell
+
+
+SA_POSITIONS = ("relative", "none")
+
+
+def mhsa_names(layer, scope="", positions="relative"):
+    """The variable names of one self-attention layer, in flat-buffer order: qkv_kernel (d, 3H), qkv_bias (3H,), out_kernel (H, H),
+    out_bias (H,) and, with relative positions, position_bias (heads, 2T - 1) -- rank 2 ON PURPOSE, as attention_pool/context is: it is
+    a weight, and decay_ranges, LARS and LAMB treat rank >= 2 as one; the two biases are exempt as every bias is."""
+    vs = ("qkv_kernel", "qkv_bias", "out_kernel", "out_bias") + (("position_bias",) if positions == "relative" else ())
+    return [scope + "self_attention/layer_%d/%s" % (layer, v) for v in vs]
+
+
+def mhsa_specs(layer, d, H, heads, T, scope="", positions="relative"):
+    """[(name, shape)] of mhsa_names(layer) for an input of width d, `heads` heads and T steps."""
+    return list(zip(mhsa_names(layer, scope, positions), ((d, 3 * H), (3 * H,), (H, H), (H,), (heads, 2 * T - 1))))
+
+
+def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="avg", what="rnn_cell"):
+    """-> (heads, positions) of rnn_cell mhsa, or None for every other cell.  Refused: sa_heads / sa_positions without mhsa; with it,
+    fusion state, and whatever misses a limit of the launches (vltf.h: vl_mhsa_fwd), before anything is allocated."""
+    given = lambda v: v not in (None, "None")
+    if cell != "mhsa":
+        for k, v in (("sa_heads", sa_heads), ("sa_positions", sa_positions)):
+            if given(v):
+                raise VltfError("%s is a key of rnn_cell mhsa, but the cell is [%s]" % (k, cell))
+        return None
+    H, T = int(hidden), int(T)
+    if fusion == "state":
+        raise VltfError("%s: mhsa with fusion state is not built: a self-attention layer has no final state (use last)" % what)
+    if not 1 <= T <= ops.MHSA_MAX_T:
+        raise VltfError("%s: mhsa needs 1 <= T <= %d steps per clip (a head's score tile lives in LDS), got %d" % (what, ops.MHSA_MAX_T, T))
+    if not 1 <= H <= ops.MHSA_MAX_HIDDEN:
+        raise VltfError("%s: mhsa needs a width H <= %d, got %d" % (what, ops.MHSA_MAX_HIDDEN, H))
+    if not given(sa_heads):
+        heads = 4 if H % 4 == 0 else 1
+    elif isinstance(sa_heads, bool) or not isinstance(sa_heads, (int, np.integer)) or int(sa_heads) < 1:
+        raise VltfError("sa_heads must be a positive integer, got [%s]" % (sa_heads,))
+    else:
+        heads = int(sa_heads)
+    if H % heads:
+        raise VltfError("%s: mhsa needs H %% heads == 0: sa_heads %d does not divide the width %d" % (what, heads, H))
+    if not ops.MHSA_MIN_HEAD <= H // heads <= ops.MHSA_MAX_HEAD:
+        raise VltfError("%s: mhsa needs a head width %d <= dh = H / heads <= %d, got %d / %d = %d"
+                        % (what, ops.MHSA_MIN_HEAD, ops.MHSA_MAX_HEAD, H, heads, H // heads))
+    positions = sa_positions if given(sa_positions) else "relative"
+    if positions not in SA_POSITIONS:
+        raise VltfError("sa_positions must be relative or none, got [%s]" % (positions,))
+    return heads, positions
+
+
+def mhsa_buffers(buf, rows, T, H, heads, positions, training):
+    """The device buffers of one self-attention layer: the projection qkv, the weights P [clips, heads, T, T], the heads' outputs ctx,
+    the layer's output hseq (and, training, dout, dctx, dqkv and the per-clip partials dposp of the position bias's gradient)."""
+    clips = rows // T
+    S = dict(qkv=buf(rows, 3 * H), P=buf(clips * heads, T * T), ctx=buf(rows, H), hseq=buf(rows, H))
+    if training:
+        S.update(dout=buf(rows, H), dctx=buf(rows, H), dqkv=buf(rows, 3 * H))
+        if positions == "relative":
+            S["dposp"] = buf(clips, heads * (2 * T - 1))
+    return S
 
 
 ATTN_MAX_DIM = 1024
@@ -236,7 +309,17 @@ def param_specs(cfg: NetConfig):
     A = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, (2 if cfg.lstm_bidirectional else 1) * cfg.lstm_hidden)
     if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "attn":
         raise VltfError("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
-    if cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
+    sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion)
+    if sa:
+        H = cfg.lstm_hidden
+        if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
+            specs += [("output_fc_w", (H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
+        specs += attn_specs(H, A) if A else []
+        d = dim
+        for l in range(cfg.lstm_layers):
+            specs += mhsa_specs(l, d, H, sa[0], cfg.fpc, positions=sa[1])
+            d = H
+    elif cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
         H = cfg.lstm_hidden
         if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
@@ -1375,7 +1458,10 @@ class LRCNEngine:
             for (gm, gn, gk) in ((N, FC_DIM, self.flat_dim), (N, self.flat_dim, FC_DIM), (self.flat_dim, FC_DIM, N), (N, 4 * H, D)):
                 ws_bytes = max(ws_bytes, ops.gemm_split_ws_bytes(gm, gn, gk))
         self.ws = torch.empty(max(ws_bytes, 64 << 20) // 4, device=dev)       # wgrad slabs / split-K slabs / GEMM operand images
-        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C))                     # colsum / bias / sumsq partials
+        # rnn_cell mhsa: (heads, positions) of the self-attention layers, else None (refusals: param_specs -> check_mhsa)
+        self.sa = check_mhsa(cfg.rnn_cell, H, T, cfg.sa_heads, cfg.sa_positions, cfg.fusion) if cfg.classifier == "lstm" else None
+        # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide)
+        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0))
         if training:
             self.wt = buf(max_w)
             self.df6 = buf(N, FC_DIM)
@@ -1394,6 +1480,7 @@ class LRCNEngine:
             self.lstm, self.blstm, self.gru = [], [], []                # per-layer buffers: unidirectional, bidirectional or GRU layers
             self.bi = bool(cfg.lstm_bidirectional)
             self.is_gru = cfg.rnn_cell == "gru"                         # (refusals: param_specs -> check_rnn_cell)
+            self.mhsa, self._mhsa_clips = [], 0                         # rnn_cell mhsa: self-attention layers (self.sa above)
             HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
                 raise VltfError("lstm_bidirectional: this device has too few compute units to hold both directions of hidden size %d in "
@@ -1404,6 +1491,9 @@ class LRCNEngine:
                     continue
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, N, H, training))
+                    continue
+                if self.sa:
+                    self.mhsa.append(mhsa_buffers(buf, N, T, H, self.sa[0], self.sa[1], training))
                     continue
                 S = dict(gx=buf(N, 4 * H), act=buf(N, 4 * H), cseq=buf(N, H), hseq=buf(N, H), hprev=buf(N, H))
                 if training:
@@ -2048,6 +2138,8 @@ class LRCNEngine:
         D, H4 = self.cfg.encode_dim(), 4 * self.cfg.lstm_hidden
         if getattr(self, "bi", False) or getattr(self, "is_gru", False):   # a bidirectional or GRU layer's dense products run on ops.gemm
             return False
+        if getattr(self, "sa", None):                                      # a self-attention layer's too
+            return False
         return (l == 0 and self._fc6_kc8(n) and os.environ.get("VLTF_LSTM_KC8", "1") != "0" and D % 8 == 0 and H4 % 8 == 0
                 and D * H4 <= self.k_w.numel() and n * max(D, H4) <= self.k_act.numel() and (not self.training or n * H4 <= self.k_d6.numel()))
 
@@ -2132,6 +2224,18 @@ class LRCNEngine:
                     self._tag_off += ops.gru_seq_tag_span(b, T, H)
                 ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb,
                                 ws=self.lstm_ws_graph if st else self.lstm_ws, **st)
+                xin, d = S["hseq"], H
+            for l, S in enumerate(self.mhsa):
+                # the qkv projection of all rows as the GRU's input projection is called (with the workspace: it follows conv_math),
+                # ONE launch for every (clip, head), then the output projection as attention_pool's (no workspace: fp32 always).  The
+                # launch takes no host-varying argument, so a captured step replays it as it is.
+                heads, positions = self.sa
+                names = mhsa_names(l, positions=positions)
+                Wqkv, bqkv, Wo, bo = (P[k] for k in names[:4])
+                ops.gemm(xin, Wqkv, S["qkv"], n, 3 * H, d, bias=bqkv, ws=self.ws)
+                ops.mhsa_fwd(S["qkv"], P[names[4]] if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads)
+                ops.gemm(S["ctx"], Wo, S["hseq"], n, H, H, bias=bo)
+                self._mhsa_clips = b
                 xin, d = S["hseq"], H
             for l, S in enumerate(self.lstm):
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
@@ -2225,6 +2329,14 @@ class LRCNEngine:
             raise VltfError("attention_weights: the model has no attention pooling (lstm_params fusion attn)")
         return self.attn["alpha"][:self._attn_clips]
 
+    def self_attention_weights(self, layer=-1):
+        """Device view [clips, heads, T, T] of the weights P the last forward gave (rnn_cell mhsa; the last layer's by default): row q
+        of a clip and head sums to 1 over the keys."""
+        if not getattr(self, "mhsa", None):
+            raise VltfError("self_attention_weights: the model has no self-attention layer (rnn_cell mhsa)")
+        T = self.cfg.fpc
+        return self.mhsa[layer]["P"][:self._mhsa_clips * self.sa[0]].view(self._mhsa_clips, self.sa[0], T, T)
+
     def forward_f32(self, frames_nhwc):
         n, b = self.feed_f32_nhwc(frames_nhwc)
         rows = self._forward(n, b, train=False)
@@ -2278,7 +2390,7 @@ class LRCNEngine:
             if self._dropout:
                 ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], cfg.dropout_keep_prob)
                 d = self.dfused
-            top = (self.blstm or self.gru or self.lstm)[-1]
+            top = (self.blstm or self.gru or self.mhsa or self.lstm)[-1]
             if self.per_step:
                 top["dout"][:r].copy_(d[:r])
             elif self.bi and self.lstm_fusion == "last":
@@ -2357,6 +2469,33 @@ class LRCNEngine:
                     self._relu_grad_behind(self.dfeat, relu_mask, n * D)
                 else:
                     ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], n, H, 3 * H, transb=True, ldb=3 * H, ws=self.ws)
+            for l in reversed(range(len(self.mhsa))):
+                S = self.mhsa[l]
+                heads, positions = self.sa
+                names = mhsa_names(l, positions=positions)
+                Wqkv, Wo = P[names[0]], P[names[2]]
+                din = D if l == 0 else H
+                xin = self.feat if l == 0 else self.mhsa[l - 1]["hseq"]
+                # through the output projection (no workspace, as attention_pool's products), then ONE launch for every (clip, head)
+                ops.gemm(S["dout"], Wo, S["dctx"], n, H, H, transb=True)
+                ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads)
+
+                def mhsa_grads(ws, sws, S=S, names=names, din=din, xin=xin, heads=heads):
+                    ops.gemm(S["ctx"], S["dout"], G[names[2]], H, H, n, transa=True)
+                    ops.colsum(S["dout"], G[names[3]], sws, n, H)
+                    ops.gemm(xin, S["dqkv"], G[names[0]], din, 3 * H, n, transa=True, ws=ws)
+                    ops.colsum(S["dqkv"], G[names[1]], sws, n, 3 * H)
+                    if "dposp" in S:                                                  # the B per-clip partials, summed in a fixed order
+                        ops.colsum(S["dposp"], G[names[4]], sws, b, heads * (2 * T - 1))
+                param_grads(mhsa_grads)
+                if l == 0 and not self.dcnn_trains:
+                    pass                                                              # frozen tower: nobody reads dfeat
+                elif l == 0:
+                    relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
+                    ops.gemm(S["dqkv"], Wqkv, self.dfeat, n, D, 3 * H, transb=True, ldb=3 * H, relu_mask=self._fused_mask(relu_mask), ws=self.ws)
+                    self._relu_grad_behind(self.dfeat, relu_mask, n * D)
+                else:
+                    ops.gemm(S["dqkv"], Wqkv, self.mhsa[l - 1]["dout"], n, H, 3 * H, transb=True, ldb=3 * H, ws=self.ws)
             for l in reversed(range(len(self.lstm))):
                 S = self.lstm[l]
                 pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l

@@ -27,7 +27,9 @@ Per-clip sequence lengths (tf.nn.dynamic_rnn's sequence_length, lstm.py:132-142;
 forward / train_step take seq_len = {pipeline name: host int32 lengths, one per clip of that `classifier: lstm` pipeline}.  Steps
 at or beyond a clip's length are dead: the recurrence of every layer carries the state through them and outputs zero, fusion
 state | last | avg read the live prefix only, and when the last pipeline's fusion is `reshape` the loss, its gradient and the
-accuracy are taken over the live rows (the reference's non_padding_index, dataset_.py:327-383).  include/vltf.h states the
+accuracy are taken over the live rows (the reference's non_padding_index, dataset_.py:327-383).  A self-attention layer (rnn_cell
+mhsa) attends over the live keys only and never reads a dead row of its projections; the first layer takes its input through
+ops.live_rows, so that a padded frame's features reach no product.  include/vltf.h states the
 contract of the kernels; without seq_len every call is what it was.
 
 The oracle of this class is oracle.lrcn_oracle.model_forward / model_backward (cross-checked against torch autograd)."""
@@ -41,7 +43,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, attn_buffers, attn_names, attn_specs, check_attn,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, attn_buffers, attn_names, attn_specs, check_attn,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -60,6 +62,9 @@ class PipelineSpec:
     attn_dim: Optional[int] = None                  # fusion attn: the width of the attention scorer (engine.attn_specs); None = the LSTM's output width
     lstm_bidirectional: bool = False                # classifier lstm: a forward and a backward cell per layer, outputs concatenated (2H wide)
     rnn_cell: str = "lstm"                          # classifier lstm: its cell, lstm | gru (engine.gru_names; no state input, H <= 512)
+                                                    # | mhsa: every layer a multi-head self-attention layer over the frames (engine.mhsa_names)
+    sa_heads: Optional[int] = None                  # rnn_cell mhsa: heads (divides the width); None = 4 where 4 divides it, else 1
+    sa_positions: Optional[str] = None              # rnn_cell mhsa: relative (None) | none
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
     train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
@@ -240,11 +245,16 @@ class PipeNode:
                                         (s.name, self.state_src.ref))
                 # fusion attn: learned attention pooling (engine.check_attn); None for every other fusion
                 self.attn_dim = check_attn(lf, s.attn_dim, "lstm", self.HO, what="pipeline [%s]: attn_dim" % s.name)
+                # rnn_cell mhsa: (heads, positions) of the self-attention layers (engine.check_mhsa); None for every other cell
+                self.sa = check_mhsa(s.rnn_cell, self.H, self.fpc, s.sa_heads, s.sa_positions, self.lfusion,
+                                     what="pipeline [%s]: rnn_cell" % s.name)
                 if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
             if s.lstm_bidirectional and self.cls != "lstm":
                 raise VltfError("pipeline [%s]: lstm_bidirectional needs classifier lstm, not [%s]" % (s.name, self.cls))
+            if self.cls != "lstm":
+                self.sa = check_mhsa(s.rnn_cell, sa_heads=s.sa_heads, sa_positions=s.sa_positions)      # the keys without the cell: refused
             self.late = ftype == "late" and self.fpc > 1 and fmethod != "reshape"
             if self.late:
                 if self.cls == "lstm" or rows % self.fpc:
@@ -279,6 +289,9 @@ class PipeNode:
                     continue
                 if self.is_gru:
                     specs += gru_specs(l, dims[l], H, sc)
+                    continue
+                if self.sa:
+                    specs += mhsa_specs(l, dims[l], H, self.sa[0], self.fpc, sc, self.sa[1])
                     continue
                 pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
                 specs += [(pre + "kernel", (dims[l] + H, 4 * H)), (pre + "bias", (4 * H,))]
@@ -344,7 +357,7 @@ class PipeNode:
         elif self.cls == "lstm":
             H, T, HO = self.H, self.fpc, self.HO
             B = R0 // T
-            self.lstm, self.blstm, self.gru = [], [], []                # per-layer buffers: unidirectional, bidirectional or GRU layers
+            self.lstm, self.blstm, self.gru, self.mhsa = [], [], [], []  # per-layer buffers: unidirectional, bidirectional, GRU or self-attention layers
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:
                 raise VltfError("pipeline [%s]: lstm_bidirectional: this device has too few compute units to hold both directions of "
                                 "hidden size %d in one launch" % (self.spec.name, H))
@@ -354,6 +367,9 @@ class PipeNode:
                     continue
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, R0, H, tr))
+                    continue
+                if self.sa:
+                    self.mhsa.append(mhsa_buffers(buf, R0, T, H, self.sa[0], self.sa[1], tr))
                     continue
                 S = dict(gx=buf(R0, 4 * H), act=buf(R0, 4 * H), cseq=buf(R0, H), hseq=buf(R0, H), hprev=buf(R0, H))
                 if tr:
@@ -383,6 +399,10 @@ class PipeNode:
                     self.dx_bw = buf(R0, max(self.feat_dim, HO))      # the backward direction's share of a layer's input gradient
                     self.dlast = buf(B, HO)                           # fusion last / state: the fused gradient with its backward half zeroed
             sw = max(sw, 64 * 4 * H, 64 * H, 64 * (self.attn_dim or 0))
+            if self.sa:
+                # under seq_len the first layer reads its input through ops.live_rows: a padded frame's features reach no product
+                self.xlive = buf(R0, self.feat_dim)
+                sw = max(sw, 64 * self.sa[0] * (2 * T - 1))
         if self.late:
             self.late_out = buf(self.max_rows, C)
             if tr:
@@ -601,6 +621,21 @@ class PipeNode:
             ops.gemm(xin, K, S["gx"], rows, 3 * H, d, bias=bk, ws=g.ws)
             ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb, ws=self.lstm_ws, **lk)
             xin, d = S["hseq"], H
+        for l, S in enumerate(self.mhsa):
+            # Dead-row contract: the launch never reads a dead row of qkv and writes zeros in the dead rows of ctx (so a dead row of a
+            # layer's output is out_bias, which nothing reads: the next layer's launch, the fusions and the masked loss skip it, and its
+            # gradient arrives as zeros).  The FIRST layer's input goes through ops.live_rows, because x^T dqkv reads every row of x.
+            heads, positions = self.sa
+            names = mhsa_names(l, sc, positions)
+            if l == 0 and lk:
+                ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
+                xin = self.xlive
+            if l == 0:
+                self._xsa = xin
+            ops.gemm(xin, P[names[0]], S["qkv"], rows, 3 * H, d, bias=P[names[1]], ws=g.ws)
+            ops.mhsa_fwd(S["qkv"], P[names[4]] if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads, **lk)
+            ops.gemm(S["ctx"], P[names[2]], S["hseq"], rows, H, H, bias=P[names[3]])
+            xin, d = S["hseq"], H
         for l, S in enumerate(self.lstm):
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]
@@ -696,7 +731,7 @@ class PipeNode:
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
             d = self.dfused
-        top = (self.blstm or self.gru or self.lstm)[-1]
+        top = (self.blstm or self.gru or self.mhsa or self.lstm)[-1]
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
         elif self.bi and last == "last":
@@ -751,6 +786,25 @@ class PipeNode:
                 ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
             elif self.wants_feat:
                 ops.gemm(S["dgx"], K, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
+        for l in reversed(range(len(self.mhsa))):
+            S = self.mhsa[l]
+            heads, positions = self.sa
+            names = mhsa_names(l, sc, positions)
+            Wqkv, Wo = P[names[0]], P[names[2]]
+            din = self.feat_dim if l == 0 else H
+            xin = self._xsa if l == 0 else self.mhsa[l - 1]["hseq"]
+            ops.gemm(S["dout"], Wo, S["dctx"], rows, H, H, transb=True)
+            ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._len_kw())
+            ops.gemm(S["ctx"], S["dout"], G[names[2]], H, H, rows, transa=True)
+            ops.colsum(S["dout"], G[names[3]], sw, rows, H)
+            ops.gemm(xin, S["dqkv"], G[names[0]], din, 3 * H, rows, transa=True, ws=g.ws)
+            ops.colsum(S["dqkv"], G[names[1]], sw, rows, 3 * H)
+            if "dposp" in S:
+                ops.colsum(S["dposp"], G[names[4]], sw, b, heads * (2 * T - 1))
+            if l > 0:
+                ops.gemm(S["dqkv"], Wqkv, self.mhsa[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
+            elif self.wants_feat:
+                ops.gemm(S["dqkv"], Wqkv, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
         for l in reversed(range(len(self.lstm))):
             S = self.lstm[l]
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l

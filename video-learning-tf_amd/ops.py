@@ -787,6 +787,60 @@ def attn_pool_bwd(dy, h, s, alpha, c, du, dh, dcp, batch, T, HO, A, seq_len=None
               stream())
 
 
+MHSA_MAX_T, MHSA_MAX_HIDDEN, MHSA_MIN_HEAD, MHSA_MAX_HEAD = 64, 1024, 8, 128       # vl_mhsa_*: vltf.h
+
+
+def _mhsa_sizes(who, batch, T, H, heads, **tensors):
+    """The limits of vl_mhsa_* (the C side's wording), then every tensor given holds at least what the launch reads or writes of it
+    (None passes: the C side refuses a null pointer it needs).  Raises before any launch."""
+    if min(batch, T, H, heads) <= 0:
+        raise _ffi.VltfError("%s: batch %d, T %d, H %d, heads %d must be positive" % (who, batch, T, H, heads))
+    if T > MHSA_MAX_T:
+        raise _ffi.VltfError("%s: T %d exceeds %d (a head's score tile lives in LDS, a key per lane)" % (who, T, MHSA_MAX_T))
+    if H > MHSA_MAX_HIDDEN:
+        raise _ffi.VltfError("%s: H %d exceeds %d" % (who, H, MHSA_MAX_HIDDEN))
+    if H % heads:
+        raise _ffi.VltfError("%s: heads %d does not divide H %d" % (who, heads, H))
+    if not MHSA_MIN_HEAD <= H // heads <= MHSA_MAX_HEAD:
+        raise _ffi.VltfError("%s: the head width H / heads = %d must lie in %d..%d" % (who, H // heads, MHSA_MIN_HEAD, MHSA_MAX_HEAD))
+    rows = batch * T
+    need = dict(qkv=rows * 3 * H, dqkv=rows * 3 * H, ctx=rows * H, dctx=rows * H, P=batch * heads * T * T, pos=heads * (2 * T - 1),
+                dposp=batch * heads * (2 * T - 1))
+    for k, t in tensors.items():
+        if t is not None and t.numel() < need[k]:
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), need[k]))
+
+
+def mhsa_fwd(qkv, pos, P, ctx, batch, T, H, heads, seq_len=None):
+    """Multi-head self-attention over time (vl_mhsa_fwd): per clip and head, P = softmax over the live keys of Q K^T / sqrt(H / heads) +
+    pos[h, k - q + T - 1], ctx = P V.  qkv [batch T, 3H] (Q | K | V); pos [heads, 2T - 1] or None; P [batch, heads, T, T];
+    ctx [batch T, H]; seq_len as gru_seq_fwd (dead rows of qkv are never read, dead rows / columns of P and dead rows of ctx are zeros)."""
+    _f32(qkv, pos, P, ctx)
+    _dense(qkv, pos, P, ctx)
+    _mhsa_sizes("mhsa_fwd", batch, T, H, heads, qkv=qkv, pos=pos, P=P, ctx=ctx)
+    _ffi.call("vl_mhsa_fwd", _p(qkv), _p(pos), None if seq_len is None else _p(_seq_len(seq_len, batch, "mhsa_fwd")), _p(P), _p(ctx),
+              batch, T, H, heads, stream())
+
+
+def mhsa_bwd(dctx, qkv, P, dqkv, dposp, batch, T, H, heads, seq_len=None):
+    """Its backward (vl_mhsa_bwd): dqkv [batch T, 3H] (dead rows zeros) and, unless None, the per-clip partials dposp
+    [batch, heads, 2T - 1] of pos's gradient (colsum them over the batch rows)."""
+    _f32(dctx, qkv, P, dqkv, dposp)
+    _dense(dctx, qkv, P, dqkv, dposp)
+    _mhsa_sizes("mhsa_bwd", batch, T, H, heads, dctx=dctx, qkv=qkv, P=P, dqkv=dqkv, dposp=dposp)
+    _ffi.call("vl_mhsa_bwd", _p(dctx), _p(qkv), _p(P), None if seq_len is None else _p(_seq_len(seq_len, batch, "mhsa_bwd")), _p(dqkv),
+              _p(dposp), batch, T, H, heads, stream())
+
+
+def live_rows(x, y, batch, T, W, seq_len):
+    """y = x in the live rows of x [batch T, W], zeros in the dead ones (vl_live_rows)."""
+    _f32(x, y)
+    _dense(x, y)
+    if min(batch, T, W) > 0 and min(x.numel(), y.numel()) < batch * T * W:
+        raise _ffi.VltfError("live_rows: x / y hold %d / %d elements, the launch needs %d" % (x.numel(), y.numel(), batch * T * W))
+    _ffi.call("vl_live_rows", _p(x), _p(_seq_len(seq_len, batch, "live_rows")), _p(y), batch, T, W, stream())
+
+
 def dropout_fwd(x, y, mask, keep, seed):
     _f32(x, y)
     _ffi.call("vl_dropout_fwd", _p(x), _p(y), _p(mask), x.numel(), keep, seed, stream())

@@ -204,6 +204,7 @@ class Settings:
         network.lstm_bidirectional = self.read_lstm_bidirectional(content, network)
         network.rnn_cell = self.read_rnn_cell(content, network)
         network.attn_dim = self.read_attn_dim(content, network)
+        network.sa_heads, network.sa_positions = self.read_self_attention(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
@@ -267,6 +268,22 @@ class Settings:
             return check_attn(network.lstm_params[2], v, network.classifier, H)
         except VltfError as ex:
             error(str(ex))
+
+    def read_self_attention(self, content, network):
+        """`sa_heads: <n>` and `sa_positions: relative | none` beside `rnn_cell: mhsa` (this project's extension of the pipeline schema):
+        the heads of the self-attention layers (must divide lstm_params' width; absent / None = 4 where 4 divides it, else 1) and their
+        learned relative-position bias (absent / None = relative).  Refused without rnn_cell mhsa; the widths the launches take are
+        checked against lstm_params here, the step count when the engine is built (engine.check_mhsa).  -> (heads, positions), or
+        (None, None) for every other cell."""
+        heads, positions = self.read_field(content, "sa_heads"), self.read_field(content, "sa_positions")
+        from .engine import VltfError, check_mhsa
+        lstm = network.classifier == defs.classifier.lstm
+        try:
+            sa = check_mhsa(network.rnn_cell, network.lstm_params[0] if lstm else 1, 1, heads, positions,
+                            network.lstm_params[2] if lstm else "avg")
+        except VltfError as ex:
+            error(str(ex))
+        return sa if sa else (None, None)
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
