@@ -480,6 +480,29 @@ int vl_mhsa_bwd(const float* dctx, const float* qkv, const float* P, const int32
  * self-attention layer under seq_len, so that a padded frame's features reach no product (x^T dqkv reads every row). */
 int vl_live_rows(const float* x, const int32_t* seq_len, float* y, int batch, int T, int W, vl_stream_t stream);
 
+/* ---- the encoder block around the self-attention layer (sa_block `encoder`; csrc/layer_norm.hip) -----------------------
+ * Rows are [clips T][W], 8 <= W <= 1024; L = min(max(seq_len[b], 0), T) live steps of clip b (seq_len NULL: L = T).
+ * vl_add_layer_norm_fwd: s = x + r (r NULL: s = x), stored to `sum` where it is not NULL; y = (s - mean) rstd gamma + beta with
+ *   mean = sum(s) / W, rstd = 1 / sqrt(sum((s - mean)^2) / W + eps) (the variance of the CENTRED values); stats [clips T][2] = mean,
+ *   rstd.  One launch is a layer norm, or a residual add with the norm that follows it.
+ * vl_layer_norm_bwd: from s and stats as the forward stored them, with x^ = (s - mean) rstd and dy^ = dy gamma:
+ *   dx = rstd (dy^ - mean(dy^) - x^ mean(dy^ x^)) + dres (dres NULL: no such term; it is the gradient that arrives on the residual
+ *   stream beside the norm), and dgb_partial [clips][2W] = the clip's sums over its live rows, t ascending, of dy x^ (columns 0 .. W:
+ *   gamma's gradient) and dy (columns W .. 2W: beta's); vl_colsum them over the clips.
+ * DEAD-ROW CONTRACT: rows t >= L of x, r, dy, s, stats and dres are never read (they may hold NaN); dead rows of y, sum, stats and dx
+ * are zeros, a clip of length 0 has a zero partial row.  One wave per row, no atomics, every sum in a fixed order: a clip's outputs
+ * depend on that clip's inputs alone, bit for bit, in any batch.  x, r, sum, y (dy, s, dres, dx) must not overlap one another.
+ * vl_gelu_fwd: f = u Phi(u), the exact (erf) form; vl_gelu_bwd: du = df (Phi(u) + u phi(u)); du may be df.  Finite for every finite u,
+ * the gradient 0 and 1 where erf saturates.
+ * A refused call (a null required pointer, a size outside the limits, eps not positive) launches nothing.  No host-varying argument
+ * but eps, a constant of the model: a captured step replays the launches as they are; there is no _st form. */
+int vl_add_layer_norm_fwd(const float* x, const float* r, float* sum, float* y, const float* gamma, const float* beta, float* stats,
+                          int clips, int T, int W, float eps, const int32_t* seq_len, vl_stream_t stream);
+int vl_layer_norm_bwd(const float* dy, const float* s, const float* gamma, const float* stats, const float* dres, float* dx,
+                      float* dgb_partial, int clips, int T, int W, const int32_t* seq_len, vl_stream_t stream);
+int vl_gelu_fwd(const float* u, float* f, int64_t count, vl_stream_t stream);
+int vl_gelu_bwd(const float* df, const float* u, float* du, int64_t count, vl_stream_t stream);
+
 /* ---- imresize: scipy.misc.imresize(image, shape) of Dataset.process_image (dataset_.py:481-495: imgproc `raw_resize` to the raw
  * shape, `resize` to the network input size; also serialize.py:424-425) = PIL Image.resize(BILINEAR) on uint8, bit-exact:
  * Pillow's two-pass fixed-point resample (22-bit coefficients, uint8 intermediate, horizontal pass first; csrc/resize.hip).

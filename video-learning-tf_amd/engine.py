@@ -58,6 +58,8 @@ class NetConfig:
                                                 # | "mhsa": every layer a multi-head self-attention layer over the fpc frames (mhsa_names)
     sa_heads: Optional[int] = None              # rnn_cell mhsa: heads (divides lstm_hidden); None = 4 where 4 divides it, else 1
     sa_positions: Optional[str] = None          # rnn_cell mhsa: "relative" (None: a learned bias per head and offset) | "none"
+    sa_block: Optional[str] = None              # rnn_cell mhsa: "plain" (None: the bare attention layer) | "encoder": the pre-LN encoder block (encoder_specs)
+    sa_ffn_dim: Optional[int] = None            # sa_block encoder: the feed-forward width F, 8..4096; None = 4 lstm_hidden
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
@@ -184,11 +186,40 @@ def mhsa_specs(layer, d, H, heads, T, scope="", positions="relative"):
     return list(zip(mhsa_names(layer, scope, positions), ((d, 3 * H), (3 * H,), (H, H), (H,), (heads, 2 * T - 1))))
 
 
-def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="avg", what="rnn_cell"):
-    """-> (heads, positions) of rnn_cell mhsa, or None for every other cell.  Refused: sa_heads / sa_positions without mhsa; with it,
-    fusion state, and whatever misses a limit of the launches (vltf.h: vl_mhsa_fwd), before anything is allocated."""
+SA_BLOCKS = ("plain", "encoder")
+SA_FFN_MIN, SA_FFN_MAX = 8, 4096
+
+
+def check_sa_block(cell, hidden=1, sa_block=None, sa_ffn_dim=None):
+    """-> the feed-forward width F of sa_block encoder (sa_ffn_dim, default 4 H), or None for sa_block plain (the default: the bare
+    attention layer of mhsa_names) and for every other cell.  Refused by name: either key without rnn_cell mhsa, sa_ffn_dim without
+    sa_block encoder, a block that is neither, F not an integer in 8..4096."""
     given = lambda v: v not in (None, "None")
     if cell != "mhsa":
+        for k, v in (("sa_block", sa_block), ("sa_ffn_dim", sa_ffn_dim)):
+            if given(v):
+                raise VltfError("%s is a key of rnn_cell mhsa, but the cell is [%s]" % (k, cell))
+        return None
+    block = sa_block if given(sa_block) else "plain"
+    if block not in SA_BLOCKS:
+        raise VltfError("sa_block must be plain or encoder, got [%s]" % (block,))
+    if block == "plain":
+        if given(sa_ffn_dim):
+            raise VltfError("sa_ffn_dim is a key of sa_block encoder, but the block is [plain]")
+        return None
+    F = sa_ffn_dim if given(sa_ffn_dim) else 4 * int(hidden)
+    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or not SA_FFN_MIN <= int(F) <= SA_FFN_MAX:
+        raise VltfError("sa_ffn_dim must be an integer in %d..%d, got [%s]" % (SA_FFN_MIN, SA_FFN_MAX, F))
+    return int(F)
+
+
+def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="avg", what="rnn_cell", sa_block=None, sa_ffn_dim=None):
+    """-> (heads, positions) of rnn_cell mhsa, or None for every other cell.  Refused: sa_heads / sa_positions / sa_block / sa_ffn_dim
+    without mhsa; with it, fusion state, whatever misses a limit of the launches (vltf.h: vl_mhsa_fwd) and what check_sa_block
+    refuses, before anything is allocated.  The block's feed-forward width is check_sa_block's answer."""
+    given = lambda v: v not in (None, "None")
+    if cell != "mhsa":
+        check_sa_block(cell, hidden, sa_block, sa_ffn_dim)
         for k, v in (("sa_heads", sa_heads), ("sa_positions", sa_positions)):
             if given(v):
                 raise VltfError("%s is a key of rnn_cell mhsa, but the cell is [%s]" % (k, cell))
@@ -200,6 +231,7 @@ def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="av
         raise VltfError("%s: mhsa needs 1 <= T <= %d steps per clip (a head's score tile lives in LDS), got %d" % (what, ops.MHSA_MAX_T, T))
     if not 1 <= H <= ops.MHSA_MAX_HIDDEN:
         raise VltfError("%s: mhsa needs a width H <= %d, got %d" % (what, ops.MHSA_MAX_HIDDEN, H))
+    check_sa_block(cell, H, sa_block, sa_ffn_dim)
     if not given(sa_heads):
         heads = 4 if H % 4 == 0 else 1
     elif isinstance(sa_heads, bool) or not isinstance(sa_heads, (int, np.integer)) or int(sa_heads) < 1:
@@ -227,6 +259,138 @@ def mhsa_buffers(buf, rows, T, H, heads, positions, training):
         if positions == "relative":
             S["dposp"] = buf(clips, heads * (2 * T - 1))
     return S
+
+
+# ---- sa_block encoder: the pre-LN Transformer encoder block around the self-attention layer ----------------------------
+ENC_LAYER_VARS = ("norm1_gamma", "norm1_beta", "qkv_kernel", "qkv_bias", "out_kernel", "out_bias", "position_bias", "norm2_gamma",
+                  "norm2_beta", "ffn1_kernel", "ffn1_bias", "ffn2_kernel", "ffn2_bias")
+
+
+def encoder_var(scope, layer, var):
+    """The name of a variable of the block stack: layer None = the embedding (var kernel | bias) in front of the blocks, layer -1 = the
+    final norm (gamma | beta) behind them."""
+    where = "embed" if layer is None else "final_norm" if layer < 0 else "layer_%d" % layer
+    return "%sself_attention/%s/%s" % (scope, where, var)
+
+
+def encoder_specs(layers, d, H, F, heads, T, scope="", positions="relative", backward=False):
+    """[(name, shape)] of the block stack in flat-buffer order: the embedding, the layers ascending with each layer's variables in the
+    order the forward meets them (ENC_LAYER_VARS), the final norm -- the layout of mhsa_specs' list (layers ascending, forward order
+    inside a layer), which the backward walks from its end to its start.  backward (GraphEngine, whose head_specs list the layers
+    descending): the final norm, the layers descending, the embedding.  Gammas, betas and biases are rank 1: exempt from decay and
+    trust scaling as every bias is; position_bias is rank 2 on purpose (mhsa_names)."""
+    shapes = dict(norm1_gamma=(H,), norm1_beta=(H,), qkv_kernel=(H, 3 * H), qkv_bias=(3 * H,), out_kernel=(H, H), out_bias=(H,),
+                  position_bias=(heads, 2 * T - 1), norm2_gamma=(H,), norm2_beta=(H,), ffn1_kernel=(H, F), ffn1_bias=(F,),
+                  ffn2_kernel=(F, H), ffn2_bias=(H,))
+    groups = [[(encoder_var(scope, None, "kernel"), (d, H)), (encoder_var(scope, None, "bias"), (H,))]]
+    for l in range(layers):
+        groups.append([(encoder_var(scope, l, v), shapes[v]) for v in ENC_LAYER_VARS if v != "position_bias" or positions == "relative"])
+    groups.append([(encoder_var(scope, -1, "gamma"), (H,)), (encoder_var(scope, -1, "beta"), (H,))])
+    return [s for grp in (reversed(groups) if backward else groups) for s in grp]
+
+
+def encoder_buffers(buf, rows, T, H, F, heads, positions, layers, training):
+    """-> E = dict(x0, n0, st0, layers=[S ...]): the embedding's output x0 (the residual stream entering layer 0), its norm n0 with the
+    stats st0; per layer qkv, P, ctx, the attention's output o, a = stream + o, n2 = LN(a) with st2, u, f = gelu(u), m, the stream xs
+    leaving the layer and hseq = LN(xs) with sty -- the next layer's norm1, or behind the last layer the final norm, which is what the
+    fusions read (hence the name the other layer kinds use).  Training: per layer dout (the gradient of hseq), dxs (of xs), df (du in
+    place), dn2, da, dctx, dqkv, dposp and the per-clip partials gb2 / gby of the two norms' gradients; dn0, dx0, gb0 in front.  Every
+    layer has its own: the parameter gradients read them from the second stream while the chain goes on."""
+    clips = rows // T
+    E = dict(x0=buf(rows, H), n0=buf(rows, H), st0=buf(rows, 2), layers=[])
+    if training:
+        E.update(dn0=buf(rows, H), dx0=buf(rows, H), gb0=buf(clips, 2 * H))
+    for _ in range(layers):
+        S = dict(qkv=buf(rows, 3 * H), P=buf(clips * heads, T * T), ctx=buf(rows, H), o=buf(rows, H), a=buf(rows, H), n2=buf(rows, H),
+                 st2=buf(rows, 2), u=buf(rows, F), f=buf(rows, F), m=buf(rows, H), xs=buf(rows, H), hseq=buf(rows, H), sty=buf(rows, 2))
+        if training:
+            S.update(dout=buf(rows, H), dxs=buf(rows, H), df=buf(rows, F), dn2=buf(rows, H), da=buf(rows, H), dctx=buf(rows, H),
+                     dqkv=buf(rows, 3 * H), gb2=buf(clips, 2 * H), gby=buf(clips, 2 * H))
+            if positions == "relative":
+                S["dposp"] = buf(clips, heads * (2 * T - 1))
+        E["layers"].append(S)
+    return E
+
+
+def encoder_forward(E, P, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk):
+    """The block stack on xin [rows, d] -> the final norm's output.  The embedding and the qkv projections take the workspace (they
+    follow conv_math, as the GRU's input projection); the output projection and the two feed-forward products do not (fp32 always, as
+    attention_pool's).  Every residual add is inside the norm launch that follows it.  lk: {} or {seq_len: lengths} -- no launch reads
+    a dead row of what a launch wrote, and a dead row of a product's output (a bias) is read by nothing."""
+    v = lambda l, name: P[encoder_var(scope, l, name)]
+    layers = E["layers"]
+    ops.gemm(xin, v(None, "kernel"), E["x0"], rows, H, d, bias=v(None, "bias"), ws=ws)
+    ops.add_layer_norm_fwd(E["x0"], None, None, E["n0"], v(0, "norm1_gamma"), v(0, "norm1_beta"), E["st0"], b, T, H, **lk)
+    xs, nin = E["x0"], E["n0"]
+    for l, S in enumerate(layers):
+        ops.gemm(nin, v(l, "qkv_kernel"), S["qkv"], rows, 3 * H, H, bias=v(l, "qkv_bias"), ws=ws)
+        ops.mhsa_fwd(S["qkv"], v(l, "position_bias") if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads, **lk)
+        ops.gemm(S["ctx"], v(l, "out_kernel"), S["o"], rows, H, H, bias=v(l, "out_bias"))
+        ops.add_layer_norm_fwd(xs, S["o"], S["a"], S["n2"], v(l, "norm2_gamma"), v(l, "norm2_beta"), S["st2"], b, T, H, **lk)
+        ops.gemm(S["n2"], v(l, "ffn1_kernel"), S["u"], rows, F, H, bias=v(l, "ffn1_bias"))
+        ops.gelu_fwd(S["u"], S["f"], rows * F)
+        ops.gemm(S["f"], v(l, "ffn2_kernel"), S["m"], rows, H, F, bias=v(l, "ffn2_bias"))
+        last = l + 1 == len(layers)
+        gy, by = (v(-1, "gamma"), v(-1, "beta")) if last else (v(l + 1, "norm1_gamma"), v(l + 1, "norm1_beta"))
+        ops.add_layer_norm_fwd(S["a"], S["m"], S["xs"], S["hseq"], gy, by, S["sty"], b, T, H, **lk)
+        xs, nin = S["xs"], S["hseq"]
+    return nin
+
+
+def encoder_backward(E, P, G, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk, param_grads):
+    """From layers[-1]["dout"] (the gradient of the final norm's output) to E["dx0"] (the gradient of the embedding's output) and every
+    gradient of the stack but the embedding's, which the caller forms as it forms its first layer's.  The gradient on the residual
+    stream enters each norm's backward as dres: there is no add launch.  param_grads(launch): launch(ws, small_ws) forms parameter
+    gradients from buffers that are complete on the calling stream (LRCNEngine: on the second stream)."""
+    v = lambda l, name: P[encoder_var(scope, l, name)]
+    g = lambda l, name: G[encoder_var(scope, l, name)]
+    layers = E["layers"]
+
+    def norm_grads(l, which, part, sws):                      # the per-clip partials, summed over the clips in a fixed order
+        names = ("gamma", "beta") if l < 0 else (which + "_gamma", which + "_beta")
+        ops.colsum(part, g(l, names[0]), sws, b, H, lda=2 * H)
+        ops.colsum(part.view(-1)[H:], g(l, names[1]), sws, b, H, lda=2 * H)
+
+    top = layers[-1]
+    ops.layer_norm_bwd(top["dout"], top["xs"], v(-1, "gamma"), top["sty"], None, top["dxs"], top["gby"], b, T, H, **lk)
+    param_grads(lambda ws_, sws: norm_grads(-1, None, top["gby"], sws))
+    for l in reversed(range(len(layers))):
+        S = layers[l]
+        below = layers[l - 1] if l else None
+        xs_in, nin, st_in = (below["xs"], below["hseq"], below["sty"]) if l else (E["x0"], E["n0"], E["st0"])
+        dnin, dxs_in, gb_in = (below["dout"], below["dxs"], below["gby"]) if l else (E["dn0"], E["dx0"], E["gb0"])
+        # the feed-forward block: dm = dxs; df = dm W2^T, du = df gelu'(u) in place, dn2 = du W1^T; norm2 with the stream's gradient
+        ops.gemm(S["dxs"], v(l, "ffn2_kernel"), S["df"], rows, F, H, transb=True)
+
+        def ffn2_grads(ws_, sws, S=S, l=l):
+            ops.gemm(S["f"], S["dxs"], g(l, "ffn2_kernel"), F, H, rows, transa=True)
+            ops.colsum(S["dxs"], g(l, "ffn2_bias"), sws, rows, H)
+        param_grads(ffn2_grads)
+        ops.gelu_bwd(S["df"], S["u"], S["df"], rows * F)
+        ops.gemm(S["df"], v(l, "ffn1_kernel"), S["dn2"], rows, H, F, transb=True)
+        ops.layer_norm_bwd(S["dn2"], S["a"], v(l, "norm2_gamma"), S["st2"], S["dxs"], S["da"], S["gb2"], b, T, H, **lk)
+
+        def ffn1_grads(ws_, sws, S=S, l=l):
+            ops.gemm(S["n2"], S["df"], g(l, "ffn1_kernel"), H, F, rows, transa=True)
+            ops.colsum(S["df"], g(l, "ffn1_bias"), sws, rows, F)
+            norm_grads(l, "norm2", S["gb2"], sws)
+        param_grads(ffn1_grads)
+        # the attention: do = da; through the output projection, ONE launch for every (clip, head), the qkv projection; norm1
+        ops.gemm(S["da"], v(l, "out_kernel"), S["dctx"], rows, H, H, transb=True)
+        ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **lk)
+        ops.gemm(S["dqkv"], v(l, "qkv_kernel"), dnin, rows, H, 3 * H, transb=True, ldb=3 * H, ws=ws)
+        ops.layer_norm_bwd(dnin, xs_in, v(l, "norm1_gamma"), st_in, S["da"], dxs_in, gb_in, b, T, H, **lk)
+
+        def attn_grads(ws_, sws, S=S, l=l, nin=nin, gb_in=gb_in):
+            ops.gemm(S["ctx"], S["da"], g(l, "out_kernel"), H, H, rows, transa=True)
+            ops.colsum(S["da"], g(l, "out_bias"), sws, rows, H)
+            ops.gemm(nin, S["dqkv"], g(l, "qkv_kernel"), H, 3 * H, rows, transa=True, ws=ws_)
+            ops.colsum(S["dqkv"], g(l, "qkv_bias"), sws, rows, 3 * H)
+            if "dposp" in S:
+                ops.colsum(S["dposp"], g(l, "position_bias"), sws, b, heads * (2 * T - 1))
+            norm_grads(l, "norm1", gb_in, sws)
+        param_grads(attn_grads)
+    return E["dx0"]
 
 
 ATTN_MAX_DIM = 1024
@@ -309,14 +473,18 @@ def param_specs(cfg: NetConfig):
     A = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, (2 if cfg.lstm_bidirectional else 1) * cfg.lstm_hidden)
     if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "attn":
         raise VltfError("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
-    sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion)
+    sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion, sa_block=cfg.sa_block,
+                    sa_ffn_dim=cfg.sa_ffn_dim)
     if sa:
         H = cfg.lstm_hidden
         if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
             specs += [("output_fc_w", (H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
         specs += attn_specs(H, A) if A else []
         d = dim
-        for l in range(cfg.lstm_layers):
+        F = check_sa_block(cfg.rnn_cell, H, cfg.sa_block, cfg.sa_ffn_dim)
+        if F:
+            specs += encoder_specs(cfg.lstm_layers, d, H, F, sa[0], cfg.fpc, positions=sa[1])
+        for l in range(0 if F else cfg.lstm_layers):
             specs += mhsa_specs(l, d, H, sa[0], cfg.fpc, positions=sa[1])
             d = H
     elif cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
@@ -1238,8 +1406,10 @@ def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
         if name.endswith("kernel") or name.endswith("attention_pool/context"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
-        elif name.endswith("bias"):
+        elif name.endswith("bias") or name.endswith("beta"):
             out[name] = np.zeros(shp, np.float32)
+        elif name.endswith("gamma"):
+            out[name] = np.ones(shp, np.float32)
         elif len(shp) > 1:
             sd = math.sqrt(2.0 / int(np.prod(shp[:-1]))) if well_scaled else stddev
             v = rng.standard_normal(shp)
@@ -1460,8 +1630,11 @@ class LRCNEngine:
         self.ws = torch.empty(max(ws_bytes, 64 << 20) // 4, device=dev)       # wgrad slabs / split-K slabs / GEMM operand images
         # rnn_cell mhsa: (heads, positions) of the self-attention layers, else None (refusals: param_specs -> check_mhsa)
         self.sa = check_mhsa(cfg.rnn_cell, H, T, cfg.sa_heads, cfg.sa_positions, cfg.fusion) if cfg.classifier == "lstm" else None
-        # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide)
-        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0))
+        # sa_block encoder: the feed-forward width of the blocks, else None (refusals: param_specs -> check_mhsa -> check_sa_block)
+        self.sa_ffn = check_sa_block(cfg.rnn_cell, H, cfg.sa_block, cfg.sa_ffn_dim) if self.sa else None
+        # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide, the
+        # block's ffn1_bias F wide)
+        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0, self.sa_ffn or 0))
         if training:
             self.wt = buf(max_w)
             self.df6 = buf(N, FC_DIM)
@@ -1481,6 +1654,10 @@ class LRCNEngine:
             self.bi = bool(cfg.lstm_bidirectional)
             self.is_gru = cfg.rnn_cell == "gru"                         # (refusals: param_specs -> check_rnn_cell)
             self.mhsa, self._mhsa_clips = [], 0                         # rnn_cell mhsa: self-attention layers (self.sa above)
+            self.enc = None                                             # sa_block encoder: encoder_buffers; self.mhsa is then its layers
+            if self.sa_ffn:
+                self.enc = encoder_buffers(buf, N, T, H, self.sa_ffn, self.sa[0], self.sa[1], cfg.lstm_layers, training)
+                self.mhsa = self.enc["layers"]
             HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
                 raise VltfError("lstm_bidirectional: this device has too few compute units to hold both directions of hidden size %d in "
@@ -1491,6 +1668,8 @@ class LRCNEngine:
                     continue
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, N, H, training))
+                    continue
+                if self.sa_ffn:
                     continue
                 if self.sa:
                     self.mhsa.append(mhsa_buffers(buf, N, T, H, self.sa[0], self.sa[1], training))
@@ -2225,7 +2404,11 @@ class LRCNEngine:
                 ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb,
                                 ws=self.lstm_ws_graph if st else self.lstm_ws, **st)
                 xin, d = S["hseq"], H
-            for l, S in enumerate(self.mhsa):
+            if self.enc:
+                # sa_block encoder: embedding, L blocks, final norm (encoder_forward); no launch takes a host-varying argument
+                xin, d = encoder_forward(self.enc, P, "", xin, n, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {}), H
+                self._mhsa_clips = b
+            for l, S in enumerate(() if self.enc else self.mhsa):
                 # the qkv projection of all rows as the GRU's input projection is called (with the workspace: it follows conv_math),
                 # ONE launch for every (clip, head), then the output projection as attention_pool's (no workspace: fp32 always).  The
                 # launch takes no host-varying argument, so a captured step replays it as it is.
@@ -2469,7 +2652,21 @@ class LRCNEngine:
                     self._relu_grad_behind(self.dfeat, relu_mask, n * D)
                 else:
                     ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], n, H, 3 * H, transb=True, ldb=3 * H, ws=self.ws)
-            for l in reversed(range(len(self.mhsa))):
+            if self.enc:
+                # sa_block encoder: the blocks (encoder_backward), then the embedding as the GRU's input projection
+                dx0 = encoder_backward(self.enc, P, G, "", self.feat, n, b, T, D, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {},
+                                       param_grads)
+
+                def embed_grads(ws, sws, dx0=dx0):
+                    ops.gemm(self.feat, dx0, G[encoder_var("", None, "kernel")], D, H, n, transa=True, ws=ws)
+                    ops.colsum(dx0, G[encoder_var("", None, "bias")], sws, n, H)
+                param_grads(embed_grads)
+                if self.dcnn_trains:                                                  # (a frozen tower: nobody reads dfeat)
+                    relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
+                    ops.gemm(dx0, P[encoder_var("", None, "kernel")], self.dfeat, n, D, H, transb=True, ldb=H,
+                             relu_mask=self._fused_mask(relu_mask), ws=self.ws)
+                    self._relu_grad_behind(self.dfeat, relu_mask, n * D)
+            for l in reversed(range(0 if self.enc else len(self.mhsa))):
                 S = self.mhsa[l]
                 heads, positions = self.sa
                 names = mhsa_names(l, positions=positions)

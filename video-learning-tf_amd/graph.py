@@ -29,7 +29,8 @@ at or beyond a clip's length are dead: the recurrence of every layer carries the
 state | last | avg read the live prefix only, and when the last pipeline's fusion is `reshape` the loss, its gradient and the
 accuracy are taken over the live rows (the reference's non_padding_index, dataset_.py:327-383).  A self-attention layer (rnn_cell
 mhsa) attends over the live keys only and never reads a dead row of its projections; the first layer takes its input through
-ops.live_rows, so that a padded frame's features reach no product.  include/vltf.h states the
+ops.live_rows, so that a padded frame's features reach no product; with sa_block encoder it is the embedding that reads
+through ops.live_rows, and the norm launches skip dead rows and write zeros there.  include/vltf.h states the
 contract of the kernels; without seq_len every call is what it was.
 
 The oracle of this class is oracle.lrcn_oracle.model_forward / model_backward (cross-checked against torch autograd)."""
@@ -43,7 +44,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, attn_buffers, attn_names, attn_specs, check_attn,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -65,6 +66,8 @@ class PipelineSpec:
                                                     # | mhsa: every layer a multi-head self-attention layer over the frames (engine.mhsa_names)
     sa_heads: Optional[int] = None                  # rnn_cell mhsa: heads (divides the width); None = 4 where 4 divides it, else 1
     sa_positions: Optional[str] = None              # rnn_cell mhsa: relative (None) | none
+    sa_block: Optional[str] = None                  # rnn_cell mhsa: plain (None) | encoder: the pre-LN encoder block (engine.encoder_specs)
+    sa_ffn_dim: Optional[int] = None                # sa_block encoder: the feed-forward width, 8..4096; None = 4 x the width
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
     train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
@@ -247,14 +250,18 @@ class PipeNode:
                 self.attn_dim = check_attn(lf, s.attn_dim, "lstm", self.HO, what="pipeline [%s]: attn_dim" % s.name)
                 # rnn_cell mhsa: (heads, positions) of the self-attention layers (engine.check_mhsa); None for every other cell
                 self.sa = check_mhsa(s.rnn_cell, self.H, self.fpc, s.sa_heads, s.sa_positions, self.lfusion,
-                                     what="pipeline [%s]: rnn_cell" % s.name)
+                                     what="pipeline [%s]: rnn_cell" % s.name, sa_block=s.sa_block, sa_ffn_dim=s.sa_ffn_dim)
+                # sa_block encoder: the feed-forward width of the blocks (engine.check_sa_block); None for the plain layer
+                self.sa_ffn = check_sa_block(s.rnn_cell, self.H, s.sa_block, s.sa_ffn_dim)
                 if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
             if s.lstm_bidirectional and self.cls != "lstm":
                 raise VltfError("pipeline [%s]: lstm_bidirectional needs classifier lstm, not [%s]" % (s.name, self.cls))
             if self.cls != "lstm":
-                self.sa = check_mhsa(s.rnn_cell, sa_heads=s.sa_heads, sa_positions=s.sa_positions)      # the keys without the cell: refused
+                self.sa = check_mhsa(s.rnn_cell, sa_heads=s.sa_heads, sa_positions=s.sa_positions, sa_block=s.sa_block,
+                                     sa_ffn_dim=s.sa_ffn_dim)                                             # the keys without the cell: refused
+                self.sa_ffn = None
             self.late = ftype == "late" and self.fpc > 1 and fmethod != "reshape"
             if self.late:
                 if self.cls == "lstm" or rows % self.fpc:
@@ -283,7 +290,9 @@ class PipeNode:
             if self.attn_dim:
                 specs += attn_specs(HO, self.attn_dim, sc)
             dims = [self.feat_dim] + [HO] * (self.L - 1)
-            for l in reversed(range(self.L)):
+            if self.sa_ffn:
+                specs += encoder_specs(self.L, self.feat_dim, H, self.sa_ffn, self.sa[0], self.fpc, sc, self.sa[1], backward=True)
+            for l in reversed(range(0 if self.sa_ffn else self.L)):
                 if self.bi:
                     specs += [(n, (dims[l] + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l, sc)]
                     continue
@@ -368,6 +377,8 @@ class PipeNode:
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, R0, H, tr))
                     continue
+                if self.sa_ffn:
+                    continue
                 if self.sa:
                     self.mhsa.append(mhsa_buffers(buf, R0, T, H, self.sa[0], self.sa[1], tr))
                     continue
@@ -403,6 +414,12 @@ class PipeNode:
                 # under seq_len the first layer reads its input through ops.live_rows: a padded frame's features reach no product
                 self.xlive = buf(R0, self.feat_dim)
                 sw = max(sw, 64 * self.sa[0] * (2 * T - 1))
+            self.enc = None
+            if self.sa_ffn:
+                # sa_block encoder: engine.encoder_buffers; self.mhsa is its layers (the top layer's hseq / dout are the final norm's)
+                self.enc = encoder_buffers(buf, R0, T, H, self.sa_ffn, self.sa[0], self.sa[1], self.L, tr)
+                self.mhsa = self.enc["layers"]
+                sw = max(sw, 64 * self.sa_ffn)
         if self.late:
             self.late_out = buf(self.max_rows, C)
             if tr:
@@ -621,7 +638,16 @@ class PipeNode:
             ops.gemm(xin, K, S["gx"], rows, 3 * H, d, bias=bk, ws=g.ws)
             ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb, ws=self.lstm_ws, **lk)
             xin, d = S["hseq"], H
-        for l, S in enumerate(self.mhsa):
+        if self.enc:
+            # sa_block encoder (engine.encoder_forward).  Under seq_len the embedding reads its input through ops.live_rows, as the
+            # plain layer's qkv projection below does: x^T dx0 reads every row of x.  The norm launches never read a dead row and write
+            # zeros there; a dead row of a product's output is a bias, which nothing reads.
+            if lk:
+                ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
+                xin = self.xlive
+            self._xsa = xin
+            xin, d = encoder_forward(self.enc, P, sc, xin, rows, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk), H
+        for l, S in enumerate(() if self.enc else self.mhsa):
             # Dead-row contract: the launch never reads a dead row of qkv and writes zeros in the dead rows of ctx (so a dead row of a
             # layer's output is out_bias, which nothing reads: the next layer's launch, the fusions and the masked loss skip it, and its
             # gradient arrives as zeros).  The FIRST layer's input goes through ops.live_rows, because x^T dqkv reads every row of x.
@@ -786,7 +812,16 @@ class PipeNode:
                 ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
             elif self.wants_feat:
                 ops.gemm(S["dgx"], K, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
-        for l in reversed(range(len(self.mhsa))):
+        if self.enc:
+            # sa_block encoder: the blocks (engine.encoder_backward: one stream here, every gradient where the chain stands), then
+            # the embedding as the plain layer's qkv projection below
+            dx0 = encoder_backward(self.enc, P, G, sc, self._xsa, rows, b, T, self.feat_dim, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws,
+                                   self._len_kw(), lambda launch: launch(g.ws, sw))
+            ops.gemm(self._xsa, dx0, G[encoder_var(sc, None, "kernel")], self.feat_dim, H, rows, transa=True, ws=g.ws)
+            ops.colsum(dx0, G[encoder_var(sc, None, "bias")], sw, rows, H)
+            if self.wants_feat:
+                ops.gemm(dx0, P[encoder_var(sc, None, "kernel")], self.dxseq, rows, self.feat_dim, H, transb=True, ldb=H, ws=g.ws)
+        for l in reversed(range(0 if self.enc else len(self.mhsa))):
             S = self.mhsa[l]
             heads, positions = self.sa
             names = mhsa_names(l, sc, positions)
@@ -911,8 +946,10 @@ def init_params_for(specs, seed=0, stddev=0.05, well_scaled=False):
         if name.endswith("kernel") or name.endswith("attention_pool/context"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
-        elif name.endswith("bias"):
+        elif name.endswith("bias") or name.endswith("beta"):
             out[name] = np.zeros(shp, np.float32)
+        elif name.endswith("gamma"):                                    # a layer norm's scale (sa_block encoder): ones
+            out[name] = np.ones(shp, np.float32)
         elif len(shp) > 1:
             out[name] = _trunc_normal(rng, shp, math.sqrt(2.0 / int(np.prod(shp[:-1]))) if well_scaled else stddev)
         else:

@@ -1,6 +1,7 @@
 """Thin torch-tensor wrappers over the C-ABI (include/vltf.h).  Tensors are device allocations
 only: every wrapper passes ``data_ptr()`` and the current HIP stream; no torch math runs here."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -839,6 +840,72 @@ def live_rows(x, y, batch, T, W, seq_len):
     if min(batch, T, W) > 0 and min(x.numel(), y.numel()) < batch * T * W:
         raise _ffi.VltfError("live_rows: x / y hold %d / %d elements, the launch needs %d" % (x.numel(), y.numel(), batch * T * W))
     _ffi.call("vl_live_rows", _p(x), _p(_seq_len(seq_len, batch, "live_rows")), _p(y), batch, T, W, stream())
+
+
+LN_MIN_WIDTH, LN_MAX_WIDTH, LN_EPS = 8, 1024, 1e-5                                  # vl_add_layer_norm_fwd / vl_layer_norm_bwd: vltf.h
+
+
+def _ln_sizes(who, clips, T, W, **tensors):
+    """The limits of the layer-norm launches (the C side's wording), then every tensor given holds at least what the launch reads or
+    writes of it (None passes: the C side refuses a null pointer it needs).  Raises before any launch."""
+    if min(clips, T) <= 0:
+        raise _ffi.VltfError("%s: clips %d, T %d must be positive" % (who, clips, T))
+    if not LN_MIN_WIDTH <= W <= LN_MAX_WIDTH:
+        raise _ffi.VltfError("%s: the row width W %d must lie in %d..%d (a row lives in one wave's registers)"
+                             % (who, W, LN_MIN_WIDTH, LN_MAX_WIDTH))
+    rows = clips * T
+    need = dict(gamma=W, beta=W, stats=2 * rows, dgb_partial=2 * clips * W)
+    for k, t in tensors.items():
+        if t is not None and t.numel() < need.get(k, rows * W):
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), need.get(k, rows * W)))
+
+
+def add_layer_norm_fwd(x, r, sum, y, gamma, beta, stats, clips, T, W, eps=LN_EPS, seq_len=None):
+    """A layer norm over the last axis with the residual add in front of it fused (vl_add_layer_norm_fwd): s = x + r (r None: s = x),
+    stored to `sum` unless None; y = (s - mean) rstd gamma + beta; stats [clips T, 2] = mean, rstd for layer_norm_bwd.  Rows
+    [clips T, W], 8 <= W <= 1024; seq_len as mhsa_fwd: dead rows of x and r are never read, dead rows of y, sum and stats are zeros."""
+    _f32(x, r, sum, y, gamma, beta, stats)
+    _dense(x, r, sum, y, gamma, beta, stats)
+    _ln_sizes("add_layer_norm_fwd", clips, T, W, x=x, r=r, sum=sum, y=y, gamma=gamma, beta=beta, stats=stats)
+    if not (eps > 0 and math.isfinite(eps)):
+        raise _ffi.VltfError("add_layer_norm_fwd: eps %g must be positive and finite" % eps)
+    _ffi.call("vl_add_layer_norm_fwd", _p(x), _p(r), _p(sum), _p(y), _p(gamma), _p(beta), _p(stats), clips, T, W, eps,
+              None if seq_len is None else _p(_seq_len(seq_len, clips, "add_layer_norm_fwd")), stream())
+
+
+def layer_norm_bwd(dy, s, gamma, stats, dres, dx, dgb_partial, clips, T, W, seq_len=None):
+    """Its backward (vl_layer_norm_bwd) from the forward's s (`sum`, or x where there was no r) and stats: dx = rstd (dy^ - mean(dy^) -
+    x^ mean(dy^ x^)) + dres with dy^ = dy gamma (dres None: no such term), dead rows zeros, and the per-clip partials dgb_partial
+    [clips, 2W] of gamma's (columns 0 .. W) and beta's (W .. 2W) gradients over the clip's live rows (colsum them over the clips)."""
+    _f32(dy, s, gamma, stats, dres, dx, dgb_partial)
+    _dense(dy, s, gamma, stats, dres, dx, dgb_partial)
+    _ln_sizes("layer_norm_bwd", clips, T, W, dy=dy, s=s, gamma=gamma, stats=stats, dres=dres, dx=dx, dgb_partial=dgb_partial)
+    _ffi.call("vl_layer_norm_bwd", _p(dy), _p(s), _p(gamma), _p(stats), _p(dres), _p(dx), _p(dgb_partial), clips, T, W,
+              None if seq_len is None else _p(_seq_len(seq_len, clips, "layer_norm_bwd")), stream())
+
+
+def _gelu_sizes(who, count, **tensors):
+    if count <= 0:
+        raise _ffi.VltfError("%s: count %d must be positive" % (who, count))
+    for k, t in tensors.items():
+        if t is not None and t.numel() < count:
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), count))
+
+
+def gelu_fwd(u, f, count):
+    """f = gelu(u) over the first `count` elements, the exact (erf) form of Keras / torch (vl_gelu_fwd)."""
+    _f32(u, f)
+    _dense(u, f)
+    _gelu_sizes("gelu_fwd", count, u=u, f=f)
+    _ffi.call("vl_gelu_fwd", _p(u), _p(f), count, stream())
+
+
+def gelu_bwd(df, u, du, count):
+    """du = df gelu'(u) (vl_gelu_bwd); du may be df."""
+    _f32(df, u, du)
+    _dense(df, u, du)
+    _gelu_sizes("gelu_bwd", count, df=df, u=u, du=du)
+    _ffi.call("vl_gelu_bwd", _p(df), _p(u), _p(du), count, stream())
 
 
 def dropout_fwd(x, y, mask, keep, seed):

@@ -71,7 +71,8 @@ def pipeline_net_config(settings, p, dataset):
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
         kw.update(lstm_hidden=p.lstm_params[0], lstm_layers=p.lstm_params[1], fusion=p.lstm_params[2],
                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
-                  attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None))
+                  attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None),
+                  sa_block=getattr(p, "sa_block", None), sa_ffn_dim=getattr(p, "sa_ffn_dim", None))
     else:
         kw.update(frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None)
     return NetConfig(**kw)
@@ -103,7 +104,8 @@ def graph_config(settings, feeder, batch):
                                   classifier=p.classifier, lstm_params=tuple(p.lstm_params) if p.lstm_params else None,
                                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
                                   attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None),
-                                  sa_positions=getattr(p, "sa_positions", None),
+                                  sa_positions=getattr(p, "sa_positions", None), sa_block=getattr(p, "sa_block", None),
+                                  sa_ffn_dim=getattr(p, "sa_ffn_dim", None),
                                   frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None, input_fusion=p.input_fusion,
                                   train_from=getattr(p, "train_from", None)))
     infos, dsets = {}, {}

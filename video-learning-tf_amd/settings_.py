@@ -205,6 +205,7 @@ class Settings:
         network.rnn_cell = self.read_rnn_cell(content, network)
         network.attn_dim = self.read_attn_dim(content, network)
         network.sa_heads, network.sa_positions = self.read_self_attention(content, network)
+        network.sa_block, network.sa_ffn_dim = self.read_sa_block(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
@@ -284,6 +285,21 @@ class Settings:
         except VltfError as ex:
             error(str(ex))
         return sa if sa else (None, None)
+
+    def read_sa_block(self, content, network):
+        """`sa_block: plain | encoder` and `sa_ffn_dim: <F>` beside `rnn_cell: mhsa` (this project's extension of the pipeline schema):
+        `encoder` wraps every self-attention layer in the pre-LN Transformer encoder block (layer norm, residual, feed-forward block of
+        width F; absent / None = 4 x lstm_params' width; 8..4096) behind an embedding and in front of a final norm
+        (engine.encoder_specs); absent / None / plain = the bare layer.  Refused: either key without rnn_cell mhsa, sa_ffn_dim without
+        sa_block encoder (engine.check_sa_block).  -> (block, F) as the engine takes them: (None, None) for the plain layer."""
+        block, ffn = self.read_field(content, "sa_block"), self.read_field(content, "sa_ffn_dim")
+        from .engine import VltfError, check_sa_block
+        lstm = network.classifier == defs.classifier.lstm
+        try:
+            F = check_sa_block(network.rnn_cell, network.lstm_params[0] if lstm else 1, block, ffn)
+        except VltfError as ex:
+            error(str(ex))
+        return ("encoder", F) if F else (None, None)
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
