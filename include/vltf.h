@@ -503,6 +503,54 @@ int vl_layer_norm_bwd(const float* dy, const float* s, const float* gamma, const
 int vl_gelu_fwd(const float* u, float* f, int64_t count, vl_stream_t stream);
 int vl_gelu_bwd(const float* df, const float* u, float* du, int64_t count, vl_stream_t stream);
 
+/* ---- dropout of the self-attention model: weights, residual branches, drop path (sa_attn_dropout, sa_dropout, sa_drop_path;
+ * csrc/self_attention.hip, csrc/layer_norm.hip).  No mask buffer: every draw is a function of counters.
+ * MASK DEFINITION.  The generator of vl_fc_dropout_fwd under a stream constant of its own:
+ *   s = seed ^ splitmix64(0x5AD000000000 + salt);  h = splitmix64(s ^ splitmix64(e));  kept = (h >> 40) * 2^-24 < keep
+ * The constant is above 2^45, so with a 32-bit salt no stream is one of vl_fc_dropout_fwd's (0xFC00 + salt) and none is the bare
+ * seed of vl_dropout_fwd.  The engines pack salt = node << 12 | layer << 2 | site with site 0 = attention weights, 1 = elements of
+ * the attention branch, 2 = elements of the feed-forward branch, 3 = path draws: every (node, layer, site) is a stream of its own.
+ * Counters e are GLOBAL: clip0 is the index in the whole batch of the launch's first clip, so clip g of the batch draws the same
+ * masks whichever rank or launch holds it (0 <= clip0 < 2^31 - clips):
+ *   weights          e = (((clip0 + b) heads + h) T + q) T + k
+ *   branch elements  e = ((clip0 + b) T + t) W + col
+ *   path             e = 2 (clip0 + b) + branch            branch 0 = attention, 1 = feed-forward
+ * Under seq_len the dead rows' and keys' draws are simply unused.  keep and keep_path lie in (0, 1] (NaN refused); a keep of exactly 1
+ * draws nothing.  The _st forms take seed = (state->step << 20) ^ 0x5DEECE66D from the step state when the kernel runs.
+ * vl_mhsa_drop_fwd: vl_mhsa_fwd with ctx = (P o F) V, F = kept ? fl(1 / keep) : 0, one fp32 product per weight; P is stored UNDROPPED.
+ * vl_mhsa_drop_bwd: F drawn again; dV = (P o F)^T dctx, dP = (dctx V^T) o F, dS = P o (dP - rowsum(dP o P)), the rest as vl_mhsa_bwd.
+ *   Same launch shape, LDS and dead-row contract as vl_mhsa_fwd / _bwd, and at keep = 1 their bits.
+ * BRANCH FACTOR, in fp32 so that a host restatement gives the same bits:  fe = kept_e ? 1.0f / keep : 0,  fp = path_kept ? 1.0f /
+ *   keep_path : 0,  f = fmul(fe, fp)  (a factor whose keep is 1 is exactly 1).
+ * vl_add_layer_norm_drop_fwd: vl_add_layer_norm_fwd with s = fadd(x, fmul(r, f)), no fma (r required); `sum` receives the dropped sum,
+ *   so vl_layer_norm_bwd needs no change.  With both keeps 1 it is vl_add_layer_norm_fwd bit for bit.
+ * vl_branch_drop_grad: dr = fmul(ds, f) over [clips T][W], zeros in the dead rows (ds is not read there): the gradient that enters a
+ *   dropped branch.  16-byte accesses where both pointers are 16-byte aligned; the bits do not depend on alignment.  dr must not
+ *   overlap ds.
+ * A refused call (null pointer, a size outside the limits of the sibling launch, a keep outside (0, 1], clip0 out of range) launches
+ * nothing. */
+int vl_mhsa_drop_fwd(const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch, int T, int H, int heads,
+                     float keep, uint64_t seed, uint32_t salt, int64_t clip0, vl_stream_t stream);
+int vl_mhsa_drop_fwd_st(const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch, int T, int H,
+                        int heads, float keep, const vl_step_state* state, uint32_t salt, int64_t clip0, vl_stream_t stream);
+int vl_mhsa_drop_bwd(const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv, float* dposp, int batch,
+                     int T, int H, int heads, float keep, uint64_t seed, uint32_t salt, int64_t clip0, vl_stream_t stream);
+int vl_mhsa_drop_bwd_st(const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv, float* dposp, int batch,
+                        int T, int H, int heads, float keep, const vl_step_state* state, uint32_t salt, int64_t clip0,
+                        vl_stream_t stream);
+int vl_add_layer_norm_drop_fwd(const float* x, const float* r, float* sum, float* y, const float* gamma, const float* beta, float* stats,
+                               int clips, int T, int W, float eps, const int32_t* seq_len, float keep, float keep_path, uint64_t seed,
+                               uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0, vl_stream_t stream);
+int vl_add_layer_norm_drop_fwd_st(const float* x, const float* r, float* sum, float* y, const float* gamma, const float* beta,
+                                  float* stats, int clips, int T, int W, float eps, const int32_t* seq_len, float keep, float keep_path,
+                                  const vl_step_state* state, uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0,
+                                  vl_stream_t stream);
+int vl_branch_drop_grad(const float* ds, float* dr, int clips, int T, int W, const int32_t* seq_len, float keep, float keep_path,
+                        uint64_t seed, uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0, vl_stream_t stream);
+int vl_branch_drop_grad_st(const float* ds, float* dr, int clips, int T, int W, const int32_t* seq_len, float keep, float keep_path,
+                           const vl_step_state* state, uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0,
+                           vl_stream_t stream);
+
 /* ---- imresize: scipy.misc.imresize(image, shape) of Dataset.process_image (dataset_.py:481-495: imgproc `raw_resize` to the raw
  * shape, `resize` to the network input size; also serialize.py:424-425) = PIL Image.resize(BILINEAR) on uint8, bit-exact:
  * Pillow's two-pass fixed-point resample (22-bit coefficients, uint8 intermediate, horizontal pass first; csrc/resize.hip).

@@ -101,6 +101,14 @@ SIGNATURES = {
     "vl_layer_norm_bwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, p, p]),
     "vl_gelu_fwd": (i32, [p, p, i64, p]),
     "vl_gelu_bwd": (i32, [p, p, p, i64, p]),
+    "vl_mhsa_drop_fwd": (i32, [p, p, p, p, p, i32, i32, i32, i32, f32, u64, u32, i64, p]),
+    "vl_mhsa_drop_fwd_st": (i32, [p, p, p, p, p, i32, i32, i32, i32, f32, p, u32, i64, p]),
+    "vl_mhsa_drop_bwd": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, f32, u64, u32, i64, p]),
+    "vl_mhsa_drop_bwd_st": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, f32, p, u32, i64, p]),
+    "vl_add_layer_norm_drop_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, f32, p, f32, f32, u64, u32, u32, i32, i64, p]),
+    "vl_add_layer_norm_drop_fwd_st": (i32, [p, p, p, p, p, p, p, i32, i32, i32, f32, p, f32, f32, p, u32, u32, i32, i64, p]),
+    "vl_branch_drop_grad": (i32, [p, p, i32, i32, i32, p, f32, f32, u64, u32, u32, i32, i64, p]),
+    "vl_branch_drop_grad_st": (i32, [p, p, i32, i32, i32, p, f32, f32, p, u32, u32, i32, i64, p]),
     "vl_dropout_fwd": (i32, [p, p, p, i64, f32, u64, p]),
     "vl_dropout_bwd": (i32, [p, p, p, i64, f32, p]),
     "vl_dropout_fwd_st": (i32, [p, p, p, i64, f32, p, p]),

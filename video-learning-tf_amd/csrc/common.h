@@ -126,6 +126,42 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// ---- dropout of the self-attention model (vl_mhsa_drop_*, vl_add_layer_norm_drop_fwd, vl_branch_drop_grad; vltf.h) -----
+// The generator of vl_fc_dropout_fwd under a stream constant of its own: SA_DROP_STREAM + salt is above 2^45 for every 32-bit salt, so
+// no stream here is one of 0xFC00 + salt, and vl_dropout_fwd uses the bare seed.  What a launch draws with: the seed (st NULL) or the
+// step state it is formed from when the kernel runs, and the index in the whole batch of the launch's first clip.
+#define SA_DROP_STREAM 0x5AD000000000ull
+struct SaDraw {
+    uint64_t seed;
+    const vl_step_state* st;
+    int64_t clip0;
+};
+__device__ __forceinline__ uint64_t sa_drop_stream(const SaDraw& dw, uint32_t salt) {
+    const uint64_t seed = dw.st ? (((uint64_t)dw.st->step << 20) ^ 0x5DEECE66Dull) : dw.seed;
+    return seed ^ splitmix64(SA_DROP_STREAM + (uint64_t)salt);
+}
+__device__ __forceinline__ bool sa_drop_kept(uint64_t s, uint64_t e, float keep) {
+    const uint64_t h = splitmix64(s ^ splitmix64(e));
+    return (float)(h >> 40) * (1.0f / 16777216.0f) < keep;
+}
+// the factor of a branch element: fe = kept_e ? 1 / keep : 0, fp = path_kept ? 1 / keep_path : 0, f = fe * fp; a keep of 1 draws nothing
+// and gives exactly 1.  se / sp: the element and path streams; e: the element's counter, pe: the path counter 2 * clip + branch.
+__device__ __forceinline__ float sa_path_factor(uint64_t sp, uint64_t pe, float keep_path) {
+    return keep_path < 1.f ? (sa_drop_kept(sp, pe, keep_path) ? __fdiv_rn(1.0f, keep_path) : 0.f) : 1.f;
+}
+__device__ __forceinline__ float sa_branch_factor(uint64_t se, uint64_t e, float keep, float inv_keep, float fp) {
+#pragma clang fp contract(off)
+    const float fe = keep < 1.f ? (sa_drop_kept(se, e, keep) ? inv_keep : 0.f) : 1.f;
+    return fe * fp;
+}
+// s = fadd(x, fmul(r, f)), never an fma
+__device__ __forceinline__ float sa_branch_add(float x, float r, float f) {
+#pragma clang fp contract(off)
+    const float rf = r * f;
+    return x + rf;
+}
+static inline bool sa_keep_ok(float keep) { return keep > 0.f && keep <= 1.f; }      // (false for NaN)
+
 // ---- random erasing (vl_erase_boxes in pointwise.hip, vl_erase_boxes_s2d in conv_c8.hip) -------------------------------
 // A clip's row of the device table: {t0, t1, y0, y1, x0, x1, key_lo, key_hi}.  The box is clamped as a CutMix box is (cut_box_get), so
 // no content of the words reaches an address; false when an axis is then empty.  Wave-uniform.

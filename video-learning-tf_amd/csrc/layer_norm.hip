@@ -92,12 +92,24 @@ __device__ __forceinline__ float ln_row_sum(const float (&v)[LN_REGS]) {
     return wave_sum(a);
 }
 
-template <bool V4>
+// what the drop forms draw with: the branch's element keep and path keep (either may be 1: that option draws nothing), the
+// salts of the element and path streams, which of the layer's two branches this is, and seed / step state / clip0 (common.h: SaDraw)
+struct LnDrop {
+    float keep, keep_path;
+    uint32_t salt_elem, salt_path;
+    int branch;
+    SaDraw dw;
+};
+
+// DROP (vl_add_layer_norm_drop_fwd): s = x + r f with the branch factor f of common.h, drawn in registers between the load of r and
+// the add; the element's counter is ((clip0 + b) T + t) W + col, the path's 2 (clip0 + b) + branch.  Everything else is the kernel
+// as it was, and without DROP it is that kernel instruction for instruction.
+template <bool V4, bool DROP>
 __global__ __launch_bounds__(LN_THREADS) void add_layer_norm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ r,
                                                                         float* __restrict__ sum, float* __restrict__ y,
                                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                         float* __restrict__ stats, const int32_t* __restrict__ seq_len,
-                                                                        int64_t rows, int T, int W, float eps, bool al16) {
+                                                                        int64_t rows, int T, int W, float eps, bool al16, LnDrop dp) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = (int64_t)blockIdx.x * LN_WAVES + wave;
     if (row >= rows) return;                                  // (no barrier in this kernel)
@@ -123,8 +135,21 @@ __global__ __launch_bounds__(LN_THREADS) void add_layer_norm_fwd_kernel(const fl
     if (r) {
         float q[LN_REGS];
         ln_load<V4>(q, r + off, W, lane, al16);
+        if (DROP) {
+            const uint64_t clip = (uint64_t)dp.dw.clip0 + (uint32_t)row / (uint32_t)T;
+            const float fp = sa_path_factor(sa_drop_stream(dp.dw, dp.salt_path), 2 * clip + (uint64_t)dp.branch, dp.keep_path);
+            const uint64_t se = sa_drop_stream(dp.dw, dp.salt_elem);
+            const uint64_t e0 = ((uint64_t)dp.dw.clip0 * (uint64_t)T + (uint64_t)row) * (uint64_t)W;
+            const float inv = __fdiv_rn(1.0f, dp.keep);
 #pragma unroll
-        for (int i = 0; i < LN_REGS; ++i) s[i] = __fadd_rn(s[i], q[i]);
+            for (int i = 0; i < LN_REGS; ++i) {
+                const int e = ln_elem<V4>(i, lane);
+                if (e < W) s[i] = sa_branch_add(s[i], q[i], sa_branch_factor(se, e0 + (uint64_t)e, dp.keep, inv, fp));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < LN_REGS; ++i) s[i] = __fadd_rn(s[i], q[i]);
+        }
     }
     if (sum) ln_store<V4>(s, sum + off, W, lane, al16);
     const float w = (float)W;                                 // (a division, not a reciprocal: a row of one value has exactly that mean)
@@ -262,14 +287,131 @@ extern "C" int vl_add_layer_norm_fwd(const float* x, const float* r, float* sum,
     const int64_t rows = (int64_t)clips * T;
     const bool al = al16_of(x) && al16_of(r) && al16_of(sum) && al16_of(y) && al16_of(gamma) && al16_of(beta);
     const dim3 grid((unsigned)((rows + LN_WAVES - 1) / LN_WAVES));
+    const LnDrop none = {1.f, 1.f, 0u, 0u, 0, {0, nullptr, 0}};
     if (W % 4 == 0)
-        hipLaunchKernelGGL(add_layer_norm_fwd_kernel<true>, grid, dim3(LN_THREADS), 0, (hipStream_t)stream, x, r, sum, y, gamma, beta, stats,
-                           seq_len, rows, T, W, eps, al);
+        hipLaunchKernelGGL((add_layer_norm_fwd_kernel<true, false>), grid, dim3(LN_THREADS), 0, (hipStream_t)stream, x, r, sum, y, gamma,
+                           beta, stats, seq_len, rows, T, W, eps, al, none);
     else
-        hipLaunchKernelGGL(add_layer_norm_fwd_kernel<false>, grid, dim3(LN_THREADS), 0, (hipStream_t)stream, x, r, sum, y, gamma, beta,
-                           stats, seq_len, rows, T, W, eps, false);
+        hipLaunchKernelGGL((add_layer_norm_fwd_kernel<false, false>), grid, dim3(LN_THREADS), 0, (hipStream_t)stream, x, r, sum, y, gamma,
+                           beta, stats, seq_len, rows, T, W, eps, false, none);
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- the drop forms ----------------------------------------------------------------------------------------------------
+static int ln_drop_check(const char* who, const LnDrop& dp, int clips) {
+    VL_CHECK(sa_keep_ok(dp.keep), "%s: keep %g must lie in (0, 1]", who, (double)dp.keep);
+    VL_CHECK(sa_keep_ok(dp.keep_path), "%s: keep_path %g must lie in (0, 1]", who, (double)dp.keep_path);
+    VL_CHECK(dp.branch == 0 || dp.branch == 1, "%s: branch %d must be 0 (attention) or 1 (feed-forward)", who, dp.branch);
+    VL_CHECK(dp.dw.clip0 >= 0 && dp.dw.clip0 < (1ll << 31) - clips, "%s: clip0 %lld must lie in 0 .. 2^31 - clips", who,
+             (long long)dp.dw.clip0);
+    return 0;
+}
+
+static int add_layer_norm_drop_run(const char* who, const float* x, const float* r, float* sum, float* y, const float* gamma,
+                                   const float* beta, float* stats, int clips, int T, int W, float eps, const int32_t* seq_len, LnDrop dp,
+                                   hipStream_t stream) {
+    VL_CHECK(x && r && y && gamma && beta && stats, "%s: null pointer", who);
+    if (int rc = ln_check(who, clips, T, W)) return rc;
+    VL_CHECK(eps > 0.f && eps - eps == 0.f, "%s: eps %g must be positive and finite", who, (double)eps);
+    if (int rc = ln_drop_check(who, dp, clips)) return rc;
+    const int64_t rows = (int64_t)clips * T;
+    const bool al = al16_of(x) && al16_of(r) && al16_of(sum) && al16_of(y) && al16_of(gamma) && al16_of(beta);
+    const dim3 grid((unsigned)((rows + LN_WAVES - 1) / LN_WAVES));
+    if (W % 4 == 0)
+        hipLaunchKernelGGL((add_layer_norm_fwd_kernel<true, true>), grid, dim3(LN_THREADS), 0, stream, x, r, sum, y, gamma, beta, stats,
+                           seq_len, rows, T, W, eps, al, dp);
+    else
+        hipLaunchKernelGGL((add_layer_norm_fwd_kernel<false, true>), grid, dim3(LN_THREADS), 0, stream, x, r, sum, y, gamma, beta, stats,
+                           seq_len, rows, T, W, eps, false, dp);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_add_layer_norm_drop_fwd(const float* x, const float* r, float* sum, float* y, const float* gamma, const float* beta,
+                                          float* stats, int clips, int T, int W, float eps, const int32_t* seq_len, float keep,
+                                          float keep_path, uint64_t seed, uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0,
+                                          vl_stream_t stream) {
+    return add_layer_norm_drop_run("vl_add_layer_norm_drop_fwd", x, r, sum, y, gamma, beta, stats, clips, T, W, eps, seq_len,
+                                   LnDrop{keep, keep_path, salt_elem, salt_path, branch, {seed, nullptr, clip0}}, (hipStream_t)stream);
+}
+
+extern "C" int vl_add_layer_norm_drop_fwd_st(const float* x, const float* r, float* sum, float* y, const float* gamma, const float* beta,
+                                             float* stats, int clips, int T, int W, float eps, const int32_t* seq_len, float keep,
+                                             float keep_path, const vl_step_state* state, uint32_t salt_elem, uint32_t salt_path,
+                                             int branch, int64_t clip0, vl_stream_t stream) {
+    VL_CHECK(state, "vl_add_layer_norm_drop_fwd_st: null pointer");
+    return add_layer_norm_drop_run("vl_add_layer_norm_drop_fwd_st", x, r, sum, y, gamma, beta, stats, clips, T, W, eps, seq_len,
+                                   LnDrop{keep, keep_path, salt_elem, salt_path, branch, {0, state, clip0}}, (hipStream_t)stream);
+}
+
+// dr = ds f over rows [clips T][W], zeros in the dead rows (ds never read there): the gradient that enters a branch the forward
+// dropped, f drawn again from the same counters.  The counter of flat element i is clip0 T W + i, so the draw is a function of the
+// element alone: the 16-byte interior (n4 granules where both pointers allow it) and the dword tail give the same bits.
+__device__ __forceinline__ float branch_drop_grad_elem(const float* __restrict__ ds, int64_t i, const int32_t* __restrict__ seq_len,
+                                                       int T, int W, const LnDrop& dp, uint64_t se, uint64_t sp, float inv, float v,
+                                                       bool have) {
+#pragma clang fp contract(off)
+    const int64_t row = i / W;
+    const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+    if (t >= ln_len(seq_len, b, T)) return 0.f;
+    const float fp = sa_path_factor(sp, 2 * ((uint64_t)dp.dw.clip0 + (uint64_t)b) + (uint64_t)dp.branch, dp.keep_path);
+    const uint64_t e = (uint64_t)dp.dw.clip0 * (uint64_t)T * (uint64_t)W + (uint64_t)i;
+    const float d = have ? v : ds[i];
+    return d * sa_branch_factor(se, e, dp.keep, inv, fp);
+}
+
+__global__ __launch_bounds__(256) void branch_drop_grad_kernel(const float* __restrict__ ds, float* __restrict__ dr,
+                                                               const int32_t* __restrict__ seq_len, int T, int W, int64_t n4,
+                                                               int64_t count, LnDrop dp) {
+    const int64_t step = (int64_t)gridDim.x * 256;
+    const uint64_t se = sa_drop_stream(dp.dw, dp.salt_elem), sp = sa_drop_stream(dp.dw, dp.salt_path);
+    const float inv = __fdiv_rn(1.0f, dp.keep);
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += step) {
+        // (W >= 8: a granule lies in one row or two.  Both live: one 16-byte read; else its live elements alone are read)
+        const int64_t i = 4 * g, row0 = i / W, row1 = (i + 3) / W;
+        const int b0 = (int)(row0 / T), b1 = (int)(row1 / T);
+        const bool live = (int)(row0 - (int64_t)b0 * T) < ln_len(seq_len, b0, T) && (int)(row1 - (int64_t)b1 * T) < ln_len(seq_len, b1, T);
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) q = reinterpret_cast<const float4*>(ds)[g];
+        float4 o;
+        o.x = branch_drop_grad_elem(ds, i, seq_len, T, W, dp, se, sp, inv, q.x, live);
+        o.y = branch_drop_grad_elem(ds, i + 1, seq_len, T, W, dp, se, sp, inv, q.y, live);
+        o.z = branch_drop_grad_elem(ds, i + 2, seq_len, T, W, dp, se, sp, inv, q.z, live);
+        o.w = branch_drop_grad_elem(ds, i + 3, seq_len, T, W, dp, se, sp, inv, q.w, live);
+        reinterpret_cast<float4*>(dr)[g] = o;
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += step)
+        dr[i] = branch_drop_grad_elem(ds, i, seq_len, T, W, dp, se, sp, inv, 0.f, false);
+}
+
+static int branch_drop_grad_run(const char* who, const float* ds, float* dr, int clips, int T, int W, const int32_t* seq_len, LnDrop dp,
+                                hipStream_t stream) {
+    VL_CHECK(ds && dr, "%s: null pointer", who);
+    if (int rc = ln_check(who, clips, T, W)) return rc;
+    if (int rc = ln_drop_check(who, dp, clips)) return rc;
+    const int64_t count = (int64_t)clips * T * W;
+    const int64_t n4 = ((uintptr_t)ds & 15) == 0 && ((uintptr_t)dr & 15) == 0 ? count / 4 : 0;
+    const int64_t work = (count + 3) / 4, blocks = (work + 255) / 256;
+    hipLaunchKernelGGL(branch_drop_grad_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, ds, dr, seq_len, T,
+                       W, n4, count, dp);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_branch_drop_grad(const float* ds, float* dr, int clips, int T, int W, const int32_t* seq_len, float keep,
+                                   float keep_path, uint64_t seed, uint32_t salt_elem, uint32_t salt_path, int branch, int64_t clip0,
+                                   vl_stream_t stream) {
+    return branch_drop_grad_run("vl_branch_drop_grad", ds, dr, clips, T, W, seq_len,
+                                LnDrop{keep, keep_path, salt_elem, salt_path, branch, {seed, nullptr, clip0}}, (hipStream_t)stream);
+}
+
+extern "C" int vl_branch_drop_grad_st(const float* ds, float* dr, int clips, int T, int W, const int32_t* seq_len, float keep,
+                                      float keep_path, const vl_step_state* state, uint32_t salt_elem, uint32_t salt_path, int branch,
+                                      int64_t clip0, vl_stream_t stream) {
+    VL_CHECK(state, "vl_branch_drop_grad_st: null pointer");
+    return branch_drop_grad_run("vl_branch_drop_grad_st", ds, dr, clips, T, W, seq_len,
+                                LnDrop{keep, keep_path, salt_elem, salt_path, branch, {0, state, clip0}}, (hipStream_t)stream);
 }
 
 extern "C" int vl_layer_norm_bwd(const float* dy, const float* s, const float* gamma, const float* stats, const float* dres, float* dx,

@@ -35,9 +35,14 @@ __device__ __forceinline__ void sa_stage(float* __restrict__ tile, const float* 
     }
 }
 
+// DROP (vl_mhsa_drop_fwd): P is stored UNDROPPED, and the thread that stores element (q, k) puts P M / keep back into the
+// score tile, from which ctx is formed: one more barrier, the same LDS.  The draw's counter is the element's index in the P of the
+// whole batch, (((clip0 + b) heads + h) T + q) T + k.  Without DROP the kernel is what it was, instruction for instruction.
+template <bool DROP>
 __global__ __launch_bounds__(SA_THREADS) void mhsa_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ pos,
                                                               const int32_t* __restrict__ seq_len, float* __restrict__ P,
-                                                              float* __restrict__ ctx, int T, int H, int heads, int dh, float scale) {
+                                                              float* __restrict__ ctx, int T, int H, int heads, int dh, float scale,
+                                                              float keep, uint32_t salt, SaDraw dw) {
     extern __shared__ __attribute__((aligned(16))) float sa_lds[];
     const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -74,9 +79,23 @@ __global__ __launch_bounds__(SA_THREADS) void mhsa_fwd_kernel(const float* __res
     }
     __syncthreads();
     float* Pb = P + (int64_t)blockIdx.x * T * T;
-    for (int idx = tid; idx < T * T; idx += SA_THREADS) {
-        const int q = idx / T, k = idx - q * T;
-        Pb[idx] = (q < L && k < L) ? S[q * SP + k] : 0.f;
+    if (DROP) {
+        const uint64_t ds = sa_drop_stream(dw, salt);
+        const uint64_t e0 = ((uint64_t)dw.clip0 * heads + blockIdx.x) * (uint64_t)(T * T);
+        const float inv = __fdiv_rn(1.0f, keep);
+        for (int idx = tid; idx < T * T; idx += SA_THREADS) {
+            const int q = idx / T, k = idx - q * T;
+            const bool live = q < L && k < L;
+            const float p = live ? S[q * SP + k] : 0.f;
+            Pb[idx] = p;
+            if (live) S[q * SP + k] = sa_drop_kept(ds, e0 + idx, keep) ? __fmul_rn(p, inv) : 0.f;
+        }
+        __syncthreads();
+    } else {
+        for (int idx = tid; idx < T * T; idx += SA_THREADS) {
+            const int q = idx / T, k = idx - q * T;
+            Pb[idx] = (q < L && k < L) ? S[q * SP + k] : 0.f;
+        }
     }
     // ctx = P V: a thread per (q, d), lanes over d, k ascending
     for (int idx = tid; idx < T * dh; idx += SA_THREADS) {
@@ -90,10 +109,14 @@ __global__ __launch_bounds__(SA_THREADS) void mhsa_fwd_kernel(const float* __res
     }
 }
 
+// DROP (vl_mhsa_drop_bwd): the mask is drawn again from the counters.  The thread that stages element (q, k) of P leaves the DROPPED
+// weight P M / keep in Ps (what dV needs) and the factor M / keep in the dS tile, where the same thread multiplies it into dP; the
+// softmax's backward then reads the undropped P of its row from global memory.  No mask buffer, no second P, the same LDS.
+template <bool DROP>
 __global__ __launch_bounds__(SA_THREADS) void mhsa_bwd_kernel(const float* __restrict__ dctx, const float* __restrict__ qkv,
                                                               const float* __restrict__ P, const int32_t* __restrict__ seq_len,
                                                               float* __restrict__ dqkv, float* __restrict__ dposp, int T, int H,
-                                                              int heads, int dh, float scale) {
+                                                              int heads, int dh, float scale, float keep, uint32_t salt, SaDraw dw) {
     extern __shared__ __attribute__((aligned(16))) float sa_lds[];
     const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -107,9 +130,21 @@ __global__ __launch_bounds__(SA_THREADS) void mhsa_bwd_kernel(const float* __res
     sa_stage(A, dctx, row0, H, h * dh, L, dh, dhp, tid);
     sa_stage(B, qkv, row0, 3 * H, 2 * H + h * dh, L, dh, dhp, tid);
     const float* Pb = P + (int64_t)blockIdx.x * T * T;
-    for (int idx = tid; idx < L * L; idx += SA_THREADS) {
-        const int q = idx / L, k = idx - q * L;
-        Ps[q * SP + k] = Pb[q * T + k];
+    if (DROP) {
+        const uint64_t ds = sa_drop_stream(dw, salt);
+        const uint64_t e0 = ((uint64_t)dw.clip0 * heads + blockIdx.x) * (uint64_t)(T * T);
+        const float inv = __fdiv_rn(1.0f, keep);
+        for (int idx = tid; idx < L * L; idx += SA_THREADS) {
+            const int q = idx / L, k = idx - q * L;
+            const float f = sa_drop_kept(ds, e0 + (uint64_t)(q * T + k), keep) ? inv : 0.f;
+            Ps[q * SP + k] = __fmul_rn(Pb[q * T + k], f);
+            dS[q * SP + k] = f;
+        }
+    } else {
+        for (int idx = tid; idx < L * L; idx += SA_THREADS) {
+            const int q = idx / L, k = idx - q * L;
+            Ps[q * SP + k] = Pb[q * T + k];
+        }
     }
     __syncthreads();
     // dP = dO V^T: a thread per live (q, k), lanes over k
@@ -119,7 +154,7 @@ __global__ __launch_bounds__(SA_THREADS) void mhsa_bwd_kernel(const float* __res
         const float* vr = B + k * dhp;
         float acc = 0.f;
         for (int d = 0; d < dh; ++d) acc = __fmaf_rn(ar[d], vr[d], acc);
-        dS[q * SP + k] = acc;
+        dS[q * SP + k] = DROP ? __fmul_rn(acc, dS[q * SP + k]) : acc;      // (the factor this thread left there)
     }
     // dV = P^T dO: a thread per (k, d), q ascending; dead rows zero
     float* dq = dqkv + row0 * 3 * H + h * dh;
@@ -133,7 +168,7 @@ __global__ __launch_bounds__(SA_THREADS) void mhsa_bwd_kernel(const float* __res
     __syncthreads();
     // dS = P o (dP - rowsum(dP o P)): one wave per live row, in place
     for (int q = wave; q < L; q += SA_WAVES) {
-        const float p = lane < L ? Ps[q * SP + lane] : 0.f;
+        const float p = lane < L ? (DROP ? Pb[q * T + lane] : Ps[q * SP + lane]) : 0.f;
         const float g = lane < L ? dS[q * SP + lane] : 0.f;
         const float r = wave_sum(p * g);
         if (lane < L) dS[q * SP + lane] = p * (g - r);
@@ -191,9 +226,13 @@ static int sa_check(const char* who, int batch, int T, int H, int heads) {
 static int sa_raise_lds() {
     static bool done = false;
     if (!done) {
-        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)sa_fwd_lds(SA_MAX_T, SA_MAX_DH)));
-        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)sa_bwd_lds(SA_MAX_T, SA_MAX_DH)));
+        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)sa_fwd_lds(SA_MAX_T, SA_MAX_DH)));
+        VL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mhsa_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)sa_bwd_lds(SA_MAX_T, SA_MAX_DH)));
         done = true;
     }
@@ -206,8 +245,8 @@ extern "C" int vl_mhsa_fwd(const float* qkv, const float* pos, const int32_t* se
     if (int rc = sa_check("vl_mhsa_fwd", batch, T, H, heads)) return rc;
     if (int rc = sa_raise_lds()) return rc;
     const int dh = H / heads;
-    hipLaunchKernelGGL(mhsa_fwd_kernel, dim3(batch * heads), dim3(SA_THREADS), sa_fwd_lds(T, dh), (hipStream_t)stream, qkv, pos, seq_len,
-                       P, ctx, T, H, heads, dh, 1.0f / sqrtf((float)dh));
+    hipLaunchKernelGGL(mhsa_fwd_kernel<false>, dim3(batch * heads), dim3(SA_THREADS), sa_fwd_lds(T, dh), (hipStream_t)stream, qkv, pos,
+                       seq_len, P, ctx, T, H, heads, dh, 1.0f / sqrtf((float)dh), 1.0f, 0u, SaDraw{0, nullptr, 0});
     VL_LAUNCH_CHECK();
     return 0;
 }
@@ -218,10 +257,72 @@ extern "C" int vl_mhsa_bwd(const float* dctx, const float* qkv, const float* P, 
     if (int rc = sa_check("vl_mhsa_bwd", batch, T, H, heads)) return rc;
     if (int rc = sa_raise_lds()) return rc;
     const int dh = H / heads;
-    hipLaunchKernelGGL(mhsa_bwd_kernel, dim3(batch * heads), dim3(SA_THREADS), sa_bwd_lds(T, dh), (hipStream_t)stream, dctx, qkv, P,
-                       seq_len, dqkv, dposp, T, H, heads, dh, 1.0f / sqrtf((float)dh));
+    hipLaunchKernelGGL(mhsa_bwd_kernel<false>, dim3(batch * heads), dim3(SA_THREADS), sa_bwd_lds(T, dh), (hipStream_t)stream, dctx, qkv, P,
+                       seq_len, dqkv, dposp, T, H, heads, dh, 1.0f / sqrtf((float)dh), 1.0f, 0u, SaDraw{0, nullptr, 0});
     VL_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- the drop forms: the same launch shape and LDS, the seed given or formed from the step state when the kernel runs ----
+static int sa_drop_check(const char* who, float keep, int64_t clip0, int batch) {
+    VL_CHECK(sa_keep_ok(keep), "%s: keep %g must lie in (0, 1]", who, (double)keep);
+    VL_CHECK(clip0 >= 0 && clip0 < (1ll << 31) - batch, "%s: clip0 %lld must lie in 0 .. 2^31 - batch", who, (long long)clip0);
+    return 0;
+}
+
+static int mhsa_drop_fwd_run(const char* who, const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch,
+                             int T, int H, int heads, float keep, uint32_t salt, SaDraw dw, hipStream_t stream) {
+    VL_CHECK(qkv && P && ctx, "%s: null pointer", who);
+    if (int rc = sa_check(who, batch, T, H, heads)) return rc;
+    if (int rc = sa_drop_check(who, keep, dw.clip0, batch)) return rc;
+    if (int rc = sa_raise_lds()) return rc;
+    const int dh = H / heads;
+    hipLaunchKernelGGL(mhsa_fwd_kernel<true>, dim3(batch * heads), dim3(SA_THREADS), sa_fwd_lds(T, dh), stream, qkv, pos, seq_len, P, ctx,
+                       T, H, heads, dh, 1.0f / sqrtf((float)dh), keep, salt, dw);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+static int mhsa_drop_bwd_run(const char* who, const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv,
+                             float* dposp, int batch, int T, int H, int heads, float keep, uint32_t salt, SaDraw dw, hipStream_t stream) {
+    VL_CHECK(dctx && qkv && P && dqkv, "%s: null pointer", who);
+    if (int rc = sa_check(who, batch, T, H, heads)) return rc;
+    if (int rc = sa_drop_check(who, keep, dw.clip0, batch)) return rc;
+    if (int rc = sa_raise_lds()) return rc;
+    const int dh = H / heads;
+    hipLaunchKernelGGL(mhsa_bwd_kernel<true>, dim3(batch * heads), dim3(SA_THREADS), sa_bwd_lds(T, dh), stream, dctx, qkv, P, seq_len,
+                       dqkv, dposp, T, H, heads, dh, 1.0f / sqrtf((float)dh), keep, salt, dw);
+    VL_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vl_mhsa_drop_fwd(const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch, int T, int H,
+                                int heads, float keep, uint64_t seed, uint32_t salt, int64_t clip0, vl_stream_t stream) {
+    return mhsa_drop_fwd_run("vl_mhsa_drop_fwd", qkv, pos, seq_len, P, ctx, batch, T, H, heads, keep, salt, SaDraw{seed, nullptr, clip0},
+                             (hipStream_t)stream);
+}
+
+extern "C" int vl_mhsa_drop_fwd_st(const float* qkv, const float* pos, const int32_t* seq_len, float* P, float* ctx, int batch, int T,
+                                   int H, int heads, float keep, const vl_step_state* state, uint32_t salt, int64_t clip0,
+                                   vl_stream_t stream) {
+    VL_CHECK(state, "vl_mhsa_drop_fwd_st: null pointer");
+    return mhsa_drop_fwd_run("vl_mhsa_drop_fwd_st", qkv, pos, seq_len, P, ctx, batch, T, H, heads, keep, salt, SaDraw{0, state, clip0},
+                             (hipStream_t)stream);
+}
+
+extern "C" int vl_mhsa_drop_bwd(const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv, float* dposp,
+                                int batch, int T, int H, int heads, float keep, uint64_t seed, uint32_t salt, int64_t clip0,
+                                vl_stream_t stream) {
+    return mhsa_drop_bwd_run("vl_mhsa_drop_bwd", dctx, qkv, P, seq_len, dqkv, dposp, batch, T, H, heads, keep, salt,
+                             SaDraw{seed, nullptr, clip0}, (hipStream_t)stream);
+}
+
+extern "C" int vl_mhsa_drop_bwd_st(const float* dctx, const float* qkv, const float* P, const int32_t* seq_len, float* dqkv, float* dposp,
+                                   int batch, int T, int H, int heads, float keep, const vl_step_state* state, uint32_t salt,
+                                   int64_t clip0, vl_stream_t stream) {
+    VL_CHECK(state, "vl_mhsa_drop_bwd_st: null pointer");
+    return mhsa_drop_bwd_run("vl_mhsa_drop_bwd_st", dctx, qkv, P, seq_len, dqkv, dposp, batch, T, H, heads, keep, salt,
+                             SaDraw{0, state, clip0}, (hipStream_t)stream);
 }
 
 extern "C" int vl_live_rows(const float* x, const int32_t* seq_len, float* y, int batch, int T, int W, vl_stream_t stream) {

@@ -13,6 +13,7 @@ classifier -> fc -> conv5..conv1, i.e. the order backward produces gradients, so
 data-parallel all-reduce of the first (large: fc6 = 85 % of bytes) bucket overlaps the conv backward.
 """
 import collections
+import copy
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
@@ -60,6 +61,10 @@ class NetConfig:
     sa_positions: Optional[str] = None          # rnn_cell mhsa: "relative" (None: a learned bias per head and offset) | "none"
     sa_block: Optional[str] = None              # rnn_cell mhsa: "plain" (None: the bare attention layer) | "encoder": the pre-LN encoder block (encoder_specs)
     sa_ffn_dim: Optional[int] = None            # sa_block encoder: the feed-forward width F, 8..4096; None = 4 lstm_hidden
+    sa_attn_dropout: Optional[float] = None     # rnn_cell mhsa: dropout rate on the softmax weights of a training forward, [0, 1); None / 0 = off
+    sa_dropout: Optional[float] = None          # sa_block encoder: dropout rate on the elements of the two residual branches; None / 0 = off
+    sa_drop_path: Optional[float] = None        # sa_block encoder: stochastic depth, layer l of L keeps a clip's branch with 1 - p (l + 1) / L; None / 0 = off
+    sa_drop_salt: int = 0                       # which mask streams the self-attention dropouts draw from (SaDrop): 0 for an LRCNEngine of its own
     frame_fusion: Optional[Tuple[str, str]] = None   # classifier fc: (early|late, avg|last) (model.py:103-106,149-151)
     dropout_keep_prob: float = 0.0              # <= 0 disables (lstm.py:52)
     optimizer: str = "sgd"                      # defs.optim.{sgd, adam}
@@ -190,19 +195,33 @@ SA_BLOCKS = ("plain", "encoder")
 SA_FFN_MIN, SA_FFN_MAX = 8, 4096
 
 
-def check_sa_block(cell, hidden=1, sa_block=None, sa_ffn_dim=None):
+def check_sa_rate(key, rate):
+    """A dropout rate of the self-attention model (sa_attn_dropout, sa_dropout, sa_drop_path) as a float in [0, 1); None read as 0
+    (off).  Refused by the key's name: bools, strings, NaN, values outside [0, 1)."""
+    if rate is None or (isinstance(rate, str) and rate == "None"):
+        return 0.0
+    if isinstance(rate, (bool, str)) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 <= float(rate) < 1.0:
+        raise VltfError("%s must be a rate in [0, 1), got [%s]" % (key, rate))
+    return float(rate)
+
+
+def check_sa_block(cell, hidden=1, sa_block=None, sa_ffn_dim=None, sa_dropout=None, sa_drop_path=None):
     """-> the feed-forward width F of sa_block encoder (sa_ffn_dim, default 4 H), or None for sa_block plain (the default: the bare
-    attention layer of mhsa_names) and for every other cell.  Refused by name: either key without rnn_cell mhsa, sa_ffn_dim without
-    sa_block encoder, a block that is neither, F not an integer in 8..4096."""
-    given = lambda v: v not in (None, "None")
+    attention layer of mhsa_names) and for every other cell.  Refused by name: a key without rnn_cell mhsa; sa_ffn_dim, sa_dropout or
+    sa_drop_path without sa_block encoder; a block that is neither; F not an integer in 8..4096; a rate check_sa_rate refuses."""
+    given = lambda v: not (v is None or (isinstance(v, str) and v == "None"))
     if cell != "mhsa":
-        for k, v in (("sa_block", sa_block), ("sa_ffn_dim", sa_ffn_dim)):
+        for k, v in (("sa_block", sa_block), ("sa_ffn_dim", sa_ffn_dim), ("sa_dropout", sa_dropout), ("sa_drop_path", sa_drop_path)):
             if given(v):
                 raise VltfError("%s is a key of rnn_cell mhsa, but the cell is [%s]" % (k, cell))
         return None
     block = sa_block if given(sa_block) else "plain"
     if block not in SA_BLOCKS:
         raise VltfError("sa_block must be plain or encoder, got [%s]" % (block,))
+    for k, v in (("sa_dropout", sa_dropout), ("sa_drop_path", sa_drop_path)):
+        check_sa_rate(k, v)
+        if block == "plain" and given(v):
+            raise VltfError("%s is a key of sa_block encoder, but the block is [plain]" % k)
     if block == "plain":
         if given(sa_ffn_dim):
             raise VltfError("sa_ffn_dim is a key of sa_block encoder, but the block is [plain]")
@@ -213,17 +232,20 @@ def check_sa_block(cell, hidden=1, sa_block=None, sa_ffn_dim=None):
     return int(F)
 
 
-def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="avg", what="rnn_cell", sa_block=None, sa_ffn_dim=None):
-    """-> (heads, positions) of rnn_cell mhsa, or None for every other cell.  Refused: sa_heads / sa_positions / sa_block / sa_ffn_dim
-    without mhsa; with it, fusion state, whatever misses a limit of the launches (vltf.h: vl_mhsa_fwd) and what check_sa_block
-    refuses, before anything is allocated.  The block's feed-forward width is check_sa_block's answer."""
-    given = lambda v: v not in (None, "None")
+def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="avg", what="rnn_cell", sa_block=None, sa_ffn_dim=None,
+               sa_attn_dropout=None, sa_dropout=None, sa_drop_path=None):
+    """-> (heads, positions) of rnn_cell mhsa, or None for every other cell.  Refused: sa_heads / sa_positions / sa_block / sa_ffn_dim /
+    sa_attn_dropout / sa_dropout / sa_drop_path without mhsa; with it, fusion state, whatever misses a limit of the launches (vltf.h:
+    vl_mhsa_fwd), a rate check_sa_rate refuses and what check_sa_block refuses, before anything is allocated.  The block's
+    feed-forward width is check_sa_block's answer, the rates' plan is sa_drop_of's."""
+    given = lambda v: not (v is None or (isinstance(v, str) and v == "None"))
     if cell != "mhsa":
-        check_sa_block(cell, hidden, sa_block, sa_ffn_dim)
-        for k, v in (("sa_heads", sa_heads), ("sa_positions", sa_positions)):
+        check_sa_block(cell, hidden, sa_block, sa_ffn_dim, sa_dropout, sa_drop_path)
+        for k, v in (("sa_heads", sa_heads), ("sa_positions", sa_positions), ("sa_attn_dropout", sa_attn_dropout)):
             if given(v):
                 raise VltfError("%s is a key of rnn_cell mhsa, but the cell is [%s]" % (k, cell))
         return None
+    check_sa_rate("sa_attn_dropout", sa_attn_dropout)
     H, T = int(hidden), int(T)
     if fusion == "state":
         raise VltfError("%s: mhsa with fusion state is not built: a self-attention layer has no final state (use last)" % what)
@@ -231,7 +253,7 @@ def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="av
         raise VltfError("%s: mhsa needs 1 <= T <= %d steps per clip (a head's score tile lives in LDS), got %d" % (what, ops.MHSA_MAX_T, T))
     if not 1 <= H <= ops.MHSA_MAX_HIDDEN:
         raise VltfError("%s: mhsa needs a width H <= %d, got %d" % (what, ops.MHSA_MAX_HIDDEN, H))
-    check_sa_block(cell, H, sa_block, sa_ffn_dim)
+    check_sa_block(cell, H, sa_block, sa_ffn_dim, sa_dropout, sa_drop_path)
     if not given(sa_heads):
         heads = 4 if H % 4 == 0 else 1
     elif isinstance(sa_heads, bool) or not isinstance(sa_heads, (int, np.integer)) or int(sa_heads) < 1:
@@ -247,6 +269,59 @@ def check_mhsa(cell, hidden=1, T=1, sa_heads=None, sa_positions=None, fusion="av
     if positions not in SA_POSITIONS:
         raise VltfError("sa_positions must be relative or none, got [%s]" % (positions,))
     return heads, positions
+
+
+class SaDrop:
+    """The dropouts of the self-attention model in one engine: the three rates as keeps, the node salt, and -- bound to a
+    training pass by bind() -- what its launches draw with (clip0 and the seed, or the step state of a captured step).  None stands
+    for "every rate is 0" wherever one is passed: then no drop launch is called and no buffer of theirs exists."""
+
+    def __init__(self, attn, elem, path, layers, node=0):
+        self.attn, self.elem, self.path, self.layers, self.node = float(attn), float(elem), float(path), int(layers), int(node)
+        self.attn_keep, self.elem_keep = sa_keep(attn), sa_keep(elem)
+        self.branch = self.elem > 0 or self.path > 0           # the two residual branches are dropped (sa_block encoder)
+        self.kw = None
+
+    @staticmethod
+    def plan(attn, elem, path, layers, node=0):
+        """-> a SaDrop, or None with every rate None / 0 (the rates as check_mhsa let them through)."""
+        rates = [check_sa_rate(k, v) for k, v in (("sa_attn_dropout", attn), ("sa_dropout", elem), ("sa_drop_path", path))]
+        return SaDrop(*rates, layers, node) if any(r > 0 for r in rates) else None
+
+    def path_keep(self, layer):
+        return sa_path_keep(self.path, layer, self.layers)
+
+    def salt(self, layer, site):
+        return ops.sa_drop_salt(self.node, layer, site)
+
+    def bind(self, clip0, seed=None, state=None):
+        d = copy.copy(self)
+        d.kw = dict(clip0=int(clip0), seed=seed, state=state)
+        return d
+
+    def branch_kw(self, layer, branch):
+        """The arguments of add_layer_norm_drop_fwd / branch_drop_grad for branch 0 (attention) | 1 (feed-forward) of `layer`."""
+        return dict(keep=self.elem_keep, keep_path=self.path_keep(layer), salt_elem=self.salt(layer, ops.SA_DROP_SITES[1 + branch]),
+                    salt_path=self.salt(layer, "path"), branch=branch, **self.kw)
+
+    def weights_kw(self, layer):
+        return dict(keep=self.attn_keep, salt=self.salt(layer, "weights"), **self.kw)
+
+
+def sa_keep(rate):
+    """The keep probability of a rate as the launches get it: the fp32 nearest to 1 - rate, formed in double."""
+    return float(np.float32(1.0 - float(rate)))
+
+
+def sa_path_keep(rate, layer, layers):
+    """k_l = 1 - p (l + 1) / L (Huang et al. 2016, the linear rule; it drops in a one-layer model too), as the fp32 the launches get."""
+    return float(np.float32(1.0 - float(rate) * (int(layer) + 1) / int(layers)))
+
+
+def sa_drop_of(cfg, layers, node=None):
+    """The SaDrop of a NetConfig / PipelineSpec (its sa_attn_dropout, sa_dropout, sa_drop_path), or None where all are off."""
+    return SaDrop.plan(getattr(cfg, "sa_attn_dropout", None), getattr(cfg, "sa_dropout", None), getattr(cfg, "sa_drop_path", None),
+                       layers, getattr(cfg, "sa_drop_salt", 0) if node is None else node)
 
 
 def mhsa_buffers(buf, rows, T, H, heads, positions, training):
@@ -289,13 +364,14 @@ def encoder_specs(layers, d, H, F, heads, T, scope="", positions="relative", bac
     return [s for grp in (reversed(groups) if backward else groups) for s in grp]
 
 
-def encoder_buffers(buf, rows, T, H, F, heads, positions, layers, training):
+def encoder_buffers(buf, rows, T, H, F, heads, positions, layers, training, drop=None):
     """-> E = dict(x0, n0, st0, layers=[S ...]): the embedding's output x0 (the residual stream entering layer 0), its norm n0 with the
     stats st0; per layer qkv, P, ctx, the attention's output o, a = stream + o, n2 = LN(a) with st2, u, f = gelu(u), m, the stream xs
     leaving the layer and hseq = LN(xs) with sty -- the next layer's norm1, or behind the last layer the final norm, which is what the
     fusions read (hence the name the other layer kinds use).  Training: per layer dout (the gradient of hseq), dxs (of xs), df (du in
     place), dn2, da, dctx, dqkv, dposp and the per-clip partials gb2 / gby of the two norms' gradients; dn0, dx0, gb0 in front.  Every
-    layer has its own: the parameter gradients read them from the second stream while the chain goes on."""
+    layer has its own: the parameter gradients read them from the second stream while the chain goes on.  drop (a SaDrop that drops
+    the branches, training): per layer do and dm, the gradients that enter the two dropped branches (vl_branch_drop_grad)."""
     clips = rows // T
     E = dict(x0=buf(rows, H), n0=buf(rows, H), st0=buf(rows, 2), layers=[])
     if training:
@@ -308,43 +384,60 @@ def encoder_buffers(buf, rows, T, H, F, heads, positions, layers, training):
                      dqkv=buf(rows, 3 * H), gb2=buf(clips, 2 * H), gby=buf(clips, 2 * H))
             if positions == "relative":
                 S["dposp"] = buf(clips, heads * (2 * T - 1))
+            if drop is not None and drop.branch:
+                S.update(do=buf(rows, H), dm=buf(rows, H))
         E["layers"].append(S)
     return E
 
 
-def encoder_forward(E, P, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk):
+def encoder_forward(E, P, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk, drop=None):
     """The block stack on xin [rows, d] -> the final norm's output.  The embedding and the qkv projections take the workspace (they
     follow conv_math, as the GRU's input projection); the output projection and the two feed-forward products do not (fp32 always, as
     attention_pool's).  Every residual add is inside the norm launch that follows it.  lk: {} or {seq_len: lengths} -- no launch reads
-    a dead row of what a launch wrote, and a dead row of a product's output (a bias) is read by nothing."""
+    a dead row of what a launch wrote, and a dead row of a product's output (a bias) is read by nothing.  drop: a bound SaDrop in a
+    TRAINING forward with a rate on (the drop forms of the attention and of the two add-and-norm launches), else None."""
     v = lambda l, name: P[encoder_var(scope, l, name)]
     layers = E["layers"]
+
+    def add_norm(l, branch, x, r, sum, y, gamma, beta, stats):
+        if drop is not None and drop.branch:
+            ops.add_layer_norm_drop_fwd(x, r, sum, y, gamma, beta, stats, b, T, H, **drop.branch_kw(l, branch), **lk)
+        else:
+            ops.add_layer_norm_fwd(x, r, sum, y, gamma, beta, stats, b, T, H, **lk)
+
     ops.gemm(xin, v(None, "kernel"), E["x0"], rows, H, d, bias=v(None, "bias"), ws=ws)
     ops.add_layer_norm_fwd(E["x0"], None, None, E["n0"], v(0, "norm1_gamma"), v(0, "norm1_beta"), E["st0"], b, T, H, **lk)
     xs, nin = E["x0"], E["n0"]
     for l, S in enumerate(layers):
         ops.gemm(nin, v(l, "qkv_kernel"), S["qkv"], rows, 3 * H, H, bias=v(l, "qkv_bias"), ws=ws)
-        ops.mhsa_fwd(S["qkv"], v(l, "position_bias") if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads, **lk)
+        pos = v(l, "position_bias") if positions == "relative" else None
+        if drop is not None and drop.attn > 0:
+            ops.mhsa_drop_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **drop.weights_kw(l), **lk)
+        else:
+            ops.mhsa_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **lk)
         ops.gemm(S["ctx"], v(l, "out_kernel"), S["o"], rows, H, H, bias=v(l, "out_bias"))
-        ops.add_layer_norm_fwd(xs, S["o"], S["a"], S["n2"], v(l, "norm2_gamma"), v(l, "norm2_beta"), S["st2"], b, T, H, **lk)
+        add_norm(l, 0, xs, S["o"], S["a"], S["n2"], v(l, "norm2_gamma"), v(l, "norm2_beta"), S["st2"])
         ops.gemm(S["n2"], v(l, "ffn1_kernel"), S["u"], rows, F, H, bias=v(l, "ffn1_bias"))
         ops.gelu_fwd(S["u"], S["f"], rows * F)
         ops.gemm(S["f"], v(l, "ffn2_kernel"), S["m"], rows, H, F, bias=v(l, "ffn2_bias"))
         last = l + 1 == len(layers)
         gy, by = (v(-1, "gamma"), v(-1, "beta")) if last else (v(l + 1, "norm1_gamma"), v(l + 1, "norm1_beta"))
-        ops.add_layer_norm_fwd(S["a"], S["m"], S["xs"], S["hseq"], gy, by, S["sty"], b, T, H, **lk)
+        add_norm(l, 1, S["a"], S["m"], S["xs"], S["hseq"], gy, by, S["sty"])
         xs, nin = S["xs"], S["hseq"]
     return nin
 
 
-def encoder_backward(E, P, G, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk, param_grads):
+def encoder_backward(E, P, G, scope, xin, rows, b, T, d, H, F, heads, positions, ws, lk, param_grads, drop=None):
     """From layers[-1]["dout"] (the gradient of the final norm's output) to E["dx0"] (the gradient of the embedding's output) and every
     gradient of the stack but the embedding's, which the caller forms as it forms its first layer's.  The gradient on the residual
     stream enters each norm's backward as dres: there is no add launch.  param_grads(launch): launch(ws, small_ws) forms parameter
-    gradients from buffers that are complete on the calling stream (LRCNEngine: on the second stream)."""
+    gradients from buffers that are complete on the calling stream (LRCNEngine: on the second stream).  drop: the bound SaDrop the
+    forward ran with, or None.  With the branches dropped, the gradient that enters a branch is the stream's gradient times the
+    branch's factor (vl_branch_drop_grad: dm from dxs, do from da), and the products and parameter gradients behind it read that."""
     v = lambda l, name: P[encoder_var(scope, l, name)]
     g = lambda l, name: G[encoder_var(scope, l, name)]
     layers = E["layers"]
+    branch = drop is not None and drop.branch
 
     def norm_grads(l, which, part, sws):                      # the per-clip partials, summed over the clips in a fixed order
         names = ("gamma", "beta") if l < 0 else (which + "_gamma", which + "_beta")
@@ -360,11 +453,14 @@ def encoder_backward(E, P, G, scope, xin, rows, b, T, d, H, F, heads, positions,
         xs_in, nin, st_in = (below["xs"], below["hseq"], below["sty"]) if l else (E["x0"], E["n0"], E["st0"])
         dnin, dxs_in, gb_in = (below["dout"], below["dxs"], below["gby"]) if l else (E["dn0"], E["dx0"], E["gb0"])
         # the feed-forward block: dm = dxs; df = dm W2^T, du = df gelu'(u) in place, dn2 = du W1^T; norm2 with the stream's gradient
-        ops.gemm(S["dxs"], v(l, "ffn2_kernel"), S["df"], rows, F, H, transb=True)
+        dm = S["dm"] if branch else S["dxs"]
+        if branch:
+            ops.branch_drop_grad(S["dxs"], dm, b, T, H, **drop.branch_kw(l, 1), **lk)
+        ops.gemm(dm, v(l, "ffn2_kernel"), S["df"], rows, F, H, transb=True)
 
-        def ffn2_grads(ws_, sws, S=S, l=l):
-            ops.gemm(S["f"], S["dxs"], g(l, "ffn2_kernel"), F, H, rows, transa=True)
-            ops.colsum(S["dxs"], g(l, "ffn2_bias"), sws, rows, H)
+        def ffn2_grads(ws_, sws, S=S, l=l, dm=dm):
+            ops.gemm(S["f"], dm, g(l, "ffn2_kernel"), F, H, rows, transa=True)
+            ops.colsum(dm, g(l, "ffn2_bias"), sws, rows, H)
         param_grads(ffn2_grads)
         ops.gelu_bwd(S["df"], S["u"], S["df"], rows * F)
         ops.gemm(S["df"], v(l, "ffn1_kernel"), S["dn2"], rows, H, F, transb=True)
@@ -376,14 +472,20 @@ def encoder_backward(E, P, G, scope, xin, rows, b, T, d, H, F, heads, positions,
             norm_grads(l, "norm2", S["gb2"], sws)
         param_grads(ffn1_grads)
         # the attention: do = da; through the output projection, ONE launch for every (clip, head), the qkv projection; norm1
-        ops.gemm(S["da"], v(l, "out_kernel"), S["dctx"], rows, H, H, transb=True)
-        ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **lk)
+        do = S["do"] if branch else S["da"]
+        if branch:
+            ops.branch_drop_grad(S["da"], do, b, T, H, **drop.branch_kw(l, 0), **lk)
+        ops.gemm(do, v(l, "out_kernel"), S["dctx"], rows, H, H, transb=True)
+        if drop is not None and drop.attn > 0:
+            ops.mhsa_drop_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **drop.weights_kw(l), **lk)
+        else:
+            ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **lk)
         ops.gemm(S["dqkv"], v(l, "qkv_kernel"), dnin, rows, H, 3 * H, transb=True, ldb=3 * H, ws=ws)
         ops.layer_norm_bwd(dnin, xs_in, v(l, "norm1_gamma"), st_in, S["da"], dxs_in, gb_in, b, T, H, **lk)
 
-        def attn_grads(ws_, sws, S=S, l=l, nin=nin, gb_in=gb_in):
-            ops.gemm(S["ctx"], S["da"], g(l, "out_kernel"), H, H, rows, transa=True)
-            ops.colsum(S["da"], g(l, "out_bias"), sws, rows, H)
+        def attn_grads(ws_, sws, S=S, l=l, nin=nin, gb_in=gb_in, do=do):
+            ops.gemm(S["ctx"], do, g(l, "out_kernel"), H, H, rows, transa=True)
+            ops.colsum(do, g(l, "out_bias"), sws, rows, H)
             ops.gemm(nin, S["dqkv"], g(l, "qkv_kernel"), H, 3 * H, rows, transa=True, ws=ws_)
             ops.colsum(S["dqkv"], g(l, "qkv_bias"), sws, rows, 3 * H)
             if "dposp" in S:
@@ -474,7 +576,8 @@ def param_specs(cfg: NetConfig):
     if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "attn":
         raise VltfError("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
     sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion, sa_block=cfg.sa_block,
-                    sa_ffn_dim=cfg.sa_ffn_dim)
+                    sa_ffn_dim=cfg.sa_ffn_dim, sa_attn_dropout=cfg.sa_attn_dropout, sa_dropout=cfg.sa_dropout,
+                    sa_drop_path=cfg.sa_drop_path)
     if sa:
         H = cfg.lstm_hidden
         if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
@@ -1632,6 +1735,9 @@ class LRCNEngine:
         self.sa = check_mhsa(cfg.rnn_cell, H, T, cfg.sa_heads, cfg.sa_positions, cfg.fusion) if cfg.classifier == "lstm" else None
         # sa_block encoder: the feed-forward width of the blocks, else None (refusals: param_specs -> check_mhsa -> check_sa_block)
         self.sa_ffn = check_sa_block(cfg.rnn_cell, H, cfg.sa_block, cfg.sa_ffn_dim) if self.sa else None
+        # sa_attn_dropout / sa_dropout / sa_drop_path: what a TRAINING forward draws with, else None (refusals: param_specs -> check_mhsa)
+        self.sa_drop = sa_drop_of(cfg, cfg.lstm_layers) if self.sa and training else None
+        self._sa_drop = None                                        # the SaDrop bound to the pass the last forward ran, for its backward
         # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide, the
         # block's ffn1_bias F wide)
         self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0, self.sa_ffn or 0))
@@ -1656,7 +1762,7 @@ class LRCNEngine:
             self.mhsa, self._mhsa_clips = [], 0                         # rnn_cell mhsa: self-attention layers (self.sa above)
             self.enc = None                                             # sa_block encoder: encoder_buffers; self.mhsa is then its layers
             if self.sa_ffn:
-                self.enc = encoder_buffers(buf, N, T, H, self.sa_ffn, self.sa[0], self.sa[1], cfg.lstm_layers, training)
+                self.enc = encoder_buffers(buf, N, T, H, self.sa_ffn, self.sa[0], self.sa[1], cfg.lstm_layers, training, self.sa_drop)
                 self.mhsa = self.enc["layers"]
             HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
@@ -2404,9 +2510,12 @@ class LRCNEngine:
                 ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb,
                                 ws=self.lstm_ws_graph if st else self.lstm_ws, **st)
                 xin, d = S["hseq"], H
+            self._sa_drop = self._sa_drop_bound() if train and self.sa_drop is not None else None
             if self.enc:
-                # sa_block encoder: embedding, L blocks, final norm (encoder_forward); no launch takes a host-varying argument
-                xin, d = encoder_forward(self.enc, P, "", xin, n, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {}), H
+                # sa_block encoder: embedding, L blocks, final norm (encoder_forward); without a dropout rate no launch takes a
+                # host-varying argument, with one the seed is the only such (a captured step: the _st forms)
+                xin, d = encoder_forward(self.enc, P, "", xin, n, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {},
+                                         self._sa_drop), H
                 self._mhsa_clips = b
             for l, S in enumerate(() if self.enc else self.mhsa):
                 # the qkv projection of all rows as the GRU's input projection is called (with the workspace: it follows conv_math),
@@ -2416,7 +2525,11 @@ class LRCNEngine:
                 names = mhsa_names(l, positions=positions)
                 Wqkv, bqkv, Wo, bo = (P[k] for k in names[:4])
                 ops.gemm(xin, Wqkv, S["qkv"], n, 3 * H, d, bias=bqkv, ws=self.ws)
-                ops.mhsa_fwd(S["qkv"], P[names[4]] if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads)
+                pos = P[names[4]] if positions == "relative" else None
+                if self._sa_drop is not None:                         # sa_attn_dropout, a training forward
+                    ops.mhsa_drop_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **self._sa_drop.weights_kw(l))
+                else:
+                    ops.mhsa_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads)
                 ops.gemm(S["ctx"], Wo, S["hseq"], n, H, H, bias=bo)
                 self._mhsa_clips = b
                 xin, d = S["hseq"], H
@@ -2655,7 +2768,7 @@ class LRCNEngine:
             if self.enc:
                 # sa_block encoder: the blocks (encoder_backward), then the embedding as the GRU's input projection
                 dx0 = encoder_backward(self.enc, P, G, "", self.feat, n, b, T, D, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {},
-                                       param_grads)
+                                       param_grads, self._sa_drop)
 
                 def embed_grads(ws, sws, dx0=dx0):
                     ops.gemm(self.feat, dx0, G[encoder_var("", None, "kernel")], D, H, n, transa=True, ws=ws)
@@ -2675,7 +2788,10 @@ class LRCNEngine:
                 xin = self.feat if l == 0 else self.mhsa[l - 1]["hseq"]
                 # through the output projection (no workspace, as attention_pool's products), then ONE launch for every (clip, head)
                 ops.gemm(S["dout"], Wo, S["dctx"], n, H, H, transb=True)
-                ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads)
+                if self._sa_drop is not None:
+                    ops.mhsa_drop_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._sa_drop.weights_kw(l))
+                else:
+                    ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads)
 
                 def mhsa_grads(ws, sws, S=S, names=names, din=din, xin=xin, heads=heads):
                     ops.gemm(S["ctx"], S["dout"], G[names[2]], H, H, n, transa=True)
@@ -2922,6 +3038,14 @@ class LRCNEngine:
             ops.fc_dropout_fwd_st(y, self.fc_keep, self.state, salt)
         else:
             ops.fc_dropout_fwd(y, self.fc_keep, dropout_seed(self._draw_index()), salt)
+
+    def _sa_drop_bound(self):
+        """self.sa_drop bound to the pass being issued: clip0 = rank * max_clips (the counters are those of the global batch), the seed
+        of this draw index, or -- captured -- the step state it is formed from when the launches run."""
+        clip0 = self.dp.rank * self.B if self.dp is not None else 0
+        if self._tag_off is not None:
+            return self.sa_drop.bind(clip0, state=self.state)
+        return self.sa_drop.bind(clip0, seed=dropout_seed(self._draw_index()))
 
     def _relu_grad(self, d, y, count):
         """ReluGrad of f6 / f7 on its own launch; after a forward pass that dropped them, with the dropout's gradient."""

@@ -44,7 +44,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -68,6 +68,9 @@ class PipelineSpec:
     sa_positions: Optional[str] = None              # rnn_cell mhsa: relative (None) | none
     sa_block: Optional[str] = None                  # rnn_cell mhsa: plain (None) | encoder: the pre-LN encoder block (engine.encoder_specs)
     sa_ffn_dim: Optional[int] = None                # sa_block encoder: the feed-forward width, 8..4096; None = 4 x the width
+    sa_attn_dropout: Optional[float] = None         # rnn_cell mhsa: dropout rate on the softmax weights in a training forward, [0, 1); None / 0 = off
+    sa_dropout: Optional[float] = None              # sa_block encoder: dropout rate on the elements of the two residual branches; None / 0 = off
+    sa_drop_path: Optional[float] = None            # sa_block encoder: stochastic depth, the linear rule 1 - p (l + 1) / L; None / 0 = off
     frame_fusion: Optional[Tuple[str, str]] = None  # (early | late | none, avg | last | reshape)
     input_fusion: Optional[str] = None              # avg | maximum | concat | ibias
     train_from: Optional[str] = None                # dcnn: first trainable layer of the tower (engine.TRAIN_FROM); not a reference key
@@ -250,7 +253,10 @@ class PipeNode:
                 self.attn_dim = check_attn(lf, s.attn_dim, "lstm", self.HO, what="pipeline [%s]: attn_dim" % s.name)
                 # rnn_cell mhsa: (heads, positions) of the self-attention layers (engine.check_mhsa); None for every other cell
                 self.sa = check_mhsa(s.rnn_cell, self.H, self.fpc, s.sa_heads, s.sa_positions, self.lfusion,
-                                     what="pipeline [%s]: rnn_cell" % s.name, sa_block=s.sa_block, sa_ffn_dim=s.sa_ffn_dim)
+                                     what="pipeline [%s]: rnn_cell" % s.name, sa_block=s.sa_block, sa_ffn_dim=s.sa_ffn_dim,
+                                     sa_attn_dropout=s.sa_attn_dropout, sa_dropout=s.sa_dropout, sa_drop_path=s.sa_drop_path)
+                # sa_attn_dropout / sa_dropout / sa_drop_path (engine.SaDrop), salted by the node index as the head's dropout is
+                self.sa_drop = sa_drop_of(s, self.L, 1 + index) if self.sa else None
                 # sa_block encoder: the feed-forward width of the blocks (engine.check_sa_block); None for the plain layer
                 self.sa_ffn = check_sa_block(s.rnn_cell, self.H, s.sa_block, s.sa_ffn_dim)
                 if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
@@ -260,8 +266,9 @@ class PipeNode:
                 raise VltfError("pipeline [%s]: lstm_bidirectional needs classifier lstm, not [%s]" % (s.name, self.cls))
             if self.cls != "lstm":
                 self.sa = check_mhsa(s.rnn_cell, sa_heads=s.sa_heads, sa_positions=s.sa_positions, sa_block=s.sa_block,
-                                     sa_ffn_dim=s.sa_ffn_dim)                                             # the keys without the cell: refused
-                self.sa_ffn = None
+                                     sa_ffn_dim=s.sa_ffn_dim, sa_attn_dropout=s.sa_attn_dropout, sa_dropout=s.sa_dropout,
+                                     sa_drop_path=s.sa_drop_path)                                         # the keys without the cell: refused
+                self.sa_ffn = self.sa_drop = None
             self.late = ftype == "late" and self.fpc > 1 and fmethod != "reshape"
             if self.late:
                 if self.cls == "lstm" or rows % self.fpc:
@@ -417,7 +424,7 @@ class PipeNode:
             self.enc = None
             if self.sa_ffn:
                 # sa_block encoder: engine.encoder_buffers; self.mhsa is its layers (the top layer's hseq / dout are the final norm's)
-                self.enc = encoder_buffers(buf, R0, T, H, self.sa_ffn, self.sa[0], self.sa[1], self.L, tr)
+                self.enc = encoder_buffers(buf, R0, T, H, self.sa_ffn, self.sa[0], self.sa[1], self.L, tr, self.sa_drop if tr else None)
                 self.mhsa = self.enc["layers"]
                 sw = max(sw, 64 * self.sa_ffn)
         if self.late:
@@ -638,6 +645,11 @@ class PipeNode:
             ops.gemm(xin, K, S["gx"], rows, 3 * H, d, bias=bk, ws=g.ws)
             ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb, ws=self.lstm_ws, **lk)
             xin, d = S["hseq"], H
+        # the dropouts of the self-attention model in a training forward: the counters are those of the global batch (clip0)
+        self._sa_drop = None
+        if train and self.sa and self.sa_drop is not None:
+            rank = g.dp.rank if g.dp is not None else 0
+            self._sa_drop = self.sa_drop.bind(rank * (self.max_rows0 // T), seed=dropout_seed(g._draw_index()))
         if self.enc:
             # sa_block encoder (engine.encoder_forward).  Under seq_len the embedding reads its input through ops.live_rows, as the
             # plain layer's qkv projection below does: x^T dx0 reads every row of x.  The norm launches never read a dead row and write
@@ -646,7 +658,8 @@ class PipeNode:
                 ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
                 xin = self.xlive
             self._xsa = xin
-            xin, d = encoder_forward(self.enc, P, sc, xin, rows, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk), H
+            xin, d = encoder_forward(self.enc, P, sc, xin, rows, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk,
+                                     self._sa_drop), H
         for l, S in enumerate(() if self.enc else self.mhsa):
             # Dead-row contract: the launch never reads a dead row of qkv and writes zeros in the dead rows of ctx (so a dead row of a
             # layer's output is out_bias, which nothing reads: the next layer's launch, the fusions and the masked loss skip it, and its
@@ -659,7 +672,11 @@ class PipeNode:
             if l == 0:
                 self._xsa = xin
             ops.gemm(xin, P[names[0]], S["qkv"], rows, 3 * H, d, bias=P[names[1]], ws=g.ws)
-            ops.mhsa_fwd(S["qkv"], P[names[4]] if positions == "relative" else None, S["P"], S["ctx"], b, T, H, heads, **lk)
+            pos = P[names[4]] if positions == "relative" else None
+            if self._sa_drop is not None:
+                ops.mhsa_drop_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **self._sa_drop.weights_kw(l), **lk)
+            else:
+                ops.mhsa_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **lk)
             ops.gemm(S["ctx"], P[names[2]], S["hseq"], rows, H, H, bias=P[names[3]])
             xin, d = S["hseq"], H
         for l, S in enumerate(self.lstm):
@@ -816,7 +833,7 @@ class PipeNode:
             # sa_block encoder: the blocks (engine.encoder_backward: one stream here, every gradient where the chain stands), then
             # the embedding as the plain layer's qkv projection below
             dx0 = encoder_backward(self.enc, P, G, sc, self._xsa, rows, b, T, self.feat_dim, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws,
-                                   self._len_kw(), lambda launch: launch(g.ws, sw))
+                                   self._len_kw(), lambda launch: launch(g.ws, sw), self._sa_drop)
             ops.gemm(self._xsa, dx0, G[encoder_var(sc, None, "kernel")], self.feat_dim, H, rows, transa=True, ws=g.ws)
             ops.colsum(dx0, G[encoder_var(sc, None, "bias")], sw, rows, H)
             if self.wants_feat:
@@ -829,7 +846,11 @@ class PipeNode:
             din = self.feat_dim if l == 0 else H
             xin = self._xsa if l == 0 else self.mhsa[l - 1]["hseq"]
             ops.gemm(S["dout"], Wo, S["dctx"], rows, H, H, transb=True)
-            ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._len_kw())
+            if self._sa_drop is not None:
+                ops.mhsa_drop_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._sa_drop.weights_kw(l),
+                                  **self._len_kw())
+            else:
+                ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._len_kw())
             ops.gemm(S["ctx"], S["dout"], G[names[2]], H, H, rows, transa=True)
             ops.colsum(S["dout"], G[names[3]], sw, rows, H)
             ops.gemm(xin, S["dqkv"], G[names[0]], din, 3 * H, rows, transa=True, ws=g.ws)

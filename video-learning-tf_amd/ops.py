@@ -908,6 +908,87 @@ def gelu_bwd(df, u, du, count):
     _ffi.call("vl_gelu_bwd", _p(df), _p(u), _p(du), count, stream())
 
 
+# ---- dropout of the self-attention model (vltf.h: vl_mhsa_drop_fwd ...) ---------------------------------------------------
+SA_DROP_STREAM = 0x5AD000000000      # the stream constant of these launches' draws (csrc/common.h)
+SA_DROP_SITES = ("weights", "attn_branch", "ffn_branch", "path")
+
+
+def sa_drop_salt(node, layer, site):
+    """The salt of one (node, layer, site) stream: node << 12 | layer << 2 | site (site: an entry of SA_DROP_SITES)."""
+    layer, node = int(layer), int(node)
+    if not (0 <= layer < 1024 and 0 <= node < (1 << 20)):
+        raise _ffi.VltfError("sa_drop_salt: layer %d must lie in 0..1023 and node %d in 0..2^20 - 1" % (layer, node))
+    return (node << 12) | (layer << 2) | SA_DROP_SITES.index(site)
+
+
+def _sa_keep(who, **keeps):
+    for k, v in keeps.items():
+        if not (isinstance(v, (int, float, np.floating)) and not isinstance(v, bool) and 0.0 < float(v) <= 1.0):
+            raise _ffi.VltfError("%s: %s %s must lie in (0, 1]" % (who, k, v))
+
+
+def _sa_seed(who, seed, state, clip0, clips):
+    """-> (suffix of the symbol, the seed argument): exactly one of seed / state; clip0 inside the range the launches take."""
+    if (seed is None) == (state is None):
+        raise _ffi.VltfError("%s: give the seed or the step state, one of the two" % who)
+    if not 0 <= int(clip0) < (1 << 31) - max(int(clips), 0):
+        raise _ffi.VltfError("%s: clip0 %d must lie in 0 .. 2^31 - clips" % (who, clip0))
+    return ("", int(seed) & 0xFFFFFFFFFFFFFFFF) if state is None else ("_st", _state(state))
+
+
+def mhsa_drop_fwd(qkv, pos, P, ctx, batch, T, H, heads, keep, salt, clip0=0, seed=None, state=None, seq_len=None):
+    """mhsa_fwd with dropout on the weights (vl_mhsa_drop_fwd / _st): ctx = (P o M / keep) V, P stored undropped; element (b, h, q, k)
+    draws from (seed, salt) at the counter (((clip0 + b) heads + h) T + q) T + k.  seed, or state: the step state it is formed from."""
+    _f32(qkv, pos, P, ctx)
+    _dense(qkv, pos, P, ctx)
+    _mhsa_sizes("mhsa_drop_fwd", batch, T, H, heads, qkv=qkv, pos=pos, P=P, ctx=ctx)
+    _sa_keep("mhsa_drop_fwd", keep=keep)
+    sfx, sd = _sa_seed("mhsa_drop_fwd", seed, state, clip0, batch)
+    _ffi.call("vl_mhsa_drop_fwd" + sfx, _p(qkv), _p(pos), None if seq_len is None else _p(_seq_len(seq_len, batch, "mhsa_drop_fwd")),
+              _p(P), _p(ctx), batch, T, H, heads, keep, sd, int(salt), int(clip0), stream())
+
+
+def mhsa_drop_bwd(dctx, qkv, P, dqkv, dposp, batch, T, H, heads, keep, salt, clip0=0, seed=None, state=None, seq_len=None):
+    """Its backward (vl_mhsa_drop_bwd / _st): the mask is drawn again from the same counters; P is the undropped one the forward stored."""
+    _f32(dctx, qkv, P, dqkv, dposp)
+    _dense(dctx, qkv, P, dqkv, dposp)
+    _mhsa_sizes("mhsa_drop_bwd", batch, T, H, heads, dctx=dctx, qkv=qkv, P=P, dqkv=dqkv, dposp=dposp)
+    _sa_keep("mhsa_drop_bwd", keep=keep)
+    sfx, sd = _sa_seed("mhsa_drop_bwd", seed, state, clip0, batch)
+    _ffi.call("vl_mhsa_drop_bwd" + sfx, _p(dctx), _p(qkv), _p(P), None if seq_len is None else _p(_seq_len(seq_len, batch, "mhsa_drop_bwd")),
+              _p(dqkv), _p(dposp), batch, T, H, heads, keep, sd, int(salt), int(clip0), stream())
+
+
+def add_layer_norm_drop_fwd(x, r, sum, y, gamma, beta, stats, clips, T, W, keep, keep_path, salt_elem, salt_path, branch, clip0=0,
+                            seed=None, state=None, eps=LN_EPS, seq_len=None):
+    """add_layer_norm_fwd with the branch r dropped (vl_add_layer_norm_drop_fwd / _st): s = x + r f, f = (kept_e / keep) (path_kept /
+    keep_path); element (b, t, col) draws at ((clip0 + b) T + t) W + col of the salt_elem stream, the clip's path at 2 (clip0 + b) +
+    branch of the salt_path stream.  Either keep may be 1; `sum` receives the dropped sum."""
+    _f32(x, r, sum, y, gamma, beta, stats)
+    _dense(x, r, sum, y, gamma, beta, stats)
+    _ln_sizes("add_layer_norm_drop_fwd", clips, T, W, x=x, r=r, sum=sum, y=y, gamma=gamma, beta=beta, stats=stats)
+    if not (eps > 0 and math.isfinite(eps)):
+        raise _ffi.VltfError("add_layer_norm_drop_fwd: eps %g must be positive and finite" % eps)
+    _sa_keep("add_layer_norm_drop_fwd", keep=keep, keep_path=keep_path)
+    sfx, sd = _sa_seed("add_layer_norm_drop_fwd", seed, state, clip0, clips)
+    _ffi.call("vl_add_layer_norm_drop_fwd" + sfx, _p(x), _p(r), _p(sum), _p(y), _p(gamma), _p(beta), _p(stats), clips, T, W, eps,
+              None if seq_len is None else _p(_seq_len(seq_len, clips, "add_layer_norm_drop_fwd")), keep, keep_path, sd, int(salt_elem),
+              int(salt_path), int(branch), int(clip0), stream())
+
+
+def branch_drop_grad(ds, dr, clips, T, W, keep, keep_path, salt_elem, salt_path, branch, clip0=0, seed=None, state=None, seq_len=None):
+    """dr = ds f: the gradient that enters a branch add_layer_norm_drop_fwd dropped, f drawn again (vl_branch_drop_grad / _st); dead
+    rows zeros."""
+    _f32(ds, dr)
+    _dense(ds, dr)
+    _ln_sizes("branch_drop_grad", clips, T, W, ds=ds, dr=dr)
+    _sa_keep("branch_drop_grad", keep=keep, keep_path=keep_path)
+    sfx, sd = _sa_seed("branch_drop_grad", seed, state, clip0, clips)
+    _ffi.call("vl_branch_drop_grad" + sfx, _p(ds), _p(dr), clips, T, W,
+              None if seq_len is None else _p(_seq_len(seq_len, clips, "branch_drop_grad")), keep, keep_path, sd, int(salt_elem),
+              int(salt_path), int(branch), int(clip0), stream())
+
+
 def dropout_fwd(x, y, mask, keep, seed):
     _f32(x, y)
     _ffi.call("vl_dropout_fwd", _p(x), _p(y), _p(mask), x.numel(), keep, seed, stream())

@@ -72,7 +72,9 @@ def pipeline_net_config(settings, p, dataset):
         kw.update(lstm_hidden=p.lstm_params[0], lstm_layers=p.lstm_params[1], fusion=p.lstm_params[2],
                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
                   attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None),
-                  sa_block=getattr(p, "sa_block", None), sa_ffn_dim=getattr(p, "sa_ffn_dim", None))
+                  sa_block=getattr(p, "sa_block", None), sa_ffn_dim=getattr(p, "sa_ffn_dim", None),
+                  sa_attn_dropout=getattr(p, "sa_attn_dropout", None), sa_dropout=getattr(p, "sa_dropout", None),
+                  sa_drop_path=getattr(p, "sa_drop_path", None))
     else:
         kw.update(frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None)
     return NetConfig(**kw)
@@ -105,7 +107,8 @@ def graph_config(settings, feeder, batch):
                                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
                                   attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None),
                                   sa_positions=getattr(p, "sa_positions", None), sa_block=getattr(p, "sa_block", None),
-                                  sa_ffn_dim=getattr(p, "sa_ffn_dim", None),
+                                  sa_ffn_dim=getattr(p, "sa_ffn_dim", None), sa_attn_dropout=getattr(p, "sa_attn_dropout", None),
+                                  sa_dropout=getattr(p, "sa_dropout", None), sa_drop_path=getattr(p, "sa_drop_path", None),
                                   frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None, input_fusion=p.input_fusion,
                                   train_from=getattr(p, "train_from", None)))
     infos, dsets = {}, {}

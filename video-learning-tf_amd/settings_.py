@@ -206,6 +206,7 @@ class Settings:
         network.attn_dim = self.read_attn_dim(content, network)
         network.sa_heads, network.sa_positions = self.read_self_attention(content, network)
         network.sa_block, network.sa_ffn_dim = self.read_sa_block(content, network)
+        network.sa_attn_dropout, network.sa_dropout, network.sa_drop_path = self.read_sa_dropout(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
@@ -300,6 +301,26 @@ class Settings:
         except VltfError as ex:
             error(str(ex))
         return ("encoder", F) if F else (None, None)
+
+    def read_sa_dropout(self, content, network):
+        """`sa_attn_dropout: p`, `sa_dropout: p` and `sa_drop_path: p` beside `rnn_cell: mhsa` (this project's extension of the pipeline
+        schema): rates in [0, 1) of the dropout on the softmax weights, on the elements of the encoder block's two residual branches,
+        and of stochastic depth over those branches (the linear rule 1 - p (l + 1) / L), in a training forward only (engine.SaDrop).
+        Absent / None / 0 = off.  Refused by name: a key without rnn_cell mhsa, sa_dropout / sa_drop_path without sa_block encoder,
+        bools, strings, NaN, values outside [0, 1) (engine.check_mhsa).  -> the three rates, None where off."""
+        keys = ("sa_attn_dropout", "sa_dropout", "sa_drop_path")
+        vals = [self.read_field(content, k) for k in keys]
+        vals = [None if isinstance(v, str) and v == "None" else v for v in vals]
+        from .engine import VltfError, check_mhsa, check_sa_rate
+        lstm = network.classifier == defs.classifier.lstm
+        try:
+            check_mhsa(network.rnn_cell, network.lstm_params[0] if lstm else 1, 1, network.sa_heads, network.sa_positions,
+                       network.lstm_params[2] if lstm else "avg", sa_block=network.sa_block, sa_ffn_dim=network.sa_ffn_dim,
+                       sa_attn_dropout=vals[0], sa_dropout=vals[1], sa_drop_path=vals[2])
+            rates = [check_sa_rate(k, v) for k, v in zip(keys, vals)]
+        except VltfError as ex:
+            error(str(ex))
+        return tuple(r if r > 0 else None for r in rates)
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
