@@ -455,6 +455,30 @@ int vl_attn_pool_fwd(const float* u, const float* c, const float* h, const int32
 int vl_attn_pool_bwd(const float* dy, const float* h, const float* s, const float* alpha, const float* c, const int32_t* seq_len,
                      float* du, float* dh, float* dcp, int batch, int T, int HO, int A, vl_stream_t stream);
 
+/* ---- NetVLAD pooling over time (fusion `vlad`: Arandjelovic et al. 2016, Girdhar et al. 2017, Miech et al. 2017; csrc/netvlad.hip,
+ * DESIGN 4.30).  Per clip b with L = min(max(seq_len[b], 1), T) live steps (seq_len NULL: L = T), rows h[b][t][HO], K centres c[k][HO]
+ * and projections s[b][t][K] (s = h W + beta, vl_gemm):
+ *   a_t = softmax_k(s_t) for t < L (max-subtracted), 0 for t >= L;   m_k = sum_t a_tk;   V_k = sum_t a_tk h_t - m_k c_k (t ascending);
+ *   r_k = rsqrt(max(|V_k|^2, 1e-12)) (tf.nn.l2_normalize's rule and epsilon);   y[k HO + j] = V_k[j] r_k / sqrt(K) (cluster-major).
+ * The whole-descriptor L2 normalisation of the papers is the CONSTANT 1 / sqrt(K), on purpose: behind the intra-normalisation every
+ * |U_k| is 1, so the descriptor's norm is sqrt(K), and the radial term of that norm's backward is annihilated by the
+ * intra-normalisation's projection.  Clusters are therefore independent of each other in both directions.  A cluster whose |V_k|^2 is
+ * not above the epsilon is scaled by the constant 1e6 (stored in r exactly) and shrinks smoothly to nothing.
+ * fwd writes a [batch][T][K] (may alias s; dead rows zero), r [batch][K] and y [batch][K HO].
+ * bwd reads dy [batch][K HO] and the stored a, r, y; with U_k = sqrt(K) y_k and dU_k = dy_k / sqrt(K),
+ *   dV_k = r_k (dU_k - U_k (U_k . dU_k)) where r_k < 1e6, else r_k dU_k;   da_tk = dV_k . (h_t - c_k);
+ *   dh [batch][T][HO] = sum_k a_tk dV_k (the direct term only: ds W^T is the caller's product);
+ *   ds [batch][T][K] = a_t o (da_t - sum_k a_tk da_tk);   dcp [batch][K HO] = -m_k dV_k, the per-clip partials of c's gradient
+ *   (vl_colsum them); dead rows of ds and dh are zeros.  ds, dh and dcp must not overlap an input.
+ * One workgroup per clip, no atomics, every sum in a fixed order: a clip's outputs depend on that clip's inputs alone, bit for bit, in
+ * any batch.  Rows t >= L of h and s are never read (they may hold NaN).  No host-varying scalar: a captured step replays the launches
+ * as they are.  Limits (an error names the one missed, nothing is launched): 2 <= K <= 64, 1 <= HO <= 1024, K HO <= 16384,
+ * 1 <= T <= 1024. */
+int vl_netvlad_fwd(const float* s, const float* c, const float* h, const int32_t* seq_len, float* a, float* r, float* y, int batch,
+                   int T, int HO, int K, vl_stream_t stream);
+int vl_netvlad_bwd(const float* dy, const float* h, const float* a, const float* r, const float* y, const float* c,
+                   const int32_t* seq_len, float* ds, float* dh, float* dcp, int batch, int T, int HO, int K, vl_stream_t stream);
+
 /* ---- multi-head self-attention over the frames of a clip (rnn_cell `mhsa`; csrc/self_attention.hip) --------------------
  * qkv [batch T][3H]: a row is Q(H) | K(H) | V(H) (the caller's projection x Wqkv + bqkv, vl_gemm); head h of `heads` owns columns
  * h dh .. (h + 1) dh of each block, dh = H / heads.  Per clip b with L = min(max(seq_len[b], 0), T) live steps (seq_len NULL: L = T)

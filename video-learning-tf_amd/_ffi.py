@@ -94,6 +94,8 @@ SIGNATURES = {
     "vl_temporal_fusion_bwd_len": (i32, [p, p, i32, i32, i32, i32, p, p]),
     "vl_attn_pool_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_attn_pool_bwd": (i32, [p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
+    "vl_netvlad_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
+    "vl_netvlad_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_mhsa_fwd": (i32, [p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_mhsa_bwd": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_live_rows": (i32, [p, p, p, i32, i32, i32, p]),

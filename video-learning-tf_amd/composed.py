@@ -69,6 +69,9 @@ class ComposedEngine(GraphEngine):
         if head.fusion == "attn" or (enc_cfg.classifier == "lstm" and enc_cfg.fusion == "attn") or getattr(enc_cfg, "attn_dim", None) is not None:
             raise VltfError("lstm_params fusion attn / attn_dim are not built for the two-pipeline model, which keeps avg | last | reshape | "
                             "state (use LRCNEngine, or GraphEngine with PipelineSpec(lstm_params=(H, layers, \"attn\")))")
+        if head.fusion == "vlad" or (enc_cfg.classifier == "lstm" and enc_cfg.fusion == "vlad") or getattr(enc_cfg, "vlad_clusters", None) is not None:
+            raise VltfError("lstm_params fusion vlad / vlad_clusters are not built for the two-pipeline model, which keeps avg | last | reshape | "
+                            "state (use LRCNEngine, or GraphEngine with PipelineSpec(lstm_params=(H, layers, \"vlad\")))")
         if head.fusion not in ("avg", "last", "reshape", "state"):
             raise VltfError("Undefined frame fusion type : %s" % head.fusion)
         if head.input_fusion not in (None, "concat", "ibias"):

@@ -54,6 +54,7 @@ class defs:
     class fusion_method:
         avg, last, concat, reshape, state, ibias, maximum = "avg", "last", "concat", "reshape", "state", "ibias", "maximum"
         attn = "attn"        # not in the reference: learned attention pooling over time, lstm_params[2] only
+        vlad = "vlad"        # not in the reference: NetVLAD pooling over time (K centres, pipeline key vlad_clusters), lstm_params[2] only
 
     class fusion_type:
         early, late, none, main, aux = "early", "late", "none", "main", "aux"

@@ -52,8 +52,9 @@ class NetConfig:
     classifier: str = "lstm"                    # defs.classifier.{lstm, fc}; "none": a feature pipeline (classifier: None, model.py:110-112)
     lstm_hidden: int = 256
     lstm_layers: int = 1
-    fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state, attn}
+    fusion: str = "avg"                         # lstm_params[2]: defs.fusion_method.{avg, last, reshape, state, attn, vlad}
     attn_dim: Optional[int] = None              # fusion attn: width A of the attention scorer (attn_specs); None = the recurrent output width
+    vlad_clusters: Optional[int] = None         # fusion vlad: the number K of NetVLAD centres (vlad_specs), 2..64, K * output width <= 16384; None = 8
     lstm_bidirectional: bool = False            # every LSTM layer a forward and a backward cell, outputs concatenated (blstm_names); H <= 512
     rnn_cell: str = "lstm"                      # the recurrent cell of classifier lstm: "lstm" (BasicLSTMCell) | "gru" (reset-after, gru_names); H <= 512
                                                 # | "mhsa": every layer a multi-head self-attention layer over the fpc frames (mhsa_names)
@@ -535,6 +536,51 @@ def attn_buffers(buf, clips, T, HO, A, training):
     return S
 
 
+VLAD_MIN_K, VLAD_MAX_K, VLAD_MAX_HO, VLAD_MAX_WIDTH, VLAD_DEFAULT_K = 2, 64, 1024, 16384, 8
+
+
+def vlad_names(scope=""):
+    """The variable names of the NetVLAD pooling of fusion `vlad`, in flat-buffer order (the order in which the backward produces
+    them): kernel (HO, K), bias (K,), centers (K, HO).  kernel and centers are rank 2: weights for decay_ranges, LARS and LAMB; the
+    bias is exempt as every bias is."""
+    return [scope + "netvlad/" + v for v in ("kernel", "bias", "centers")]
+
+
+def vlad_specs(HO, K, scope=""):
+    """[(name, shape)] of vlad_names for a recurrent output of width HO and K centres."""
+    return list(zip(vlad_names(scope), ((HO, K), (K,), (K, HO))))
+
+
+def check_vlad(fusion, vlad_clusters=None, classifier="lstm", out_width=1, what="vlad_clusters"):
+    """-> the number of centres K of fusion `vlad` (vlad_clusters, default 8), or None for every other fusion.  The descriptor the head
+    reads is K * out_width wide.  Refused: fusion vlad without the recurrent classifier, vlad_clusters without fusion vlad,
+    vlad_clusters not an integer in 2..64, an output width above 1024, K * out_width above 16384 (the launches' limits, vltf.h)."""
+    if fusion == "vlad" and classifier != "lstm":
+        raise VltfError("lstm_params: fusion vlad pools the outputs of the recurrent classifier, but the classifier is [%s]" % classifier)
+    if fusion != "vlad":
+        if vlad_clusters not in (None, "None"):
+            raise VltfError("%s is the number of centres of fusion vlad, but the fusion is [%s]" % (what, fusion))
+        return None
+    K = VLAD_DEFAULT_K if vlad_clusters in (None, "None") else vlad_clusters
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not VLAD_MIN_K <= int(K) <= VLAD_MAX_K:
+        raise VltfError("%s must be an integer in %d..%d, got [%s]" % (what, VLAD_MIN_K, VLAD_MAX_K, K))
+    if int(out_width) > VLAD_MAX_HO:
+        raise VltfError("%s: fusion vlad takes a recurrent output of width 1..%d, got [%d]" % (what, VLAD_MAX_HO, out_width))
+    if int(K) * int(out_width) > VLAD_MAX_WIDTH:
+        raise VltfError("%s: the descriptor of fusion vlad is %d x %d = %d wide, above %d" %
+                        (what, int(K), int(out_width), int(K) * int(out_width), VLAD_MAX_WIDTH))
+    return int(K)
+
+
+def vlad_buffers(buf, clips, T, HO, K, training):
+    """The device buffers of fusion vlad: sa (the projection s, then the assignments a in place), the per-cluster scales r (and,
+    training, the per-clip partials dcp of the centres' gradient, ds, and dproj = ds W^T)."""
+    S = dict(sa=buf(clips * T, K), r=buf(clips, K))
+    if training:
+        S.update(dcp=buf(clips, K * HO), ds=buf(clips * T, K), dproj=buf(clips * T, HO))
+    return S
+
+
 def gru_buffers(buf, rows, H, training):
     """The device buffers of one GRU layer: projections gx, activated gates act, the candidate's recurrent term hcand, outputs hseq,
     entering outputs hprev (and, training, the gradients dgx / dgh of the two pre-activation terms and dout of the output)."""
@@ -575,14 +621,20 @@ def param_specs(cfg: NetConfig):
     A = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, (2 if cfg.lstm_bidirectional else 1) * cfg.lstm_hidden)
     if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "attn":
         raise VltfError("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
+    # fusion vlad: as attn's, its three variables sit between the head and the recurrent layers; the head reads K x HO columns
+    KV = check_vlad(cfg.fusion, cfg.vlad_clusters, cfg.classifier, (2 if cfg.lstm_bidirectional else 1) * cfg.lstm_hidden)
+    if cfg.frame_fusion and len(cfg.frame_fusion) > 1 and cfg.frame_fusion[1] == "vlad":
+        raise VltfError("frame_fusion: vlad is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
+    kv = KV or 1
     sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion, sa_block=cfg.sa_block,
                     sa_ffn_dim=cfg.sa_ffn_dim, sa_attn_dropout=cfg.sa_attn_dropout, sa_dropout=cfg.sa_dropout,
                     sa_drop_path=cfg.sa_drop_path)
     if sa:
         H = cfg.lstm_hidden
-        if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
-            specs += [("output_fc_w", (H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
+        if kv * H != cfg.num_classes:                     # the head's names are the LSTM classifier's
+            specs += [("output_fc_w", (kv * H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
         specs += attn_specs(H, A) if A else []
+        specs += vlad_specs(H, KV) if KV else []
         d = dim
         F = check_sa_block(cfg.rnn_cell, H, cfg.sa_block, cfg.sa_ffn_dim)
         if F:
@@ -592,10 +644,11 @@ def param_specs(cfg: NetConfig):
             d = H
     elif cfg.classifier == "lstm" and cfg.rnn_cell == "gru":
         H = cfg.lstm_hidden
-        if H != cfg.num_classes:                          # the head's names are the LSTM classifier's
+        if kv * H != cfg.num_classes:                     # the head's names are the LSTM classifier's
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
-            specs += [(head + "_w", (H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+            specs += [(head + "_w", (kv * H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
         specs += attn_specs(H, A) if A else []
+        specs += vlad_specs(H, KV) if KV else []
         d = dim
         for l in range(cfg.lstm_layers):
             specs += gru_specs(l, d, H)
@@ -603,20 +656,22 @@ def param_specs(cfg: NetConfig):
     elif cfg.classifier == "lstm" and cfg.lstm_bidirectional:
         check_blstm(cfg.lstm_hidden)
         H = cfg.lstm_hidden
-        if 2 * H != cfg.num_classes:                      # the head reads the 2H-wide fused vector
+        if kv * 2 * H != cfg.num_classes:                 # the head reads the 2H-wide fused vector (fusion vlad: K of them)
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
-            specs += [(head + "_w", (2 * H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+            specs += [(head + "_w", (kv * 2 * H, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
         specs += attn_specs(2 * H, A) if A else []
+        specs += vlad_specs(2 * H, KV) if KV else []
         d = dim
         for l in range(cfg.lstm_layers):
             specs += [(n, (d + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l)]
             d = 2 * H
     elif cfg.classifier == "lstm":
-        if cfg.lstm_hidden != cfg.num_classes:
+        if kv * cfg.lstm_hidden != cfg.num_classes:
             # fusion `state`: logits = convert_dim_fc(final h) under its default name (model.py:137-141), else "output_fc" (lstm.py:90)
             head = "fc_convert" if cfg.fusion == "state" else "output_fc"
-            specs += [(head + "_w", (cfg.lstm_hidden, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
+            specs += [(head + "_w", (kv * cfg.lstm_hidden, cfg.num_classes)), (head + "_b", (cfg.num_classes,))]
         specs += attn_specs(cfg.lstm_hidden, A) if A else []
+        specs += vlad_specs(cfg.lstm_hidden, KV) if KV else []
         d = dim
         for l in range(cfg.lstm_layers):
             pre = "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
@@ -1506,7 +1561,7 @@ def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in param_specs(cfg):
-        if name.endswith("kernel") or name.endswith("attention_pool/context"):
+        if name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias") or name.endswith("beta"):
@@ -1740,7 +1795,10 @@ class LRCNEngine:
         self._sa_drop = None                                        # the SaDrop bound to the pass the last forward ran, for its backward
         # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide, the
         # block's ffn1_bias F wide)
-        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0, self.sa_ffn or 0))
+        # (fusion vlad: the centres' gradient is a column sum K HO wide)
+        ho_ = (2 if cfg.lstm_bidirectional else 1) * H
+        vlad_w = (check_vlad(cfg.fusion, cfg.vlad_clusters, cfg.classifier, ho_) or 0) * ho_ if cfg.classifier == "lstm" else 0
+        self.small_ws = buf(64 * max(4 * H, FC_DIM, 1024, C, self.sa[0] * (2 * T - 1) if self.sa else 0, self.sa_ffn or 0, vlad_w))
         if training:
             self.wt = buf(max_w)
             self.df6 = buf(N, FC_DIM)
@@ -1749,7 +1807,7 @@ class LRCNEngine:
             self.dfeat = self.df8 if self.df8 is not None else (self.df7 if self.df7 is not None else self.df6)
         # ---- classifier
         if cfg.classifier == "lstm":
-            if cfg.fusion not in ops.FUSION_CODE and cfg.fusion not in ("state", "reshape", "attn"):
+            if cfg.fusion not in ops.FUSION_CODE and cfg.fusion not in ("state", "reshape", "attn", "vlad"):
                 raise VltfError("Undefined frame fusion type : %s" % cfg.fusion)          # tf_util.py:28-29
             # `state` = final h of the last layer = its output at t = T-1 (full-length sequences, lstm.py:136), no dropout;
             # `reshape` (tf_util.py:26-27) keeps every step: one logits row per frame, labels [clips * fpc, classes]
@@ -1787,17 +1845,22 @@ class LRCNEngine:
             self.gh = buf(B, 4 * H)
             self.lstm_ws = ops.lstm_seq_ws(B, T, H, dev) if H <= 1024 else None
             R = N if self.per_step else B                             # logits rows
-            self.fused = buf(R, HO)
-            self.dropped = buf(R, HO)
-            self.drop_mask = buf(R, HO, dtype=torch.uint8)
-            self.logits = buf(R, C) if HO != C else self.dropped
+            # fusion vlad (check_vlad: param_specs): NetVLAD pooling; the fused vector and the head's input are K x HO wide
+            self.vlad_k = check_vlad(cfg.fusion, cfg.vlad_clusters, cfg.classifier, HO)
+            self.vlad = vlad_buffers(buf, B, T, HO, self.vlad_k, training) if self.vlad_k else None
+            self._vlad_clips = 0
+            HW = self.head_in = (self.vlad_k or 1) * HO               # width of the fused vector = the head's input
+            self.fused = buf(R, HW)
+            self.dropped = buf(R, HW)
+            self.drop_mask = buf(R, HW, dtype=torch.uint8)
+            self.logits = buf(R, C) if HW != C else self.dropped
             # fusion attn (check_attn: param_specs): learned attention pooling in the place of avg / last
             self.attn_dim = check_attn(cfg.fusion, cfg.attn_dim, cfg.classifier, HO)
             self.attn = attn_buffers(buf, B, T, HO, self.attn_dim, training) if self.attn_dim else None
             self._attn_clips = 0
             if training:
                 self.dh, self.dc = buf(B, H), buf(B, H)
-                self.dfused, self.ddropped = buf(R, HO), buf(R, HO)
+                self.dfused, self.ddropped = buf(R, HW), buf(R, HW)
                 if self.bi:
                     self.dx_bw = buf(N, max(D, HO))                   # the backward direction's share of a layer's input gradient
         else:
@@ -2577,6 +2640,15 @@ class LRCNEngine:
                 ops.attn_pool_fwd(S["us"], ca, xin, S["us"], S["alpha"], self.fused, b, T, HO, At)
                 self._attn_clips = b
                 v = self.fused
+            elif self.vlad is not None:
+                # s = hseq W + beta over all rows (no workspace, as attn's and the head's products: fp32 whatever conv_math says), then
+                # ONE launch: the soft assignment in place, the residual sums per centre, the intra-normalisation, into K x HO columns
+                Wv, bv, cv = (P[k] for k in vlad_names())
+                Kv, S = self.vlad_k, self.vlad
+                ops.gemm(xin, Wv, S["sa"], n, Kv, HO, bias=bv)
+                ops.netvlad_fwd(S["sa"], cv, xin, S["sa"], S["r"], self.fused, b, T, HO, Kv)
+                self._vlad_clips = b
+                v = self.fused
             else:
                 ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, self.lstm_fusion)
                 v = self.fused
@@ -2589,8 +2661,9 @@ class LRCNEngine:
                                 (self._draw_index() << 20) ^ 0x5DEECE66D)
                 v = self.dropped
             self._v = v
-            if HO != C:
-                ops.gemm(v, P[self.head + "_w"], self.logits, r, C, HO, bias=P[self.head + "_b"])
+            HW = self.head_in
+            if HW != C:
+                ops.gemm(v, P[self.head + "_w"], self.logits, r, C, HW, bias=P[self.head + "_b"])
             elif v is not self.logits:
                 self.logits[:r].copy_(v[:r])
             self._rows = r
@@ -2624,6 +2697,13 @@ class LRCNEngine:
         if getattr(self, "attn", None) is None:
             raise VltfError("attention_weights: the model has no attention pooling (lstm_params fusion attn)")
         return self.attn["alpha"][:self._attn_clips]
+
+    def vlad_assignments(self):
+        """Device view [clips, T, K] of the soft assignments a the last forward gave each time step (fusion vlad): a live row sums to
+        1 over the centres, a dead row is zero."""
+        if getattr(self, "vlad", None) is None:
+            raise VltfError("vlad_assignments: the model has no NetVLAD pooling (lstm_params fusion vlad)")
+        return self.vlad["sa"][:self._vlad_clips * self.T].view(self._vlad_clips, self.T, self.vlad_k)
 
     def self_attention_weights(self, layer=-1):
         """Device view [clips, heads, T, T] of the weights P the last forward gave (rnn_cell mhsa; the last layer's by default): row q
@@ -2675,13 +2755,13 @@ class LRCNEngine:
 
         if cfg.classifier == "lstm":
             d, r = self.dlogits, self._rows
-            HO = self.lstm_out
-            if HO != C:
+            HO, HW = self.lstm_out, self.head_in
+            if HW != C:
                 def head_grads(ws, sws, r=r):
-                    ops.gemm(self._v, self.dlogits, G[self.head + "_w"], HO, C, r, transa=True)
+                    ops.gemm(self._v, self.dlogits, G[self.head + "_w"], HW, C, r, transa=True)
                     ops.colsum(self.dlogits, G[self.head + "_b"], sws, r, C)
                 param_grads(head_grads)
-                ops.gemm(self.dlogits, P[self.head + "_w"], self.ddropped, r, HO, C, transb=True)
+                ops.gemm(self.dlogits, P[self.head + "_w"], self.ddropped, r, HW, C, transb=True)
                 d = self.ddropped
             if self._dropout:
                 ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], cfg.dropout_keep_prob)
@@ -2706,6 +2786,19 @@ class LRCNEngine:
                     ops.colsum(S["dcp"], G[names[2]], sws, b, At)
                 param_grads(attn_grads)
                 ops.gemm(S["du"], P[names[0]], S["dproj"], n, HO, At, transb=True)
+                ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", n * HO)
+            elif self.vlad is not None:
+                # ONE launch: ds, the direct term sum_k a_tk dV_k straight into dout, the per-clip partials of the centres' gradient
+                names = vlad_names()
+                Kv, S, hs = self.vlad_k, self.vlad, top["hseq"]
+                ops.netvlad_bwd(d, hs, S["sa"], S["r"], self.fused, P[names[2]], S["ds"], top["dout"], S["dcp"], b, T, HO, Kv)
+
+                def vlad_grads(ws, sws, S=S, names=names, hs=hs, Kv=Kv):
+                    ops.gemm(hs, S["ds"], G[names[0]], HO, Kv, n, transa=True)
+                    ops.colsum(S["ds"], G[names[1]], sws, n, Kv)
+                    ops.colsum(S["dcp"], G[names[2]], sws, b, Kv * HO)
+                param_grads(vlad_grads)
+                ops.gemm(S["ds"], P[names[0]], S["dproj"], n, HO, Kv, transb=True)
                 ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", n * HO)
             else:
                 ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, self.lstm_fusion)

@@ -44,7 +44,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn, check_vlad, vlad_buffers, vlad_names, vlad_specs,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -59,8 +59,9 @@ class PipelineSpec:
     frame_encoding_layer: Optional[str] = None      # dcnn
     fc_output_dim: Optional[int] = None             # fc
     classifier: Optional[str] = None                # None | fc | lstm
-    lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state | attn)
+    lstm_params: Optional[Tuple[int, int, str]] = None   # (hidden, layers, fusion avg | last | reshape | state | attn | vlad)
     attn_dim: Optional[int] = None                  # fusion attn: the width of the attention scorer (engine.attn_specs); None = the LSTM's output width
+    vlad_clusters: Optional[int] = None             # fusion vlad: the number of NetVLAD centres (engine.vlad_specs), 2..64; None = 8
     lstm_bidirectional: bool = False                # classifier lstm: a forward and a backward cell per layer, outputs concatenated (2H wide)
     rnn_cell: str = "lstm"                          # classifier lstm: its cell, lstm | gru (engine.gru_names; no state input, H <= 512)
                                                     # | mhsa: every layer a multi-head self-attention layer over the frames (engine.mhsa_names)
@@ -121,8 +122,16 @@ class PipeNode:
         if ftype is not None and fmethod == "attn":
             raise VltfError("pipeline [%s]: frame_fusion attn is not built: attention pooling is a fusion of the recurrent classifier "
                             "(lstm_params)" % s.name)
+        if ftype is not None and fmethod == "vlad":
+            raise VltfError("pipeline [%s]: frame_fusion vlad is not built: NetVLAD pooling is a fusion of the recurrent classifier "
+                            "(lstm_params)" % s.name)
         if ftype is not None and fmethod not in ("avg", "last", "reshape"):
             raise VltfError("Undefined frame fusion type : %s" % fmethod)                 # apply_temporal_fusion, tf_util.py:28-29
+        if s.input_fusion == "vlad":
+            raise VltfError("pipeline [%s]: input_fusion vlad is not built: NetVLAD pooling is a fusion of the recurrent classifier "
+                            "(lstm_params)" % s.name)
+        if s.classifier != "lstm" and (s.vlad_clusters not in (None, "None") or (s.lstm_params and s.lstm_params[2] == "vlad")):
+            raise VltfError("pipeline [%s]: lstm_params fusion vlad / vlad_clusters need classifier lstm, not [%s]" % (s.name, s.classifier))
         if s.input_fusion == "attn":
             raise VltfError("pipeline [%s]: input_fusion attn is not built: attention pooling is a fusion of the recurrent classifier "
                             "(lstm_params)" % s.name)
@@ -237,7 +246,7 @@ class PipeNode:
                 if ftype is not None:
                     raise VltfError("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % ftype)
                 self.H, self.L, self.lfusion = int(s.lstm_params[0]), int(s.lstm_params[1]), s.lstm_params[2]
-                if self.lfusion not in ("avg", "last", "reshape", "state", "attn"):
+                if self.lfusion not in ("avg", "last", "reshape", "state", "attn", "vlad"):
                     raise VltfError("Undefined frame fusion type : %s" % self.lfusion)
                 self.per_step = self.lfusion == "reshape"
                 self.head_name = "fc_convert" if self.lfusion == "state" else "output_fc"
@@ -251,6 +260,9 @@ class PipeNode:
                                         (s.name, self.state_src.ref))
                 # fusion attn: learned attention pooling (engine.check_attn); None for every other fusion
                 self.attn_dim = check_attn(lf, s.attn_dim, "lstm", self.HO, what="pipeline [%s]: attn_dim" % s.name)
+                # fusion vlad: NetVLAD pooling (engine.check_vlad); None for every other fusion.  HW: the head's input width, K x HO
+                self.vlad_k = check_vlad(lf, s.vlad_clusters, "lstm", self.HO, what="pipeline [%s]: vlad_clusters" % s.name)
+                self.HW = (self.vlad_k or 1) * self.HO
                 # rnn_cell mhsa: (heads, positions) of the self-attention layers (engine.check_mhsa); None for every other cell
                 self.sa = check_mhsa(s.rnn_cell, self.H, self.fpc, s.sa_heads, s.sa_positions, self.lfusion,
                                      what="pipeline [%s]: rnn_cell" % s.name, sa_block=s.sa_block, sa_ffn_dim=s.sa_ffn_dim,
@@ -259,7 +271,7 @@ class PipeNode:
                 self.sa_drop = sa_drop_of(s, self.L, 1 + index) if self.sa else None
                 # sa_block encoder: the feed-forward width of the blocks (engine.check_sa_block); None for the plain layer
                 self.sa_ffn = check_sa_block(s.rnn_cell, self.H, s.sa_block, s.sa_ffn_dim)
-                if self.HO != C and self.head_name == "fc_convert" and self.rep_fc:
+                if self.HW != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
             if s.lstm_bidirectional and self.cls != "lstm":
@@ -292,10 +304,12 @@ class PipeNode:
             specs += [(sc + "fc_convert_w", (self.feat_dim, C)), (sc + "fc_convert_b", (C,))]
         if self.cls == "lstm":
             H, HO = self.H, self.HO
-            if HO != C:
-                specs += [(sc + self.head_name + "_w", (HO, C)), (sc + self.head_name + "_b", (C,))]
+            if self.HW != C:
+                specs += [(sc + self.head_name + "_w", (self.HW, C)), (sc + self.head_name + "_b", (C,))]
             if self.attn_dim:
                 specs += attn_specs(HO, self.attn_dim, sc)
+            if self.vlad_k:
+                specs += vlad_specs(HO, self.vlad_k, sc)
             dims = [self.feat_dim] + [HO] * (self.L - 1)
             if self.sa_ffn:
                 specs += encoder_specs(self.L, self.feat_dim, H, self.sa_ffn, self.sa[0], self.fpc, sc, self.sa[1], backward=True)
@@ -398,11 +412,13 @@ class PipeNode:
                 raise VltfError("GraphEngine: LSTM hidden size above 1024 is not built")
             self.seq_len_buf = torch.zeros(B, dtype=torch.int32, device=dev)     # per-clip lengths of a call that gives them
             r = R0 if self.per_step else B
-            self.fused = buf(r, HO) if not self.per_step else None
-            self.dropped = buf(r, HO)
-            self.drop_mask = buf(r, HO, dtype=torch.uint8)
-            self.cls_out = buf(r, C) if HO != C else None
+            HW = self.HW
+            self.fused = buf(r, HW) if not self.per_step else None
+            self.dropped = buf(r, HW)
+            self.drop_mask = buf(r, HW, dtype=torch.uint8)
+            self.cls_out = buf(r, C) if HW != C else None
             self.attn = attn_buffers(buf, B, T, HO, self.attn_dim, tr) if self.attn_dim else None
+            self.vlad = vlad_buffers(buf, B, T, HO, self.vlad_k, tr) if self.vlad_k else None
             if self.state_src is not None:
                 sd = self.state_src.dim
                 self.rep_state = buf(B, sd) if self.state_ratio > 1 else None
@@ -411,12 +427,12 @@ class PipeNode:
                     self.dstate = buf(B, H)
                     self.drep_state = buf(B, sd) if (sd != H and self.state_src.kind == "pipe") else None
             if tr:
-                self.dpre, self.dfused = buf(r, HO), buf(r, HO)
+                self.dpre, self.dfused = buf(r, HW), buf(r, HW)
                 self.dxseq = buf(R0, self.feat_dim)
                 if self.bi:
                     self.dx_bw = buf(R0, max(self.feat_dim, HO))      # the backward direction's share of a layer's input gradient
                     self.dlast = buf(B, HO)                           # fusion last / state: the fused gradient with its backward half zeroed
-            sw = max(sw, 64 * 4 * H, 64 * H, 64 * (self.attn_dim or 0))
+            sw = max(sw, 64 * 4 * H, 64 * H, 64 * (self.attn_dim or 0), 64 * (self.vlad_k or 0) * HO)
             if self.sa:
                 # under seq_len the first layer reads its input through ops.live_rows: a padded frame's features reach no product
                 self.xlive = buf(R0, self.feat_dim)
@@ -697,6 +713,14 @@ class PipeNode:
             ops.gemm(xin, Wa, S["us"], rows, self.attn_dim, HO, bias=ba)
             ops.attn_pool_fwd(S["us"], ca, xin, S["us"], S["alpha"], self.fused, b, T, HO, self.attn_dim, **lk)
             v = self.fused
+        elif self.vlad is not None:
+            # s = hseq W + beta over all rows (no workspace: fp32 whatever conv_math says), then the one pooling launch, which reads no
+            # dead row of hseq or s
+            Wv, bv, cv = (P[k] for k in vlad_names(sc))
+            S = self.vlad
+            ops.gemm(xin, Wv, S["sa"], rows, self.vlad_k, HO, bias=bv)
+            ops.netvlad_fwd(S["sa"], cv, xin, S["sa"], S["r"], self.fused, b, T, HO, self.vlad_k, **lk)
+            v = self.fused
         else:
             # with lengths `state` and `last` are h of step len - 1 (dynamic_rnn's final state), `avg` the mean over the live steps
             ops.temporal_fusion_fwd(xin, self.fused, b, T, HO, last, **lk)
@@ -710,8 +734,8 @@ class PipeNode:
                             (g._draw_index() << 20) ^ (0x2545F4914F6CDD1D + 0x9E3779B9 * self.index))
             v = self.dropped
         self._v = v
-        if HO != C:
-            ops.gemm(v, P[sc + self.head_name + "_w"], self.cls_out, r, C, HO, bias=P[sc + self.head_name + "_b"])
+        if self.HW != C:
+            ops.gemm(v, P[sc + self.head_name + "_w"], self.cls_out, r, C, self.HW, bias=P[sc + self.head_name + "_b"])
             v = self.cls_out
         return v, r
 
@@ -766,10 +790,10 @@ class PipeNode:
         rows = b * T
         r = rows if self.per_step else b
         HO, last = self.HO, "last" if self.lfusion == "state" else self.lfusion
-        if HO != C:
-            ops.gemm(self._v, d, G[sc + self.head_name + "_w"], HO, C, r, transa=True)
+        if self.HW != C:
+            ops.gemm(self._v, d, G[sc + self.head_name + "_w"], self.HW, C, r, transa=True)
             ops.colsum(d, G[sc + self.head_name + "_b"], sw, r, C)
-            ops.gemm(d, P[sc + self.head_name + "_w"], self.dpre, r, HO, C, transb=True)
+            ops.gemm(d, P[sc + self.head_name + "_w"], self.dpre, r, self.HW, C, transb=True)
             d = self.dpre
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
@@ -792,6 +816,15 @@ class PipeNode:
             ops.colsum(S["du"], G[names[1]], sw, rows, At)
             ops.colsum(S["dcp"], G[names[2]], sw, b, At)
             ops.gemm(S["du"], P[names[0]], S["dproj"], rows, HO, At, transb=True)
+            ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", rows * HO)
+        elif self.vlad is not None:
+            # ds, the direct term sum_k a_tk dV_k straight into dout (zeros in the dead rows of both), the centres' per-clip partials
+            names, S, Kv, hs = vlad_names(sc), self.vlad, self.vlad_k, top["hseq"]
+            ops.netvlad_bwd(d, hs, S["sa"], S["r"], self.fused, P[names[2]], S["ds"], top["dout"], S["dcp"], b, T, HO, Kv, **self._len_kw())
+            ops.gemm(hs, S["ds"], G[names[0]], HO, Kv, rows, transa=True)
+            ops.colsum(S["ds"], G[names[1]], sw, rows, Kv)
+            ops.colsum(S["dcp"], G[names[2]], sw, b, Kv * HO)
+            ops.gemm(S["ds"], P[names[0]], S["dproj"], rows, HO, Kv, transb=True)
             ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", rows * HO)
         else:
             ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, last, **self._len_kw())
@@ -964,7 +997,7 @@ def init_params_for(specs, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in specs:
-        if name.endswith("kernel") or name.endswith("attention_pool/context"):
+        if name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias") or name.endswith("beta"):

@@ -989,6 +989,43 @@ def branch_drop_grad(ds, dr, clips, T, W, keep, keep_path, salt_elem, salt_path,
               int(salt_path), int(branch), int(clip0), stream())
 
 
+VLAD_MAX_K, VLAD_MAX_HO, VLAD_MAX_KHO, VLAD_MAX_T = 64, 1024, 16384, 1024       # vl_netvlad_*'s limits (vltf.h)
+
+
+def _vlad_sizes(who, batch, T, HO, K, **tensors):
+    """Every tensor given holds at least what the launch reads or writes of it, where the sizes are ones the launch takes (None and
+    sizes outside the limits pass: the C side refuses them by name)."""
+    if not (batch > 0 and 2 <= K <= VLAD_MAX_K and 1 <= HO <= VLAD_MAX_HO and K * HO <= VLAD_MAX_KHO and 1 <= T <= VLAD_MAX_T):
+        return
+    need = dict(s=batch * T * K, a=batch * T * K, ds=batch * T * K, h=batch * T * HO, dh=batch * T * HO, r=batch * K,
+                y=batch * K * HO, dy=batch * K * HO, dcp=batch * K * HO, c=K * HO)
+    for k, t in tensors.items():
+        if t is not None and t.numel() < need[k]:
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), need[k]))
+
+
+def netvlad_fwd(s, c, h, a, r, y, batch, T, HO, K, seq_len=None):
+    """NetVLAD pooling over time (vl_netvlad_fwd): a = softmax_k(s) over the live steps (a may be s), V_k = sum_t a_tk (h_t - c_k),
+    y = V_k / max(|V_k|, 1e-6) / sqrt(K), cluster-major.  s, a [batch, T, K]; c [K, HO]; h [batch, T, HO]; r [batch, K];
+    y [batch, K HO]; seq_len as temporal_fusion_fwd.  2 <= K <= 64, HO <= 1024, K HO <= 16384, T <= 1024."""
+    _f32(s, c, h, a, r, y)
+    _dense(s, c, h, a, r, y)
+    _vlad_sizes("netvlad_fwd", batch, T, HO, K, s=s, c=c, h=h, a=a, r=r, y=y)
+    _ffi.call("vl_netvlad_fwd", _p(s), _p(c), _p(h), None if seq_len is None else _p(_seq_len(seq_len, batch, "netvlad_fwd")),
+              _p(a), _p(r), _p(y), batch, T, HO, K, stream())
+
+
+def netvlad_bwd(dy, h, a, r, y, c, ds, dh, dcp, batch, T, HO, K, seq_len=None):
+    """Its backward (vl_netvlad_bwd): ds [batch, T, K], the direct term dh [batch, T, HO] = sum_k a_tk dV_k and the per-clip partials
+    dcp [batch, K HO] of c's gradient; dead rows of ds and dh are zeros."""
+    _f32(dy, h, a, r, y, c, ds, dh, dcp)
+    _dense(dy, h, a, r, y, c, ds, dh, dcp)
+    _vlad_sizes("netvlad_bwd", batch, T, HO, K, dy=dy, h=h, a=a, r=r, y=y, c=c, ds=ds, dh=dh, dcp=dcp)
+    _ffi.call("vl_netvlad_bwd", _p(dy), _p(h), _p(a), _p(r), _p(y), _p(c),
+              None if seq_len is None else _p(_seq_len(seq_len, batch, "netvlad_bwd")), _p(ds), _p(dh), _p(dcp), batch, T, HO, K,
+              stream())
+
+
 def dropout_fwd(x, y, mask, keep, seed):
     _f32(x, y)
     _ffi.call("vl_dropout_fwd", _p(x), _p(y), _p(mask), x.numel(), keep, seed, stream())

@@ -71,7 +71,8 @@ def pipeline_net_config(settings, p, dataset):
             error("The LSTM classifier should be used only with [none] fusion, but it's [%s]" % p.frame_fusion[0])
         kw.update(lstm_hidden=p.lstm_params[0], lstm_layers=p.lstm_params[1], fusion=p.lstm_params[2],
                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
-                  attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None),
+                  attn_dim=getattr(p, "attn_dim", None), vlad_clusters=getattr(p, "vlad_clusters", None),
+                  sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None),
                   sa_block=getattr(p, "sa_block", None), sa_ffn_dim=getattr(p, "sa_ffn_dim", None),
                   sa_attn_dropout=getattr(p, "sa_attn_dropout", None), sa_dropout=getattr(p, "sa_dropout", None),
                   sa_drop_path=getattr(p, "sa_drop_path", None))
@@ -105,7 +106,8 @@ def graph_config(settings, feeder, batch):
                                   frame_encoding_layer=p.frame_encoding_layer, fc_output_dim=getattr(p, "fc_output_dim", None),
                                   classifier=p.classifier, lstm_params=tuple(p.lstm_params) if p.lstm_params else None,
                                   lstm_bidirectional=bool(getattr(p, "lstm_bidirectional", False)), rnn_cell=getattr(p, "rnn_cell", "lstm"),
-                                  attn_dim=getattr(p, "attn_dim", None), sa_heads=getattr(p, "sa_heads", None),
+                                  attn_dim=getattr(p, "attn_dim", None), vlad_clusters=getattr(p, "vlad_clusters", None),
+                                  sa_heads=getattr(p, "sa_heads", None),
                                   sa_positions=getattr(p, "sa_positions", None), sa_block=getattr(p, "sa_block", None),
                                   sa_ffn_dim=getattr(p, "sa_ffn_dim", None), sa_attn_dropout=getattr(p, "sa_attn_dropout", None),
                                   sa_dropout=getattr(p, "sa_dropout", None), sa_drop_path=getattr(p, "sa_drop_path", None),

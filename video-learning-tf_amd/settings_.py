@@ -204,6 +204,7 @@ class Settings:
         network.lstm_bidirectional = self.read_lstm_bidirectional(content, network)
         network.rnn_cell = self.read_rnn_cell(content, network)
         network.attn_dim = self.read_attn_dim(content, network)
+        network.vlad_clusters = self.read_vlad_clusters(content, network)
         network.sa_heads, network.sa_positions = self.read_self_attention(content, network)
         network.sa_block, network.sa_ffn_dim = self.read_sa_block(content, network)
         network.sa_attn_dropout, network.sa_dropout, network.sa_drop_path = self.read_sa_dropout(content, network)
@@ -211,10 +212,14 @@ class Settings:
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
             error("frame_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
+        if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.vlad:
+            error("frame_fusion: vlad is a fusion of the recurrent classifier (lstm_params), not a frame fusion")
         network.input_shape = self.read_field(content, "input_shape", listify=True)
         network.input_fusion = self.read_field(content, "input_fusion", validate=defs.fusion_method)
         if network.input_fusion == defs.fusion_method.attn:
             error("input_fusion: attn is a fusion of the recurrent classifier (lstm_params), not an input fusion")
+        if network.input_fusion == defs.fusion_method.vlad:
+            error("input_fusion: vlad is a fusion of the recurrent classifier (lstm_params), not an input fusion")
         network.train_from = self.read_train_from(content, network)
         unread = [x for x in content if x not in self.pipeline_field_cache]
         if unread:
@@ -321,6 +326,22 @@ class Settings:
         except VltfError as ex:
             error(str(ex))
         return tuple(r if r > 0 else None for r in rates)
+
+    def read_vlad_clusters(self, content, network):
+        """`vlad_clusters: <K>` beside lstm_params (this project's extension of the pipeline schema): the number of centres of fusion
+        vlad, NetVLAD pooling over the recurrent outputs (engine.vlad_specs).  Absent / None = 8.  Refused without fusion vlad, unless
+        an integer in 2..64, and where K x the recurrent output width exceeds 16384; fusion vlad itself is refused without the recurrent
+        classifier (engine.check_vlad).  -> K, or None for every other fusion."""
+        v = self.read_field(content, "vlad_clusters")
+        lstm = network.classifier == defs.classifier.lstm
+        from .engine import VltfError, check_vlad
+        try:
+            if not lstm:
+                return check_vlad(None, v, network.classifier)
+            H = network.lstm_params[0] * (2 if network.lstm_bidirectional else 1)
+            return check_vlad(network.lstm_params[2], v, network.classifier, H)
+        except VltfError as ex:
+            error(str(ex))
 
     def read_train_from(self, content, network):
         """`train_from: <layer>` (this project's extension of the pipeline schema): the first dcnn layer that trains -- every dcnn layer
@@ -647,6 +668,8 @@ class Settings:
                 v.clip_fusion_type, v.clip_fusion_method = defs.check(cf[0], defs.fusion_type), defs.check(cf[1], defs.fusion_method)
                 if v.clip_fusion_method == defs.fusion_method.attn:
                     error("val.clip_fusion: attn is a fusion of the recurrent classifier (lstm_params), not a fusion of a video's clips")
+                if v.clip_fusion_method == defs.fusion_method.vlad:
+                    error("val.clip_fusion: vlad is a fusion of the recurrent classifier (lstm_params), not a fusion of a video's clips")
                 # evaluate the averaged weights a training run with train.ema_decay stored beside its weights: absent / None = the weights
                 ue = obj.get("use_ema") if obj.get("use_ema") not in (None, "None") else False
                 if not isinstance(ue, bool):
