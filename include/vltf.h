@@ -504,6 +504,28 @@ int vl_mhsa_bwd(const float* dctx, const float* qkv, const float* P, const int32
  * self-attention layer under seq_len, so that a padded frame's features reach no product (x^T dqkv reads every row). */
 int vl_live_rows(const float* x, const int32_t* seq_len, float* y, int batch, int T, int W, vl_stream_t stream);
 
+/* ---- the taps of a dilated 1-D convolution over the frames of a clip (rnn_cell `tcn`; csrc/temporal_conv.hip) ----------
+ * x [batch T][C], rows clip-major r = b T + t; L = min(max(seq_len[b], 0), T) live steps of clip b (seq_len NULL: L = T).  Tap j of
+ * `taps` reads at offset off_j = (j - (taps - 1) / 2) dilation, or, causal, off_j = (j - (taps - 1)) dilation (a step sees itself and
+ * the past only).
+ *   fwd: cols[b T + t][j C + c] = x[b T + t + off_j][c]  where t < L and 0 <= t + off_j < L, +0.0f everywhere else (dead rows, taps
+ *        before the clip's first step or at or behind its L-th): a clip of length L in a T-step batch gives what it gives in an
+ *        L-step model with zero padding.  Every element of cols [batch T][taps C] is written; nothing is read where a zero is stored.
+ *        The convolution is then the product cols W with W the (taps C, out) flat form of a (taps, C, out) kernel (vl_gemm).
+ *   bwd: for t < L, dx[b T + t][c] = dres[b T + t][c] + sum over j ASCENDING with 0 <= t - off_j < L of dcols[b T + t - off_j][j C + c]:
+ *        plain fp32 adds in that order, starting from the dres term (the gradient of a residual path around the convolution), or from
+ *        +0.0f when dres is NULL.  Dead rows of dx are +0.0f.  A gather per output element: no atomics.
+ * DEAD-ROW CONTRACT: rows t >= L of x, dcols and dres are never read (they may hold NaN).  A clip's outputs depend on that clip's
+ * inputs alone, bit for bit, in any batch.  16-byte loads and stores where C % 4 == 0 and every pointer is 16-byte aligned, a scalar
+ * path otherwise.  Index arithmetic is 64-bit.
+ * Limits (an error names the one missed, nothing is launched): batch, T, C >= 1; 1 <= taps <= 9, odd unless causal;
+ * 1 <= dilation <= 65536 (a dilation of T or more is legal: only the zero-offset tap is live); C <= 1024; seq_len and dres alone may
+ * be NULL.  The launches take no host-varying scalar, so a captured step replays them as they are: there is no _st form. */
+int vl_tconv_cols_fwd(const float* x, const int32_t* seq_len, float* cols, int batch, int T, int C, int taps, int dilation, int causal,
+                      vl_stream_t stream);
+int vl_tconv_cols_bwd(const float* dcols, const float* dres, const int32_t* seq_len, float* dx, int batch, int T, int C, int taps,
+                      int dilation, int causal, vl_stream_t stream);
+
 /* ---- the encoder block around the self-attention layer (sa_block `encoder`; csrc/layer_norm.hip) -----------------------
  * Rows are [clips T][W], 8 <= W <= 1024; L = min(max(seq_len[b], 0), T) live steps of clip b (seq_len NULL: L = T).
  * vl_add_layer_norm_fwd: s = x + r (r NULL: s = x), stored to `sum` where it is not NULL; y = (s - mean) rstd gamma + beta with

@@ -99,6 +99,8 @@ SIGNATURES = {
     "vl_mhsa_fwd": (i32, [p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_mhsa_bwd": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, p]),
     "vl_live_rows": (i32, [p, p, p, i32, i32, i32, p]),
+    "vl_tconv_cols_fwd": (i32, [p, p, p, i32, i32, i32, i32, i32, i32, p]),
+    "vl_tconv_cols_bwd": (i32, [p, p, p, p, i32, i32, i32, i32, i32, i32, p]),
     "vl_add_layer_norm_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, f32, p, p]),
     "vl_layer_norm_bwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, p, p]),
     "vl_gelu_fwd": (i32, [p, p, i64, p]),

@@ -14,7 +14,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-inline-asm -fno-slp-vectorize ${EXP:-}"
 mkdir -p "$obj"
 pids=()
-for f in api mfma_gemm pointwise lstm_cluster resize conv_c8 self_attention layer_norm netvlad; do
+for f in api mfma_gemm pointwise lstm_cluster resize conv_c8 self_attention layer_norm netvlad temporal_conv; do
   if [ ! -f "$obj/$f.o" ] || [ "$here/$f.hip" -nt "$obj/$f.o" ] || [ "$here/common.h" -nt "$obj/$f.o" ] || [ "$here/conv_desc.h" -nt "$obj/$f.o" ] \
      || [ "$here/../../include/vltf.h" -nt "$obj/$f.o" ] || [ "$here/build.sh" -nt "$obj/$f.o" ]; then
     $HIPCC $FLAGS -c "$here/$f.hip" -o "$obj/$f.o" &
@@ -22,6 +22,6 @@ for f in api mfma_gemm pointwise lstm_cluster resize conv_c8 self_attention laye
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$out" "$obj/api.o" "$obj/mfma_gemm.o" "$obj/pointwise.o" "$obj/lstm_cluster.o" "$obj/resize.o" "$obj/conv_c8.o" "$obj/self_attention.o" "$obj/layer_norm.o" "$obj/netvlad.o"
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$out" "$obj/api.o" "$obj/mfma_gemm.o" "$obj/pointwise.o" "$obj/lstm_cluster.o" "$obj/resize.o" "$obj/conv_c8.o" "$obj/self_attention.o" "$obj/layer_norm.o" "$obj/netvlad.o" "$obj/temporal_conv.o"
 [ -n "${EXP:-}" ] || gcc -O3 -msse4.2 -std=c11 -fPIC -shared -Wall -pthread -o "$here/../libvltf_host.so" "$here/host_io.c"
 echo "built $out and $here/../libvltf_host.so"

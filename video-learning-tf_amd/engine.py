@@ -60,6 +60,9 @@ class NetConfig:
                                                 # | "mhsa": every layer a multi-head self-attention layer over the fpc frames (mhsa_names)
     sa_heads: Optional[int] = None              # rnn_cell mhsa: heads (divides lstm_hidden); None = 4 where 4 divides it, else 1
     sa_positions: Optional[str] = None          # rnn_cell mhsa: "relative" (None: a learned bias per head and offset) | "none"
+    tcn_kernel: Optional[int] = None            # rnn_cell tcn: the taps k of every layer's dilated convolution, 1..9, odd unless tcn_causal; None = 3
+    tcn_dilation: Optional[str] = None          # rnn_cell tcn: "exponential" (None: layer l dilates by 2^l, lstm_layers <= 17) | "none" (1 everywhere)
+    tcn_causal: Optional[bool] = None           # rnn_cell tcn: True = a step sees itself and the past only; None / False = centred taps
     sa_block: Optional[str] = None              # rnn_cell mhsa: "plain" (None: the bare attention layer) | "encoder": the pre-LN encoder block (encoder_specs)
     sa_ffn_dim: Optional[int] = None            # sa_block encoder: the feed-forward width F, 8..4096; None = 4 lstm_hidden
     sa_attn_dropout: Optional[float] = None     # rnn_cell mhsa: dropout rate on the softmax weights of a training forward, [0, 1); None / 0 = off
@@ -134,6 +137,7 @@ def check_blstm(hidden, what="lstm_bidirectional"):
 
 
 RNN_CELLS = ("lstm", "gru", "mhsa")
+TEMPORAL_CELLS = RNN_CELLS + ("tcn",)   # what check_rnn_cell admits: the recurrences, self-attention and the temporal convolution (tcn_specs)
 GRU_MAX_HIDDEN = ops.GRU_MAX_HIDDEN     # the GRU recurrence exists in the cluster form only (vltf.h: vl_gru_seq_fwd)
 
 
@@ -152,8 +156,18 @@ def gru_specs(layer, d, H, scope=""):
 
 def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state_input=False, what="rnn_cell"):
     """Refuses what the GRU classifier is not built for; -> the cell.  `classifier`: "lstm" where the pipeline has the recurrent classifier."""
-    if cell not in RNN_CELLS:
-        raise VltfError("%s must be lstm or gru (or mhsa, the self-attention layer), got [%s]" % (what, cell))
+    if cell not in TEMPORAL_CELLS:
+        raise VltfError("%s must be lstm or gru (or mhsa, the self-attention layer), got [%s] (tcn, the dilated temporal convolution, "
+                        "is the fourth)" % (what, cell))
+    if cell == "tcn":
+        if classifier != "lstm":
+            raise VltfError("%s: tcn is the temporal layer of classifier lstm, but the classifier is [%s]" % (what, classifier))
+        if bidirectional:
+            raise VltfError("%s: tcn with lstm_bidirectional is not built (centred taps read both directions already; the "
+                            "bidirectional launch runs LSTM cells)" % what)
+        if state_input:
+            raise VltfError("%s: tcn takes no state input: the reference hands an LSTM ONE vector as c = h, and a temporal "
+                            "convolution has no state" % what)
     if cell == "mhsa":
         if classifier != "lstm":
             raise VltfError("%s: mhsa is the temporal layer of classifier lstm, but the classifier is [%s]" % (what, classifier))
@@ -174,6 +188,135 @@ def check_rnn_cell(cell, classifier="lstm", hidden=1, bidirectional=False, state
             raise VltfError("%s: the GRU recurrence runs in the cluster form only and needs a hidden size <= %d, got %d"
                             % (what, GRU_MAX_HIDDEN, hidden))
     return cell
+
+
+# ---- rnn_cell tcn: a stack of dilated residual 1-D convolutions over the frames of a clip ------------------------------
+TCN_DILATIONS = ("exponential", "none")
+TCN_MAX_LAYERS = 17                     # exponential: layer l dilates by 2^l, and the launches take a dilation <= 65536 = 2^16
+TCN_LAYER_VARS = ("conv_kernel", "conv_bias", "out_kernel", "out_bias")
+
+
+def tcn_var(scope, layer, var):
+    """The name of a variable of the convolution stack: layer None = the embedding (var kernel | bias) in front of the layers."""
+    return "%stemporal_conv/%s/%s" % (scope, "embed" if layer is None else "layer_%d" % layer, var)
+
+
+def tcn_specs(layers, d, H, k, scope="", backward=False):
+    """[(name, shape)] of the convolution stack in flat-buffer order: the embedding kernel (d, H) and bias (H,), then the layers
+    ascending with conv_kernel (k, H, H), conv_bias (H,), out_kernel (H, H), out_bias (H,).  conv_kernel is rank 3 (Keras' Conv1D
+    layout: tap, in, out) and its flat form is the (k H, H) operand of the product; like every variable of rank >= 2 it is a weight for
+    decay_ranges, LARS and LAMB, and the biases are exempt.  backward (GraphEngine, whose head_specs list the layers descending): the
+    layers descending, then the embedding."""
+    shapes = dict(conv_kernel=(k, H, H), conv_bias=(H,), out_kernel=(H, H), out_bias=(H,))
+    groups = [[(tcn_var(scope, None, "kernel"), (d, H)), (tcn_var(scope, None, "bias"), (H,))]]
+    for l in range(layers):
+        groups.append([(tcn_var(scope, l, v), shapes[v]) for v in TCN_LAYER_VARS])
+    return [s for grp in (reversed(groups) if backward else groups) for s in grp]
+
+
+def tcn_dilations(mode, layers):
+    """The dilation of every layer: 2^l (exponential) or 1 (none)."""
+    return tuple(1 << l if mode == "exponential" else 1 for l in range(int(layers)))
+
+
+def check_tcn(cell, hidden=1, layers=1, tcn_kernel=None, tcn_dilation=None, tcn_causal=None, fusion="avg", what="rnn_cell"):
+    """-> (k, dilation mode, causal) of rnn_cell tcn, or None for every other cell.  Refused by name, before anything is allocated:
+    tcn_kernel / tcn_dilation / tcn_causal without tcn; with it, fusion state, a width above the launches' (vltf.h:
+    vl_tconv_cols_fwd), a kernel outside 1..9 or even without tcn_causal, a dilation rule that is neither, more than 17 layers under
+    the exponential rule."""
+    given = lambda v: not (v is None or (isinstance(v, str) and v == "None"))
+    if cell != "tcn":
+        for k, v in (("tcn_kernel", tcn_kernel), ("tcn_dilation", tcn_dilation), ("tcn_causal", tcn_causal)):
+            if given(v):
+                raise VltfError("%s is a key of rnn_cell tcn, but the cell is [%s]" % (k, cell))
+        return None
+    H, L = int(hidden), int(layers)
+    if fusion == "state":
+        raise VltfError("%s: tcn with fusion state is not built: a temporal convolution has no final state (use last)" % what)
+    if not 1 <= H <= ops.TCONV_MAX_WIDTH:
+        raise VltfError("%s: tcn needs a width H <= %d, got %d" % (what, ops.TCONV_MAX_WIDTH, H))
+    causal = tcn_causal if given(tcn_causal) else False
+    if not isinstance(causal, (bool, np.bool_)):
+        raise VltfError("tcn_causal must be True or False, got [%s]" % (tcn_causal,))
+    causal = bool(causal)
+    k = tcn_kernel if given(tcn_kernel) else 3
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= ops.TCONV_MAX_TAPS:
+        raise VltfError("tcn_kernel must be an integer in 1..%d, got [%s]" % (ops.TCONV_MAX_TAPS, k))
+    if int(k) % 2 == 0 and not causal:
+        raise VltfError("tcn_kernel must be odd unless tcn_causal (a centred kernel has a middle tap), got [%s]" % (k,))
+    mode = tcn_dilation if given(tcn_dilation) else "exponential"
+    if mode not in TCN_DILATIONS:
+        raise VltfError("tcn_dilation must be exponential or none, got [%s]" % (mode,))
+    if mode == "exponential" and L > TCN_MAX_LAYERS:
+        raise VltfError("%s: tcn with tcn_dilation exponential needs at most %d layers (layer l dilates by 2^l <= %d), got %d"
+                        % (what, TCN_MAX_LAYERS, ops.TCONV_MAX_DILATION, L))
+    return int(k), mode, causal
+
+
+def tcn_buffers(buf, rows, H, k, layers, training):
+    """-> E = dict(x0, layers=[S ...]): the embedding's output x0; per layer the taps cols [rows, k H], z = relu(cols W1 + b1), m = z W2
+    + b2 and hseq = the layer's input + m (the name the other layer kinds give a layer's output; the last one is what the fusions
+    read).  cols and z of every layer are kept for the backward.  Training: dx0 in front; per layer dout (the gradient of hseq), dz and
+    dcols -- every layer has its own, because the parameter gradients read them from the second stream while the chain goes on."""
+    E = dict(x0=buf(rows, H), layers=[])
+    if training:
+        E["dx0"] = buf(rows, H)
+    for _ in range(layers):
+        S = dict(cols=buf(rows, k * H), z=buf(rows, H), m=buf(rows, H), hseq=buf(rows, H))
+        if training:
+            S.update(dout=buf(rows, H), dz=buf(rows, H), dcols=buf(rows, k * H))
+        E["layers"].append(S)
+    return E
+
+
+def tcn_forward(E, P, scope, xin, rows, b, T, d, H, tc, ws, lk):
+    """The convolution stack on xin [rows, d] -> the last layer's output.  The embedding takes the workspace (it follows conv_math, as
+    the encoder block's embedding); a layer's two products do not (fp32 always, as the self-attention output projection).  Per layer:
+    ONE launch moves the taps into cols, the convolution is cols W1 with bias and ReLU in the product, then z W2 + b2 and the residual
+    add.  tc: (k, dilations, causal).  lk: {} or {seq_len: lengths} -- the taps launch never reads a dead row and zeroes the dead rows
+    of cols, so a dead row of z, m and hseq holds a finite value (a function of the biases) that nothing reads.  No launch takes a
+    host-varying argument: a captured step replays them as they are."""
+    v = lambda l, name: P[tcn_var(scope, l, name)]
+    k, dils, causal = tc
+    ops.gemm(xin, v(None, "kernel"), E["x0"], rows, H, d, bias=v(None, "bias"), ws=ws)
+    x = E["x0"]
+    for l, S in enumerate(E["layers"]):
+        ops.tconv_cols_fwd(x, S["cols"], b, T, H, k, dils[l], causal, **lk)
+        ops.gemm(S["cols"], v(l, "conv_kernel"), S["z"], rows, H, k * H, bias=v(l, "conv_bias"), relu=True)
+        ops.gemm(S["z"], v(l, "out_kernel"), S["m"], rows, H, H, bias=v(l, "out_bias"))
+        ops.eltwise2(x, S["m"], S["hseq"], "add", rows * H)
+        x = S["hseq"]
+    return x
+
+
+def tcn_backward(E, P, G, scope, rows, b, T, H, tc, lk, param_grads):
+    """From layers[-1]["dout"] (the gradient of the stack's output) to E["dx0"] (the gradient of the embedding's output) and every
+    gradient of the stack but the embedding's, which the caller forms as it forms its first layer's.  Per layer, with dy = dout:
+    dz = relu_grad(dy W2^T, z), dcols = dz W1^T, and ONE launch gathers dcols back over the taps and adds dy, the gradient of the
+    residual path, so it finishes the layer's input gradient.  Dead rows of dy are zeros (the fusions write them) and the launch keeps
+    them zero down the stack.  param_grads(launch): as encoder_backward's."""
+    v = lambda l, name: P[tcn_var(scope, l, name)]
+    g = lambda l, name: G[tcn_var(scope, l, name)]
+    k, dils, causal = tc
+    layers = E["layers"]
+    for l in reversed(range(len(layers))):
+        S = layers[l]
+        dy = S["dout"]
+        ops.gemm(dy, v(l, "out_kernel"), S["dz"], rows, H, H, transb=True)
+
+        def out_grads(ws_, sws, S=S, l=l, dy=dy):
+            ops.gemm(S["z"], dy, g(l, "out_kernel"), H, H, rows, transa=True)
+            ops.colsum(dy, g(l, "out_bias"), sws, rows, H)
+        param_grads(out_grads)
+        ops.relu_grad(S["dz"], S["z"], rows * H)
+        ops.gemm(S["dz"], v(l, "conv_kernel"), S["dcols"], rows, k * H, H, transb=True)
+
+        def conv_grads(ws_, sws, S=S, l=l):
+            ops.gemm(S["cols"], S["dz"], g(l, "conv_kernel"), k * H, H, rows, transa=True)
+            ops.colsum(S["dz"], g(l, "conv_bias"), sws, rows, H)
+        param_grads(conv_grads)
+        ops.tconv_cols_bwd(S["dcols"], dy, layers[l - 1]["dout"] if l else E["dx0"], b, T, H, k, dils[l], causal, **lk)
+    return E["dx0"]
 
 
 SA_POSITIONS = ("relative", "none")
@@ -629,7 +772,15 @@ def param_specs(cfg: NetConfig):
     sa = check_mhsa(cfg.rnn_cell, cfg.lstm_hidden, cfg.fpc, cfg.sa_heads, cfg.sa_positions, cfg.fusion, sa_block=cfg.sa_block,
                     sa_ffn_dim=cfg.sa_ffn_dim, sa_attn_dropout=cfg.sa_attn_dropout, sa_dropout=cfg.sa_dropout,
                     sa_drop_path=cfg.sa_drop_path)
-    if sa:
+    tc = check_tcn(cfg.rnn_cell, cfg.lstm_hidden, cfg.lstm_layers, cfg.tcn_kernel, cfg.tcn_dilation, cfg.tcn_causal, cfg.fusion)
+    if tc:
+        H = cfg.lstm_hidden
+        if kv * H != cfg.num_classes:                     # the head's names are the LSTM classifier's
+            specs += [("output_fc_w", (kv * H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
+        specs += attn_specs(H, A) if A else []
+        specs += vlad_specs(H, KV) if KV else []
+        specs += tcn_specs(cfg.lstm_layers, dim, H, tc[0])
+    elif sa:
         H = cfg.lstm_hidden
         if kv * H != cfg.num_classes:                     # the head's names are the LSTM classifier's
             specs += [("output_fc_w", (kv * H, cfg.num_classes)), ("output_fc_b", (cfg.num_classes,))]
@@ -1561,7 +1712,10 @@ def init_params(cfg: NetConfig, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in param_specs(cfg):
-        if name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
+        if name.endswith("conv_kernel") and len(shp) == 3:        # Keras' Conv1D fans: taps x in, taps x out
+            lim = math.sqrt(6.0 / (shp[0] * shp[1] + shp[0] * shp[2]))
+            out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
+        elif name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias") or name.endswith("beta"):
@@ -1792,6 +1946,11 @@ class LRCNEngine:
         self.sa_ffn = check_sa_block(cfg.rnn_cell, H, cfg.sa_block, cfg.sa_ffn_dim) if self.sa else None
         # sa_attn_dropout / sa_dropout / sa_drop_path: what a TRAINING forward draws with, else None (refusals: param_specs -> check_mhsa)
         self.sa_drop = sa_drop_of(cfg, cfg.lstm_layers) if self.sa and training else None
+        # rnn_cell tcn: (k, dilations, causal) of the convolution stack, else None (refusals: param_specs -> check_tcn)
+        self.tc = None
+        if cfg.classifier == "lstm":
+            tc = check_tcn(cfg.rnn_cell, H, cfg.lstm_layers, cfg.tcn_kernel, cfg.tcn_dilation, cfg.tcn_causal, cfg.fusion)
+            self.tc = (tc[0], tcn_dilations(tc[1], cfg.lstm_layers), tc[2]) if tc else None
         self._sa_drop = None                                        # the SaDrop bound to the pass the last forward ran, for its backward
         # colsum / bias / sumsq partials (rnn_cell mhsa: the position bias's gradient is a column sum heads (2T - 1) wide, the
         # block's ffn1_bias F wide)
@@ -1822,6 +1981,10 @@ class LRCNEngine:
             if self.sa_ffn:
                 self.enc = encoder_buffers(buf, N, T, H, self.sa_ffn, self.sa[0], self.sa[1], cfg.lstm_layers, training, self.sa_drop)
                 self.mhsa = self.enc["layers"]
+            self.tcn, self.tconv = None, []                             # rnn_cell tcn: tcn_buffers and its layers (self.tc above)
+            if self.tc:
+                self.tcn = tcn_buffers(buf, N, H, self.tc[0], cfg.lstm_layers, training)
+                self.tconv = self.tcn["layers"]
             HO = self.lstm_out = 2 * H if self.bi else H                # width of a layer's output, of the fused vector and of the head's input
             if self.bi and ops.lstm_seq_bi_tag_span(1, 1, H) == 0:      # (H itself was checked by param_specs)
                 raise VltfError("lstm_bidirectional: this device has too few compute units to hold both directions of hidden size %d in "
@@ -1833,7 +1996,7 @@ class LRCNEngine:
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, N, H, training))
                     continue
-                if self.sa_ffn:
+                if self.sa_ffn or self.tc:
                     continue
                 if self.sa:
                     self.mhsa.append(mhsa_buffers(buf, N, T, H, self.sa[0], self.sa[1], training))
@@ -2486,7 +2649,7 @@ class LRCNEngine:
         D, H4 = self.cfg.encode_dim(), 4 * self.cfg.lstm_hidden
         if getattr(self, "bi", False) or getattr(self, "is_gru", False):   # a bidirectional or GRU layer's dense products run on ops.gemm
             return False
-        if getattr(self, "sa", None):                                      # a self-attention layer's too
+        if getattr(self, "sa", None) or getattr(self, "tc", None):         # a self-attention or convolution layer's too
             return False
         return (l == 0 and self._fc6_kc8(n) and os.environ.get("VLTF_LSTM_KC8", "1") != "0" and D % 8 == 0 and H4 % 8 == 0
                 and D * H4 <= self.k_w.numel() and n * max(D, H4) <= self.k_act.numel() and (not self.training or n * H4 <= self.k_d6.numel()))
@@ -2580,6 +2743,9 @@ class LRCNEngine:
                 xin, d = encoder_forward(self.enc, P, "", xin, n, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], self.ws, {},
                                          self._sa_drop), H
                 self._mhsa_clips = b
+            if self.tcn:
+                # rnn_cell tcn: embedding, then per layer the taps launch, two products and the residual add (tcn_forward)
+                xin, d = tcn_forward(self.tcn, P, "", xin, n, b, T, d, H, self.tc, self.ws, {}), H
             for l, S in enumerate(() if self.enc else self.mhsa):
                 # the qkv projection of all rows as the GRU's input projection is called (with the workspace: it follows conv_math),
                 # ONE launch for every (clip, head), then the output projection as attention_pool's (no workspace: fp32 always).  The
@@ -2766,7 +2932,7 @@ class LRCNEngine:
             if self._dropout:
                 ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], cfg.dropout_keep_prob)
                 d = self.dfused
-            top = (self.blstm or self.gru or self.mhsa or self.lstm)[-1]
+            top = (self.blstm or self.gru or self.mhsa or self.tconv or self.lstm)[-1]
             if self.per_step:
                 top["dout"][:r].copy_(d[:r])
             elif self.bi and self.lstm_fusion == "last":
@@ -2870,6 +3036,19 @@ class LRCNEngine:
                 if self.dcnn_trains:                                                  # (a frozen tower: nobody reads dfeat)
                     relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
                     ops.gemm(dx0, P[encoder_var("", None, "kernel")], self.dfeat, n, D, H, transb=True, ldb=H,
+                             relu_mask=self._fused_mask(relu_mask), ws=self.ws)
+                    self._relu_grad_behind(self.dfeat, relu_mask, n * D)
+            if self.tcn:
+                # rnn_cell tcn: the layers (tcn_backward), then the embedding as the GRU's input projection
+                dx0 = tcn_backward(self.tcn, P, G, "", n, b, T, H, self.tc, {}, param_grads)
+
+                def tcn_embed_grads(ws, sws, dx0=dx0):
+                    ops.gemm(self.feat, dx0, G[tcn_var("", None, "kernel")], D, H, n, transa=True, ws=ws)
+                    ops.colsum(dx0, G[tcn_var("", None, "bias")], sws, n, H)
+                param_grads(tcn_embed_grads)
+                if self.dcnn_trains:                                                  # (a frozen tower: nobody reads dfeat)
+                    relu_mask = self.feat if self.f8 is None else None       # ReluGrad of fc6 / fc7 fused here
+                    ops.gemm(dx0, P[tcn_var("", None, "kernel")], self.dfeat, n, D, H, transb=True, ldb=H,
                              relu_mask=self._fused_mask(relu_mask), ws=self.ws)
                     self._relu_grad_behind(self.dfeat, relu_mask, n * D)
             for l in reversed(range(0 if self.enc else len(self.mhsa))):

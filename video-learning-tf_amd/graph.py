@@ -44,7 +44,7 @@ import torch
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
 from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn, check_vlad, vlad_buffers, vlad_names, vlad_specs,
+                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, check_tcn, tcn_backward, tcn_buffers, tcn_dilations, tcn_forward, tcn_specs, tcn_var, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn, check_vlad, vlad_buffers, vlad_names, vlad_specs,
                      check_label_smoothing,
                      check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
                      param_specs, tier_plan)
@@ -67,6 +67,9 @@ class PipelineSpec:
                                                     # | mhsa: every layer a multi-head self-attention layer over the frames (engine.mhsa_names)
     sa_heads: Optional[int] = None                  # rnn_cell mhsa: heads (divides the width); None = 4 where 4 divides it, else 1
     sa_positions: Optional[str] = None              # rnn_cell mhsa: relative (None) | none
+    tcn_kernel: Optional[int] = None                # rnn_cell tcn (engine.tcn_specs): the taps of every layer's dilated convolution, 1..9; None = 3
+    tcn_dilation: Optional[str] = None              # rnn_cell tcn: exponential (None: layer l dilates by 2^l) | none
+    tcn_causal: Optional[bool] = None               # rnn_cell tcn: True = a step sees itself and the past only; None / False = centred
     sa_block: Optional[str] = None                  # rnn_cell mhsa: plain (None) | encoder: the pre-LN encoder block (engine.encoder_specs)
     sa_ffn_dim: Optional[int] = None                # sa_block encoder: the feed-forward width, 8..4096; None = 4 x the width
     sa_attn_dropout: Optional[float] = None         # rnn_cell mhsa: dropout rate on the softmax weights in a training forward, [0, 1); None / 0 = off
@@ -234,6 +237,7 @@ class PipeNode:
         self.cls = s.classifier
         self.late = False
         if self.cls is None:
+            self.tc = check_tcn(s.rnn_cell, tcn_kernel=s.tcn_kernel, tcn_dilation=s.tcn_dilation, tcn_causal=s.tcn_causal)   # the keys alone: refused
             self.out_dim, self.fpc_out, self.max_rows = dim, out_fpc, rows
         else:
             if self.cls == "fc":
@@ -271,6 +275,10 @@ class PipeNode:
                 self.sa_drop = sa_drop_of(s, self.L, 1 + index) if self.sa else None
                 # sa_block encoder: the feed-forward width of the blocks (engine.check_sa_block); None for the plain layer
                 self.sa_ffn = check_sa_block(s.rnn_cell, self.H, s.sa_block, s.sa_ffn_dim)
+                # rnn_cell tcn: (k, dilations, causal) of the convolution stack (engine.check_tcn); None for every other cell
+                tc = check_tcn(s.rnn_cell, self.H, self.L, s.tcn_kernel, s.tcn_dilation, s.tcn_causal, self.lfusion,
+                               what="pipeline [%s]: rnn_cell" % s.name)
+                self.tc = (tc[0], tcn_dilations(tc[1], self.L), tc[2]) if tc else None
                 if self.HW != C and self.head_name == "fc_convert" and self.rep_fc:
                     raise VltfError("Variable %sfc_convert_w already exists (representation fc and LSTM fusion state)" % self.scope)
                 rows = rows if self.per_step else rows // self.fpc
@@ -281,6 +289,7 @@ class PipeNode:
                                      sa_ffn_dim=s.sa_ffn_dim, sa_attn_dropout=s.sa_attn_dropout, sa_dropout=s.sa_dropout,
                                      sa_drop_path=s.sa_drop_path)                                         # the keys without the cell: refused
                 self.sa_ffn = self.sa_drop = None
+                self.tc = check_tcn(s.rnn_cell, tcn_kernel=s.tcn_kernel, tcn_dilation=s.tcn_dilation, tcn_causal=s.tcn_causal)
             self.late = ftype == "late" and self.fpc > 1 and fmethod != "reshape"
             if self.late:
                 if self.cls == "lstm" or rows % self.fpc:
@@ -313,7 +322,9 @@ class PipeNode:
             dims = [self.feat_dim] + [HO] * (self.L - 1)
             if self.sa_ffn:
                 specs += encoder_specs(self.L, self.feat_dim, H, self.sa_ffn, self.sa[0], self.fpc, sc, self.sa[1], backward=True)
-            for l in reversed(range(0 if self.sa_ffn else self.L)):
+            if self.tc:
+                specs += tcn_specs(self.L, self.feat_dim, H, self.tc[0], sc, backward=True)
+            for l in reversed(range(0 if self.sa_ffn or self.tc else self.L)):
                 if self.bi:
                     specs += [(n, (dims[l] + H, 4 * H) if n.endswith("kernel") else (4 * H,)) for n in blstm_names(l, sc)]
                     continue
@@ -398,7 +409,7 @@ class PipeNode:
                 if self.is_gru:
                     self.gru.append(gru_buffers(buf, R0, H, tr))
                     continue
-                if self.sa_ffn:
+                if self.sa_ffn or self.tc:
                     continue
                 if self.sa:
                     self.mhsa.append(mhsa_buffers(buf, R0, T, H, self.sa[0], self.sa[1], tr))
@@ -437,6 +448,12 @@ class PipeNode:
                 # under seq_len the first layer reads its input through ops.live_rows: a padded frame's features reach no product
                 self.xlive = buf(R0, self.feat_dim)
                 sw = max(sw, 64 * self.sa[0] * (2 * T - 1))
+            self.tcn, self.tconv = None, []
+            if self.tc:
+                # rnn_cell tcn: engine.tcn_buffers and its layers; the embedding's input goes through ops.live_rows under seq_len
+                self.tcn = tcn_buffers(buf, R0, H, self.tc[0], self.L, tr)
+                self.tconv = self.tcn["layers"]
+                self.xlive = buf(R0, self.feat_dim)
             self.enc = None
             if self.sa_ffn:
                 # sa_block encoder: engine.encoder_buffers; self.mhsa is its layers (the top layer's hseq / dout are the final norm's)
@@ -676,6 +693,15 @@ class PipeNode:
             self._xsa = xin
             xin, d = encoder_forward(self.enc, P, sc, xin, rows, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk,
                                      self._sa_drop), H
+        if self.tcn:
+            # rnn_cell tcn (engine.tcn_forward).  Under seq_len the embedding reads its input through ops.live_rows, as the
+            # self-attention layers' first product does: x^T dx0 reads every row of x.  The taps launch never reads a dead row and
+            # zeroes the dead rows of cols; a dead row of the products' outputs is finite and read by nothing.
+            if lk:
+                ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
+                xin = self.xlive
+            self._xsa = xin
+            xin, d = tcn_forward(self.tcn, P, sc, xin, rows, b, T, d, H, self.tc, g.ws, lk), H
         for l, S in enumerate(() if self.enc else self.mhsa):
             # Dead-row contract: the launch never reads a dead row of qkv and writes zeros in the dead rows of ctx (so a dead row of a
             # layer's output is out_bias, which nothing reads: the next layer's launch, the fusions and the masked loss skip it, and its
@@ -798,7 +824,7 @@ class PipeNode:
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
             d = self.dfused
-        top = (self.blstm or self.gru or self.mhsa or self.lstm)[-1]
+        top = (self.blstm or self.gru or self.mhsa or self.tconv or self.lstm)[-1]
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
         elif self.bi and last == "last":
@@ -871,6 +897,13 @@ class PipeNode:
             ops.colsum(dx0, G[encoder_var(sc, None, "bias")], sw, rows, H)
             if self.wants_feat:
                 ops.gemm(dx0, P[encoder_var(sc, None, "kernel")], self.dxseq, rows, self.feat_dim, H, transb=True, ldb=H, ws=g.ws)
+        if self.tcn:
+            # rnn_cell tcn: the layers (engine.tcn_backward: one stream here, every gradient where the chain stands), then the embedding
+            dx0 = tcn_backward(self.tcn, P, G, sc, rows, b, T, H, self.tc, self._len_kw(), lambda launch: launch(g.ws, sw))
+            ops.gemm(self._xsa, dx0, G[tcn_var(sc, None, "kernel")], self.feat_dim, H, rows, transa=True, ws=g.ws)
+            ops.colsum(dx0, G[tcn_var(sc, None, "bias")], sw, rows, H)
+            if self.wants_feat:
+                ops.gemm(dx0, P[tcn_var(sc, None, "kernel")], self.dxseq, rows, self.feat_dim, H, transb=True, ldb=H, ws=g.ws)
         for l in reversed(range(0 if self.enc else len(self.mhsa))):
             S = self.mhsa[l]
             heads, positions = self.sa
@@ -997,7 +1030,10 @@ def init_params_for(specs, seed=0, stddev=0.05, well_scaled=False):
     rng = np.random.default_rng(seed)
     out = {}
     for name, shp in specs:
-        if name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
+        if name.endswith("conv_kernel") and len(shp) == 3:             # rnn_cell tcn: Keras' Conv1D fans, taps x in and taps x out
+            lim = math.sqrt(6.0 / (shp[0] * shp[1] + shp[0] * shp[2]))
+            out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
+        elif name.endswith("kernel") or name.endswith("attention_pool/context") or name.endswith("netvlad/centers"):
             lim = math.sqrt(6.0 / (shp[0] + shp[1]))
             out[name] = rng.uniform(-lim, lim, shp).astype(np.float32)
         elif name.endswith("bias") or name.endswith("beta"):

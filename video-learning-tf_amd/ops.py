@@ -842,7 +842,53 @@ def live_rows(x, y, batch, T, W, seq_len):
     _ffi.call("vl_live_rows", _p(x), _p(_seq_len(seq_len, batch, "live_rows")), _p(y), batch, T, W, stream())
 
 
-LN_MIN_WIDTH, LN_MAX_WIDTH, LN_EPS = 8, 1024, 1e-5                                  # vl_add_layer_norm_fwd / vl_layer_norm_bwd: vltf.h
+TCONV_MAX_TAPS, TCONV_MAX_DILATION, TCONV_MAX_WIDTH = 9, 65536, 1024                 # vl_tconv_cols_*: vltf.h
+
+
+def _tconv_sizes(who, batch, T, C, taps, dilation, causal, **tensors):
+    """The limits of vl_tconv_cols_* (the C side's wording), then every tensor given holds at least what the launch reads or writes of
+    it (None passes: the C side refuses a null pointer it needs).  Raises before any launch."""
+    if min(batch, T, C) <= 0:
+        raise _ffi.VltfError("%s: batch %d, T %d, C %d must be positive" % (who, batch, T, C))
+    if not 1 <= taps <= TCONV_MAX_TAPS:
+        raise _ffi.VltfError("%s: taps %d must lie in 1..%d" % (who, taps, TCONV_MAX_TAPS))
+    if not causal and taps % 2 == 0:
+        raise _ffi.VltfError("%s: taps %d must be odd unless causal (a centred kernel has a middle tap)" % (who, taps))
+    if not 1 <= dilation <= TCONV_MAX_DILATION:
+        raise _ffi.VltfError("%s: dilation %d must lie in 1..%d" % (who, dilation, TCONV_MAX_DILATION))
+    if C > TCONV_MAX_WIDTH:
+        raise _ffi.VltfError("%s: C %d exceeds %d" % (who, C, TCONV_MAX_WIDTH))
+    rows = batch * T
+    need = dict(x=rows * C, dx=rows * C, dres=rows * C, cols=rows * taps * C, dcols=rows * taps * C)
+    for k, t in tensors.items():
+        if t is not None and t.numel() < need[k]:
+            raise _ffi.VltfError("%s: %s has %d elements, the launch needs %d" % (who, k, t.numel(), need[k]))
+
+
+def tconv_cols_fwd(x, cols, batch, T, C, taps, dilation=1, causal=False, seq_len=None):
+    """The taps of a dilated convolution over time as the operand of a product (vl_tconv_cols_fwd): cols[b T + t, j C + c] =
+    x[b T + t + off_j, c] inside the clip's live steps, +0.0 elsewhere; off_j = (j - (taps - 1) // 2) dilation, causal:
+    (j - (taps - 1)) dilation.  x [batch T, C]; cols [batch T, taps C], every element written; seq_len as mhsa_fwd (dead rows of x
+    are never read)."""
+    _f32(x, cols)
+    _dense(x, cols)
+    _tconv_sizes("tconv_cols_fwd", batch, T, C, taps, dilation, causal, x=x, cols=cols)
+    _ffi.call("vl_tconv_cols_fwd", _p(x), None if seq_len is None else _p(_seq_len(seq_len, batch, "tconv_cols_fwd")), _p(cols),
+              batch, T, C, taps, dilation, int(bool(causal)), stream())
+
+
+def tconv_cols_bwd(dcols, dres, dx, batch, T, C, taps, dilation=1, causal=False, seq_len=None):
+    """Its backward (vl_tconv_cols_bwd): dx[b T + t, c] = dres[b T + t, c] + the sum over the taps j ascending of
+    dcols[b T + t - off_j, j C + c] inside the live steps; dres (the gradient of a residual path) may be None; dead rows of dx are
+    +0.0 and dead rows of dcols / dres are never read."""
+    _f32(dcols, dres, dx)
+    _dense(dcols, dres, dx)
+    _tconv_sizes("tconv_cols_bwd", batch, T, C, taps, dilation, causal, dcols=dcols, dres=dres, dx=dx)
+    _ffi.call("vl_tconv_cols_bwd", _p(dcols), _p(dres), None if seq_len is None else _p(_seq_len(seq_len, batch, "tconv_cols_bwd")),
+              _p(dx), batch, T, C, taps, dilation, int(bool(causal)), stream())
+
+
+LN_MIN_WIDTH, LN_MAX_WIDTH, LN_EPS = 8, 1024, 1e-5                               # vl_add_layer_norm_fwd / vl_layer_norm_bwd: vltf.h
 
 
 def _ln_sizes(who, clips, T, W, **tensors):

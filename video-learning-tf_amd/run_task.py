@@ -75,7 +75,8 @@ def pipeline_net_config(settings, p, dataset):
                   sa_heads=getattr(p, "sa_heads", None), sa_positions=getattr(p, "sa_positions", None),
                   sa_block=getattr(p, "sa_block", None), sa_ffn_dim=getattr(p, "sa_ffn_dim", None),
                   sa_attn_dropout=getattr(p, "sa_attn_dropout", None), sa_dropout=getattr(p, "sa_dropout", None),
-                  sa_drop_path=getattr(p, "sa_drop_path", None))
+                  sa_drop_path=getattr(p, "sa_drop_path", None), tcn_kernel=getattr(p, "tcn_kernel", None),
+                  tcn_dilation=getattr(p, "tcn_dilation", None), tcn_causal=getattr(p, "tcn_causal", None))
     else:
         kw.update(frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None)
     return NetConfig(**kw)
@@ -111,6 +112,8 @@ def graph_config(settings, feeder, batch):
                                   sa_positions=getattr(p, "sa_positions", None), sa_block=getattr(p, "sa_block", None),
                                   sa_ffn_dim=getattr(p, "sa_ffn_dim", None), sa_attn_dropout=getattr(p, "sa_attn_dropout", None),
                                   sa_dropout=getattr(p, "sa_dropout", None), sa_drop_path=getattr(p, "sa_drop_path", None),
+                                  tcn_kernel=getattr(p, "tcn_kernel", None), tcn_dilation=getattr(p, "tcn_dilation", None),
+                                  tcn_causal=getattr(p, "tcn_causal", None),
                                   frame_fusion=tuple(p.frame_fusion) if p.frame_fusion else None, input_fusion=p.input_fusion,
                                   train_from=getattr(p, "train_from", None)))
     infos, dsets = {}, {}

@@ -208,6 +208,7 @@ class Settings:
         network.sa_heads, network.sa_positions = self.read_self_attention(content, network)
         network.sa_block, network.sa_ffn_dim = self.read_sa_block(content, network)
         network.sa_attn_dropout, network.sa_dropout, network.sa_drop_path = self.read_sa_dropout(content, network)
+        network.tcn_kernel, network.tcn_dilation, network.tcn_causal = self.read_temporal_conv(content, network)
         network.weights_file = self.read_field(content, "weights_file")
         network.frame_fusion = self.read_field(content, "frame_fusion", validate=(defs.fusion_type, defs.fusion_method))
         if network.frame_fusion and network.frame_fusion[1] == defs.fusion_method.attn:
@@ -326,6 +327,24 @@ class Settings:
         except VltfError as ex:
             error(str(ex))
         return tuple(r if r > 0 else None for r in rates)
+
+    def read_temporal_conv(self, content, network):
+        """`tcn_kernel: <k>`, `tcn_dilation: exponential | none` and `tcn_causal: True | False` beside `rnn_cell: tcn` (this project's
+        extension of the pipeline schema): the layers of classifier lstm are dilated residual 1-D convolutions over the frames
+        (engine.tcn_specs) of k taps (absent / None = 3; 1..9, odd unless causal), layer l dilated by 2^l (absent / None / exponential;
+        at most 17 layers) or by 1 (none), centred (absent / None / False) or causal.  Refused by name: a key without rnn_cell tcn,
+        fusion state, a width above 1024 (engine.check_tcn).  -> (k, dilation, causal) as the engine takes them, or (None, None, None)
+        for every other cell."""
+        k, dil, causal = (self.read_field(content, key) for key in ("tcn_kernel", "tcn_dilation", "tcn_causal"))
+        causal = {"True": True, "False": False}.get(causal, causal) if isinstance(causal, str) else causal
+        from .engine import VltfError, check_tcn
+        lstm = network.classifier == defs.classifier.lstm
+        try:
+            tc = check_tcn(network.rnn_cell, network.lstm_params[0] if lstm else 1, network.lstm_params[1] if lstm else 1, k, dil, causal,
+                           network.lstm_params[2] if lstm else "avg")
+        except VltfError as ex:
+            error(str(ex))
+        return tc if tc else (None, None, None)
 
     def read_vlad_clusters(self, content, network):
         """`vlad_clusters: <K>` beside lstm_params (this project's extension of the pipeline schema): the number of centres of fusion
