@@ -43,11 +43,16 @@ import torch
 
 from . import ops
 from ._ffi import MAX_LR_TIERS, VltfError
-from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, blstm_buffers, blstm_names, check_accumulate, check_blstm, check_class_weights, check_ema, check_fc_dropout, check_focal_gamma,
-                     check_rnn_cell, gru_buffers, gru_names, gru_specs, check_mhsa, mhsa_buffers, mhsa_names, mhsa_specs, check_sa_block, check_tcn, tcn_backward, tcn_buffers, tcn_dilations, tcn_forward, tcn_specs, tcn_var, sa_drop_of, dropout_seed, encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var,attn_buffers, attn_names, attn_specs, check_attn, check_vlad, vlad_buffers, vlad_names, vlad_specs,
-                     check_label_smoothing,
-                     check_cutmix, check_erase, check_label_type, check_lamb, check_lars, check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, finetune_plan, frozen_layers,
-                     param_specs, tier_plan)
+from .engine import (FORGET_BIAS, LRCNEngine, MicroSequence, NetConfig, check_accumulate, check_class_weights, check_cutmix, check_ema,
+                     check_erase, check_fc_dropout, check_focal_gamma, check_label_smoothing, check_label_type, check_lamb, check_lars,
+                     check_mixup, check_momentum, check_top_k, check_weight_decay, dcnn_layers, decay_ranges, dropout_seed, finetune_plan,
+                     frozen_layers, param_specs, tier_plan)
+from .temporal import (attn_backward, attn_buffers, attn_forward, attn_specs, blstm_backward, blstm_buffers, blstm_forward, blstm_names,
+                       check_attn, check_blstm, check_mhsa, check_rnn_cell, check_sa_block, check_tcn, check_vlad, embed_grads,
+                       encoder_backward, encoder_buffers, encoder_forward, encoder_specs, encoder_var, gru_backward, gru_buffers,
+                       gru_forward, gru_names, gru_specs, mhsa_backward, mhsa_buffers, mhsa_forward, mhsa_names, mhsa_specs, sa_drop_of,
+                       tcn_backward, tcn_buffers, tcn_dilations, tcn_forward, tcn_specs, tcn_var, vlad_buffers, vlad_backward,
+                       vlad_forward, vlad_specs)
 
 
 @dataclass
@@ -666,61 +671,32 @@ class PipeNode:
         self._s0, self._b = s0, b
         xin, d = x, self.feat_dim
         HO, last = self.HO, "last" if self.lfusion == "state" else self.lfusion
-        for l, S in enumerate(self.blstm):
-            Kf, bf, Kb, bb = (P[k] for k in blstm_names(l, sc))
-            ops.gemm(xin, Kf, S["gx"][0], rows, 4 * H, d, bias=bf, ws=g.ws)
-            ops.gemm(xin, Kb, S["gx"][1], rows, 4 * H, d, bias=bb, ws=g.ws)
-            ops.lstm_seq_bi_fwd(S["gx"], (Kf[d:], Kb[d:]), S["act"], S["cseq"], S["hhalf"], S["hprev"], b, T, H, FORGET_BIAS, ws=self.lstm_ws,
-                                hseq_ld=HO, **lk)
-            xin, d = S["hseq"], HO
-        for l, S in enumerate(self.gru):
-            K, U, bk, rb = (P[k] for k in gru_names(l, sc))
-            ops.gemm(xin, K, S["gx"], rows, 3 * H, d, bias=bk, ws=g.ws)
-            ops.gru_seq_fwd(S["gx"], U, S["act"], S["hcand"], S["hseq"], S["hprev"], b, T, H, rb=rb, ws=self.lstm_ws, **lk)
-            xin, d = S["hseq"], H
+        rk = lambda span: dict(ws=self.lstm_ws, **lk)
+        if self.blstm:
+            xin, d = blstm_forward(self.blstm, P, sc, xin, rows, b, T, d, H, g.ws, rk), HO
+        if self.gru:
+            xin, d = gru_forward(self.gru, P, sc, xin, rows, b, T, d, H, g.ws, rk), H
         # the dropouts of the self-attention model in a training forward: the counters are those of the global batch (clip0)
         self._sa_drop = None
         if train and self.sa and self.sa_drop is not None:
             rank = g.dp.rank if g.dp is not None else 0
             self._sa_drop = self.sa_drop.bind(rank * (self.max_rows0 // T), seed=dropout_seed(g._draw_index()))
-        if self.enc:
-            # sa_block encoder (engine.encoder_forward).  Under seq_len the embedding reads its input through ops.live_rows, as the
-            # plain layer's qkv projection below does: x^T dx0 reads every row of x.  The norm launches never read a dead row and write
-            # zeros there; a dead row of a product's output is a bias, which nothing reads.
+        if self.mhsa or self.tcn:
+            # Under seq_len the first product of a self-attention or convolution stack (the qkv projection, the embedding) reads its
+            # input through ops.live_rows, because its weight gradient x^T dy reads every row of x: a padded frame's features reach no
+            # product.  Above it no launch reads a dead row of what a launch wrote, and what a product leaves in a dead row of its
+            # output (a bias) is read by nothing.
             if lk:
                 ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
                 xin = self.xlive
             self._xsa = xin
+        if self.enc:
             xin, d = encoder_forward(self.enc, P, sc, xin, rows, b, T, d, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk,
                                      self._sa_drop), H
+        elif self.mhsa:
+            xin, d = mhsa_forward(self.mhsa, P, sc, xin, rows, b, T, d, H, self.sa[0], self.sa[1], g.ws, lk, self._sa_drop), H
         if self.tcn:
-            # rnn_cell tcn (engine.tcn_forward).  Under seq_len the embedding reads its input through ops.live_rows, as the
-            # self-attention layers' first product does: x^T dx0 reads every row of x.  The taps launch never reads a dead row and
-            # zeroes the dead rows of cols; a dead row of the products' outputs is finite and read by nothing.
-            if lk:
-                ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
-                xin = self.xlive
-            self._xsa = xin
             xin, d = tcn_forward(self.tcn, P, sc, xin, rows, b, T, d, H, self.tc, g.ws, lk), H
-        for l, S in enumerate(() if self.enc else self.mhsa):
-            # Dead-row contract: the launch never reads a dead row of qkv and writes zeros in the dead rows of ctx (so a dead row of a
-            # layer's output is out_bias, which nothing reads: the next layer's launch, the fusions and the masked loss skip it, and its
-            # gradient arrives as zeros).  The FIRST layer's input goes through ops.live_rows, because x^T dqkv reads every row of x.
-            heads, positions = self.sa
-            names = mhsa_names(l, sc, positions)
-            if l == 0 and lk:
-                ops.live_rows(xin, self.xlive, b, T, d, lk["seq_len"])
-                xin = self.xlive
-            if l == 0:
-                self._xsa = xin
-            ops.gemm(xin, P[names[0]], S["qkv"], rows, 3 * H, d, bias=P[names[1]], ws=g.ws)
-            pos = P[names[4]] if positions == "relative" else None
-            if self._sa_drop is not None:
-                ops.mhsa_drop_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **self._sa_drop.weights_kw(l), **lk)
-            else:
-                ops.mhsa_fwd(S["qkv"], pos, S["P"], S["ctx"], b, T, H, heads, **lk)
-            ops.gemm(S["ctx"], P[names[2]], S["hseq"], rows, H, H, bias=P[names[3]])
-            xin, d = S["hseq"], H
         for l, S in enumerate(self.lstm):
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
             K = P[pre + "kernel"]
@@ -732,20 +708,10 @@ class PipeNode:
         if self.per_step:
             v = xin                                                     # reshape fusion: every step's output (tf_util.py:26-27)
         elif self.attn is not None:
-            # u = hseq W + bias over all rows (a dead row of hseq is zero, its u is never read), then the one pooling launch; the
-            # attention's dense products take no workspace, as the head's: fp32 whatever conv_math says
-            Wa, ba, ca = (P[k] for k in attn_names(sc))
-            S = self.attn
-            ops.gemm(xin, Wa, S["us"], rows, self.attn_dim, HO, bias=ba)
-            ops.attn_pool_fwd(S["us"], ca, xin, S["us"], S["alpha"], self.fused, b, T, HO, self.attn_dim, **lk)
+            attn_forward(self.attn, P, sc, xin, self.fused, rows, b, T, HO, self.attn_dim, lk)
             v = self.fused
         elif self.vlad is not None:
-            # s = hseq W + beta over all rows (no workspace: fp32 whatever conv_math says), then the one pooling launch, which reads no
-            # dead row of hseq or s
-            Wv, bv, cv = (P[k] for k in vlad_names(sc))
-            S = self.vlad
-            ops.gemm(xin, Wv, S["sa"], rows, self.vlad_k, HO, bias=bv)
-            ops.netvlad_fwd(S["sa"], cv, xin, S["sa"], S["r"], self.fused, b, T, HO, self.vlad_k, **lk)
+            vlad_forward(self.vlad, P, sc, xin, self.fused, rows, b, T, HO, self.vlad_k, lk)
             v = self.fused
         else:
             # with lengths `state` and `last` are h of step len - 1 (dynamic_rnn's final state), `avg` the mean over the live steps
@@ -824,6 +790,9 @@ class PipeNode:
         if self._dropout:
             ops.dropout_bwd(d[:r], self.drop_mask[:r], self.dfused[:r], g.dropout_keep_prob)
             d = self.dfused
+        lk = self._len_kw()
+        rk = lambda span: dict(ws=self.lstm_ws, **lk)
+        param_grads = lambda launch: launch(g.ws, sw)
         top = (self.blstm or self.gru or self.mhsa or self.tconv or self.lstm)[-1]
         if self.per_step:
             top["dout"][:r].copy_(d[:r])
@@ -835,98 +804,34 @@ class PipeNode:
             ops.temporal_fusion_bwd(self.dlast, top["dout"], b, T, HO, last, **self._len_kw())
             ops.copy2d(d[:, H:], top["dout"][:, H:], b, H, src_ld=HO, dst_ld=T * HO)
         elif self.attn is not None:
-            # du, the direct term alpha_t dy straight into dout (zeros in the dead rows of both), the context gradient's per-clip partials
-            names, S, At, hs = attn_names(sc), self.attn, self.attn_dim, top["hseq"]
-            ops.attn_pool_bwd(d, hs, S["us"], S["alpha"], P[names[2]], S["du"], top["dout"], S["dcp"], b, T, HO, At, **self._len_kw())
-            ops.gemm(hs, S["du"], G[names[0]], HO, At, rows, transa=True)
-            ops.colsum(S["du"], G[names[1]], sw, rows, At)
-            ops.colsum(S["dcp"], G[names[2]], sw, b, At)
-            ops.gemm(S["du"], P[names[0]], S["dproj"], rows, HO, At, transb=True)
-            ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", rows * HO)
+            attn_backward(self.attn, P, G, sc, d, top["hseq"], top["dout"], rows, b, T, HO, self.attn_dim, lk, param_grads)
         elif self.vlad is not None:
-            # ds, the direct term sum_k a_tk dV_k straight into dout (zeros in the dead rows of both), the centres' per-clip partials
-            names, S, Kv, hs = vlad_names(sc), self.vlad, self.vlad_k, top["hseq"]
-            ops.netvlad_bwd(d, hs, S["sa"], S["r"], self.fused, P[names[2]], S["ds"], top["dout"], S["dcp"], b, T, HO, Kv, **self._len_kw())
-            ops.gemm(hs, S["ds"], G[names[0]], HO, Kv, rows, transa=True)
-            ops.colsum(S["ds"], G[names[1]], sw, rows, Kv)
-            ops.colsum(S["dcp"], G[names[2]], sw, b, Kv * HO)
-            ops.gemm(S["ds"], P[names[0]], S["dproj"], rows, HO, Kv, transb=True)
-            ops.eltwise2(top["dout"], S["dproj"], top["dout"], "add", rows * HO)
+            vlad_backward(self.vlad, P, G, sc, d, top["hseq"], self.fused, top["dout"], rows, b, T, HO, self.vlad_k, lk, param_grads)
         else:
             ops.temporal_fusion_bwd(d, top["dout"], b, T, HO, last, **self._len_kw())
         has_state = self._s0 is not None
-        for l in reversed(range(len(self.blstm))):
-            S = self.blstm[l]
-            names = blstm_names(l, sc)
-            Kf, Kb = P[names[0]], P[names[2]]
-            din = self.feat_dim if l == 0 else HO
-            xin = self._xcls if l == 0 else self.blstm[l - 1]["hseq"]
-            ops.lstm_seq_bi_bwd(S["dhalf"], (Kf[din:], Kb[din:]), S["act"], S["cseq"], S["dz"], b, T, H, ws=self.lstm_ws, dout_ld=HO,
-                                **self._len_kw())
-            for k in range(2):
-                gK = G[names[2 * k]]
-                ops.gemm(xin, S["dz"][k], gK, din, 4 * H, rows, transa=True, ws=g.ws)
-                ops.gemm(S["hprev"][k], S["dz"][k], gK[din:], H, 4 * H, rows, transa=True, ws=g.ws)
-                ops.colsum(S["dz"][k], G[names[2 * k + 1]], sw, rows, 4 * H)
-            if l > 0 or self.wants_feat:                                # the input gradient: the sum of both directions' dz Kx^T
-                target = self.blstm[l - 1]["dout"] if l > 0 else self.dxseq
-                ops.gemm(S["dz"][0], Kf, target, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
-                ops.gemm(S["dz"][1], Kb, self.dx_bw, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
-                ops.eltwise2(target, self.dx_bw, target, "add", rows * din)
-        for l in reversed(range(len(self.gru))):
-            S = self.gru[l]
-            names = gru_names(l, sc)
-            K, U = P[names[0]], P[names[1]]
-            din = self.feat_dim if l == 0 else H
-            xin = self._xcls if l == 0 else self.gru[l - 1]["hseq"]
-            ops.gru_seq_bwd(S["dout"], U, S["act"], S["hcand"], S["hprev"], S["dgx"], S["dgh"], b, T, H, ws=self.lstm_ws, **self._len_kw())
-            ops.gemm(xin, S["dgx"], G[names[0]], din, 3 * H, rows, transa=True, ws=g.ws)
-            ops.gemm(S["hprev"], S["dgh"], G[names[1]], H, 3 * H, rows, transa=True, ws=g.ws)
-            ops.colsum(S["dgx"], G[names[2]], sw, rows, 3 * H)
-            ops.colsum(S["dgh"], G[names[3]], sw, rows, 3 * H)
-            if l > 0:
-                ops.gemm(S["dgx"], K, self.gru[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
-            elif self.wants_feat:
-                ops.gemm(S["dgx"], K, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
+        # the shared pairs of temporal.py: one stream here, every parameter gradient where the chain stands; each returns its first
+        # layer's gradient and _feat_grad forms the input gradient from it where somebody reads it (wants_feat)
+        D = self.feat_dim
+        if self.blstm:
+            blstm_backward(self.blstm, P, G, sc, self._xcls, rows, b, T, D, H, g.ws, rk, param_grads,
+                           self.dxseq if self.wants_feat else None, self.dx_bw)
+        if self.gru:
+            dgx = gru_backward(self.gru, P, G, sc, self._xcls, rows, b, T, D, H, g.ws, rk, param_grads)
+            self._feat_grad(dgx, P[gru_names(0, sc)[0]], rows, 3 * H)
         if self.enc:
-            # sa_block encoder: the blocks (engine.encoder_backward: one stream here, every gradient where the chain stands), then
-            # the embedding as the plain layer's qkv projection below
-            dx0 = encoder_backward(self.enc, P, G, sc, self._xsa, rows, b, T, self.feat_dim, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws,
-                                   self._len_kw(), lambda launch: launch(g.ws, sw), self._sa_drop)
-            ops.gemm(self._xsa, dx0, G[encoder_var(sc, None, "kernel")], self.feat_dim, H, rows, transa=True, ws=g.ws)
-            ops.colsum(dx0, G[encoder_var(sc, None, "bias")], sw, rows, H)
-            if self.wants_feat:
-                ops.gemm(dx0, P[encoder_var(sc, None, "kernel")], self.dxseq, rows, self.feat_dim, H, transb=True, ldb=H, ws=g.ws)
+            dx0 = encoder_backward(self.enc, P, G, sc, self._xsa, rows, b, T, D, H, self.sa_ffn, self.sa[0], self.sa[1], g.ws, lk,
+                                   param_grads, self._sa_drop)
+            embed_grads(G, encoder_var, sc, self._xsa, dx0, rows, D, H, param_grads)
+            self._feat_grad(dx0, P[encoder_var(sc, None, "kernel")], rows, H)
+        elif self.mhsa:
+            dqkv = mhsa_backward(self.mhsa, P, G, sc, self._xsa, rows, b, T, D, H, self.sa[0], self.sa[1], g.ws, lk, param_grads,
+                                 self._sa_drop)
+            self._feat_grad(dqkv, P[mhsa_names(0, sc, self.sa[1])[0]], rows, 3 * H)
         if self.tcn:
-            # rnn_cell tcn: the layers (engine.tcn_backward: one stream here, every gradient where the chain stands), then the embedding
-            dx0 = tcn_backward(self.tcn, P, G, sc, rows, b, T, H, self.tc, self._len_kw(), lambda launch: launch(g.ws, sw))
-            ops.gemm(self._xsa, dx0, G[tcn_var(sc, None, "kernel")], self.feat_dim, H, rows, transa=True, ws=g.ws)
-            ops.colsum(dx0, G[tcn_var(sc, None, "bias")], sw, rows, H)
-            if self.wants_feat:
-                ops.gemm(dx0, P[tcn_var(sc, None, "kernel")], self.dxseq, rows, self.feat_dim, H, transb=True, ldb=H, ws=g.ws)
-        for l in reversed(range(0 if self.enc else len(self.mhsa))):
-            S = self.mhsa[l]
-            heads, positions = self.sa
-            names = mhsa_names(l, sc, positions)
-            Wqkv, Wo = P[names[0]], P[names[2]]
-            din = self.feat_dim if l == 0 else H
-            xin = self._xsa if l == 0 else self.mhsa[l - 1]["hseq"]
-            ops.gemm(S["dout"], Wo, S["dctx"], rows, H, H, transb=True)
-            if self._sa_drop is not None:
-                ops.mhsa_drop_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._sa_drop.weights_kw(l),
-                                  **self._len_kw())
-            else:
-                ops.mhsa_bwd(S["dctx"], S["qkv"], S["P"], S["dqkv"], S.get("dposp"), b, T, H, heads, **self._len_kw())
-            ops.gemm(S["ctx"], S["dout"], G[names[2]], H, H, rows, transa=True)
-            ops.colsum(S["dout"], G[names[3]], sw, rows, H)
-            ops.gemm(xin, S["dqkv"], G[names[0]], din, 3 * H, rows, transa=True, ws=g.ws)
-            ops.colsum(S["dqkv"], G[names[1]], sw, rows, 3 * H)
-            if "dposp" in S:
-                ops.colsum(S["dposp"], G[names[4]], sw, b, heads * (2 * T - 1))
-            if l > 0:
-                ops.gemm(S["dqkv"], Wqkv, self.mhsa[l - 1]["dout"], rows, H, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
-            elif self.wants_feat:
-                ops.gemm(S["dqkv"], Wqkv, self.dxseq, rows, din, 3 * H, transb=True, ldb=3 * H, ws=g.ws)
+            dx0 = tcn_backward(self.tcn, P, G, sc, rows, b, T, H, self.tc, lk, param_grads)
+            embed_grads(G, tcn_var, sc, self._xsa, dx0, rows, D, H, param_grads)
+            self._feat_grad(dx0, P[tcn_var(sc, None, "kernel")], rows, H)
         for l in reversed(range(len(self.lstm))):
             S = self.lstm[l]
             pre = sc + "rnn/multi_rnn_cell/cell_%d/basic_lstm_cell/" % l
@@ -946,8 +851,8 @@ class PipeNode:
                     ops.eltwise2(self.dstate, S["dh0"], self.dstate, "add", count=b * H)
             if l > 0:
                 ops.gemm(S["dz"], K, self.lstm[l - 1]["dout"], rows, H, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
-            elif self.wants_feat:
-                ops.gemm(S["dz"], K, self.dxseq, rows, din, 4 * H, transb=True, ldb=4 * H, ws=g.ws)
+            else:
+                self._feat_grad(S["dz"], K, rows, 4 * H)
         if has_state:
             ds, sd = self.dstate, self.state_src.dim
             to_pipe = self.state_src.kind == "pipe"
@@ -963,6 +868,11 @@ class PipeNode:
                     ds = self.din[1]
                 self._dstate_out = ds
         return self.dxseq, rows
+
+    def _feat_grad(self, dg, K, rows, W):
+        """dxseq = dg K^T, the gradient of the classifier's input from its first layer's dg [rows, W], where somebody reads it."""
+        if self.wants_feat:
+            ops.gemm(dg, K, self.dxseq, rows, self.feat_dim, W, transb=True, ldb=W, ws=self.g.ws)
 
     def _input_grads(self, d, rows):
         """Gradient w.r.t. the fused stage-0 tensor -> the pipeline inputs' producers."""
